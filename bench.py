@@ -25,7 +25,11 @@ No torch anywhere: the control plane (rendezvous, barrier, max over ranks, the R
 
 Precision: "auto" (engine.resolve_precision) traces a phase-integrating volume in float64 -- the only build whose
 interferogram reproduces the oracle's from the same rays -- and a volume without the phase (counts diagnostics) with
-the mixed build.  The other build is timed in the same run (key "other_build"), outside the timed region.
+the mixed build.  With --full the other build is timed in the same run (key "other_build"), outside the timed region.
+
+A plain run sets up, warms up, times the K steps and prints its line; everything else it can measure or check (the other
+build, the oracle check and CPU baseline, the reference's API flow, the N > 1 image checks) runs after the job with --full
+only, and those keys are null without it.  --dump-outputs DIR writes what the timed path computed (dump_outputs).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -79,13 +83,20 @@ def parse_args(argv=None):
     ap.add_argument("--precision", choices=["auto", "mixed", "f64"], default="auto",
                     help="auto: float64 when the phase is integrated (interferometry), else mixed (float64 state and "
                          "accumulation, float32 stage arithmetic); see engine.resolve_precision")
-    ap.add_argument("--other-steps", type=int, default=3, help="steps of the OTHER build timed after the job (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the job, everything beside the headline: the other build (--other-steps), the check against the oracle and "
+                         "the CPU baseline (--cpu-sample), the reference's API flow (--api-flow-reps), the N > 1 image checks.  Off: the run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in the job's last step as DIR/<name>.npy (float64 / float32, at most "
+                         "64 MB in all; seeded samples of the larger arrays): see dump_outputs")
+    ap.add_argument("--other-steps", type=int, default=3, help="--full: steps of the OTHER build timed after the job (0 = skip)")
     ap.add_argument("--no-sort", action="store_true")
     ap.add_argument("--no-phase", action="store_true", help="shadowgraphy + schlieren deposit instead of the interferogram")
     ap.add_argument("--api-flow-reps", type=int, default=5,
-                    help="N = 1: passes of the same workload through the reference's own API (ScalarDomain.solve -> diagnostics "
+                    help="--full, N = 1: passes of the same workload through the reference's own API (ScalarDomain.solve -> diagnostics "
                          "classes), timed outside the job and printed as `api_flow` (0 = skip)")
-    ap.add_argument("--cpu-sample", type=float, default=2e5, help="rays traced by the CPU baseline / checker (0 = skip)")
+    ap.add_argument("--cpu-sample", type=float, default=2e5, help="--full: rays traced by the CPU baseline / checker (0 = skip)")
     ap.add_argument("--chunk", type=float, default=None,
                     help="c5: rays per pipeline chunk.  Default: dense chunks, so that every slab is traced by the tile kernel -- N = 1: "
                          "all --rays in ONE chunk (2e7: 38 rays per lateral cell of the beam); N > 1: 1.25e7 (24 per cell; 8 chunks of 1e8)")
@@ -469,6 +480,55 @@ def build_id_of(version: str) -> str:
     return version.split("src:")[-1].strip() if "src:" in version else "unknown"
 
 
+DUMP_BYTES = 64 * 2 ** 20  # --dump-outputs: at most this much in all
+DUMP_RAYS = 2 ** 17        # rays in the seeded sample of a bundle's exit state
+DUMP_SEED = 20240607       # the samples' seed: the same rays and pixels from run to run and build to build
+
+
+def dump_outputs(path, rays=None, images=()):
+    """--dump-outputs DIR: what the timed path handed its caller, as DIR/<name>.npy, so that two builds of the project can be
+    compared output for output on the same (seeded) inputs.
+    rays = (sf (9, n), rf (4, n), Jf (2, n) complex | None), the exit state of the job's last step -> a fixed seeded sample of
+    DUMP_RAYS rays (all of them when there are fewer), float64: rays_index (m,), rays_sf (9, m), rays_rf (4, m) and, with Jf,
+    rays_Jf_re / rays_Jf_im (2, m).
+    images = [(name, 2-D array)]: the job's detector images (interferogram amplitude, counts) -> image_<name>, float32, whole
+    when it fits in an equal share of what the rays leave of DUMP_BYTES, else a seeded sample of its pixels in row-major order,
+    image_<name> (k,) with image_<name>_index (k,) float64 beside it.  Returns {name: bytes written}."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    if rays is not None:
+        sf, rf, Jf = rays
+        n = rf.shape[1]
+        idx = np.arange(n) if n <= DUMP_RAYS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_RAYS, replace=False))
+        out["rays_index"] = idx.astype(np.float64)
+        out["rays_sf"] = np.ascontiguousarray(sf[:, idx], dtype=np.float64)
+        out["rays_rf"] = np.ascontiguousarray(rf[:, idx], dtype=np.float64)
+        if Jf is not None:
+            out["rays_Jf_re"] = np.ascontiguousarray(Jf.real[:, idx], dtype=np.float64)
+            out["rays_Jf_im"] = np.ascontiguousarray(Jf.imag[:, idx], dtype=np.float64)
+    images = list(images)
+    if images:
+        share = (DUMP_BYTES - sum(a.nbytes for a in out.values()) - 4096 * (len(out) + 2 * len(images))) // len(images)
+        for q, (name, H) in enumerate(images):
+            H = np.asarray(H)
+            if H.size * 4 <= share:
+                out["image_" + name] = H.astype(np.float32)
+                continue
+            k = int(share // (4 + 8))  # a float32 pixel and its float64 index
+            pix = np.sort(np.random.default_rng(DUMP_SEED + 1 + q).choice(H.size, k, replace=False))
+            out["image_" + name] = H.reshape(-1)[pix].astype(np.float32)
+            out["image_" + name + "_index"] = pix.astype(np.float64)
+    written = {}
+    for name, a in out.items():
+        fn = os.path.join(path, name + ".npy")
+        np.save(fn, a)
+        written[name] = os.path.getsize(fn)
+    assert sum(written.values()) <= DUMP_BYTES, written
+    return written
+
+
 # --------------------------------------------------------------------------------------------------------------
 # C5: the slab pipeline
 # --------------------------------------------------------------------------------------------------------------
@@ -480,8 +540,9 @@ def bench_c5(args):
     resident too -- 21.5 GB of the 288 -- for the check).  A "step" = all --rays rays through the whole volume; the rays
     are drawn on the first slab's GPU (sr_rays_generate: init_beam's distributions, Philox stream), so no host upload
     sits in the pipeline (--host-rays uploads a host bundle per chunk instead, as the reference's drivers would).
-    check (rank 0, N = 1): the chain of slabs against the WHOLE volume, bit for bit, and against the oracle FROM s0 on a
-    1e5-ray sample (exit rays, shadowgram counts, interferogram); cpu_baseline: the oracle's trace of that sample."""
+    check (--full, rank 0, N = 1): the chain of slabs against the WHOLE volume, bit for bit, and against the oracle FROM s0 on a
+    1e5-ray sample (exit rays, shadowgram counts, interferogram); cpu_baseline: the oracle's trace of that sample.
+    --dump-outputs: the last rank's image of the last pass and, at N = 1, the exit state of the last chunk's rays."""
     import numpy as np
 
     from synthpy_amd import _ffi, engine
@@ -533,7 +594,7 @@ def bench_c5(args):
                        cut="stripe" if args.stripe_chunks else "index")
     chunk, sizes = plan["chunk"], plan["sizes"]
     t_end = engine.default_t_end(ext)
-    ns = int(min(args.cpu_sample, 100000, sizes[0]))
+    ns = int(min(args.cpu_sample, 100000, sizes[0])) if args.full else 0
     # one host bundle: --host-rays re-uploads it per chunk; otherwise only the check's sample is drawn on the host
     s0_chunk = make_rays(max(sizes) if args.host_rays else max(ns, 1), ext, seed=0)
     stripes = None
@@ -550,6 +611,7 @@ def bench_c5(args):
     beam = dict(beam_size=4e-3, divergence=5e-5, ne_extent=ext, beam_type="circular", probing_direction="z", seed=0)
     kern_ms, tile_segs, tile_recs = [], [], []
     c5_bundles = {}  # N = 1: the bundles live as long as the job (their buffers are allocated once)
+    last_bundle = []  # N = 1: the bundle of the pass's last chunk
 
     def one_pass():
         img.zero()
@@ -563,6 +625,7 @@ def bench_c5(args):
             key = (ci, m) if stripes is not None else m
             fresh = key not in c5_bundles
             r = c5_bundles.get(key) or c5_bundles.setdefault(key, engine.RayBundle(m))
+            last_bundle[:] = [r]
             t_a = time.perf_counter()
             if stripes is not None:
                 if fresh:  # once, in the first warm-up pass: the chunks are resident in HBM when the timed region starts
@@ -612,6 +675,8 @@ def bench_c5(args):
     ranks_seen = grp.comm_ranks()[1] if grp.world > 1 else 1
     if grp.world > 1 and ranks_seen != args.gpus:
         raise SystemExit(f"the data-path communicator reports {ranks_seen} ranks, the job was started with --gpus {args.gpus}")
+    if args.dump_outputs and grp.rank == grp.world - 1:  # the rank that deposits; at N = 1 the last chunk's bundle is the caller's too
+        dump_outputs(args.dump_outputs, rays=last_bundle[0].download() if last_bundle else None, images=[("interferogram", img.amplitude())])
     check, cpu = None, None
     if grp.rank == 0 and grp.world == 1 and ns > 0:
         # (a) the cut changes nothing: the sample through the chain of slabs == through the WHOLE volume, bit for bit
@@ -663,7 +728,7 @@ def bench_c5(args):
             "value": all_steps / elapsed, "unit": "ray-steps/s", "rays_per_s": n_rays * args.steps / elapsed,
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64" if precision == "f64" else "f64 state+accumulation / f32 stage arithmetic", "data": "synthetic",
+            "dtype": "f64" if precision == "f64" else "f64 state+accumulation / f32 stage arithmetic", "data": "synthetic", "full": args.full,
             "config": {"workload": f"C5: {n_rays:.3g} rays in chunks of {chunk:.3g} x {n}^3 k^-11/3 turbulent n_e (gaussian3D.domain_fft, res {n // 2}), "
                                    f"{n_slabs} slabs of node planes ({'one per GPU, RCCL hand-off' if grp.world > 1 else 'all on one GPU, hand-off in place'}), "
                                    "phase integral + interferogram on the last slab's GPU",
@@ -824,9 +889,15 @@ def bench_rays(args):
     all_steps = grp.sum_over_ranks(float(steps_total))
     all_rays = grp.sum_over_ranks(float(n_rays * args.steps))
 
-    # ---- the other build on the same rays, same volume, same deposits (outside the timed job) ----
+    # ---- what the timed path computed: rank 0's exit rays of the last step and the job's images (its K steps summed over the ranks) ----
+    if args.dump_outputs and grp.rank == 0:
+        names = (["interferogram"] if wl_diag in ("interferometry", "all") else []) + (["shadowgram", "schlieren"] if wl_diag in ("shadow+schlieren", "all") else [])
+        dump_outputs(args.dump_outputs, rays=rays.download(),
+                     images=[(nm, img.amplitude() if img.kind == engine.IMG_COMPLEX else img.download()) for nm, (img, _, _) in zip(names, images)])
+
+    # ---- --full: the other build on the same rays, same volume, same deposits (outside the timed job) ----
     other_out = None
-    if args.other_steps > 0:
+    if args.full and args.other_steps > 0:
         oims = make_images()
         one_step(ims=oims, prec=other)  # warm-up
         for img, _, _ in oims:
@@ -851,9 +922,9 @@ def bench_rays(args):
         for img, _, _ in oims:
             img.close()
 
-    # ---- N > 1: the reduced image against the ranks' own totals and against ONE GPU doing every rank's rays ----
+    # ---- --full, N > 1: the reduced image against the ranks' own totals and against ONE GPU doing every rank's rays ----
     multi = None
-    if grp.world > 1:
+    if args.full and grp.world > 1:
         cims = [(engine.DetectorImage.counts(bin_scale=1), engine.chain_shadow_two(), {})]
         if phase:
             cims.append((engine.DetectorImage.complex_field(bin_scale=1), engine.chain_shadow_two(),
@@ -889,10 +960,10 @@ def bench_rays(args):
                 multi["interferogram_sums_max_diff_over_max"] = float(np.max(np.abs(A_red - A_solo)) / np.max(np.abs(A_solo)))
         grp.barrier()
 
-    # ---- correctness next to the timing + the CPU baseline (rank 0, N = 1 only for the baseline) ----
+    # ---- --full: correctness next to the timing + the CPU baseline (rank 0, N = 1 only for the baseline) ----
     check, cpu = None, None
     if grp.rank == 0:
-        ns = int(min(args.cpu_sample, n_rays))
+        ns = int(min(args.cpu_sample, n_rays)) if args.full else 0
         if ns > 0:
             from oracle import oracle as orc  # the checker / reported CPU baseline, never the product
 
@@ -963,7 +1034,7 @@ def bench_rays(args):
             check = dict(check or {}, multi_gpu=multi)
 
     flow = None
-    if grp.rank == 0 and grp.world == 1 and args.api_flow_reps > 0 and args.substeps == 1 and not args.no_sort:
+    if args.full and grp.rank == 0 and grp.world == 1 and args.api_flow_reps > 0 and args.substeps == 1 and not args.no_sort:
         flow = api_flow(engine, ne, x, s0, ext, lwl, wl_diag, args.api_flow_reps)
         flow["engine_path_ms_per_step"] = elapsed / args.steps * 1e3
         flow["ms_over_engine_path"] = flow["ms"] / flow["engine_path_ms_per_step"]
@@ -1000,6 +1071,7 @@ def bench_rays(args):
             "vs_baseline": None,
             "dtype": "f64" if precision == "f64" else "f64 state+accumulation / f32 stage arithmetic",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": (args.workload.upper() + ": " if (int(args.rays), grid) == (int(wl_rays), wl_grid) else "") +
                             (f"rank {args.share_rank}'s share of {args.share_of} ({'a stripe of the beam' if args.shard == 'stripe' else 'an index range'}) of {int(args.rays):.3g} rays" if args.share_of else

@@ -245,6 +245,53 @@ def test_driver_chunks_do_not_depend_on_the_number_of_gpus():
         assert spans[0][0] == 0 and spans[-1][1] == n and all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
 
 
+def test_bench_dump_outputs_within_budget_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float64 / float32 .npy files, at most 64 MB in all even for C4's three detector images beside the
+    rays; a bundle larger than the sample and an image that does not fit are sampled with fixed seeds (the same rays and pixels
+    every time, their indices written beside them); what fits is written whole."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    n = 3 * bench.DUMP_RAYS
+    sf, rf = rng.standard_normal((9, n)), rng.standard_normal((4, n))
+    Jf = rng.standard_normal((2, n)) + 1j * rng.standard_normal((2, n))
+    interf = rng.random((2573, 3447))
+    counts = [rng.integers(0, 50, (2574, 3448), dtype=np.uint32) for _ in range(2)]
+    c3 = bench.dump_outputs(str(tmp_path / "c3"), rays=(sf, rf, Jf), images=[("interferogram", interf)])
+    assert sorted(c3) == ["image_interferogram", "rays_Jf_im", "rays_Jf_re", "rays_index", "rays_rf", "rays_sf"]
+    H = np.load(tmp_path / "c3" / "image_interferogram.npy")
+    assert H.dtype == np.float32 and np.array_equal(H, interf.astype(np.float32))  # whole: it fits
+    idx = np.load(tmp_path / "c3" / "rays_index.npy").astype(np.int64)
+    assert idx.shape == (bench.DUMP_RAYS,) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "c3" / "rays_rf.npy"), rf[:, idx])
+    assert np.array_equal(np.load(tmp_path / "c3" / "rays_Jf_im.npy"), Jf.imag[:, idx])
+    c4 = bench.dump_outputs(str(tmp_path / "c4"), rays=(sf, rf, Jf),
+                            images=[("interferogram", interf), ("shadowgram", counts[0]), ("schlieren", counts[1])])
+    again = bench.dump_outputs(str(tmp_path / "again"), rays=(sf, rf, Jf),
+                               images=[("interferogram", interf), ("shadowgram", counts[0]), ("schlieren", counts[1])])
+    for d, w in (("c3", c3), ("c4", c4)):
+        assert sum(w.values()) <= 64 * 2 ** 20
+        assert all(np.load(tmp_path / d / (k + ".npy")).dtype in (np.float32, np.float64) for k in w)
+    for k in c4:
+        assert np.array_equal(np.load(tmp_path / "c4" / (k + ".npy")), np.load(tmp_path / "again" / (k + ".npy"))), k
+    pix = np.load(tmp_path / "c4" / "image_schlieren_index.npy").astype(np.int64)
+    assert 10 ** 6 < pix.size < counts[1].size and np.all(np.diff(pix) > 0)
+    assert np.array_equal(np.load(tmp_path / "c4" / "image_schlieren.npy"), counts[1].reshape(-1)[pix].astype(np.float32))
+    small = bench.dump_outputs(str(tmp_path / "small"), rays=(sf[:, :100], rf[:, :100], None))
+    assert sorted(small) == ["rays_index", "rays_rf", "rays_sf"]
+    assert np.array_equal(np.load(tmp_path / "small" / "rays_sf.npy"), sf[:, :100])
+
+
+def test_bench_plain_run_options():
+    """--full is off unless asked for; --dump-outputs takes a directory."""
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+
+
 def test_bench_roofline_is_recomputable_from_profiles(built):
     """bench.py's roofline object: the VALU-issue fraction is computed from committed files only (the per-class instruction
     counts of profiles/kernel_model.json, measured on THIS build of the library, priced at the hardware's issue cost) plus

@@ -1501,7 +1501,7 @@ def test_bench_n_gt_1_job_rehearsed_on_one_gpu(scaling):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu", "--scaling", scaling, "--grid", "96",
-           "--rays", "200000", "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--other-steps", "0", "--spawn-timeout", "240"]
+           "--rays", "200000", "--steps", "1", "--warmup", "0", "--full", "--cpu-sample", "0", "--other-steps", "0", "--spawn-timeout", "240"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -1526,7 +1526,7 @@ def test_bench_says_so_when_rccl_cannot_sum_the_images():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--shared-gpu-rccl", "--grid", "96", "--rays", "200000",
-           "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--other-steps", "0", "--spawn-timeout", "240"]
+           "--steps", "1", "--warmup", "0", "--full", "--cpu-sample", "0", "--other-steps", "0", "--spawn-timeout", "240"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "RCCL COULD NOT SUM THE IMAGES" in res.stderr
@@ -1537,6 +1537,45 @@ def test_bench_says_so_when_rccl_cannot_sum_the_images():
     assert d["value"] is None and d["rays_per_s"] is None and d["value_with_the_host_sum"] > 0  # a host sum is not the N-GPU metric
     m = d["check"]["multi_gpu"]
     assert m["ranks_seen"] == 2 and m["counts_sum_equals_sum_of_deposited"] and m["counts_image_equals_single_gpu_image"]
+
+
+def test_bench_plain_run_is_the_job_and_dumps_what_it_computed(tmp_path):
+    """`python bench.py` without --full: set-up, warm-up, the timed steps and one line -- the other build, the oracle check, the CPU
+    baseline and the API flow are --full's (null here, present there).  --dump-outputs writes the timed path's results; with the
+    same arguments the two runs (plain and --full) dump the same exit rays bit for bit and the same interferogram to rounding."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--grid", "96", "--rays", "200000", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--cpu-sample", "20000", "--other-steps", "1", "--api-flow-reps", "1"])):
+        res = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, res.stdout
+        lines[tag] = json.loads(out[0])
+    p, f = lines["plain"], lines["full"]
+    for d in (p, f):
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "ray-steps/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["config"]["precision"] == "f64"
+    assert p["full"] is False and all(p[k] is None for k in ("check", "cpu_baseline", "other_build", "api_flow"))
+    assert f["full"] is True and all(f[k] is not None for k in ("check", "cpu_baseline", "other_build", "api_flow"))
+    assert "max_dx_m" in f["check"] and f["other_build"]["steps"] == 1
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) == sorted(
+        ["rays_index.npy", "rays_sf.npy", "rays_rf.npy", "rays_Jf_re.npy", "rays_Jf_im.npy", "image_interferogram.npy"])
+    assert sum(os.path.getsize(tmp_path / "plain" / n) for n in names) <= 64 * 2 ** 20
+    a = {n[:-4]: np.load(tmp_path / "plain" / n) for n in names}
+    b = {n[:-4]: np.load(tmp_path / "full" / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["rays_rf"].shape == (4, 2 ** 17) and a["rays_sf"].shape == (9, 2 ** 17) and a["image_interferogram"].shape == (2573, 3447)
+    for k in ("rays_index", "rays_sf", "rays_rf", "rays_Jf_re", "rays_Jf_im"):
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    assert np.isfinite(a["rays_rf"]).sum() > 0.9 * a["rays_rf"].size
+    Ha, Hb = a["image_interferogram"].astype(np.float64), b["image_interferogram"].astype(np.float64)
+    assert Ha.max() > 0 and np.max(np.abs(Ha - Hb)) <= 1e-5 * Ha.max()
 
 
 # ---------------------------------------------------------------- the step before the path: volume synthesis on the GPU

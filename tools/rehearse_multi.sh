@@ -16,11 +16,11 @@ print(d["n_gpus"], d["scaling"], "rays this rank", c.get("rays_this_gpu"), "all"
       "| multi_gpu:", (d.get("check") or {}).get("multi_gpu"))
 PY
 }
-run strong2 --gpus 2 --steps 2 --warmup 1 --scaling strong --cpu-sample 20000 --other-steps 1
-run weak2_full --gpus 2 --steps 2 --warmup 1 --scaling weak --cpu-sample 0 --other-steps 0
-run weak3 --gpus 3 --steps 2 --warmup 1 --scaling weak --rays 2e6 --cpu-sample 0 --other-steps 0
-run weak6 --gpus 6 --steps 1 --warmup 1 --scaling weak --grid 128 --rays 2e5 --cpu-sample 0 --other-steps 0
-run c4_4 --gpus 4 --workload c4 --steps 1 --warmup 1 --grid 256 --rays 5e5 --cpu-sample 0 --other-steps 0
-run c5_2 --gpus 2 --workload c5 --grid 256 --rays 2e6 --chunk 5e5 --steps 1 --warmup 1
-run c5_3 --gpus 3 --workload c5 --grid 192 --rays 1e6 --chunk 2.5e5 --steps 1 --warmup 0
-run c5_2_stripes --gpus 2 --workload c5 --grid 256 --rays 2e6 --stripe-chunks --steps 1 --warmup 1   # chunks cut by position (plan_chunks(cut='stripe'))
+run strong2 --full --gpus 2 --steps 2 --warmup 1 --scaling strong --cpu-sample 20000 --other-steps 1
+run weak2_full --full --gpus 2 --steps 2 --warmup 1 --scaling weak --cpu-sample 0 --other-steps 0
+run weak3 --full --gpus 3 --steps 2 --warmup 1 --scaling weak --rays 2e6 --cpu-sample 0 --other-steps 0
+run weak6 --full --gpus 6 --steps 1 --warmup 1 --scaling weak --grid 128 --rays 2e5 --cpu-sample 0 --other-steps 0
+run c4_4 --full --gpus 4 --workload c4 --steps 1 --warmup 1 --grid 256 --rays 5e5 --cpu-sample 0 --other-steps 0
+run c5_2 --full --gpus 2 --workload c5 --grid 256 --rays 2e6 --chunk 5e5 --steps 1 --warmup 1
+run c5_3 --full --gpus 3 --workload c5 --grid 192 --rays 1e6 --chunk 2.5e5 --steps 1 --warmup 0
+run c5_2_stripes --full --gpus 2 --workload c5 --grid 256 --rays 2e6 --stripe-chunks --steps 1 --warmup 1   # chunks cut by position (plan_chunks(cut='stripe'))

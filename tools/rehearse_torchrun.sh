@@ -13,4 +13,4 @@ d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(d["n_gpus"], d["scaling"], "collective:", d.get("collective"), "| multi_gpu:", (d.get("check") or {}).get("multi_gpu"), "| timing:", d.get("timing", {}).get("per_rank_ms_for_the_steps"))
 PY
 }
-run host --rehearse-shared-gpu && run rccl --shared-gpu-rccl
+run host --full --rehearse-shared-gpu && run rccl --full --shared-gpu-rccl

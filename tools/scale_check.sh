@@ -13,7 +13,7 @@ out=gpurun_out/scale; mkdir -p $out
 run() {  # name, args...
   local name=$1; shift
   echo "== $name: python bench.py $*"
-  timeout -k 10 1500 python bench.py "$@" > $out/$name.json 2> $out/$name.err || { echo "$name FAILED (rc $?)"; tail -5 $out/$name.err; return; }
+  timeout -k 10 1500 python bench.py --full "$@" > $out/$name.json 2> $out/$name.err || { echo "$name FAILED (rc $?)"; tail -5 $out/$name.err; return; }
   python - $out/$name.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
