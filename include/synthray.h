@@ -230,7 +230,8 @@ int sr_rays_download_s0(const sr_rays *r, double *s0);            /* the bundle 
 /* Per ray (original order), a bound [rad] on how far the exit angles of the last trace may be from the SR_PREC_F64
  * build's: 0 for rays a float64 kernel wrote (SR_PREC_F64, the mixed build's second level, rays an exact-counts deposit
  * has traced again, SR_PREC_MIXED with sub-steps or optional terms: the float64 kernels ran), the mixed kernel's own estimate
- * otherwise (8 * 2^-24 * sum of |lateral velocity changes| / v_a).  Positions: the bound times the volume's length along the
+ * otherwise (8 * 2^-24 * [sum of |lateral velocity changes| + sum over node planes of h * largest |bilinear coefficient| / v_a]
+ * / v_a: trace_mx.inc).  Positions: the bound times the volume's length along the
  * probing axis plus the distance from its last node plane to the plane `extent`.  This is what sr_deposit_params.exact_counts
  * works from. */
 int sr_rays_error_bound(const sr_rays *r, float *bound);

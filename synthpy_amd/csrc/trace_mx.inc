@@ -34,15 +34,27 @@ __host__ __device__ inline size_t mixed_lds_bytes(int nb, int nc) { return sizeo
 //    (weight pinned inside [0, 1) by a reciprocal width of +-1e-30) and its field slopes are scaled by 0;
 //  * node plane k+2 is requested at the end of step k straight into the dead lower buffer, as raw corner records, and
 //    turned into coefficients in place after stage 1 of step k+1: nothing waits for it and it costs no register.
-//  * EDGE GUARD (deposit.hip): the kernel keeps, per ray, the sum of the absolute lateral velocity changes of its steps,
-//    E = |v_b| + |v_c| at entry + sum_k h_k/6 * (|K_b| + |K_c|)  (K = k1 + 2 k2 + 2 k3 + k4), two float32 instructions per
-//    step.  Every float32 quantity of a stage (cell offset, weights, blend, reciprocal, slopes) carries a relative
-//    rounding error of 2^-24 of a value that is bounded by the stage's own slope, so to first order the exit direction
-//    differs from the float64 build's by at most a small multiple of 2^-24 * E / v_a: the kernel writes
-//    guard = kGuardK * 2^-24 * E / v_a [rad] beside its outputs (kGuardK = 8; measured on the BASELINE workloads the
-//    largest |angle error| / guard is 0.2, tests/test_gpu_parity.py::test_edge_guard_bound_holds).  An exact-counts deposit
-//    re-traces in float64 every ray whose detector coordinate lies within that bound (times the chain's lever) of a bin
-//    edge or of an aperture's edge.
+//  * EDGE GUARD (deposit.hip): the kernel keeps, per ray, a sum E that bounds the float32 rounding of its lateral
+//    velocity changes, and writes guard = kGuardK * 2^-24 * E / v_a [rad] beside its outputs (kGuardK = 8).  Two kinds of
+//    rounding enter a stage's lateral slope F / v_a:
+//      - relative to the slope itself: the reciprocal 1/v_a, the products and the RK4 sums (and, through the position
+//        increments, the entry direction);
+//      - relative to the plane's bilinear COEFFICIENTS {A, B, C, D}: the blend A + w_b*B + w_c*(C + w_b*D) rounds each
+//        partial sum, and the float32 weights (cell offset, reciprocal width) carry 2^-24 of themselves into w*B, w*C,
+//        w*D.  Where the interpolated field crosses zero inside a cell, |F| is small and these are not; a ray that keeps
+//        its weights from plane to plane (a collimated beam on a field that does not vary along the probing axis) makes
+//        the same rounding at every step, so it adds up linearly.
+//    Hence E = |v_b| + |v_c| at entry + sum_k h_k/6 * (|K_b| + |K_c|)  (K = k1 + 2 k2 + 2 k3 + k4)
+//            + sum_k h_k/6 * (M_b + M_c) * (1/v_a + 2/v_a + 2/v_a + 1/v_a),  M = max(|A|, |B|, |C|, |D|) of d_b (d_c) on node
+//    plane k+1 of the ray's cell: each partial sum of the blend and each w*B, w*C, w*D is at most 2 M, so the blend rounds
+//    at a few 2^-24 M whatever |F|; every node plane is weighted 6/v_a once (the steps before and after it weigh it 3 + 3),
+//    read from the upper plane that the step holds in registers anyway (a few float32 instructions per step, no register;
+//    k_trace_mx +3 % on C2).  Measured largest |angle error| / guard: 0.04 on the BASELINE turbulence and 0.07 on the C1
+//    blob (tests/test_gpu_parity.py::test_edge_guard_bound_holds), 0.21 on collimated beams near the zero crossings of a
+//    field that varies along one lateral axis (tests/test_edge_guard.py), where the first two sums alone were exceeded up
+//    to 940-fold.  The price: refractometry traces 2.8 % / 4.0 % of the rays again on C2 / C4's share (was 0.9 % / 1.3 %).
+//    An exact-counts deposit re-traces in float64 every ray whose detector coordinate lies within that bound (times the
+//    chain's lever) of a bin edge or of an aperture's edge.
 typedef unsigned int u32;
 constexpr float kGuardK = 8.f * 5.9604644775390625e-8f;  // 8 * 2^-24
 
@@ -292,7 +304,11 @@ __global__ __launch_bounds__(256, SR_MX_WAVES) void k_trace_mx(TraceArgs A) {
       y4 = fma(S.h6, (double)abc.y, y4);
       if (PHASE) y5 = fma(S.h6w, (double)aan.y, y5);
       y6 = fma(S.h6, (double)at, y6);
+      // edge guard (header): the slopes' own size, then the scale the blend rounds at, the largest coefficient of plane k+1
       eacc += fabsf(abc.x) + fabsf(abc.y);
+      const float mb = fmaxf(fmaxf(fabsf(HI.A[0].x), fabsf(HI.B[0].x)), fmaxf(fabsf(HI.C[0].x), fabsf(HI.D[0].x)));
+      const float mc = fmaxf(fmaxf(fabsf(HI.A[0].y), fabsf(HI.B[0].y)), fmaxf(fabsf(HI.C[0].y), fabsf(HI.D[0].y)));
+      eacc = fmaf(mb + mc, at, eacc);
       if (!ok || !(y2 > 0)) alive = false;  // turned around: not a plane-form ray
       if (k + 2 < V.na) load_raw(k + 2, LO);  // node plane k+2 goes where the dead lower plane was, raw until used
     }
