@@ -133,9 +133,23 @@ void sr_volume_destroy(sr_volume *v);
 int sr_field_ifft_real(const double *noise, const float *amp, int n0, int n1, int n2, int normalise, double *out);
 /* ---- the step after the path: radially binned power spectrum of a detector image -----------
  * radial_2Dspectrum (src/utils/power_spectrum.py:372-421): |fft2(img)|^2/(n0*n1)^2 summed and counted over the
- * wavenumber bins [edges[b], edges[b+1]); k0 (n0), k1 (n1): wavenumber of each index of the unshifted transform. */
+ * wavenumber bins [edges[b], edges[b+1]); k0 (n0), k1 (n1): wavenumber of each index of the unshifted transform.
+ * The 2-D case of sr_power_spectrum's edges rule. */
 int sr_radial_spectrum2d(const double *img, int n0, int n1, const double *k0, const double *k1,
                          const double *edges, int n_edges, double *sum, uint64_t *count);
+/* The power spectra of src/utils/power_spectrum.py (radial_*Dspectrum, scalar*D_fft, scalar*D_knyquist): one forward
+ * Z2Z transform of a float64 field of ndim = 1, 2 or 3 axes (shape[ndim], C order; hipFFT, cached plan) and one pass
+ * that bins every mode.  coords holds shape[0] + ... + shape[ndim-1] values: per axis, the coordinate of each index of
+ * the UNSHIFTED transform; a NaN coordinate drops the mode.  Mode (i, j, l) has m = sqrt((a0[i]^2 + a1[j]^2) + a2[l]^2),
+ * rounded as numpy rounds that expression, and power p = (re^2 + im^2) / norm.  rule:
+ *   SR_SPECTRUM_EDGES: edges (n_bins + 1, ascending); sum[b], count[b] over edges[b] <= m < edges[b+1];
+ *   SR_SPECTRUM_SHELL: edges unused; sum[k], count[k] over the shells rint(m) = k < n_bins; *overflow (may be NULL)
+ *                      = the number of modes whose shell is >= n_bins (0 under the edges rule).
+ * sum and count hold n_bins values; the caller divides (an empty bin is NaN there, as np.mean of nothing). */
+#define SR_SPECTRUM_EDGES 0
+#define SR_SPECTRUM_SHELL 1
+int sr_power_spectrum(const double *field, int ndim, const int64_t *shape, const double *coords, int rule,
+                      const double *edges, int n_bins, double norm, double *sum, uint64_t *count, uint64_t *overflow);
 
 /* ---- A2 + A3 + A4 + A6: ScalarDomain.solve / propagator.solve -----------------
  * replaces full_solver.py:376-403 (solve), :516-544 (dsdt), :317-347 (dndr, phase: the

@@ -17,6 +17,7 @@ struct Fft {
   void *h = nullptr;
   hipfftResult (*Plan3d)(hipfftHandle *, int, int, int, hipfftType) = nullptr;
   hipfftResult (*Plan2d)(hipfftHandle *, int, int, hipfftType) = nullptr;
+  hipfftResult (*Plan1d)(hipfftHandle *, int, hipfftType, int) = nullptr;
   hipfftResult (*SetStream)(hipfftHandle, hipStream_t) = nullptr;
   hipfftResult (*ExecZ2Z)(hipfftHandle, hipfftDoubleComplex *, hipfftDoubleComplex *, int) = nullptr;
   hipfftResult (*Destroy)(hipfftHandle) = nullptr;
@@ -36,6 +37,7 @@ int fft_lib(Fft **out) {
   if (!F.field) return sr::fail(SR_ERR_HIP, "libhipfft.so lacks symbol %s", name);
     SR_SYM(Plan3d, "hipfftPlan3d")
     SR_SYM(Plan2d, "hipfftPlan2d")
+    SR_SYM(Plan1d, "hipfftPlan1d")
     SR_SYM(SetStream, "hipfftSetStream")
     SR_SYM(ExecZ2Z, "hipfftExecZ2Z")
     SR_SYM(Destroy, "hipfftDestroy")
@@ -46,15 +48,17 @@ int fft_lib(Fft **out) {
 }
 
 // Plans are kept for the life of the process: creating one costs 1-2 s (rocFFT builds its kernels at run time), using
-// it milliseconds.  Key: (n0, n1, n2) with n2 = 0 for a 2-D plan.
-int fft_plan(Fft *F, int n0, int n1, int n2, hipfftHandle *out) {
-  static std::map<std::tuple<int, int, int>, hipfftHandle> cache;
-  const auto key = std::make_tuple(n0, n1, n2);
+// it milliseconds.  Key: (rank, n0, n1, n2), the sizes past the rank 0.
+int fft_plan(Fft *F, int rank, int n0, int n1, int n2, hipfftHandle *out) {
+  static std::map<std::tuple<int, int, int, int>, hipfftHandle> cache;
+  const auto key = std::make_tuple(rank, n0, rank > 1 ? n1 : 0, rank > 2 ? n2 : 0);
   auto it = cache.find(key);
   if (it == cache.end()) {
     hipfftHandle plan = nullptr;
-    const hipfftResult r = n2 > 0 ? F->Plan3d(&plan, n0, n1, n2, HIPFFT_Z2Z) : F->Plan2d(&plan, n0, n1, HIPFFT_Z2Z);
-    if (r != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "hipfftPlan%dd(%d, %d, %d) failed: hipfftResult %d", n2 > 0 ? 3 : 2, n0, n1, n2, (int)r);
+    const hipfftResult r = rank == 3   ? F->Plan3d(&plan, n0, n1, n2, HIPFFT_Z2Z)
+                           : rank == 2 ? F->Plan2d(&plan, n0, n1, HIPFFT_Z2Z)
+                                       : F->Plan1d(&plan, n0, HIPFFT_Z2Z, 1);
+    if (r != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "hipfftPlan%dd(%d, %d, %d) failed: hipfftResult %d", rank, n0, n1, n2, (int)r);
     it = cache.emplace(key, plan).first;
   }
   *out = it->second;
@@ -98,69 +102,89 @@ __global__ void k_to_complex(const double *__restrict__ r, int64_t n, double2 *_
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) w[i] = make_double2(r[i], 0.0);
 }
 
-// |F|^2 / (n0*n1)^2 summed and counted per radial bin [edges[b], edges[b+1])  (power_spectrum.py:395-413)
-__global__ void k_radial_bins(const double2 *__restrict__ F, int n0, int n1, const double *__restrict__ k0,
-                              const double *__restrict__ k1, const double *__restrict__ edges, int n_edges, double norm,
-                              double *__restrict__ sum, unsigned long long *__restrict__ cnt) {
-  // the bins are few (99 in the reference's call): per-workgroup sums in LDS, one global atomic per bin and workgroup
-  constexpr int kMaxBins = 512;
-  __shared__ double lsum[kMaxBins];
-  __shared__ unsigned long long lcnt[kMaxBins];
-  const bool in_lds = n_edges - 1 <= kMaxBins;
-  for (int t = threadIdx.x; t < kMaxBins; t += blockDim.x) {
-    lsum[t] = 0.0;
-    lcnt[t] = 0ull;
-  }
+// The power spectrum's one binning pass (power_spectrum.py: radial_*Dspectrum, scalar*D_fft, scalar*D_knyquist).
+// Mode (i, j, l) of an (n0, n1, n2) transform (C order, n2 fastest; n1 = n2 = 1 in 1-D) has the magnitude
+// m = sqrt((a0[i]^2 + a1[j]^2) + a2[l]^2), grouped as numpy's (KX**2 + KY**2) + KZ**2 and, the library being built with
+// -ffp-contract=off, rounded as numpy rounds it (sqrt is correctly rounded): bin membership is numpy's, bit for bit.
+// A NaN coordinate drops the mode.  p = (re^2 + im^2) / norm is summed and counted per bin:
+//   SR_SPECTRUM_EDGES: bin b holds edges[b] <= m < edges[b+1] (binary search over the n_bins+1 ascending edges);
+//   SR_SPECTRUM_SHELL: bin rint(m) (the reference's int(np.round(rk))); a shell >= n_bins is counted in *over.
+// Bins go to per-workgroup copies in LDS when they fit (lds != 0), else straight to the global atomics.
+constexpr int kMaxLdsBins = 2048;  // 32 KiB of sums and counts per workgroup
+
+template <int RULE>
+__global__ void k_spectrum_bins(const double2 *__restrict__ F, int64_t n, int64_t n1, int64_t n2,
+                                const double *__restrict__ a0, const double *__restrict__ a1,
+                                const double *__restrict__ a2, const double *__restrict__ edges, int n_bins,
+                                double norm, int lds, double *__restrict__ sum, unsigned long long *__restrict__ cnt,
+                                unsigned long long *__restrict__ over) {
+  extern __shared__ double lds_bins[];  // [n_bins] sums, then [n_bins] counts
+  double *lsum = lds_bins;
+  unsigned long long *lcnt = reinterpret_cast<unsigned long long *>(lds_bins + (lds ? n_bins : 0));
+  if (lds)
+    for (int t = threadIdx.x; t < n_bins; t += blockDim.x) {
+      lsum[t] = 0.0;
+      lcnt[t] = 0ull;
+    }
   __syncthreads();
-  const int64_t n = (int64_t)n0 * n1;
+  unsigned long long n_over = 0;
   for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(q / n1), j = (int)(q % n1);
-    const double k = sqrt(k0[i] * k0[i] + k1[j] * k1[j]);
-    if (!(k >= edges[0] && k < edges[n_edges - 1])) continue;
-    int lo = 0, hi = n_edges - 1;  // edges[lo] <= k < edges[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (k < edges[mid])
-        hi = mid;
-      else
-        lo = mid;
+    const int64_t l = q % n2, r = q / n2;
+    const int64_t j = r % n1, i = r / n1;
+    const double x = a0[i], y = a1[j], z = a2[l];
+    const double m = sqrt((x * x + y * y) + z * z);
+    int b;
+    if (RULE == SR_SPECTRUM_EDGES) {
+      if (!(m >= edges[0] && m < edges[n_bins])) continue;  // NaN fails both
+      int lo = 0, hi = n_bins;  // edges[lo] <= m < edges[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (m < edges[mid])
+          hi = mid;
+        else
+          lo = mid;
+      }
+      b = lo;
+    } else {
+      if (m != m) continue;
+      const double s = rint(m);  // round half to even, as np.round; m is the sqrt of an integer, so never a tie
+      if (s >= (double)n_bins) {
+        ++n_over;
+        continue;
+      }
+      b = (int)s;
     }
     const double2 v = F[q];
-    const double pw = (v.x * v.x + v.y * v.y) / norm;
-    if (in_lds) {
-      atomicAdd(&lsum[lo], pw);
-      atomicAdd(&lcnt[lo], 1ull);
+    const double p = (v.x * v.x + v.y * v.y) / norm;
+    if (lds) {
+      atomicAdd(&lsum[b], p);
+      atomicAdd(&lcnt[b], 1ull);
     } else {
-      atomicAdd(&sum[lo], pw);
-      atomicAdd(&cnt[lo], 1ull);
+      atomicAdd(&sum[b], p);
+      atomicAdd(&cnt[b], 1ull);
     }
   }
+  if (RULE == SR_SPECTRUM_SHELL && n_over) atomicAdd(over, n_over);  // an error case: rare, one add per thread at most
   __syncthreads();
-  if (in_lds)
-    for (int t = threadIdx.x; t < n_edges - 1; t += blockDim.x)
+  if (lds)
+    for (int t = threadIdx.x; t < n_bins; t += blockDim.x)
       if (lcnt[t]) {
         atomicAdd(&sum[t], lsum[t]);
         atomicAdd(&cnt[t], lcnt[t]);
       }
 }
 
-}  // namespace
-
-// After the path: radially binned 2-D power spectrum of a detector image (radial_2Dspectrum,
-// src/utils/power_spectrum.py:372-421): |fft2(img)|^2/(n0*n1)^2 averaged over the wavenumber bins [edges[b], edges[b+1]).
-// k0 (n0) and k1 (n1) give the wavenumber of every index of the UNSHIFTED transform along each axis; sum and count
-// (n_edges-1 each) come back, the caller divides (an empty bin is NaN there, as np.mean of nothing).
-extern "C" int sr_radial_spectrum2d(const double *img, int n0, int n1, const double *k0, const double *k1,
-                                    const double *edges, int n_edges, double *sum, uint64_t *count) {
-  SR_CHECK(img && k0 && k1 && edges && sum && count, "sr_radial_spectrum2d: NULL argument");
-  SR_CHECK(n0 > 0 && n1 > 0 && n_edges >= 2, "sr_radial_spectrum2d: bad sizes");
+// One transform + one binning pass; axis[d] (n[d] values, host) are the coordinates of the unshifted indices of axis d.
+int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[3], const double *const axis[3], int rule,
+                const double *edges, int n_bins, double norm, double *sum, uint64_t *count, uint64_t *over) {
   int rc = sr::ensure_init();
   if (rc) return rc;
   Fft *F;
   if ((rc = fft_lib(&F))) return rc;
   hipStream_t st = sr::ctx().stream;
-  const int64_t n = (int64_t)n0 * n1;
-  const int nb = n_edges - 1;
+  const int64_t nn = n[0] * n[1] * n[2];
+  const int64_t n_axes = n[0] + n[1] + n[2];
+  const int n_edges = rule == SR_SPECTRUM_EDGES ? n_bins + 1 : 0;
   double *d_r = nullptr, *d_k = nullptr, *d_sum = nullptr;
   double2 *d_w = nullptr;
   unsigned long long *d_cnt = nullptr;
@@ -172,25 +196,26 @@ extern "C" int sr_radial_spectrum2d(const double *img, int n0, int n1, const dou
     sr::dev_free(d_w);
     sr::dev_free(d_cnt);
   };
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_r), sizeof(double) * n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_w), sizeof(double2) * n);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_k), sizeof(double) * (size_t)(n0 + n1 + n_edges));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_sum), sizeof(double) * nb);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long) * nb);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_r, img, sizeof(double) * n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_k, k0, sizeof(double) * n0, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_k + n0, k1, sizeof(double) * n1, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_k + n0 + n1, edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_sum, 0, sizeof(double) * nb, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * nb, st);
+  // d_k: the axes' coordinates, then the edges; d_cnt: n_bins counts, then the overflow count
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_r), sizeof(double) * nn);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_w), sizeof(double2) * nn);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_k), sizeof(double) * (size_t)(n_axes + n_edges));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_sum), sizeof(double) * n_bins);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long) * (n_bins + 1));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_r, field, sizeof(double) * nn, hipMemcpyHostToDevice, st);
+  for (int d = 0; d < 3 && e == hipSuccess; ++d)
+    e = hipMemcpyAsync(d_k + (d > 0 ? n[0] : 0) + (d > 1 ? n[1] : 0), axis[d], sizeof(double) * n[d], hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_k + n_axes, edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_sum, 0, sizeof(double) * n_bins, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * (n_bins + 1), st);
   if (e != hipSuccess) {
     cleanup();
-    return sr::fail(SR_ERR_HIP, "sr_radial_spectrum2d: %s", hipGetErrorString(e));
+    return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   const int block = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
-  hipLaunchKernelGGL(k_to_complex, dim3(grid), dim3(block), 0, st, (const double *)d_r, n, d_w);
-  if ((rc = fft_plan(F, n0, n1, 0, &plan))) {
+  const unsigned grid = (unsigned)std::min<int64_t>((nn + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+  hipLaunchKernelGGL(k_to_complex, dim3(grid), dim3(block), 0, st, (const double *)d_r, nn, d_w);
+  if ((rc = fft_plan(F, ndim, (int)n[0], (int)n[1], (int)n[2], &plan))) {
     cleanup();
     return rc;
   }
@@ -198,19 +223,67 @@ extern "C" int sr_radial_spectrum2d(const double *img, int n0, int n1, const dou
   if (fr == HIPFFT_SUCCESS) fr = F->ExecZ2Z(plan, d_w, d_w, HIPFFT_FORWARD);
   if (fr != HIPFFT_SUCCESS) {
     cleanup();
-    return sr::fail(SR_ERR_HIP, "sr_radial_spectrum2d: hipfftResult %d", (int)fr);
+    return sr::fail(SR_ERR_HIP, "%s: hipfftResult %d", who, (int)fr);
   }
-  const double nn = (double)n0 * (double)n1;
-  const unsigned bgrid = std::min<unsigned>(grid, (unsigned)sr::ctx().n_cu * 4);
-  hipLaunchKernelGGL(k_radial_bins, dim3(bgrid), dim3(block), 0, st, (const double2 *)d_w, n0, n1, (const double *)d_k,
-                     (const double *)(d_k + n0), (const double *)(d_k + n0 + n1), n_edges, nn * nn, d_sum, d_cnt);
+  const int lds = n_bins <= kMaxLdsBins;
+  const size_t lds_bytes = lds ? (sizeof(double) + sizeof(unsigned long long)) * (size_t)n_bins : 0;
+  const unsigned bgrid = std::min<unsigned>(grid, (unsigned)sr::ctx().n_cu * 8);
+  const double *k0 = d_k, *k1 = d_k + n[0], *k2 = d_k + n[0] + n[1];
+  if (rule == SR_SPECTRUM_EDGES)
+    hipLaunchKernelGGL(k_spectrum_bins<SR_SPECTRUM_EDGES>, dim3(bgrid), dim3(block), lds_bytes, st, (const double2 *)d_w, nn,
+                       n[1], n[2], k0, k1, k2, (const double *)(d_k + n_axes), n_bins, norm, lds, d_sum, d_cnt,
+                       d_cnt + n_bins);
+  else
+    hipLaunchKernelGGL(k_spectrum_bins<SR_SPECTRUM_SHELL>, dim3(bgrid), dim3(block), lds_bytes, st, (const double2 *)d_w, nn,
+                       n[1], n[2], k0, k1, k2, (const double *)nullptr, n_bins, norm, lds, d_sum, d_cnt, d_cnt + n_bins);
+  uint64_t n_over = 0;
   e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(sum, d_sum, sizeof(double) * nb, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(count, d_cnt, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(sum, d_sum, sizeof(double) * n_bins, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(count, d_cnt, sizeof(uint64_t) * n_bins, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&n_over, d_cnt + n_bins, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   cleanup();
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_radial_spectrum2d: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  if (over) *over = n_over;
   return SR_OK;
+}
+
+}  // namespace
+
+extern "C" int sr_power_spectrum(const double *field, int ndim, const int64_t *shape, const double *coords, int rule,
+                                 const double *edges, int n_bins, double norm, double *sum, uint64_t *count,
+                                 uint64_t *overflow) {
+  SR_CHECK(field && shape && coords && sum && count, "sr_power_spectrum: NULL argument");
+  SR_CHECK(ndim >= 1 && ndim <= 3, "sr_power_spectrum: ndim %d (1, 2 or 3)", ndim);
+  SR_CHECK(rule == SR_SPECTRUM_EDGES || rule == SR_SPECTRUM_SHELL, "sr_power_spectrum: unknown rule %d", rule);
+  SR_CHECK(rule == SR_SPECTRUM_SHELL || edges, "sr_power_spectrum: the edges rule needs edges");
+  SR_CHECK(n_bins >= 1, "sr_power_spectrum: n_bins %d", n_bins);
+  static const double zero = 0.0;  // the coordinate of the one index of an axis past ndim
+  int64_t n[3] = {1, 1, 1};
+  const double *axis[3] = {&zero, &zero, &zero};
+  int64_t off = 0;
+  for (int d = 0; d < ndim; ++d) {
+    SR_CHECK(shape[d] >= 1 && shape[d] <= INT32_MAX, "sr_power_spectrum: bad size %lld of axis %d", (long long)shape[d], d);
+    n[d] = shape[d];
+    axis[d] = coords + off;
+    off += shape[d];
+  }
+  return spectrum_nd("sr_power_spectrum", field, ndim, n, axis, rule, edges, n_bins, norm, sum, count, overflow);
+}
+
+// After the path: radially binned 2-D power spectrum of a detector image (radial_2Dspectrum,
+// src/utils/power_spectrum.py:372-421): |fft2(img)|^2/(n0*n1)^2 summed and counted over the wavenumber bins
+// [edges[b], edges[b+1]), the N-D path's edges rule.
+extern "C" int sr_radial_spectrum2d(const double *img, int n0, int n1, const double *k0, const double *k1,
+                                    const double *edges, int n_edges, double *sum, uint64_t *count) {
+  SR_CHECK(img && k0 && k1 && edges && sum && count, "sr_radial_spectrum2d: NULL argument");
+  SR_CHECK(n0 > 0 && n1 > 0 && n_edges >= 2, "sr_radial_spectrum2d: bad sizes");
+  static const double zero = 0.0;
+  const int64_t n[3] = {n0, n1, 1};
+  const double *axis[3] = {k0, k1, &zero};
+  const double nn = (double)n0 * (double)n1;
+  return spectrum_nd("sr_radial_spectrum2d", img, 2, n, axis, SR_SPECTRUM_EDGES, edges, n_edges - 1, nn * nn, sum, count,
+                     nullptr);
 }
 
 extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0, int n1, int n2, int normalise, double *out) {
@@ -259,7 +332,7 @@ extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0,
   const unsigned grid = (unsigned)std::min<int64_t>((n + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
   hipLaunchKernelGGL(k_shape_noise, dim3(grid), dim3(block), 0, st, d_w, (const float *)d_a, n);
   SR_TRY(hipGetLastError());
-  if ((rc = fft_plan(F, n0, n1, n2, &plan))) {  // C order: n2 fastest, as the NumPy array
+  if ((rc = fft_plan(F, 3, n0, n1, n2, &plan))) {  // C order: n2 fastest, as the NumPy array
     cleanup();
     return rc;
   }
