@@ -131,6 +131,14 @@ void sr_volume_destroy(sr_volume *v);
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))
  * float32, out float64; C order.  3-D inverse FFT by hipFFT (bound at first use). */
 int sr_field_ifft_real(const double *noise, const float *amp, int n0, int n1, int n2, int normalise, double *out);
+/* gaussian1D/2D/3D.cos (src/field_generator/gaussian{1,2,3}D.py): for every cell (i, j, l) of shape[ndim] (C order),
+ *   out = sum_m amp[m] * sum_s cos(k[0][m]*x0[i] + sg1(s)*k[1][m]*x1[j] + sg2(s)*k[2][m]*x2[l] + phase[s][m]),
+ * s over the reference's 2^(ndim-1) terms in its order (3-D: ++, +-, -+, -- with psi_1..psi_4; 2-D: +phi, -psi;
+ * 1-D: +phi).  coords: per axis, the cell centres (shape[0] + ... + shape[ndim-1] values); k: ndim x nmodes;
+ * amp: nmodes (A_m*sqrt(2)); phase: 2^(ndim-1) x nmodes.  float64 throughout; the sum over modes is in a fixed order,
+ * so a repeated call returns the identical field.  Arguments are checked before the device is touched. */
+int sr_field_modesum(int ndim, const int64_t *shape, const double *coords, int nmodes, const double *k,
+                     const double *amp, const double *phase, double *out);
 /* ---- the step after the path: radially binned power spectrum of a detector image -----------
  * radial_2Dspectrum (src/utils/power_spectrum.py:372-421): |fft2(img)|^2/(n0*n1)^2 summed and counted over the
  * wavenumber bins [edges[b], edges[b+1]); k0 (n0), k1 (n1): wavenumber of each index of the unshifted transform.

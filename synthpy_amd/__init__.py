@@ -6,7 +6,8 @@ kernels (synthpy_amd/csrc) through the C ABI in include/synthray.h:
     synthpy_amd.solvers_legacy.full_solver   ScalarDomain(x, y, z, extent) / init_beam / solve
     synthpy_amd.solvers_legacy.rtm_solver    Shadowgraphy / Schlieren / Refractometry / Interferometry
     synthpy_amd.simulator.{domain,beam,propagator,diagnostics}   the JAX-generation surface
-    synthpy_amd.field_generator.gaussian3D   benchmark volumes (host NumPy, an input of the path)
+    synthpy_amd.field_generator.gaussian{1,2,3}D   field generators (host NumPy, seeded as the reference; cos and
+                                             gaussian3D.domain_fft take device=True: the sum / inverse FFT on the GPU)
     synthpy_amd.engine                       device volumes, ray bundles, detector images
     synthpy_amd.distributed                  ray sharding over GPUs + the image sum
 

@@ -1,4 +1,5 @@
-// The step before the path: volume synthesis (gaussian3D.domain_fft, src/field_generator/gaussian3D.py:215-271).
+// The step before the path: volume synthesis (gaussian3D.domain_fft, src/field_generator/gaussian3D.py:215-271; the cosine
+// mode sum of gaussian{1,2,3}D.cos, sr_field_modesum at the end of this file).
 // The reference shapes complex Gaussian noise with sqrt(S(k)) and takes np.fft.ifftn(...).real / max|.| on the host
 // (15 s of the 25 s a 512^3 volume takes there).  Here the noise and the float32 amplitude sqrt(S) arrive from the
 // host (the noise must come from the caller's seeded np.random stream to reproduce the reference's field), the
@@ -6,8 +7,10 @@
 #include <dlfcn.h>
 #include <hipfft/hipfft.h>
 
+#include <algorithm>
 #include <map>
 #include <tuple>
+#include <vector>
 
 #include "common.hpp"
 
@@ -248,6 +251,136 @@ int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[
   return SR_OK;
 }
 
+// ---- gaussian{1,2,3}D.cos (src/field_generator/gaussian{1,2,3}D.py): the cosine mode sum -------------------------------
+// The reference evaluates amp_m * cos(kx x + ky y + kz z + psi_s) for every cell, mode and term: ~4 float64 cosines per
+// point-mode.  Here the cosines are factored into phasors per axis.  On the kernel's axes (a0, a1, a2) = (i, j, l), l
+// fastest in `out`, with X[i,m] = amp_m e^{i k0 x0_i}, Y[j,m] = e^{i k1 x1_j}, Z[l,m] = e^{i k2 x2_l}, P_s = e^{i psi_s}:
+//   Zp = Z P1 + conj(Z) P2,  Zm = Z P3 + conj(Z) P4,  S = Zp + Zm,  D = Zp - Zm
+//   G = Y Zp + conj(Y) Zm:   G.re = Y.re S.re - Y.im D.im,   G.im = Y.re S.im + Y.im D.re
+//   out[i,j,l] = sum_m Re(X G) = sum_m X.re G.re - X.im G.im
+// which is the reference's sum of the four terms (++ P1, +- P2, -+ P3, -- P4).  A problem of fewer axes keeps its last axis
+// on a2 (the lanes) and gives the missing ones one cell at coordinate 0 with k = 0 (e^{i0} = 1 exactly):
+//   3-D (x, y, z): P1..P4 = psi_1..psi_4;   2-D (x, -, y): P1 = phi (+ky), P2 = psi (-ky);   1-D (-, -, x): P1 = phi;
+// an absent P_s is 0.  float64 throughout (arguments reach ~pi n rad).
+//
+// k_modesum_tables: the per-axis tables, mode-major ([m][index]) so that a wave's per-lane S, D loads are coalesced and a
+// tile's rows of X and Y are consecutive.  X and Y are padded to p0 >= n0 and p1 >= n1 rows (whole tiles; a padding row
+// repeats the last cell, and what it adds is never stored), so the main kernel reads them without clamping.  One float64
+// sincos per table value: (p0 + p1 + n2) M of them.
+__global__ void k_modesum_tables(const double *__restrict__ c, const double *__restrict__ k, const double *__restrict__ amp,
+                                 const double *__restrict__ ph, int pmask, int M, int64_t n0, int64_t n1, int64_t n2,
+                                 int64_t p0, int64_t p1, double2 *__restrict__ X, double2 *__restrict__ Y,
+                                 double2 *__restrict__ S, double2 *__restrict__ D) {
+  const int64_t nx = p0 * M, ny = p1 * M, n = (p0 + p1 + n2) * M;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+    double sn, cs;
+    if (q < nx) {
+      const int64_t m = q / p0, i = q - m * p0;
+      sincos(k[m] * c[i < n0 ? i : n0 - 1], &sn, &cs);
+      X[q] = make_double2(amp[m] * cs, amp[m] * sn);
+    } else if (q < nx + ny) {
+      const int64_t r = q - nx, m = r / p1, j = r - m * p1;
+      sincos(k[M + m] * c[n0 + (j < n1 ? j : n1 - 1)], &sn, &cs);
+      Y[r] = make_double2(cs, sn);
+    } else {
+      const int64_t r = q - nx - ny, m = r / n2, l = r - m * n2;
+      sincos(k[2 * M + m] * c[n0 + n1 + l], &sn, &cs);
+      double2 p[4];
+      for (int s = 0; s < 4; ++s) {
+        p[s] = make_double2(0.0, 0.0);
+        if (pmask >> s & 1) sincos(ph[s * M + m], &p[s].y, &p[s].x);
+      }
+      // Z P = (cs + i sn) P,  conj(Z) P = (cs - i sn) P
+      const double zp_re = (cs * p[0].x - sn * p[0].y) + (cs * p[1].x + sn * p[1].y);
+      const double zp_im = (cs * p[0].y + sn * p[0].x) + (cs * p[1].y - sn * p[1].x);
+      const double zm_re = (cs * p[2].x - sn * p[2].y) + (cs * p[3].x + sn * p[3].y);
+      const double zm_im = (cs * p[2].y + sn * p[2].x) + (cs * p[3].y - sn * p[3].x);
+      S[r] = make_double2(zp_re + zm_re, zp_im + zm_im);
+      D[r] = make_double2(zp_re - zm_re, zp_im - zm_im);
+    }
+  }
+}
+
+// k_modesum: a wave owns a tile of T rows i x JT rows j x 64 lanes l.  Per mode it loads S, D for its lane (coalesced, one
+// mode ahead), the tile's T values of X and JT of Y (wave-uniform: scalar loads), forms G once per (j, l) in registers and
+// adds it into T x JT accumulators: 4 JT + 2 T JT float64 FMA-class operations per mode for T JT points.  Modes are summed
+// in order, one accumulator per point, no atomics: a repeated call returns the identical field.  A lane past n2 reads the
+// last column and stores nothing; rows past n0, n1 are the tables' padding and are not stored.
+constexpr int kModesumBlock = 256;  // 4 waves, each its own tile
+
+template <int T, int JT>
+__global__ __launch_bounds__(kModesumBlock) void k_modesum(const double2 *__restrict__ X, const double2 *__restrict__ Y,
+                                                           const double2 *__restrict__ S, const double2 *__restrict__ D,
+                                                           int M, int64_t n0, int64_t n1, int64_t n2, int64_t p0, int64_t p1,
+                                                           int64_t tiles_l, int64_t n_tiles, double *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t waves = kModesumBlock / 64;
+  const int64_t wave = (int64_t)blockIdx.x * waves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t tiles_j = p1 / JT;
+  for (int64_t w = wave; w < n_tiles; w += (int64_t)gridDim.x * waves) {
+    const int64_t r = w / tiles_l;
+    const int64_t l = (w - r * tiles_l) * 64 + lane, j0 = (r % tiles_j) * JT, i0 = (r / tiles_j) * T;
+    const int64_t lc = l < n2 ? l : n2 - 1;
+    double acc[T][JT];
+    for (int t = 0; t < T; ++t)
+      for (int u = 0; u < JT; ++u) acc[t][u] = 0.0;
+    const double2 *xs = X + i0, *ys = Y + j0, *ss = S + lc, *ds = D + lc;
+    double2 s_next = *ss, d_next = *ds;
+    for (int m = 0; m < M; ++m) {
+      const double2 s = s_next, d = d_next;
+      if (m + 1 < M) {  // the next mode's S, D in flight during this mode's arithmetic
+        ss += n2;
+        ds += n2;
+        s_next = *ss;
+        d_next = *ds;
+      }
+      double gr[JT], gi[JT];
+#pragma unroll
+      for (int u = 0; u < JT; ++u) {
+        const double2 y = ys[u];
+        gr[u] = fma(-y.y, d.y, y.x * s.x);
+        gi[u] = fma(y.y, d.x, y.x * s.y);
+      }
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const double2 x = xs[t];
+#pragma unroll
+        for (int u = 0; u < JT; ++u) acc[t][u] = fma(-x.y, gi[u], fma(x.x, gr[u], acc[t][u]));
+      }
+      xs += p0;
+      ys += p1;
+    }
+    if (l < n2)
+      for (int t = 0; t < T; ++t)
+        for (int u = 0; u < JT; ++u)
+          if (i0 + t < n0 && j0 + u < n1) out[((i0 + t) * n1 + (j0 + u)) * n2 + l] = acc[t][u];
+  }
+}
+
+// The tables for a T x JT tile (padded rows p0, p1), then the sum.  Returns the HIP error of the launches.
+template <int T, int JT>
+hipError_t run_modesum(const double *d_in, int pmask, int M, const int64_t n[3], double2 *d_tab, double *out, hipStream_t st) {
+  const int64_t p0 = (n[0] + T - 1) / T * T, p1 = (n[1] + JT - 1) / JT * JT, n_axes = n[0] + n[1] + n[2];
+  double2 *X = d_tab, *Y = X + p0 * M, *S = Y + p1 * M, *D = S + n[2] * M;
+  const int block = 256;
+  const int64_t n_tab = (p0 + p1 + n[2]) * M;
+  const unsigned tgrid = (unsigned)std::min<int64_t>((n_tab + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+  hipLaunchKernelGGL(k_modesum_tables, dim3(tgrid), dim3(block), 0, st, d_in, d_in + n_axes, d_in + n_axes + 3 * M,
+                     d_in + n_axes + 4 * M, pmask, M, n[0], n[1], n[2], p0, p1, X, Y, S, D);
+  const int64_t tiles_l = (n[2] + 63) / 64, n_tiles = tiles_l * (p1 / JT) * (p0 / T);
+  const int64_t waves = kModesumBlock / 64;
+  const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + waves - 1) / waves, (int64_t)sr::ctx().n_cu * 64);
+  hipLaunchKernelGGL((k_modesum<T, JT>), dim3(grid), dim3(kModesumBlock), 0, st, (const double2 *)X, (const double2 *)Y,
+                     (const double2 *)S, (const double2 *)D, M, n[0], n[1], n[2], p0, p1, tiles_l, n_tiles, out);
+  return hipGetLastError();
+}
+
+// table bytes of a T x JT tile
+template <int T, int JT>
+size_t modesum_table_bytes(int64_t M, const int64_t n[3]) {
+  return sizeof(double2) * (size_t)(((n[0] + T - 1) / T * T + (n[1] + JT - 1) / JT * JT + 2 * n[2]) * M);
+}
+
 }  // namespace
 
 extern "C" int sr_power_spectrum(const double *field, int ndim, const int64_t *shape, const double *coords, int rule,
@@ -349,5 +482,64 @@ extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0,
 #undef SR_TRY
 #undef SR_TRY_FFT
   cleanup();
+  return SR_OK;
+}
+
+extern "C" int sr_field_modesum(int ndim, const int64_t *shape, const double *coords, int nmodes, const double *k,
+                                const double *amp, const double *phase, double *out) {
+  SR_CHECK(shape && coords && k && amp && phase && out, "sr_field_modesum: NULL argument");
+  SR_CHECK(ndim >= 1 && ndim <= 3, "sr_field_modesum: ndim %d (1, 2 or 3)", ndim);
+  SR_CHECK(nmodes >= 1, "sr_field_modesum: nmodes %d (>= 1)", nmodes);
+  for (int d = 0; d < ndim; ++d)
+    SR_CHECK(shape[d] >= 1 && shape[d] <= INT32_MAX, "sr_field_modesum: bad size %lld of axis %d", (long long)shape[d], d);
+  // the problem's axes on the kernel's (a0, a1, a2): the last axis on a2; 2-D leaves a1, 1-D a0 and a1 at one cell
+  static const int kAxis[3][3] = {{2, -1, -1}, {0, 2, -1}, {0, 1, 2}};
+  static const int kPmask[3] = {0x1, 0x3, 0xf};  // P1; P1, P2; P1..P4
+  const int64_t M = nmodes;
+  int64_t n[3] = {1, 1, 1}, cpos[3] = {0, 0, 0};
+  int64_t off = 0;
+  for (int d = 0; d < ndim; ++d) {
+    n[kAxis[ndim - 1][d]] = shape[d];
+    cpos[d] = off;
+    off += shape[d];
+  }
+  SR_CHECK(n[0] * n[1] <= INT64_MAX / n[2], "sr_field_modesum: field too large");
+  const int64_t n_cells = n[0] * n[1] * n[2], n_axes = n[0] + n[1] + n[2];
+  // staging: [coords on a0, a1, a2 (n_axes) | k on a0, a1, a2 (3 M) | amp (M) | P1..P4 (4 M)]; missing entries 0
+  std::vector<double> h((size_t)(n_axes + 8 * M), 0.0);
+  for (int d = 0; d < ndim; ++d) {
+    const int a = kAxis[ndim - 1][d];
+    const int64_t dst = (a > 0 ? n[0] : 0) + (a > 1 ? n[1] : 0);
+    std::copy(coords + cpos[d], coords + cpos[d] + shape[d], h.begin() + dst);
+    std::copy(k + d * M, k + (d + 1) * M, h.begin() + n_axes + a * M);
+  }
+  std::copy(amp, amp + M, h.begin() + n_axes + 3 * M);
+  std::copy(phase, phase + ((int64_t)1 << (ndim - 1)) * M, h.begin() + n_axes + 4 * M);
+  int rc = sr::ensure_init();
+  if (rc) return rc;
+  hipStream_t st = sr::ctx().stream;
+  double *d_in = nullptr, *d_out = nullptr;
+  double2 *d_tab = nullptr;
+  auto cleanup = [&]() {
+    sr::dev_free(d_in);
+    sr::dev_free(d_out);
+    sr::dev_free(d_tab);
+  };
+  const bool tile_j = n[1] > 1;  // 3-D: G is reused over T = 8 rows i and formed for 4 rows j; Y == 1: 16 rows i
+  const size_t tab_bytes = tile_j ? modesum_table_bytes<8, 4>(M, n) : modesum_table_bytes<16, 1>(M, n);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), sizeof(double) * h.size());
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tab), tab_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(double) * (size_t)n_cells);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    cleanup();
+    return sr::fail(SR_ERR_HIP, "sr_field_modesum: %s", hipGetErrorString(e));
+  }
+  e = tile_j ? run_modesum<8, 4>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st)
+             : run_modesum<16, 1>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_cells, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  cleanup();
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_field_modesum: %s", hipGetErrorString(e));
   return SR_OK;
 }
