@@ -164,7 +164,8 @@ __device__ __forceinline__ uint32_t spread_bits(uint32_t v) {
   return v;
 }
 
-__global__ void k_keys(VolDev V, const double *__restrict__ s0, int64_t N, int axis, uint32_t oob_key,
+// shift > 0: the key of the coarser cell (ib >> shift, ic >> shift), for lateral grids wider than the LDS counters of the sort
+__global__ void k_keys(VolDev V, const double *__restrict__ s0, int64_t N, int axis, uint32_t oob_key, int shift,
                        uint32_t *__restrict__ keys) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
@@ -182,7 +183,7 @@ __global__ void k_keys(VolDev V, const double *__restrict__ s0, int64_t N, int a
   if (pb >= gb0 && pb <= gbL && pc >= gc0 && pc <= gcL) {
     const int ib = find_cell(V.g[1], V.nb, pb, gb0, (V.nb - 1) / (gbL - gb0));
     const int ic = find_cell(V.g[2], V.nc, pc, gc0, (V.nc - 1) / (gcL - gc0));
-    key = (spread_bits((uint32_t)ib) << 1) | spread_bits((uint32_t)ic);
+    key = (spread_bits((uint32_t)(ib >> shift)) << 1) | spread_bits((uint32_t)(ic >> shift));
   }
   keys[i] = key;
 }
@@ -196,7 +197,7 @@ __global__ void k_keys(VolDev V, const double *__restrict__ s0, int64_t N, int a
 //   4. k_bin_fine: one workgroup per coarse digit orders its group by the fine digit (LDS counts + scan) -> perm
 // The order of the rays inside one cell is whatever the LDS atomics gave: results do not depend on it.
 constexpr int kBinTile = 4096;
-constexpr int kBinMaxDigits = 2048;  // LDS counters per workgroup (2^11: lateral grids up to 2048 x 2048 cells)
+constexpr int kBinMaxDigits = 2048;  // LDS counters per workgroup (2^11 digits a level: 2^22 keys; wider grids coarsen the key)
 
 __global__ __launch_bounds__(256) void k_bin_count(const uint32_t *__restrict__ keys, int64_t N, int lo_bits, int n_coarse,
                                                    uint32_t *__restrict__ counts, unsigned n_wg) {
@@ -825,17 +826,24 @@ int bin_rays(sr_rays *r, int64_t N, int lo_bits, int n_coarse, uint32_t *out, hi
 int bin_by_band(sr_rays *r, const sr_volume *v, const TileGeom &g, const double *rec, uint32_t *out, hipStream_t st) {
   const int64_t N = r->n;
   const int64_t n_bands = (v->nb - 1 + g.band - 1) / g.band;
-  const int64_t key_max = n_bands * (int64_t)(v->nc - 1) * g.band;  // the key of rays outside the volume / dead rays
+  const int64_t n_keys = n_bands * (int64_t)(v->nc - 1) * g.band;  // band keys of the cells: 0 .. n_keys - 1
+  // More keys than the two LDS levels of the sort hold (2^22, about 2048 x 2048 cells): drop low key bits, so that a few
+  // neighbouring cells of a band share a key and their rays come in any order -- which changes no result, only locality.
   int bits = 1;
+  while (((int64_t)1 << bits) < n_keys) ++bits;
+  const int shift = std::max(0, bits - 22);
+  const int64_t key_max = ((n_keys - 1) >> shift) + 1;  // the key of rays outside the volume / dead rays: behind every cell
+  bits = 1;
   while (((int64_t)1 << bits) <= key_max) ++bits;
   const int lo_bits = std::min(11, (bits + 1) / 2);
   const int n_coarse = (int)(key_max >> lo_bits) + 1;
-  SR_CHECK(n_coarse <= kBinMaxDigits + 1, "lateral grid too large for the LDS counters of the ray binning");
+  SR_CHECK(n_coarse <= kBinMaxDigits + 1, "band key of %lld does not fit the LDS counters of the ray binning", (long long)key_max);
   const unsigned nblk = sr::grid_for(N, 256);
   if (rec)
-    hipLaunchKernelGGL(k_keys_band_rec, dim3(nblk), dim3(256), 0, st, vol_dev(v), rec, N, g.band, (uint32_t)key_max, r->keys);
+    hipLaunchKernelGGL(k_keys_band_rec, dim3(nblk), dim3(256), 0, st, vol_dev(v), rec, N, g.band, (uint32_t)key_max, shift, r->keys);
   else
-    hipLaunchKernelGGL(k_keys_band, dim3(nblk), dim3(256), 0, st, vol_dev(v), (const double *)r->s0, N, v->axis, g.band, (uint32_t)key_max, r->keys);
+    hipLaunchKernelGGL(k_keys_band, dim3(nblk), dim3(256), 0, st, vol_dev(v), (const double *)r->s0, N, v->axis, g.band, (uint32_t)key_max,
+                       shift, r->keys);
   return bin_rays(r, N, lo_bits, n_coarse, out, st);
 }
 
@@ -1543,10 +1551,11 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   } else if (p->sort_rays) {
     int bits = 1;
     while ((1 << bits) < std::max(v->nb - 1, v->nc - 1)) ++bits;
-    SR_CHECK(bits <= 15, "lateral grid too large for the 32-bit Morton ray key");
-    SR_CHECK(bits <= 11, "lateral grid too large for the LDS counters of the ray binning (2048 x 2048 cells)");
+    // a lateral axis of more than 2048 cells: the Morton key of a coarser cell, 2^shift cells a side, whose rays come in any order
+    const int shift = std::max(0, bits - 11);
+    bits -= shift;
     const uint32_t oob_key = (uint32_t)1 << (2 * bits);  // out-of-volume / NaN rays: one more coarse group, after all cells
-    hipLaunchKernelGGL(k_keys, dim3(nblk), dim3(block), 0, st, V, (const double *)r->s0, N, v->axis, oob_key, r->keys);
+    hipLaunchKernelGGL(k_keys, dim3(nblk), dim3(block), 0, st, V, (const double *)r->s0, N, v->axis, oob_key, shift, r->keys);
     int rc = bin_rays(r, N, bits, (1 << bits) + 1, r->perm, st);  // 2*bits key bits: the coarser Morton cell, then the cell inside it
     if (rc) return rc;
   } else {

@@ -120,7 +120,8 @@ __device__ __forceinline__ uint32_t band_key(int ib, int ic, int ncc, int band) 
   return ((uint32_t)bnd * (uint32_t)ncc + (uint32_t)col) * (uint32_t)band + (uint32_t)row;
 }
 
-__global__ void k_keys_band(VolDev V, const double *__restrict__ s0, int64_t N, int axis, int band, uint32_t oob_key,
+// shift: low key bits dropped (bin_by_band: band keys past what the LDS counters of the sort hold)
+__global__ void k_keys_band(VolDev V, const double *__restrict__ s0, int64_t N, int axis, int band, uint32_t oob_key, int shift,
                             uint32_t *__restrict__ keys) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
@@ -138,14 +139,14 @@ __global__ void k_keys_band(VolDev V, const double *__restrict__ s0, int64_t N, 
   if (pb >= gb0 && pb <= gbL && pc >= gc0 && pc <= gcL) {
     const int ib = find_cell(V.g[1], V.nb, pb, gb0, (V.nb - 1) / (gbL - gb0));
     const int ic = find_cell(V.g[2], V.nc, pc, gc0, (V.nc - 1) / (gcL - gc0));
-    key = band_key(ib, ic, V.nc - 1, band);
+    key = band_key(ib, ic, V.nc - 1, band) >> shift;
   }
   keys[i] = key;
 }
 
 // between two segments: the key of a ray's CURRENT cell, from its hand-off record (rows 0, 1 = p_b, p_c; row 2 = v_a; NaN: not a
 // plane-form ray, -inf: a straggler, gone from the tile path -- both sort behind every cell)
-__global__ void k_keys_band_rec(VolDev V, const double *__restrict__ rec, int64_t N, int band, uint32_t oob_key,
+__global__ void k_keys_band_rec(VolDev V, const double *__restrict__ rec, int64_t N, int band, uint32_t oob_key, int shift,
                                 uint32_t *__restrict__ keys) {
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j >= N) return;
@@ -155,7 +156,7 @@ __global__ void k_keys_band_rec(VolDev V, const double *__restrict__ rec, int64_
   if (va > 0 && pb >= gb0 && pb <= gbL && pc >= gc0 && pc <= gcL) {
     const int ib = find_cell(V.g[1], V.nb, pb, gb0, (V.nb - 1) / (gbL - gb0));
     const int ic = find_cell(V.g[2], V.nc, pc, gc0, (V.nc - 1) / (gcL - gc0));
-    key = band_key(ib, ic, V.nc - 1, band);
+    key = band_key(ib, ic, V.nc - 1, band) >> shift;
   }
   keys[j] = key;
 }

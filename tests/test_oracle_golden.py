@@ -97,6 +97,37 @@ def test_rk4_planes_vs_reference_tight(orc, name):
     assert steps == (len(g["x"]) - 1) * g["s0"].shape[1]
 
 
+def test_calc_dndr_bit_exact_non_cubic(orc):
+    """A1 on g14 (41 x 29 x 23 nodes over +-5, +-4, +-3 mm): every node count and spacing differs, so a swapped axis or
+    stride changes the gradients."""
+    g = golden("g14_shapes")
+    om, gx, gy, gz = orc.calc_dndr(g["ne"], g["x"], g["y"], g["z"], float(g["lwl"]))
+    assert om == float(g["omega"])
+    for mine, ref in ((gx, g["dndx"]), (gy, g["dndy"]), (gz, g["dndz"])):
+        assert ref.dtype == np.float32 and ref.shape == (41, 29, 23)
+        assert np.array_equal(mine, ref)
+
+
+@pytest.mark.parametrize("pdir", ["x", "y", "z"])
+def test_rk4_planes_vs_reference_tight_non_cubic(orc, pdir):
+    """test_rk4_planes_vs_reference_tight on g14, probed along each axis: the probing axis has 41, 29 or 23 nodes and the
+    lateral axes the other two counts, with unequal half-lengths; same tolerances."""
+    g = golden("g14_shapes")
+    ext, a = float(g[f"extent_{pdir}"]), "xyz".index(pdir)
+    dom = orc.Domain.from_ne(g["ne"], g["x"], g["y"], g["z"], float(g["lwl"]), phaseshift=True)
+    ax = np.float32(g["xyz"[a]])
+    s0 = g[f"s0_{pdir}"]
+    sf, steps = orc.trace_rk4(dom, s0, float(ax[1] - ax[0]) / orc.c, orc.default_t_end(ext), pdir, "planes", 1)
+    rf, Jf = orc.ray_to_jones(sf, ext, pdir, "legacy")
+    rt, st = g[f"rf_tight_{pdir}"], g[f"sf_tight_{pdir}"]
+    assert np.max(np.abs(rf[0::2] - rt[0::2])) <= 1e-8 and np.max(np.abs(rf[1::2] - rt[1::2])) <= 1e-6
+    assert np.max(np.abs(sf[:3] - st[:3])) <= 2e-8
+    phmax = max(1.0, np.max(np.abs(st[7])))
+    assert np.max(np.abs(sf[7] - st[7])) <= 1e-5 * phmax
+    assert np.max(np.abs(Jf - g[f"Jf_tight_{pdir}"])) <= 1e-5 * phmax
+    assert steps == (len(ax) - 1) * s0.shape[1]
+
+
 @pytest.mark.parametrize("name", [t for t in TRACES if "turb" in t or "blob32" in t])
 def test_rk4_planes_converges(orc, name):
     """Two sub-steps per cell cut the error >=3x (4th order until a ray crosses a lateral cell face mid-step)."""
