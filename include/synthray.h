@@ -159,6 +159,40 @@ int sr_radial_spectrum2d(const double *img, int n0, int n1, const double *k0, co
 int sr_power_spectrum(const double *field, int ndim, const int64_t *shape, const double *coords, int rule,
                       const double *edges, int n_bins, double norm, double *sum, uint64_t *count, uint64_t *overflow);
 
+/* ---- after the path: Fresnel propagation of the traced field (src/simulator/fresnel_integral.py) -------------
+ * Scatter to grid (fresnel_integral.py:69-78, propagate's two LinearNDInterpolators): the rays (rx[i], ry[i]) carry
+ * amp[i] and phase[i]; node (j, i) of the (ny, nx) grid sits at (gx[i], gy[j]) (np.meshgrid(x, y)).  A node inside the
+ * rays' convex hull gets the linear interpolation of amp and phase in the Delaunay triangle of all rays that holds it
+ * (barycentric weights, float64), a node outside gets 0 -- scipy's LinearNDInterpolator(..., fill_value=0) evaluated at
+ * every node, without building the triangulation.  tri_out (may be NULL): the triangle's three ray indices per node,
+ * ascending, (ny, nx, 3), -1 outside.  stats (may be NULL): SR_FRESNEL_STATS values (hull vertices, rays left by the hull
+ * pre-filter, bins along x and y, nodes outside, nodes the second pass resolved).  Rays must have finite positions and be
+ * at least 3 (checked before the device is touched); collinear rays span no triangle: every node is outside. */
+#define SR_FRESNEL_STATS 6
+int sr_fresnel_grid(int64_t n_rays, const double *rx, const double *ry, const double *amp, const double *phase, int nx,
+                    const double *gx, int ny, const double *gy, double *amp_out, double *phase_out, int32_t *tri_out,
+                    int64_t *stats);
+/* fresnel_propagate (fresnel_integral.py:25-59) on an (m0, m1) complex128 field: forward 2-D Z2Z FFT, times
+ * H = exp(-i pi_lz (fx^2 + fy^2)) (fx: m0 values, fy: m1), times exp(-psf (fx^2 + fy^2)) when psf > 0 (the LANEX PSF,
+ * psf = 2 (pi sigma)^2), inverse FFT, times post (the caller folds numpy's 1/(m0 m1) into it), then the rows r0..r0+nr
+ * and columns c0..c0+nc go to out (nr x nc complex128, interleaved). */
+typedef struct {
+  double pi_lz;            /* pi * wavelength * z */
+  double psf;              /* 2 (pi sigma)^2, or 0: no PSF */
+  double post_re, post_im; /* exp(i 2 pi z / wavelength) / (i wavelength z) / (m0 m1) */
+  int32_t r0, nr, c0, nc;  /* the crop */
+} sr_fresnel_params;
+int sr_fresnel_propagate(const double *u0, int m0, int m1, const double *fx, const double *fy, const sr_fresnel_params *p,
+                         double *out);
+/* propagate (fresnel_integral.py:61-94) in one call: the rays gridded as sr_fresnel_grid does, U0 = amp exp(-i phase),
+ * padded and windowed (prepare_field_for_propagation, :7-22): U[r][c] = U0[src0[r]][src1[c]] * (w0[r] * w1[c]) over the
+ * (m0, m1) padded frame (src0, src1: numpy's reflect-pad source index of each padded row / column; w0, w1: the Tukey
+ * windows), then propagated as sr_fresnel_propagate does.  stats (may be NULL) as sr_fresnel_grid's. */
+int sr_fresnel_rays(int64_t n_rays, const double *rx, const double *ry, const double *amp, const double *phase, int nx,
+                    const double *gx, int ny, const double *gy, const int32_t *src0, const int32_t *src1, const double *w0,
+                    const double *w1, int m0, int m1, const double *fx, const double *fy, const sr_fresnel_params *p,
+                    double *out, int64_t *stats);
+
 /* ---- A2 + A3 + A4 + A6: ScalarDomain.solve / propagator.solve -----------------
  * replaces full_solver.py:376-403 (solve), :516-544 (dsdt), :317-347 (dndr, phase: the
  * RegularGridInterpolator gathers), :838-894 (ray_to_Jonesvector);

@@ -34,6 +34,13 @@ class TraceStats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+class FresnelParams(C.Structure):
+    _fields_ = [("pi_lz", C.c_double), ("psf", C.c_double), ("post_re", C.c_double), ("post_im", C.c_double),
+                ("r0", C.c_int32), ("nr", C.c_int32), ("c0", C.c_int32), ("nc", C.c_int32)]
+
+
+FRESNEL_STATS = 6  # SR_FRESNEL_STATS
+
 MAX_REF_BEAMS = 4  # SR_MAX_REF_BEAMS
 
 
@@ -67,6 +74,10 @@ SYMBOLS = {
     "sr_field_modesum": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sr_radial_spectrum2d": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "sr_power_spectrum": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _d, _vp, _vp, _vp]),
+    "sr_fresnel_grid": (_i, [_i64, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sr_fresnel_propagate": (_i, [_vp, _i, _i, _vp, _vp, C.POINTER(FresnelParams), _vp]),
+    "sr_fresnel_rays": (_i, [_i64, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp,
+                             C.POINTER(FresnelParams), _vp, _vp]),
     "sr_volume_sample": (_i, [_vp, _vp, _i64, _vp]),
     "sr_volume_attach_aux": (_i, [_vp, _vp, _vp, _vp, _d]),
     "sr_volume_create_slab": (_i, [_pp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _i, _i, _i]),

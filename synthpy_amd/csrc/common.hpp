@@ -81,6 +81,8 @@ void scratch_release();
 // one thread (8-30 GB/s on this box); here several threads copy slices into page-locked bounce buffers of the library and
 // each slice goes to the device by DMA as soon as it is in: the link's rate.  Page-locked sources are copied directly.
 int upload_sync(void *dst, const void *src, size_t bytes, hipStream_t st);
+// Exclusive scan of v[0..n) in place on `st` (trace.hip, the ray binning's scan); sums: (n + 2047) / 2048 words of workspace.
+void exclusive_scan_u32(uint32_t *v, int64_t n, uint32_t *sums, hipStream_t st);
 
 // Per-launch totals (ray steps, deposited rays) are summed by one atomic per wavefront.  156 000 wavefronts adding to ONE
 // address take ~2 ms of serialised device-scope atomics (it was the whole duration of the deposit kernel), so the totals

@@ -5,7 +5,6 @@
 // host (the noise must come from the caller's seeded np.random stream to reproduce the reference's field), the
 // product, the 3-D inverse FFT (hipFFT Z2Z, bound at first use like RCCL) and the normalisation run on the GPU.
 #include <dlfcn.h>
-#include <hipfft/hipfft.h>
 
 #include <algorithm>
 #include <map>
@@ -13,18 +12,9 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fft.hpp"
 
-namespace {
-
-struct Fft {
-  void *h = nullptr;
-  hipfftResult (*Plan3d)(hipfftHandle *, int, int, int, hipfftType) = nullptr;
-  hipfftResult (*Plan2d)(hipfftHandle *, int, int, hipfftType) = nullptr;
-  hipfftResult (*Plan1d)(hipfftHandle *, int, hipfftType, int) = nullptr;
-  hipfftResult (*SetStream)(hipfftHandle, hipStream_t) = nullptr;
-  hipfftResult (*ExecZ2Z)(hipfftHandle, hipfftDoubleComplex *, hipfftDoubleComplex *, int) = nullptr;
-  hipfftResult (*Destroy)(hipfftHandle) = nullptr;
-};
+namespace sr {
 
 int fft_lib(Fft **out) {
   static Fft F;
@@ -67,6 +57,14 @@ int fft_plan(Fft *F, int rank, int n0, int n1, int n2, hipfftHandle *out) {
   *out = it->second;
   return SR_OK;
 }
+
+}  // namespace sr
+
+namespace {
+
+using sr::Fft;
+using sr::fft_lib;
+using sr::fft_plan;
 
 // fft_field = noise * sqrt(S): complex128 times float32 promoted to float64, as numpy does
 __global__ void k_shape_noise(double2 *__restrict__ w, const float *__restrict__ amp, int64_t n) {

@@ -1368,6 +1368,14 @@ void launch_time(const sr_volume *v, TraceArgs &A, hipStream_t st) {
 
 }  // namespace
 
+// The ray binning's two-level exclusive scan, for other counting sorts of the library (fresnel.hip).
+void sr::exclusive_scan_u32(uint32_t *v, int64_t n, uint32_t *sums, hipStream_t st) {
+  const int64_t nsb = (n + kScanPerBlock - 1) / kScanPerBlock;
+  hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nsb), dim3(256), 0, st, v, n, sums);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, sums, nsb);
+  hipLaunchKernelGGL(k_scan_add, dim3(sr::grid_for(n, 256)), dim3(256), 0, st, v, n, (const uint32_t *)sums);
+}
+
 // Edge guard (deposit.hip): the launch slots list[0..*count) of a bundle the mixed build traced are traced again by the
 // float64 levels, from s0, into the same slots (guard 0); their steps go to striped total 2, their own rejects to the
 // time-stepping form through r->keys / counters[5].  Queued on the current stream.

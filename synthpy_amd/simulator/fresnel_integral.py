@@ -1,0 +1,169 @@
+"""Fresnel propagation of the traced field: mirror of src/simulator/fresnel_integral.py, its three functions, and the
+gridding step on its own.
+
+    prepare_field_for_propagation(U0, pad_factor=2, alpha=0.4)                                       host numpy
+    fresnel_propagate(U0_prepared, L, wavelength, z, original_shape, pad_factor=2, lanex_fwhm_m=None)   GPU
+    propagate(lwl, x, y, x_length, y_length, jones_vector, amplitudes, phases, z, pad_factor=2)         GPU, one call
+    grid_rays(x, y, jones_vector, amplitudes, phases, return_triangles=False)                          GPU, the gridding
+
+`propagate` uploads the rays once and runs, in one library call (sr_fresnel_rays): the gridding of the rays'
+amplitudes and phases, U0 = amp * exp(-1j * phase), the reflect pad and Tukey window, the forward 2-D FFT, the
+transfer function, the inverse FFT, the phase factor and the centre crop.  Only the (len(y), len(x)) result comes back.
+
+The gridding is scipy's LinearNDInterpolator((x_rays, y_rays), v, fill_value=0.0) evaluated at every node of
+np.meshgrid(x, y): a node inside the rays' convex hull gets the linear interpolation of v in the Delaunay triangle of all
+rays that holds it, a node outside gets 0.  The library finds that triangle node by node without building the
+triangulation (synthpy_amd/csrc/fresnel.hip), so the values are scipy's up to the rounding of the
+barycentric weights.  Amplitude and phase share the triangle, as the reference's two interpolators over the same points
+share their triangulation.
+
+Kept as the reference has them:
+  * fresnel_propagate pairs the axes as written: Nx_orig, Ny_orig = original_shape, dx = L[0] / original_shape[0] and
+    fx = fftfreq(U0_prepared.shape[0], dx), although axis 0 of the grid propagate builds is y (length len(y)) and
+    L = (x_length, y_length).  With len(x) != len(y) or x_length != y_length the spacings are those of the other axis.
+  * propagate passes lanex_fwhm_m=None (no PSF); only fresnel_propagate takes it.
+  * prepare_field_for_propagation pads with numpy's 'reflect' (pad widths beyond the axis reflect again and again, with
+    period 2(n-1); an axis of length 1 repeats its value) and multiplies by the outer product of two symmetric Tukey
+    windows.  The window is scipy.signal.windows.tukey restated in numpy (`tukey` below, scipy's expressions in its order,
+    equal bit for bit; alpha >= 1 is scipy's hann(M)), so that nothing here imports scipy.
+Decided here:
+  * propagate does not compute the Fresnel number the reference computes and discards.
+  * Rays with a non-finite position raise ValueError before anything is uploaded (scipy refuses them too: "Points
+    cannot contain NaN"); fewer than 3 rays raise ValueError (scipy's qhull raises).  Rays that all lie on one line span
+    no triangle: every node is outside and gets 0 (scipy's qhull raises QhullError).
+  * Where the Delaunay triangulation is not unique, scipy's qhull makes its own choice and this search another: ties
+    go to the lower ray index.  Rays at the same position: the lowest index is the vertex.  Four or more co-circular
+    rays: the triangle the search reaches, a valid Delaunay triangle, which may differ from qhull's inside that polygon
+    (both are linear interpolants of the same rays).  Nodes exactly on a triangle edge may take either neighbour.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from .._ffi import FRESNEL_STATS, FresnelParams, check, f64, lib, ptr
+
+GridStats = namedtuple("GridStats", "hull_vertices filter_survivors bins_x bins_y outside second_pass")
+GridStats.__doc__ = """What one gridding did: the rays' hull vertices, the rays the hull pre-filter kept, the bins along x
+and y, the nodes outside the hull, and the nodes the second pass (a workgroup per node) resolved."""
+
+
+def tukey(M, alpha=0.5):
+    """scipy.signal.windows.tukey(M, alpha) (sym=True) in numpy, scipy's expressions in its order."""
+    if int(M) != M or M < 0:
+        raise ValueError("Window length M must be a non-negative integer")
+    if M <= 1:
+        return np.ones(M)
+    if alpha <= 0:
+        return np.ones(M, "d")
+    if alpha >= 1.0:  # hann(M) = general_cosine(M, [0.5, 0.5])
+        fac = np.linspace(-np.pi, np.pi, M)
+        w = np.zeros(M)
+        for k, a in enumerate((0.5, 1.0 - 0.5)):
+            w += a * np.cos(k * fac)
+        return w
+    n = np.arange(0, M)
+    width = int(np.floor(alpha * (M - 1) / 2.0))
+    n1 = n[0:width + 1]
+    n2 = n[width + 1:M - width - 1]
+    n3 = n[M - width - 1:]
+    w1 = 0.5 * (1 + np.cos(np.pi * (-1 + 2.0 * n1 / alpha / (M - 1))))
+    w2 = np.ones(n2.shape)
+    w3 = 0.5 * (1 + np.cos(np.pi * (-2.0 / alpha + 1 + 2.0 * n3 / alpha / (M - 1))))
+    return np.concatenate((w1, w2, w3))
+
+
+def prepare_field_for_propagation(U0, pad_factor=2, alpha=0.4):
+    """fresnel_integral.py:7-22: reflect-pad each side by pad_factor * shape, times outer(tukey(M0), tukey(M1))."""
+    U0 = np.asarray(U0)
+    pad_width_x = U0.shape[0] * pad_factor
+    pad_width_y = U0.shape[1] * pad_factor
+    U0_padded = np.pad(U0, ((pad_width_x, pad_width_x), (pad_width_y, pad_width_y)), mode="reflect")
+    window_2d = np.outer(tukey(U0_padded.shape[0], alpha=alpha), tukey(U0_padded.shape[1], alpha=alpha))
+    return U0_padded * window_2d
+
+
+def _params(shape, L, wavelength, z, original_shape, pad_factor, lanex_fwhm_m):
+    """fresnel_propagate's frequencies, factors and crop, as the reference forms them (fresnel_integral.py:31-59)."""
+    Nx_orig, Ny_orig = original_shape
+    dx, dy = L[0] / Nx_orig, L[1] / Ny_orig
+    fx = np.ascontiguousarray(np.fft.fftfreq(shape[0], d=dx), dtype=np.float64)
+    fy = np.ascontiguousarray(np.fft.fftfreq(shape[1], d=dy), dtype=np.float64)
+    psf = 0.0
+    if lanex_fwhm_m is not None and lanex_fwhm_m > 0:
+        sigma = lanex_fwhm_m / (2 * np.sqrt(2 * np.log(2)))
+        psf = 2 * (np.pi * sigma) ** 2
+    post = complex(np.exp(1j * (2 * np.pi / wavelength) * z) / (1j * wavelength * z)) / (shape[0] * shape[1])
+    rows = range(shape[0])[Nx_orig * pad_factor:Nx_orig * pad_factor + Nx_orig]
+    cols = range(shape[1])[Ny_orig * pad_factor:Ny_orig * pad_factor + Ny_orig]
+    p = FresnelParams(float(np.pi * wavelength * z), float(psf), post.real, post.imag,
+                      rows.start if len(rows) else 0, len(rows), cols.start if len(cols) else 0, len(cols))
+    return p, fx, fy
+
+
+def fresnel_propagate(U0_prepared, L, wavelength, z, original_shape, pad_factor=2, lanex_fwhm_m=None):
+    """fresnel_integral.py:25-59 on the GPU: fft2, times exp(-1j pi wavelength z (FX**2 + FY**2)) (and the LANEX PSF
+    when lanex_fwhm_m > 0), ifft2, times exp(1j 2 pi z / wavelength) / (1j wavelength z), the centre crop
+    [Nx_orig*pad_factor : +Nx_orig, Ny_orig*pad_factor : +Ny_orig].  Returns complex128."""
+    U = np.ascontiguousarray(U0_prepared, dtype=np.complex128)
+    if U.ndim != 2:
+        raise ValueError(f"fresnel_propagate takes a 2-D field, not shape {U.shape}")
+    p, fx, fy = _params(U.shape, L, wavelength, z, original_shape, pad_factor, lanex_fwhm_m)
+    out = np.empty((p.nr, p.nc), dtype=np.complex128)
+    check(lib.sr_fresnel_propagate(ptr(U), U.shape[0], U.shape[1], ptr(fx), ptr(fy), C.byref(p), ptr(out)))
+    return out
+
+
+def _rays(x, y, jones_vector, amplitudes, phases):
+    xr, yr = f64(jones_vector[0]).ravel(), f64(jones_vector[2]).ravel()
+    amp, ph = f64(amplitudes).ravel(), f64(phases).ravel()
+    if not len(xr) == len(yr) == len(amp) == len(ph):
+        raise ValueError(f"{len(xr)} x, {len(yr)} y positions, {len(amp)} amplitudes, {len(ph)} phases")
+    if len(xr) < 3:
+        raise ValueError(f"{len(xr)} rays: the interpolation needs at least 3")
+    if not (np.isfinite(xr).all() and np.isfinite(yr).all()):
+        raise ValueError("ray positions (jones_vector[0], jones_vector[2]) must be finite: Points cannot contain NaN")
+    return xr, yr, amp, ph, f64(x).ravel(), f64(y).ravel()
+
+
+def grid_rays(x, y, jones_vector, amplitudes, phases, return_triangles=False):
+    """The gridding propagate runs (fresnel_integral.py:69-78): amplitude and phase of the rays at
+    (jones_vector[0], jones_vector[2]) interpolated onto np.meshgrid(x, y), shape (len(y), len(x)), as scipy's
+    LinearNDInterpolator(..., fill_value=0.0) does.  Returns (amplitude, phase); with return_triangles=True also the
+    three ray indices (ascending) of the Delaunay triangle each node was interpolated in, shape (len(y), len(x), 3),
+    -1 outside the hull, and a GridStats."""
+    xr, yr, amp, ph, gx, gy = _rays(x, y, jones_vector, amplitudes, phases)
+    ny, nx = len(gy), len(gx)
+    a_out, p_out = np.empty((ny, nx)), np.empty((ny, nx))
+    tri = np.empty((ny, nx, 3), dtype=np.int32) if return_triangles else None
+    stats = np.zeros(FRESNEL_STATS, dtype=np.int64)
+    check(lib.sr_fresnel_grid(len(xr), ptr(xr), ptr(yr), ptr(amp), ptr(ph), nx, ptr(gx), ny, ptr(gy), ptr(a_out), ptr(p_out),
+                              ptr(tri), ptr(stats)))
+    if return_triangles:
+        return a_out, p_out, tri.astype(np.int64), GridStats(*(int(s) for s in stats))
+    return a_out, p_out
+
+
+def _pad_tables(n, pad_factor, alpha=0.4):
+    """numpy's reflect-pad source index of each padded position along an axis of n, and the Tukey window over them"""
+    w = n * pad_factor
+    src = np.ascontiguousarray(np.pad(np.arange(n, dtype=np.int32), (w, w), mode="reflect"), dtype=np.int32)
+    return src, np.ascontiguousarray(tukey(len(src), alpha=alpha), dtype=np.float64)
+
+
+def propagate(lwl, x, y, x_length, y_length, jones_vector, amplitudes, phases, z, pad_factor=2):
+    """fresnel_integral.py:61-94 in one GPU call: the rays' amplitudes and phases gridded onto np.meshgrid(x, y),
+    U0 = amp * exp(-1j * phase), prepare_field_for_propagation(U0, pad_factor), fresnel_propagate(..., (x_length,
+    y_length), lwl, z, U0.shape, pad_factor, lanex_fwhm_m=None).  Returns complex128 of shape (len(y), len(x))."""
+    xr, yr, amp, ph, gx, gy = _rays(x, y, jones_vector, amplitudes, phases)
+    n0, n1 = len(gy), len(gx)
+    src0, w0 = _pad_tables(n0, pad_factor)
+    src1, w1 = _pad_tables(n1, pad_factor)
+    m0, m1 = len(src0), len(src1)
+    p, fx, fy = _params((m0, m1), (x_length, y_length), lwl, z, (n0, n1), pad_factor, None)
+    out = np.empty((p.nr, p.nc), dtype=np.complex128)
+    check(lib.sr_fresnel_rays(len(xr), ptr(xr), ptr(yr), ptr(amp), ptr(ph), n1, ptr(gx), n0, ptr(gy), ptr(src0), ptr(src1),
+                              ptr(w0), ptr(w1), m0, m1, ptr(fx), ptr(fy), C.byref(p), ptr(out), None))
+    return out

@@ -1,0 +1,256 @@
+"""simulator/fresnel_integral.py (src/simulator/fresnel_integral.py of the reference): prepare_field_for_propagation on
+the host, fresnel_propagate and propagate on the GPU, and the gridding of the rays (grid_rays: scipy's
+LinearNDInterpolator without building the triangulation, sr_fresnel_grid).
+
+Against the reference's own outputs (tests/golden/g15_fresnel.npz, made by tests/golden/make_g15_fresnel.py, which also
+draws the inputs): the padded and windowed field bit for bit, the propagated fields to 1e-10 of their maximum, the gridded
+fields node for node (inside / outside equal, values to 1e-12).  Beyond the fixtures' sizes (1e5 rays onto 256^2,
+1e6 onto 512^2, a Gaussian core in a sparse halo; rays along a thin arc, whose hull triangles are slivers): every
+returned triangle holds its node and its circumcircle holds no ray, checked by brute force in numpy, and where scipy
+imports the grids equal LinearNDInterpolator's.
+"""
+import importlib.util
+import math
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, golden
+
+from synthpy_amd.simulator import fresnel_integral as fi
+
+_spec = importlib.util.spec_from_file_location("make_g15_fresnel", os.path.join(GOLDEN, "make_g15_fresnel.py"))
+mk = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(mk)
+
+
+@pytest.fixture(scope="module")
+def g15():
+    return golden("g15_fresnel")
+
+
+def assert_close(a, ref, rel, what):
+    scale = np.abs(ref).max()
+    err = np.abs(a - ref).max()
+    assert a.shape == ref.shape, (what, a.shape, ref.shape)
+    assert err <= rel * scale, f"{what}: max |diff| {err:.3e} > {rel:g} * {scale:.3e}"
+
+
+# ---------------------------------------------------------------- host: no GPU needed
+@pytest.mark.parametrize("tag", sorted(mk.FIELD_CASES))
+def test_prepare_field_equals_reference(g15, tag):
+    pf = mk.FIELD_CASES[tag][3]
+    out = fi.prepare_field_for_propagation(mk.field(tag), pad_factor=pf)
+    assert out.dtype == np.complex128 and np.array_equal(out, g15[f"prep_{tag}"]), tag
+
+
+@pytest.mark.parametrize("M", [0, 1, 2, 7, 10, 51, 64, 325])
+@pytest.mark.parametrize("alpha", [-0.5, 0.0, 0.4, 0.5, 0.99, 1.0, 1.5])
+def test_tukey_equals_scipy_bit_for_bit(M, alpha):
+    windows = pytest.importorskip("scipy.signal.windows")
+    ref = windows.tukey(M, alpha=alpha)
+    w = fi.tukey(M, alpha=alpha)
+    assert w.dtype == ref.dtype and np.array_equal(w, ref), (M, alpha, np.abs(w - ref).max() if M else 0)
+
+
+@pytest.mark.parametrize("n,pf", [(1, 2), (2, 3), (5, 1), (5, 2), (12, 2), (7, 0)])
+def test_pad_tables_are_numpys_reflect_pad(n, pf):
+    """what the device pads with: U0[src0][:, src1] * outer(w0, w1) is prepare_field_for_propagation(U0)"""
+    rng = np.random.RandomState(n)
+    U0 = rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3))
+    s0, w0 = fi._pad_tables(n, pf)
+    s1, w1 = fi._pad_tables(3, pf)
+    U = U0[s0][:, s1] * np.outer(w0, w1)
+    assert np.array_equal(U, fi.prepare_field_for_propagation(U0, pad_factor=pf))
+
+
+def test_non_finite_ray_positions_are_refused():
+    """ValueError before anything is uploaded (scipy: "Points cannot contain NaN"); the C entry points refuse them too,
+    before the device is touched"""
+    from synthpy_amd import _ffi
+
+    x, y, jones, amp, phase = mk.rays("sparse")
+    for row, bad in ((0, np.nan), (2, np.inf), (2, -np.inf)):
+        j = jones.copy()
+        j[row, 17] = bad
+        with pytest.raises(ValueError, match="finite"):
+            fi.grid_rays(x, y, j, amp, phase)
+        with pytest.raises(ValueError, match="finite"):
+            fi.propagate(mk.LWL, x, y, 4e-3, 3e-3, j, amp, phase, mk.Z)
+        xr, yr = np.ascontiguousarray(j[0]), np.ascontiguousarray(j[2])
+        out = np.empty(len(x) * len(y))
+        rc = _ffi.lib.sr_fresnel_grid(len(xr), _ffi.ptr(xr), _ffi.ptr(yr), _ffi.ptr(amp), _ffi.ptr(phase), len(x), _ffi.ptr(x),
+                                      len(y), _ffi.ptr(y), _ffi.ptr(out), _ffi.ptr(out), None, None)
+        assert rc == -1 and "non-finite position" in _ffi.last_error()
+    with pytest.raises(ValueError, match="at least 3"):
+        fi.grid_rays(x, y, jones[:, :2], amp[:2], phase[:2])
+
+
+# ---------------------------------------------------------------- GPU against the reference's outputs
+@pytest.fixture(scope="module")
+def dev():
+    from synthpy_amd import engine
+
+    engine.init(0)
+    return engine
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", sorted(mk.FIELD_CASES))
+def test_fresnel_propagate_equals_reference(dev, g15, tag):
+    seed, shape, L, pf, lanex = mk.FIELD_CASES[tag]
+    out = fi.fresnel_propagate(g15[f"prep_{tag}"], L, mk.LWL, mk.Z, shape, pad_factor=pf, lanex_fwhm_m=lanex)
+    assert out.dtype == np.complex128
+    assert_close(out, g15[f"fp_{tag}"], 1e-10, tag)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", sorted(mk.RAY_CASES))
+def test_propagate_equals_reference(dev, g15, tag):
+    seed, n, beam, nx, ny, xl, yl, pf = mk.RAY_CASES[tag]
+    x, y, jones, amp, phase = mk.rays(tag)
+    out = fi.propagate(mk.LWL, x, y, xl, yl, jones, amp, phase, mk.Z, pad_factor=pf)
+    assert out.dtype == np.complex128 and out.shape == (ny, nx)
+    assert_close(out, g15[f"prop_{tag}"], 1e-10, tag)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", sorted(mk.RAY_CASES))
+def test_grid_equals_linear_nd_interpolator(dev, g15, tag):
+    x, y, jones, amp, phase = mk.rays(tag)
+    a, p, tri, stats = fi.grid_rays(x, y, jones, amp, phase, return_triangles=True)
+    ra, rp = g15[f"amp_{tag}"], g15[f"phase_{tag}"]
+    inside = ra != 0.0  # the amplitudes are >= 0.5: 0 only where scipy found no triangle
+    assert np.array_equal(tri[..., 0] >= 0, inside), f"{tag}: inside / outside differs at {np.argwhere((tri[..., 0] >= 0) != inside)[:5]}"
+    assert np.array_equal(a == 0.0, ~inside) and np.all(p[~inside] == 0.0)
+    assert stats.outside == int((~inside).sum())
+    assert_close(a, ra, 1e-12, f"{tag} amplitude")
+    assert_close(p, rp, 1e-12, f"{tag} phase")
+    if tag == "circle":
+        assert stats.outside > 0
+
+
+# ---------------------------------------------------------------- GPU at size: brute force, and scipy where it imports
+def core_halo(seed, n, L):
+    """90 % of the rays in a Gaussian core (sigma 0.08 L), 10 % uniform over a disc of radius 0.45 L: the density varies
+    ~140x over the grid, and the disc's edge crosses the grid's corners"""
+    rng = np.random.RandomState(seed)
+    m = n // 10
+    core = rng.normal(0.0, 0.08 * L, (2, n - m))
+    rad = 0.45 * L * np.sqrt(rng.uniform(0.0, 1.0, m))
+    th = rng.uniform(0.0, 2 * np.pi, m)
+    xr = np.concatenate([core[0], rad * np.cos(th)])
+    yr = np.concatenate([core[1], rad * np.sin(th)])
+    return xr, yr
+
+
+def arc(seed, n, L):
+    """rays along a thin arc (radius 0.45 L, relative width 4e-3): the hull's triangles are slivers whose circumcircles
+    reach across the whole beam"""
+    rng = np.random.RandomState(seed)
+    th = rng.uniform(0.15 * np.pi, 0.85 * np.pi, n)
+    r = 0.45 * L * (1.0 + rng.uniform(-2e-3, 2e-3, n))
+    return r * np.cos(th), r * np.sin(th) - 0.25 * L
+
+
+def values(xr, yr, L):
+    amp = 1.0 + 0.3 * np.cos(7.0 * xr / L) * np.sin(5.0 * yr / L)
+    phase = 50.0 * (xr * xr + yr * yr) / (L * L) + np.sin(11.0 * xr / L)
+    return amp, phase
+
+
+def brute_force(xr, yr, gx, gy, tri, nodes):
+    """each node's triangle holds the node and its circumcircle holds no ray: the rays in the circle's x-range, from the
+    rays sorted by x, against the circle"""
+    order = np.argsort(xr, kind="stable")
+    xs, ys = xr[order], yr[order]
+    nx = len(gx)
+    for q in nodes:
+        j, i = divmod(int(q), nx)
+        px, py = gx[i], gy[j]
+        t = tri[j, i]
+        assert t.min() >= 0, (q, t)
+        ax, ay = xr[t] - px, yr[t] - py
+        area = (ax[1] - ax[0]) * (ay[2] - ay[0]) - (ay[1] - ay[0]) * (ax[2] - ax[0])
+        lam = np.array([ax[1] * ay[2] - ay[1] * ax[2], ax[2] * ay[0] - ay[2] * ax[0], ax[0] * ay[1] - ay[0] * ax[1]]) / area
+        assert lam.min() >= -1e-9, (q, t, lam)
+        bx, by, cx, cy = ax[1] - ax[0], ay[1] - ay[0], ax[2] - ax[0], ay[2] - ay[0]
+        d = 2.0 * (bx * cy - by * cx)
+        ux, uy = (cy * (bx * bx + by * by) - by * (cx * cx + cy * cy)) / d, (bx * (cx * cx + cy * cy) - cx * (bx * bx + by * by)) / d
+        r2 = ux * ux + uy * uy
+        ox, oy = px + ax[0] + ux, py + ay[0] + uy
+        r = math.sqrt(r2)
+        lo, hi = np.searchsorted(xs, ox - r, "left"), np.searchsorted(xs, ox + r, "right")
+        dist2 = (xs[lo:hi] - ox) ** 2 + (ys[lo:hi] - oy) ** 2
+        inside = order[lo:hi][dist2 < r2 * (1.0 - 1e-9)]
+        assert not len(np.setdiff1d(inside, t)), (q, t, inside[:5])
+
+
+def near_hull(tri, reach):
+    """the nodes inside the hull within `reach` nodes of a node outside it"""
+    out = tri[..., 0] < 0
+    near = out.copy()
+    for dj in range(-reach, reach + 1):
+        for di in range(-reach, reach + 1):
+            near |= np.roll(np.roll(out, dj, 0), di, 1)
+    return np.flatnonzero((near & ~out).ravel())
+
+
+def against_scipy(xr, yr, gx, gy, amp, phase, a, p, tri):
+    interp = pytest.importorskip("scipy.interpolate")
+    spatial = pytest.importorskip("scipy.spatial")
+    d = spatial.Delaunay(np.c_[xr, yr])
+    XX, YY = np.meshgrid(gx, gy)
+    ra = interp.LinearNDInterpolator(d, amp, fill_value=0.0)((XX, YY))
+    rp = interp.LinearNDInterpolator(d, phase, fill_value=0.0)((XX, YY))
+    s = d.find_simplex(np.c_[XX.ravel(), YY.ravel()]).reshape(XX.shape)
+    assert np.array_equal(tri[..., 0] >= 0, s >= 0)
+    assert_close(a, ra, 1e-12, "amplitude")
+    assert_close(p, rp, 1e-12, "phase")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,g", [(100_000, 256), (1_000_000, 512)])
+def test_grid_at_size_core_and_halo(dev, n, g):
+    L = 4e-3
+    xr, yr = core_halo(n % 9973, n, L)
+    amp, phase = values(xr, yr, L)
+    jones = np.zeros((4, n))
+    jones[0], jones[2] = xr, yr
+    gx = np.linspace(-L / 2, L / 2, g)
+    gy = np.linspace(-L / 2, L / 2, g)
+    a, p, tri, stats = fi.grid_rays(gx, gy, jones, amp, phase, return_triangles=True)
+    assert stats.outside > 0 and stats.hull_vertices >= 3, stats
+    bin_w = max((xr.max() - xr.min()) / stats.bins_x, (yr.max() - yr.min()) / stats.bins_y)
+    edge = near_hull(tri, int(math.ceil(2 * bin_w / (gx[1] - gx[0]))))
+    inside = np.flatnonzero((tri[..., 0] >= 0).ravel())
+    sample = np.random.RandomState(7).choice(inside, 2000, replace=False)
+    assert len(edge) > 0
+    brute_force(xr, yr, gx, gy, tri, np.union1d(sample, edge))
+    against_scipy(xr, yr, gx, gy, amp, phase, a, p, tri)
+
+
+@pytest.mark.gpu
+def test_grid_thin_arc_runs_the_second_pass(dev):
+    L, g = 4e-3, 128
+    xr, yr = arc(5, 20000, L)
+    amp, phase = values(xr, yr, L)
+    jones = np.zeros((4, len(xr)))
+    jones[0], jones[2] = xr, yr
+    gx = np.linspace(-L / 2, L / 2, g)
+    gy = np.linspace(-L / 2, L / 2, g)
+    a, p, tri, stats = fi.grid_rays(gx, gy, jones, amp, phase, return_triangles=True)
+    inside = np.flatnonzero((tri[..., 0] >= 0).ravel())
+    assert stats.second_pass > 0 and len(inside) > 500, stats
+    brute_force(xr, yr, gx, gy, tri, inside)
+    against_scipy(xr, yr, gx, gy, amp, phase, a, p, tri)
+
+
+@pytest.mark.gpu
+def test_grid_is_repeatable(dev):
+    x, y, jones, amp, phase = mk.rays("dense")
+    first = fi.grid_rays(x, y, jones, amp, phase, return_triangles=True)
+    again = fi.grid_rays(x, y, jones, amp, phase, return_triangles=True)
+    for u, w in zip(first[:3], again[:3]):
+        assert np.array_equal(u, w)
