@@ -218,6 +218,7 @@ struct sr_rays {
 
 namespace sr {
 int retrace_f64(const sr_rays *r, const uint32_t *list, const unsigned long long *count);  // trace.hip (edge guard)
+int download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int64_t ld, int64_t off, double *staging);  // trace.hip
 }
 
 struct sr_image {

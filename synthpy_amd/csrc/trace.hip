@@ -14,17 +14,10 @@
 // are queued and re-traced by the time-stepping form with located faces (trace_one_t).
 //
 // Compiled with -ffp-contract=off; fused multiply-adds are written out with fma().
-#include <sys/mman.h>
-
 #include <algorithm>
-#include <array>
-#include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <thread>
 
 #include "common.hpp"
 
@@ -716,6 +709,26 @@ __global__ void k_unpermute(const double *__restrict__ src, double *__restrict__
   for (int r = 0; r < rows; ++r)
     for (int w = 0; w < width; ++w) dst[((int64_t)r * N + i) * width + w] = src[((int64_t)r * N + j) * width + w];
 }
+__global__ void k_unpermute_f32(const float *__restrict__ src, float *__restrict__ dst, const uint32_t *__restrict__ perm, int64_t N) {
+  const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (j < N) dst[perm[j]] = src[j];
+}
+
+// ---- runtime flags -> template arguments ---------------------------------------------------------------------------------
+// with_flags(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): every launch that picks a kernel
+// instantiation from runtime booleans is written once, as a generic lambda, and prunes the combinations that must not exist with
+// `if constexpr` (they are never instantiated).
+template <typename F>
+void with_flags(F &&f) {
+  f();
+}
+template <typename F, typename... Rest>
+void with_flags(F &&f, bool b, Rest... rest) {
+  if (b)
+    with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 // Threads per workgroup of k_trace_f64 / k_trace_mx: as FEW wavefronts as the LDS node tables allow at the kernel's
 // occupancy.  A workgroup's place on its CU (registers, LDS) is given to the next workgroup only when its slowest wavefront
@@ -747,49 +760,6 @@ VolDev vol_dev(const sr_volume *v) {
   V.R = v->R;
   return V;
 }
-
-// sf / rf / Jf of a traced bundle, original ray order, into host arrays whose rows are `ld` rays long, starting at ray
-// `off` of every row (ld == r->n, off == 0: the bundle's own arrays).  `staging`: 17*r->n doubles of device memory (9 + 4 + 4
-// rows: each array is put back into ray order in its own part, so the three copies need ONE wait), or nullptr to allocate
-// them for the call (hipFree waits for every stream: the pipelined sr_trace passes its own).
-int download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int64_t ld, int64_t off, double *staging) {
-  if (!r->traced) return sr::fail(SR_ERR_STATE, "sr_rays_download: rays have not been traced");
-  const int64_t N = r->n;
-  if (N == 0) return SR_OK;
-  hipStream_t st = sr::ctx().stream;
-  double *tmp = staging;
-  const size_t rows = (sf ? 9 : 0) + (rf ? 4 : 0) + (Jf ? 4 : 0);
-  if (rows == 0) return SR_OK;
-  if (!tmp) {  // the library's per-call staging block (kept between calls: no hipMalloc / hipFree in a loop of solve() calls)
-    tmp = static_cast<double *>(sr::scratch(sizeof(double) * rows * (size_t)N));
-    if (!tmp) return SR_ERR_HIP;
-  }
-  const unsigned grid = sr::grid_for(N, 256);
-  struct Job {
-    const double *src;
-    double *dst;
-    int rows, width;
-  } jobs[3] = {{r->sf, sf, 9, 1}, {r->rf, rf, 4, 1}, {r->Jf, Jf, 2, 2}};
-  hipError_t e = hipSuccess;
-  double *part = tmp;
-  for (auto &jb : jobs) {
-    if (!jb.dst) continue;
-    hipLaunchKernelGGL(k_unpermute, dim3(grid), dim3(256), 0, st, jb.src, part, (const uint32_t *)r->perm, N, jb.rows, jb.width);
-    const size_t row_bytes = sizeof(double) * (size_t)jb.width * (size_t)N;
-    if (ld == N)
-      e = hipMemcpyAsync(jb.dst, part, row_bytes * jb.rows, hipMemcpyDeviceToHost, st);
-    else  // one copy per row (2-D copies of pageable memory are staged row by row anyway)
-      for (int q = 0; q < jb.rows && e == hipSuccess; ++q)
-        e = hipMemcpyAsync(jb.dst + ((size_t)q * ld + off) * jb.width, part + (size_t)q * N * jb.width, row_bytes, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) break;
-    part += (size_t)jb.rows * jb.width * (size_t)N;
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (!staging) sr::scratch_trim();
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_rays_download: %s", hipGetErrorString(e));
-  return SR_OK;
-}
-
 
 // Two-level counting sort of r->keys (see k_bin_count): coarse digit = key >> lo_bits (n_coarse of them), fine digit below;
 // out[pos] = index of the ray that comes pos-th.
@@ -857,8 +827,44 @@ constexpr double kTileMinDensity = 8.0;
 struct TilePlan {
   TileGeom g;
   int seg;   // node planes per segment
-  bool rec;  // the records kernel (trace_tile.inc, REC): sr_volume::R exists
+  bool rec;  // the records kernel (trace_tile.inc, REC): wants sr_volume::R (tile_records)
 };
+
+// The environment switches of one trace.  The tests set them between two traces of one process, so they are read per call: by
+// trace_knobs(), once, at the top of sr_rays_trace and of sr::retrace_f64 -- nothing else in this file reads the environment.
+struct TraceKnobs {
+  int f64_tile = -1;          // SYNTHRAY_F64_TILE=0 / 1: the per-ray kernel / the tile kernel wherever it can run; -1: by ray density
+  bool tile_records = true;   // SYNTHRAY_TILE_RECORDS=0: the producers' kernel, no ready-made records
+  bool strag_beside = true;   // SYNTHRAY_STRAGGLERS=serial: the stragglers' launches on the library stream itself, each behind its
+                              // segment (for A/B timing)
+  bool aux_one_pass = false;  // SYNTHRAY_AUX_ONE_PASS=1: the five-field kernel for inverse bremsstrahlung alone (for A/B timing)
+  TileGeom tile{};            // SYNTHRAY_TILE="tb,tc,halo,band,planes per segment", five valid integers: tile and tile_seg,
+  int tile_seg = 0;           // else tile_seg = 0
+  std::vector<double> cuts;   // SYNTHRAY_TILE_CUTS="w0,w1,...": the segments' shares of the node planes, as far as they parse
+};
+TraceKnobs trace_knobs() {
+  TraceKnobs k;
+  if (const char *e = getenv("SYNTHRAY_F64_TILE")) k.f64_tile = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : -1);
+  if (const char *e = getenv("SYNTHRAY_TILE_RECORDS")) k.tile_records = e[0] != '0';
+  if (const char *e = getenv("SYNTHRAY_STRAGGLERS")) k.strag_beside = e[0] != 's';
+  if (const char *e = getenv("SYNTHRAY_AUX_ONE_PASS")) k.aux_one_pass = e[0] == '1';
+  if (const char *e = getenv("SYNTHRAY_TILE")) {
+    int a, b, c, d, f;
+    if (sscanf(e, "%d,%d,%d,%d,%d", &a, &b, &c, &d, &f) == 5 && a >= 2 && b >= 2 && c >= 0 && d >= 1 && f >= 1 && a * b <= SR_TILE_THREADS) {
+      k.tile = TileGeom{a, b, c, d};
+      k.tile_seg = f;
+    }
+  }
+  if (const char *e = getenv("SYNTHRAY_TILE_CUTS"))
+    for (const char *q = e; *q;) {
+      char *end = nullptr;
+      const double x = strtod(q, &end);
+      if (end == q) break;
+      k.cuts.push_back(x);
+      q = *end == ',' ? end + 1 : end;
+    }
+  return k;
+}
 // lateral cells the beam covers: its launch positions' bounding box in cells of the two lateral axes (whole grid when unknown)
 double beam_cells(const sr_rays *r, const sr_volume *v) {
   const double all = (double)(v->nb - 1) * (double)(v->nc - 1);
@@ -879,10 +885,10 @@ double beam_cells(const sr_rays *r, const sr_volume *v) {
 // that takes the tile path without the optional terms, when they fit beside everything else (at most a third of the free HBM:
 // 128 bytes per node plane and lateral cell, 17 GB for 512^3), with the volume's own arithmetic (k_build_records =
 // coefs_from_corners); otherwise -- and with SYNTHRAY_TILE_RECORDS=0 -- the producers' kernel runs.
-int tile_records(const sr_volume *v, hipStream_t st, bool &use) {
+// An error of the build itself is returned, with the buffer freed; "does not fit" is SR_OK with use = false.
+int tile_records(const sr_volume *v, const TraceKnobs &knobs, hipStream_t st, bool &use) {
   use = false;
-  const char *e = getenv("SYNTHRAY_TILE_RECORDS");
-  if (e && e[0] == '0') return SR_OK;
+  if (!knobs.tile_records) return SR_OK;
   if (!v->R && !v->R_tried) {
     v->R_tried = true;
     const size_t count = (size_t)v->na * (size_t)(v->nb - 1) * (size_t)(v->nc - 1) * 16;
@@ -894,14 +900,15 @@ int tile_records(const sr_volume *v, hipStream_t st, bool &use) {
       return SR_OK;
     }
     const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(count / 16 + 255) / 256, (int64_t)sr::ctx().n_cu * 64);
-    if (v->L)
-      hipLaunchKernelGGL(k_build_records<true>, dim3(grid), dim3(256), 0, st, vol_dev(v), R);
-    else
-      hipLaunchKernelGGL(k_build_records<false>, dim3(grid), dim3(256), 0, st, vol_dev(v), R);
-    SR_HIP(hipGetLastError());
+    with_flags([&](auto ph) { hipLaunchKernelGGL(k_build_records<ph.value>, dim3(grid), dim3(256), 0, st, vol_dev(v), R); }, v->L != nullptr);
+    hipError_t err = hipGetLastError();
     // The volume is shared by every stream that traces through it (the job driver alternates its bundles between the library's two
     // streams): the records must be COMPLETE before anybody can see the pointer.  Once per volume: 15 ms for 512^3.
-    SR_HIP(hipStreamSynchronize(st));
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+      (void)hipFree(R);
+      return sr::fail(SR_ERR_HIP, "tile records: %s", hipGetErrorString(err));
+    }
     v->R = R;
   }
   use = v->R != nullptr;
@@ -910,7 +917,10 @@ int tile_records(const sr_volume *v, hipStream_t st, bool &use) {
 
 constexpr int64_t kTileMinRays = 32768;  // below this either kernel is a handful of wavefronts: the per-ray kernel spreads them wider
 
-bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, int64_t N, TilePlan &tp, hipStream_t st) {
+// Whether a trace takes the tile path, and with which geometry: a pure function of its arguments.  `records`: the ready-made
+// records can be had (tile_records); tp.rec says whether the plan uses them.
+bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, int64_t N, const TraceKnobs &knobs, bool records,
+               TilePlan &tp) {
   // the producers' kernel, measured on BASELINE config 3 in round 3 (docs/HISTORY.md, profiles/r03_tile_geometry_ab.txt): 256-ray workgroups, 8 x 8 tiles, bands of
   // two cell rows, 171-plane segments 50.6 ms per step (128 planes: 51.6; 256 planes, where only two workgroups fit a CU: 65.8);
   // 768-ray workgroups with 12 x 16 tiles: 128 / 171 / 256 / 511 planes per segment 56.0 / 54.0 / 52.5 / 61.6
@@ -918,7 +928,7 @@ bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, i
   // inverse bremsstrahlung alone: the per-ray kernel that carries kappa only (trace_f64.inc, SEL = 1; two wavefronts per SIMD) is the
   // faster one even for dense bundles -- 4.5 ms against the tile path's 7.3 (five-field records) on 1e6 rays x 256^3,
   // profiles/r05_aux_sparse.txt, r05_aux_rate.txt -- unless the tile path is forced
-  if (v->K && !v->Q && p->substeps == 1 && !(getenv("SYNTHRAY_F64_TILE") && getenv("SYNTHRAY_F64_TILE")[0] == '1')) return false;
+  if (v->K && !v->Q && p->substeps == 1 && knobs.f64_tile != 1) return false;
   tp = TilePlan{{8, 8, 2, 2}, 171, false};
   const double density = (double)N / beam_cells(r, v);
   {
@@ -935,37 +945,28 @@ bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, i
       tp.seg = 128;
     }
   }
-  const char *on = getenv("SYNTHRAY_F64_TILE");
-  if (on && on[0] == '0') return false;
-  const bool forced = on && on[0] == '1';
-  if (!forced && (N < kTileMinRays || density < kTileMinDensity)) return false;
+  if (knobs.f64_tile == 0) return false;
+  if (knobs.f64_tile != 1 && (N < kTileMinRays || density < kTileMinDensity)) return false;
   const int threads = SR_TILE_THREADS;
   // slabs (A12) are admitted: the kernel steps a range of node planes from / to hand-off records anyway; so are the optional
   // terms (AUX: five more fields per record, a smaller tile, two workgroups per CU)
   if (p->substeps != 1 || !p->sort_rays) return false;
   const bool aux = v->K || v->Q;
-  if (!aux && threads == 256 && v->nb - 1 >= 8 && v->nc - 1 >= 7) {
+  if (records && !aux && threads == 256 && v->nb - 1 >= 8 && v->nc - 1 >= 7) {
     // The records kernel (trace_tile.inc, REC; round 5): 8 x 7 tiles, four workgroups per CU.  Measured on 512^3 (tools/
     // r05_rec4_sweep.sh, r05_low_density.sh; profiles/r05_tile_variants.txt): at 60 rays per cell of the beam's box (BASELINE config 3)
     // bands of 3 / 4 / 5 rows 45.0 / 44.1 / 45.3 ms per step in 128-plane segments, 4 rows in 171- / 103-plane segments 45.5 / 45.3;
     // at 30 rays per cell 4 rows 24.1 (3: 25.4, 5: 24.6); at 15 rays per cell 5 or 6 rows in 103-plane segments 14.4 / 14.3 (128
     // planes: 14.9 / 14.7; 4 rows: 15.4) -- one or two rows more per band than the producers' kernel wants, and shorter segments.
-    bool rec = false;
-    if (tile_records(v, st, rec) != SR_OK) rec = false;
-    if (rec) {
-      tp.rec = true;
-      tp.g.tc = 7;
-      tp.g.band = std::min(6, std::max(4, tp.g.band + 1));
-      tp.seg = tp.g.band >= 5 ? 103 : 128;
-    }
+    tp.rec = true;
+    tp.g.tc = 7;
+    tp.g.band = std::min(6, std::max(4, tp.g.band + 1));
+    tp.seg = tp.g.band >= 5 ? 103 : 128;
   }
-  if (const char *e = getenv("SYNTHRAY_TILE")) {
-    int a, b, c, d, f;
-    if (sscanf(e, "%d,%d,%d,%d,%d", &a, &b, &c, &d, &f) == 5 && a >= 2 && b >= 2 && c >= 0 && d >= 1 && f >= 1 && a * b <= threads) {
-      tp.g = TileGeom{a, b, c, d};
-      tp.seg = f;
-      tp.rec = tp.rec && a == 8 && b <= 8;  // a tile column is one DMA's kilobyte: eight cells
-    }
+  if (knobs.tile_seg > 0) {
+    tp.g = knobs.tile;
+    tp.seg = knobs.tile_seg;
+    tp.rec = tp.rec && tp.g.tb == 8 && tp.g.tc <= 8;  // a tile column is one DMA's kilobyte: eight cells
   }
   if (v->nb - 1 < tp.g.tb || v->nc - 1 < tp.g.tc || v->na < 3) return false;
   if (aux && (tp.g.tb * tp.g.tc > 64 || threads < 128)) return false;  // one wavefront of producers per kind
@@ -976,15 +977,104 @@ bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, i
   return true;
 }
 
-void launch_planes64(const sr_volume *v, const sr_trace_params *p, TraceArgs &A, hipStream_t st);
+void launch_planes64(const sr_volume *v, const sr_trace_params *p, const TraceKnobs &knobs, const TraceArgs &A, hipStream_t st);
 
 // The segments' shares of the node planes (equal until measured otherwise: tools/r05_cuts.sh)
 // Measured on BASELINE config 3 (tools/r05_cuts.sh, profiles/r05_tile_variants.txt): shares 1 : 1 : 1 48.72 ms per step and 633 000
 // stragglers, 1.3 : 1 : 0.7 48.31 ms and 494 000, 1.5 : 1.1 : 0.4 50.6 ms.  Rays start parallel and pick their angles up on the
 // way, so a tile loses few rays in the first planes and most in the last; and the LAST segment's stragglers are the only ones with
 // no tile launch to run beside.  A ramp from 1.3 down to 0.7.
-void tile_cut_weights(int n_seg, std::vector<double> &w) {
+std::vector<double> tile_cut_weights(int n_seg) {
+  std::vector<double> w((size_t)n_seg, 1.0);
   for (int q = 0; q < n_seg; ++q) w[(size_t)q] = n_seg > 1 ? 1.3 - 0.6 * q / (n_seg - 1) : 1.0;
+  return w;
+}
+
+// Segment boundaries: segment q steps from node plane cut[q] to cut[q + 1].  The weights are the knobs' (SYNTHRAY_TILE_CUTS) when
+// they are n_seg positive numbers, else the ramp.
+std::vector<int> tile_cuts(int steps, int n_seg, const TraceKnobs &knobs) {
+  bool given = (int)knobs.cuts.size() == n_seg;
+  for (double x : knobs.cuts) given = given && x > 0;
+  const std::vector<double> w = given ? knobs.cuts : tile_cut_weights(n_seg);
+  std::vector<int> cut((size_t)n_seg + 1, 0);
+  double tot = 0, acc = 0;
+  for (double x : w) tot += x;
+  for (int q = 0; q < n_seg; ++q) {
+    acc += w[(size_t)q];
+    cut[(size_t)q + 1] = q + 1 == n_seg ? steps : std::min(steps - (n_seg - 1 - q), std::max(cut[(size_t)q] + 1, (int)std::lround(steps * acc / tot)));
+  }
+  return cut;
+}
+
+// The bundle's buffers of the tile path, `cap` rays each; `second`: the records' second buffer and the new order (more than one
+// segment, or a slab's arrivals)
+int tile_buffers(sr_rays *r, size_t cap, int n_seg, bool second) {
+  int rc = SR_OK;
+  if (!r->rec && (rc = sr::dev_alloc(&r->rec, 10 * cap))) return rc;
+  if (second) {
+    if (!r->rec2 && (rc = sr::dev_alloc(&r->rec2, 10 * cap))) return rc;
+    if (!r->order2 && (rc = sr::dev_alloc(&r->order2, cap))) return rc;
+  }
+  // a ray is lost once: the straggler records never hold more entries than the bundle has rays
+  if (!r->strag_rec && (rc = sr::dev_alloc(&r->strag_rec, 10 * cap))) return rc;
+  if (r->strag_snap_cap < n_seg + 1) {  // one entry count per segment + the zero in front
+    sr::dev_free(r->strag_snap);
+    r->strag_snap_cap = 0;
+    if ((rc = sr::dev_alloc(&r->strag_snap, (size_t)std::max(n_seg + 1, 64)))) return rc;  // (nullptr when it fails)
+    r->strag_snap_cap = std::max(n_seg + 1, 64);
+  }
+  return SR_OK;
+}
+
+// One segment's tile kernel over every workgroup of the bundle (T.A.n_blocks of them).  Each instantiation is told once, before its
+// first launch, that it may use the whole LDS of a CU.
+int launch_tile(const TileArgs &T, bool phase, bool aux, bool rec, size_t lds, hipStream_t st) {
+  const unsigned grid = ((T.A.n_blocks + 7) / 8) * 8;
+  hipError_t err = hipSuccess;
+  with_flags(
+      [&](auto ph, auto ax, auto rc) {
+        if constexpr (!(ax.value && rc.value)) {  // the ready-made records hold the gradient fields only
+          auto *kernel = &k_trace_tile<ph.value, ax.value, rc.value>;
+          static const hipError_t whole_lds =
+              hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          if ((err = whole_lds) == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
+        }
+      },
+      phase, aux, rec);
+  SR_HIP(err);
+  return SR_OK;
+}
+
+// k_trace_f64's arguments for the stragglers of segment q: the entries [snap[q], snap[q + 1]) of the straggler records, from node
+// plane k0 to the end of the volume (slab), entry by entry in the records themselves (row pitch `cap`).  A: the trace's own
+// arguments (make_trace_args: no list, to the last plane, no recovery)
+TraceArgs straggler_args(const TraceArgs &A, const sr_rays *r, size_t cap, int q, int k0, bool ho_exit) {
+  TraceArgs S = A;
+  S.N = (int64_t)cap;
+  S.rec = r->strag_rec;
+  S.guard = nullptr;
+  S.in_iota = 1;
+  S.in_first = r->strag_snap + q;
+  S.in_count = r->strag_snap + q + 1;
+  S.out_list = nullptr;  // what the plane form cannot finish comes back NaN in its entry: k_strag_finish sends it on
+  S.out_count = nullptr;
+  S.handoff = SR_HANDOFF_ENTER | SR_HANDOFF_EXIT;
+  S.k_first = k0;
+  S.finish_later = ho_exit ? 0 : 1;
+  return S;
+}
+
+// after the last segment and the side stream: the gone slots' outputs (exit records) from the straggler entries
+void launch_strag_finish(const TraceArgs &A, const sr_rays *r, size_t cap, bool ho_exit, bool slab, hipStream_t st) {
+  StragFinish F{};
+  F.A = A;
+  F.A.rec = r->rec;
+  F.A.guard = r->guard;
+  F.strag = r->strag_rec;
+  F.cap = (int64_t)cap;
+  F.exit_rec = ho_exit ? 1 : 0;
+  F.slab = slab ? 1 : 0;
+  hipLaunchKernelGGL(k_strag_finish, dim3(sr::grid_for(A.N, 256)), dim3(256), 0, st, F);
 }
 
 // The tile kernel over every ray, segment by segment.  What a segment's launch loses (rays leaving their workgroup's tile or
@@ -995,120 +1085,44 @@ void tile_cut_weights(int n_seg, std::vector<double> &w) {
 // k_trace_f64 from a record is k_trace_f64 from s0 (the slab chain of A12), and the tile kernel is k_trace_f64 ray for ray,
 // so the result is the per-ray kernel's, bit for bit, whoever carried a ray where.  Rays that are no plane-form rays at all
 // end in r->fb_list (counters[1]) for the usual levels, from s0.
-int trace_tiled(sr_rays *r, const sr_volume *v, const sr_trace_params *p, const TilePlan &tp, TraceArgs &A, hipStream_t st) {
+int trace_tiled(sr_rays *r, const sr_volume *v, const sr_trace_params *p, const TraceKnobs &knobs, const TilePlan &tp, TraceArgs &A,
+                hipStream_t st) {
   const int64_t N = r->n;
-  const bool phase = v->L != nullptr;
-  static bool attr_set = false;
-  if (!attr_set) {
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_trace_tile<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
   sr::Context &c = sr::ctx();
   hipStream_t side = c.side[c.current];
   hipEvent_t ev_go = c.side_ev[c.current][0], ev_done = c.side_ev[c.current][1];
   const int steps = v->na - 1;
   const int n_seg = (steps + tp.seg - 1) / tp.seg;
-  const bool aux = v->K != nullptr || v->Q != nullptr;
-  const int threads = SR_TILE_THREADS;
-  // REC (trace_tile.inc): the node planes' coefficient records ready-made in HBM, brought into the tile's ring by LDS-DMA.  128 bytes
-  // per (node plane, lateral cell): 17 GB for 512^3, built at the first trace that takes this path and kept with the volume.
-  const bool rec = tp.rec && v->R != nullptr;
-  const size_t lds = tile_lds_bytes(tp.g, (steps + n_seg - 1) / n_seg + 1, aux, rec);
-  A.V = vol_dev(v);  // with the records, if they have just been built
+  const bool phase = v->L != nullptr, aux = v->K != nullptr || v->Q != nullptr;
+  // tp.rec (trace_tile.inc, REC): the node planes' coefficient records ready-made in HBM (tile_records), brought into the tile's
+  // ring by LDS-DMA
+  const size_t lds = tile_lds_bytes(tp.g, (steps + n_seg - 1) / n_seg + 1, aux, tp.rec);
   const bool ho_enter = (p->handoff & SR_HANDOFF_ENTER) != 0, ho_exit = (p->handoff & SR_HANDOFF_EXIT) != 0;
+  const bool slab = v->is_slab || p->handoff;
   const size_t cap = (size_t)std::max(r->cap, N);  // never by the current n (a short chunk in a full-size bundle)
-  {
-    int rc = SR_OK;
-    if (!r->rec && (rc = sr::dev_alloc(&r->rec, 10 * cap))) return rc;
-    if (n_seg > 1 || ho_enter) {
-      if (!r->rec2 && (rc = sr::dev_alloc(&r->rec2, 10 * cap))) return rc;
-      if (!r->order2 && (rc = sr::dev_alloc(&r->order2, cap))) return rc;
-    }
-    // a ray is lost once: the straggler records never hold more entries than the bundle has rays
-    if (!r->strag_rec && (rc = sr::dev_alloc(&r->strag_rec, 10 * cap))) return rc;
-    if (r->strag_snap_cap < n_seg + 2) {  // one entry count per launch (the last segment may go in two) + the zero in front
-      sr::dev_free(r->strag_snap);
-      r->strag_snap = nullptr;
-      r->strag_snap_cap = 0;
-      if ((rc = sr::dev_alloc(&r->strag_snap, (size_t)std::max(n_seg + 2, 64)))) return rc;
-      r->strag_snap_cap = std::max(n_seg + 2, 64);
-    }
-  }
-  const unsigned nb = sr::grid_for(N, threads);
+  int rc = tile_buffers(r, cap, n_seg, n_seg > 1 || ho_enter);
+  if (rc) return rc;
   unsigned long long *strag_count = r->counters + 8;
   SR_HIP(hipMemsetAsync(strag_count, 0, sizeof(unsigned long long), st));
   SR_HIP(hipMemsetAsync(r->strag_snap, 0, sizeof(unsigned long long), st));  // snap[0] = 0
-  TileArgs T{};
+  const std::vector<int> cut = tile_cuts(steps, n_seg, knobs);
+  const bool timed = n_seg <= sr::kMaxTileSegs;
+  TileArgs T{};  // rot = 0, block0 = 0: every launch takes the whole bundle
   T.G = tp.g;
-  {
-    // Opt-in: measured SLOWER (profiles/r04_tile_variants.txt: 47.5 against 45.3 ms in the kernels on C3) -- the three producer
-    // wavefronts of a CU were evidently not on one SIMD to begin with
-    const char *e = getenv("SYNTHRAY_TILE_ROTATE");
-    T.rot = (e && e[0] == '1') ? 1 : 0;
-  }
-  // SYNTHRAY_STRAGGLERS=serial: the stragglers' launches on the library stream itself, each behind its segment (for A/B timing)
-  const char *se = getenv("SYNTHRAY_STRAGGLERS");
-  const bool beside = !(se && se[0] == 's');
-  // SYNTHRAY_TILE_LAST_SPLIT=f (opt-in, MEASURED NULL): the last segment in two launches, the first f of its workgroups and the
-  // rest.  The thought: the stragglers of every other launch are carried beside the tile kernel's next launch, the last launch's
-  // have nothing to run beside (1.6 ms alone with the producers' kernel and equal segments, profiles/r05_timeline_c3_producers_equal_
-  // cuts.txt), and a quarter of the workgroups would leave one round of wavefronts, 0.4 ms.  Measured (profiles/r05_tile_variants.txt):
-  // 48.66 ms per step in one launch, 48.78 - 48.98 cut at 0.5 / 0.65 / 0.75, whatever the side stream's priority -- beside a tile
-  // launch the per-ray kernel only gets the CU slots the tile kernel's own start and end leave, so the first part's stragglers
-  // finish AFTER the second part.  What shortened the tail instead: a shorter last segment (tile_cut_weights).
-  double last_split = 0.0;
-  if (const char *e = getenv("SYNTHRAY_TILE_LAST_SPLIT")) last_split = atof(e);
-  unsigned nb_first = nb;
-  if (beside && last_split > 0.0 && last_split < 1.0 && nb >= 2048) nb_first = std::min(nb - 8, std::max(8u, (unsigned)(nb * last_split) / 8 * 8));
-  int launch = 0;  // launches so far = straggler snapshots taken
-  // Segment boundaries.  SYNTHRAY_TILE_CUTS="w0,w1,..." (n_seg weights): the segments' shares of the node planes
-  std::vector<int> cut((size_t)n_seg + 1, 0);
-  {
-    std::vector<double> w((size_t)n_seg, 1.0);
-    const char *e = getenv("SYNTHRAY_TILE_CUTS");
-    if (e && *e) {
-      std::vector<double> given;
-      for (const char *q = e; *q;) {
-        char *end = nullptr;
-        const double x = strtod(q, &end);
-        if (end == q) break;
-        given.push_back(x);
-        q = *end == ',' ? end + 1 : end;
-      }
-      bool ok = (int)given.size() == n_seg;
-      for (double x : given) ok = ok && x > 0;
-      if (ok)
-        w = given;
-      else
-        tile_cut_weights(n_seg, w);
-    } else {
-      tile_cut_weights(n_seg, w);
-    }
-    double tot = 0, acc = 0;
-    for (double x : w) tot += x;
-    for (int q = 0; q < n_seg; ++q) {
-      acc += w[(size_t)q];
-      cut[(size_t)q + 1] = q + 1 == n_seg ? steps : std::min(steps - (n_seg - 1 - q), std::max(cut[(size_t)q] + 1, (int)std::lround(steps * acc / tot)));
-    }
-  }
+  T.exit_rec = ho_exit ? 1 : 0;
+  T.slab = slab ? 1 : 0;
+  T.A = A;
+  T.A.guard = r->guard;
+  T.A.n_blocks = sr::grid_for(N, SR_TILE_THREADS);
+  T.perm_out = r->perm;
+  T.strag_rec = r->strag_rec;
+  T.strag_cap = (int64_t)cap;
+  T.strag_count = strag_count;
   for (int q = 0; q < n_seg; ++q) {
     T.k0 = cut[(size_t)q];
     T.k1 = cut[(size_t)q + 1];
     T.first = q == 0 && !ho_enter;
     T.last = q + 1 == n_seg;
-    T.exit_rec = ho_exit ? 1 : 0;
-    T.slab = (v->is_slab || p->handoff) ? 1 : 0;
-    T.A = A;
-    T.A.guard = r->guard;
-    T.perm_out = r->perm;
-    T.strag_rec = r->strag_rec;
-    T.strag_cap = (int64_t)cap;
-    T.strag_count = strag_count;
     if (T.first) {
       T.rec_in = nullptr;
       T.order = nullptr;
@@ -1116,82 +1130,35 @@ int trace_tiled(sr_rays *r, const sr_volume *v, const sr_trace_params *p, const 
     } else {
       // bin the rays again by the cell they are in now (a slab's arrivals: the sender's order is its ENTRY cells'); the kernel
       // reads the records through the new order and writes the other buffer in place; the ray index rides in row 9
-      int rc = bin_by_band(r, v, tp.g, r->rec, r->order2, st);
+      rc = bin_by_band(r, v, tp.g, r->rec, r->order2, st);
       if (rc) return rc;
       T.rec_in = r->rec;
       T.order = r->order2;
       T.A.rec = r->rec2;
     }
-    const bool timed = n_seg <= sr::kMaxTileSegs;
     if (timed) SR_HIP(hipEventRecord(c.ev[4 + 2 * q], st));
-    const int parts = (T.last && nb_first < nb) ? 2 : 1;
-    for (int part = 0; part < parts; ++part) {
-      T.block0 = part == 0 ? 0u : nb_first;
-      T.A.n_blocks = parts == 1 ? nb : (part == 0 ? nb_first : nb - nb_first);
-      const unsigned grid = ((T.A.n_blocks + 7) / 8) * 8;
-      if (aux) {
-        if (phase)
-          hipLaunchKernelGGL((k_trace_tile<true, true>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-        else
-          hipLaunchKernelGGL((k_trace_tile<false, true>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-      } else if (rec) {
-        if (phase)
-          hipLaunchKernelGGL((k_trace_tile<true, false, true>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-        else
-          hipLaunchKernelGGL((k_trace_tile<false, false, true>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-      } else if (phase) {
-        hipLaunchKernelGGL((k_trace_tile<true>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-      } else {
-        hipLaunchKernelGGL((k_trace_tile<false>), dim3(grid), dim3(SR_TILE_THREADS), lds, st, T);
-      }
-      if (timed && part + 1 == parts) SR_HIP(hipEventRecord(c.ev[5 + 2 * q], st));
-      hipLaunchKernelGGL(k_strag_snap, dim3(1), dim3(1), 0, st, (const unsigned long long *)strag_count, r->strag_snap, launch, r->counters + 3);
-      // this launch's stragglers from node plane k0 to the end of the volume (slab), entry by entry in the straggler records
-      TraceArgs S = A;
-      S.N = (int64_t)cap;  // the records' row pitch
-      S.rec = r->strag_rec;
-      S.guard = nullptr;
-      S.in_list = nullptr;
-      S.in_iota = 1;
-      S.in_first = r->strag_snap + launch;
-      S.in_count = r->strag_snap + launch + 1;
-      S.out_list = nullptr;  // what the plane form cannot finish comes back NaN in its entry: k_strag_finish sends it on
-      S.out_count = nullptr;
-      S.handoff = SR_HANDOFF_ENTER | SR_HANDOFF_EXIT;
-      S.k_first = T.k0;
-      S.k_last = -1;
-      S.recover = 0;
-      S.finish_later = ho_exit ? 0 : 1;
-      hipStream_t ss = st;
-      if (beside) {
-        SR_HIP(hipEventRecord(ev_go, st));
-        SR_HIP(hipStreamWaitEvent(side, ev_go, 0));
-        ss = side;
-      }
-      launch_planes64(v, p, S, ss);
-      ++launch;
+    if ((rc = launch_tile(T, phase, aux, tp.rec, lds, st))) return rc;
+    if (timed) SR_HIP(hipEventRecord(c.ev[5 + 2 * q], st));
+    hipLaunchKernelGGL(k_strag_snap, dim3(1), dim3(1), 0, st, (const unsigned long long *)strag_count, r->strag_snap, q, r->counters + 3);
+    // this segment's stragglers: beside the next segment on the side stream, or (knobs) behind this one on the library stream
+    hipStream_t ss = st;
+    if (knobs.strag_beside) {
+      SR_HIP(hipEventRecord(ev_go, st));
+      SR_HIP(hipStreamWaitEvent(side, ev_go, 0));
+      ss = side;
     }
+    launch_planes64(v, p, knobs, straggler_args(A, r, cap, q, T.k0, ho_exit), ss);
     if (!T.first) std::swap(r->rec, r->rec2);  // r->rec: the buffer this segment wrote
   }
-  if (beside) {
+  if (knobs.strag_beside) {
     SR_HIP(hipEventRecord(ev_done, side));
     SR_HIP(hipStreamWaitEvent(st, ev_done, 0));
   }
-  {
-    StragFinish F{};
-    F.A = A;
-    F.A.rec = r->rec;
-    F.A.guard = r->guard;
-    F.strag = r->strag_rec;
-    F.cap = (int64_t)cap;
-    F.exit_rec = ho_exit ? 1 : 0;
-    F.slab = (v->is_slab || p->handoff) ? 1 : 0;
-    hipLaunchKernelGGL(k_strag_finish, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, F);
-  }
+  launch_strag_finish(A, r, cap, ho_exit, slab, st);
   A.guard = r->guard;
-  r->tile_segs = n_seg <= sr::kMaxTileSegs ? n_seg : 0;
+  r->tile_segs = timed ? n_seg : 0;
   r->tile_segs_run = n_seg;
-  r->tile_rec = rec;
+  r->tile_rec = tp.rec;
   return SR_OK;
 }
 
@@ -1214,21 +1181,13 @@ int make_trace_args(const sr_rays *r, const sr_volume *v, const sr_trace_params 
   A.row_order = p->row_order;
   A.sub = p->substeps;
   A.counters = r->counters;
-  A.in_list = nullptr;
-  A.in_count = nullptr;
-  A.out_list = r->fb_list;
+  A.out_list = r->fb_list;  // every slot (in_list == nullptr), from s0, the whole volume: the rest stays zero
   A.out_count = r->counters + 1;
   A.n_blocks = sr::grid_for(N, 256);
   A.rec = r->rec;
   A.handoff = p->handoff;
   A.guard = r->guard;
-  A.step_stripe = 0;
-  A.k_first = 0;
   A.k_last = -1;
-  A.recover = 0;
-  A.in_first = nullptr;
-  A.in_iota = 0;
-  A.finish_later = 0;
   {
     double hmax = 0;
     for (int k = 0; k + 1 < v->na; ++k) hmax = std::max(hmax, v->hg[0][k + 1] - v->hg[0][k]);
@@ -1292,81 +1251,137 @@ int make_trace_args(const sr_rays *r, const sr_volume *v, const sr_trace_params 
 
 // the float64 plane level over every slot (A.in_list == nullptr) or over a queue: k_trace_f64 in the instantiation the
 // volume and the parameters ask for (phase integral, optional terms, sub-steps)
-void launch_planes64(const sr_volume *v, const sr_trace_params *p, TraceArgs &A, hipStream_t st) {
-  const int64_t N = A.N;
+void launch_planes64(const sr_volume *v, const sr_trace_params *p, const TraceKnobs &knobs, const TraceArgs &A, hipStream_t st) {
   const size_t lds = sizeof(double) * 2 * (size_t)(v->nb + v->nc);
   const bool phase = v->L != nullptr;
   const bool aux = v->K != nullptr || v->Q != nullptr;  // amp / pol terms (A7)
   const bool subs = p->substeps != 1;
   const bool five = aux && (subs || v->Q != nullptr);  // the five-field kernel: one wavefront per SIMD
   const int block = small_block(lds, 4 * (five ? SR_F64K_AUX_WAVES : SR_F64K_WAVES));  // else 2 wavefronts per SIMD
-  const unsigned nb64 = sr::grid_for(N, block);
-  const unsigned grid = ((nb64 + 7) / 8) * 8;
-  const unsigned saved = A.n_blocks;
-  A.n_blocks = nb64;
-#define SR_F64(PH, AX, SB) hipLaunchKernelGGL((k_trace_f64<PH, AX, SB>), dim3(grid), dim3(block), lds, st, A)
-#define SR_F64_SEL(PH, SEL) hipLaunchKernelGGL((k_trace_f64<PH, true, false, SEL>), dim3(grid), dim3(block), lds, st, A)
-  if (aux && !subs && v->K != nullptr && v->Q == nullptr && !(getenv("SYNTHRAY_AUX_ONE_PASS") && getenv("SYNTHRAY_AUX_ONE_PASS")[0] == '1')) {
-    // inverse bremsstrahlung alone: the kernel that carries kappa and nothing of the Faraday term (trace_f64.inc, SEL = 1): two
-    // wavefronts per SIMD.  (SYNTHRAY_AUX_ONE_PASS=1: the five-field kernel, for A/B timing.)
-    if (phase) SR_F64_SEL(true, 1); else SR_F64_SEL(false, 1);
-    A.n_blocks = saved;
-    return;
-  }
-  switch ((phase ? 4 : 0) | (aux ? 2 : 0) | (subs ? 1 : 0)) {
-    case 0: SR_F64(false, false, false); break;
-    case 1: SR_F64(false, false, true); break;
-    case 2: SR_F64(false, true, false); break;
-    case 3: SR_F64(false, true, true); break;
-    case 4: SR_F64(true, false, false); break;
-    case 5: SR_F64(true, false, true); break;
-    case 6: SR_F64(true, true, false); break;
-    default: SR_F64(true, true, true); break;
-  }
-#undef SR_F64_SEL
-#undef SR_F64
-  A.n_blocks = saved;
+  // inverse bremsstrahlung alone: the kernel that carries kappa and nothing of the Faraday term (trace_f64.inc, SEL = 1): two
+  // wavefronts per SIMD.  (SYNTHRAY_AUX_ONE_PASS=1: the five-field kernel, for A/B timing.)
+  const bool kappa_only = aux && !subs && v->K != nullptr && v->Q == nullptr && !knobs.aux_one_pass;
+  TraceArgs L = A;
+  L.n_blocks = sr::grid_for(A.N, block);
+  const unsigned grid = ((L.n_blocks + 7) / 8) * 8;
+  with_flags(
+      [&](auto ph, auto ax, auto sb, auto sel) {  // SEL = 1 exists for <PHASE, true, false> only
+        if constexpr (!sel.value || (ax.value && !sb.value))
+          hipLaunchKernelGGL((k_trace_f64<ph.value, ax.value, sb.value, sel.value ? 1 : 0>), dim3(grid), dim3(block), lds, st, L);
+      },
+      phase, aux, subs, kappa_only);
 }
 
 // k_trace_mx over every slot (A.in_list == nullptr) or over a queue
-void launch_mx(const sr_volume *v, TraceArgs &A, hipStream_t st) {
+void launch_mx(const sr_volume *v, const TraceArgs &A, hipStream_t st) {
   const size_t ml = mixed_lds_bytes(v->nb, v->nc);
   const int block = std::max(128, small_block(ml, 16));  // 4 wavefronts per SIMD; 64 and 128 measure the same
-  const unsigned nbx = sr::grid_for(A.N, block);
-  const unsigned grid = ((nbx + 7) / 8) * 8;
-  const unsigned saved = A.n_blocks;
-  A.n_blocks = nbx;
-  if (v->L != nullptr)
-    hipLaunchKernelGGL((k_trace_mx<true>), dim3(grid), dim3(block), ml, st, A);
-  else
-    hipLaunchKernelGGL((k_trace_mx<false>), dim3(grid), dim3(block), ml, st, A);
-  A.n_blocks = saved;
+  TraceArgs L = A;
+  L.n_blocks = sr::grid_for(A.N, block);
+  const unsigned grid = ((L.n_blocks + 7) / 8) * 8;
+  with_flags([&](auto ph) { hipLaunchKernelGGL((k_trace_mx<ph.value>), dim3(grid), dim3(block), ml, st, L); }, v->L != nullptr);
 }
 
-// time-stepping form for what the plane form cannot take: fixed small grid, strides over the device-side count
+// time-stepping form for what the plane form cannot take (the level before's rejects become its queue): fixed small grid,
+// strides over the device-side count
 void launch_time(const sr_volume *v, TraceArgs &A, hipStream_t st) {
   const int block = 256;
-  const unsigned nblk = sr::grid_for(A.N, block);
-  const bool phase = v->L != nullptr;
-  const bool aux = v->K != nullptr || v->Q != nullptr;
   A.in_list = A.out_list;
   A.in_count = A.out_count;
   A.out_list = nullptr;
   A.out_count = nullptr;
-  const unsigned fgrid = (unsigned)std::min<int64_t>(nblk, (int64_t)sr::ctx().n_cu * 4);
-  if (aux) {
-    if (phase)
-      hipLaunchKernelGGL((k_trace_time<true, true>), dim3(fgrid), dim3(block), 0, st, A);
+  const unsigned fgrid = (unsigned)std::min<int64_t>(sr::grid_for(A.N, block), (int64_t)sr::ctx().n_cu * 4);
+  with_flags(
+      [&](auto ph, auto ax) { hipLaunchKernelGGL((k_trace_time<ph.value, ax.value>), dim3(fgrid), dim3(block), 0, st, A); },
+      v->L != nullptr, v->K != nullptr || v->Q != nullptr);
+}
+
+// k_sample (out: 4 rows) or k_sample_aux (5 rows) at N caller-given points, host to host
+int sample_points(const sr_volume *v, const double *pts, int64_t N, double *out, bool aux, const char *who) {
+  if (N == 0) return SR_OK;
+  hipStream_t st = sr::ctx().stream;
+  const int rows = aux ? 5 : 4;
+  double *d = nullptr;
+  int rc = sr::dev_alloc(&d, (size_t)(3 + rows) * N);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d, pts, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const dim3 grid(sr::grid_for(N, 256));
+    if (aux)
+      hipLaunchKernelGGL(k_sample_aux, grid, dim3(256), 0, st, vol_dev(v), v->axis, (const double *)d, N, d + 3 * N);
     else
-      hipLaunchKernelGGL((k_trace_time<false, true>), dim3(fgrid), dim3(block), 0, st, A);
-  } else if (phase) {
-    hipLaunchKernelGGL((k_trace_time<true, false>), dim3(fgrid), dim3(block), 0, st, A);
-  } else {
-    hipLaunchKernelGGL((k_trace_time<false, false>), dim3(fgrid), dim3(block), 0, st, A);
+      hipLaunchKernelGGL(k_sample, grid, dim3(256), 0, st, vol_dev(v), v->axis, v->L != nullptr, (const double *)d, N, d + 3 * N);
+    e = hipGetLastError();
   }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * N, sizeof(double) * rows * N, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  sr::dev_free(d);
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  return SR_OK;
+}
+
+// the bounding box of the bundle's launch positions (counters [10..15]: free between traces) into r->bbox; waits for `st`
+int read_bbox(sr_rays *r, hipStream_t st) {
+  unsigned long long *box = r->counters + 10, hb[6];
+  SR_HIP(hipMemsetAsync(box, 0xff, 3 * sizeof(unsigned long long), st));
+  SR_HIP(hipMemsetAsync(box + 3, 0, 3 * sizeof(unsigned long long), st));
+  const unsigned grid = (unsigned)std::min<int64_t>(sr::grid_for(r->n, 256), (int64_t)sr::ctx().n_cu * 8);
+  hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(256), 0, st, (const double *)r->s0, r->n, box);
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  bool any = true;
+  for (int q = 0; q < 3; ++q) any = any && hb[q] <= hb[3 + q];
+  if (any) {
+    for (int q = 0; q < 6; ++q) r->bbox[q] = from_ordered_bits(hb[q]);
+    r->have_bbox = true;
+  }
+  return SR_OK;
 }
 
 }  // namespace
+
+// sf / rf / Jf of a traced bundle, original ray order, into host arrays whose rows are `ld` rays long, starting at ray
+// `off` of every row (ld == r->n, off == 0: the bundle's own arrays).  `staging`: 17*r->n doubles of device memory (9 + 4 + 4
+// rows: each array is put back into ray order in its own part, so the three copies need ONE wait), or nullptr to allocate
+// them for the call (hipFree waits for every stream: the pipelined sr_trace passes its own).
+int sr::download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int64_t ld, int64_t off, double *staging) {
+  if (!r->traced) return sr::fail(SR_ERR_STATE, "sr_rays_download: rays have not been traced");
+  const int64_t N = r->n;
+  if (N == 0) return SR_OK;
+  hipStream_t st = sr::ctx().stream;
+  double *tmp = staging;
+  const size_t rows = (sf ? 9 : 0) + (rf ? 4 : 0) + (Jf ? 4 : 0);
+  if (rows == 0) return SR_OK;
+  if (!tmp) {  // the library's per-call staging block (kept between calls: no hipMalloc / hipFree in a loop of solve() calls)
+    tmp = static_cast<double *>(sr::scratch(sizeof(double) * rows * (size_t)N));
+    if (!tmp) return SR_ERR_HIP;
+  }
+  const unsigned grid = sr::grid_for(N, 256);
+  struct Job {
+    const double *src;
+    double *dst;
+    int rows, width;
+  } jobs[3] = {{r->sf, sf, 9, 1}, {r->rf, rf, 4, 1}, {r->Jf, Jf, 2, 2}};
+  hipError_t e = hipSuccess;
+  double *part = tmp;
+  for (auto &jb : jobs) {
+    if (!jb.dst) continue;
+    hipLaunchKernelGGL(k_unpermute, dim3(grid), dim3(256), 0, st, jb.src, part, (const uint32_t *)r->perm, N, jb.rows, jb.width);
+    const size_t row_bytes = sizeof(double) * (size_t)jb.width * (size_t)N;
+    if (ld == N)
+      e = hipMemcpyAsync(jb.dst, part, row_bytes * jb.rows, hipMemcpyDeviceToHost, st);
+    else  // one copy per row (2-D copies of pageable memory are staged row by row anyway)
+      for (int q = 0; q < jb.rows && e == hipSuccess; ++q)
+        e = hipMemcpyAsync(jb.dst + ((size_t)q * ld + off) * jb.width, part + (size_t)q * N * jb.width, row_bytes, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) break;
+    part += (size_t)jb.rows * jb.width * (size_t)N;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (!staging) sr::scratch_trim();
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_rays_download: %s", hipGetErrorString(e));
+  return SR_OK;
+}
 
 // The ray binning's two-level exclusive scan, for other counting sorts of the library (fresnel.hip).
 void sr::exclusive_scan_u32(uint32_t *v, int64_t n, uint32_t *sums, hipStream_t st) {
@@ -1380,6 +1395,7 @@ void sr::exclusive_scan_u32(uint32_t *v, int64_t n, uint32_t *sums, hipStream_t 
 // float64 levels, from s0, into the same slots (guard 0); their steps go to striped total 2, their own rejects to the
 // time-stepping form through r->keys / counters[5].  Queued on the current stream.
 int sr::retrace_f64(const sr_rays *r, const uint32_t *list, const unsigned long long *count) {
+  const TraceKnobs knobs = trace_knobs();
   const sr_volume *v = r->last_vol;
   SR_CHECK(v != nullptr && r->guard_live, "edge guard: no mixed-precision trace of a whole volume to refine");
   sr_trace_params p = r->last_p;
@@ -1393,7 +1409,7 @@ int sr::retrace_f64(const sr_rays *r, const uint32_t *list, const unsigned long 
   A.in_count = count;
   A.out_list = r->keys;
   A.out_count = r->counters + 5;
-  launch_planes64(v, &p, A, st);
+  launch_planes64(v, &p, knobs, A, st);
   launch_time(v, A, st);
   SR_HIP(hipGetLastError());
   return SR_OK;
@@ -1403,23 +1419,10 @@ extern "C" {
 
 void sr_rays_destroy(sr_rays *r) {
   if (!r) return;
-  sr::dev_free(r->s0);
-  sr::dev_free(r->sf);
-  sr::dev_free(r->rf);
-  sr::dev_free(r->Jf);
-  sr::dev_free(r->perm);
-  sr::dev_free(r->keys);
-  sr::dev_free(r->bins);
-  sr::dev_free(r->sort_tmp);
-  sr::dev_free(r->fb_list);
-  sr::dev_free(r->counters);
-  sr::dev_free(r->rec);
-  sr::dev_free(r->rec2);
-  sr::dev_free(r->order2);
-  sr::dev_free(r->strag_rec);
-  sr::dev_free(r->strag_snap);
-  sr::dev_free(r->guard);
-  sr::dev_free(r->guard_set);
+  for (void *q : {(void *)r->s0, (void *)r->sf, (void *)r->rf, (void *)r->Jf, (void *)r->perm, (void *)r->keys, (void *)r->bins,
+                  (void *)r->sort_tmp, (void *)r->fb_list, (void *)r->counters, (void *)r->rec, (void *)r->rec2, (void *)r->order2,
+                  (void *)r->strag_rec, (void *)r->strag_snap, (void *)r->guard, r->guard_set})
+    sr::dev_free(q);
   delete r;
 }
 
@@ -1452,22 +1455,8 @@ int sr_rays_upload(sr_rays *r, const double *s0) {
   if (r->n > 0) {
     hipStream_t st = sr::ctx().stream;
     int rc = sr::upload_sync(r->s0, s0, sizeof(double) * 9 * (size_t)r->n, st);
+    if (!rc) rc = read_bbox(r, st);
     if (rc) return rc;
-    // the launch positions' bounding box (counters [10..15]: free between traces), read back with the wait the copy needs anyway
-    unsigned long long *box = r->counters + 10, hb[6];
-    SR_HIP(hipMemsetAsync(box, 0xff, 3 * sizeof(unsigned long long), st));
-    SR_HIP(hipMemsetAsync(box + 3, 0, 3 * sizeof(unsigned long long), st));
-    const unsigned grid = (unsigned)std::min<int64_t>(sr::grid_for(r->n, 256), (int64_t)sr::ctx().n_cu * 8);
-    hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(256), 0, st, (const double *)r->s0, r->n, box);
-    SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-    bool any = true;
-    for (int q = 0; q < 3; ++q) any = any && hb[q] <= hb[3 + q];
-    if (any) {
-      for (int q = 0; q < 6; ++q) r->bbox[q] = from_ordered_bits(hb[q]);
-      r->have_bbox = true;
-    }
   }
   r->have_s0 = true;
   r->traced = false;
@@ -1489,26 +1478,15 @@ int sr_rays_upload_part(sr_rays *r, const double *s0, int64_t n, int64_t first, 
   }
   if (!last) return SR_OK;
   if (r->n > 0) {  // as sr_rays_upload: the box of the whole bundle
-    unsigned long long *box = r->counters + 10, hb[6];
-    SR_HIP(hipMemsetAsync(box, 0xff, 3 * sizeof(unsigned long long), st));
-    SR_HIP(hipMemsetAsync(box + 3, 0, 3 * sizeof(unsigned long long), st));
-    const unsigned grid = (unsigned)std::min<int64_t>(sr::grid_for(r->n, 256), (int64_t)sr::ctx().n_cu * 8);
-    hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(256), 0, st, (const double *)r->s0, r->n, box);
-    SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-    bool any = true;
-    for (int q = 0; q < 3; ++q) any = any && hb[q] <= hb[3 + q];
-    if (any) {
-      for (int q = 0; q < 6; ++q) r->bbox[q] = from_ordered_bits(hb[q]);
-      r->have_bbox = true;
-    }
+    int rc = read_bbox(r, st);
+    if (rc) return rc;
   }
   r->have_s0 = true;
   return SR_OK;
 }
 
 int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_trace_stats *stats) {
+  const TraceKnobs knobs = trace_knobs();
   SR_CHECK(r && v && p, "sr_rays_trace: NULL argument");
   SR_CHECK((p->handoff & ~(SR_HANDOFF_ENTER | SR_HANDOFF_EXIT)) == 0, "handoff must be a combination of SR_HANDOFF_*");
   const bool ho_enter = (p->handoff & SR_HANDOFF_ENTER) != 0;
@@ -1536,9 +1514,16 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   VolDev V = vol_dev(v);
   r->tile_segs = r->tile_segs_run = 0;
   r->tile_rec = false;
+  // The tile path?  Planned as if the ready-made records can be had; a plan that uses them has them built (once per volume), and
+  // is made again without them where they do not fit.
   TilePlan tplan;
-  const bool tiled = tile_plan(r, v, p, N, tplan, st);
-  const TileGeom &tile_geom = tplan.g;
+  bool tiled = tile_plan(r, v, p, N, knobs, true, tplan);
+  if (tiled && tplan.rec) {
+    bool have = false;
+    int rc = tile_records(v, knobs, st, have);
+    if (rc) return rc;
+    if (!have) tiled = tile_plan(r, v, p, N, knobs, false, tplan);
+  }
 
   SR_HIP(hipEventRecord(c.ev[0], st));
   if (r->counters_carry)  // totals of earlier calls are still unread: only this call's queue lengths start at zero
@@ -1554,7 +1539,7 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   } else if (ho_enter) {  // arrival order is the sender's launch order (already binned); the ray index rides in row 9
     hipLaunchKernelGGL(k_perm_from_rec, dim3(nblk), dim3(block), 0, st, (const double *)r->rec, N, r->perm);
   } else if (p->sort_rays && tiled) {  // the band order of trace_tile.inc
-    int rc = bin_by_band(r, v, tile_geom, nullptr, r->perm, st);
+    int rc = bin_by_band(r, v, tplan.g, nullptr, r->perm, st);
     if (rc) return rc;
   } else if (p->sort_rays) {
     int bits = 1;
@@ -1587,29 +1572,23 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   if (mixed) {
     launch_mx(v, A, st);
     SR_HIP(hipEventRecord(c.ev[2], st));
-    // second level: the queue of the mixed kernel; its own rejects go to a second list (the sort keys' buffer,
-    // free once the permutation exists)
-    A.in_list = r->fb_list;
-    A.in_count = r->counters + 1;
-    A.out_list = r->keys;
-    A.out_count = r->counters + 2;
-    launch_planes64(v, p, A, st);
   } else if (tiled) {
     // the tile kernel over every ray, in segments of node planes; what it loses (rays leaving their workgroup's tile or the
     // volume, rays that are not plane-form rays) is queued for k_trace_f64, from s0
-    int rc = trace_tiled(r, v, p, tplan, A, st);
+    int rc = trace_tiled(r, v, p, knobs, tplan, A, st);
     if (rc) return rc;
     A.rec = r->rec;  // the record buffers may have changed places
+  }
+  if (mixed || tiled) {
+    // second level: the queue of the first kernel; its own rejects go to a second list (the sort keys' buffer, free once the
+    // permutation exists)
     A.in_list = r->fb_list;
     A.in_count = r->counters + 1;
     A.out_list = r->keys;
     A.out_count = r->counters + 2;
-    launch_planes64(v, p, A, st);
-    SR_HIP(hipEventRecord(c.ev[2], st));
-  } else {
-    launch_planes64(v, p, A, st);
-    SR_HIP(hipEventRecord(c.ev[2], st));
   }
+  launch_planes64(v, p, knobs, A, st);
+  if (!mixed) SR_HIP(hipEventRecord(c.ev[2], st));
   // Not on a slab, which holds only its own planes (the plane kernel has written NaN for such rays).
   if (!p->handoff) launch_time(v, A, st);
   hipLaunchKernelGGL(k_carry, dim3(1), dim3(1), 0, st, r->counters);
@@ -1669,12 +1648,7 @@ double sr_tile_min_density(void) { return kTileMinDensity; }
 
 int sr_rays_download(const sr_rays *r, double *sf, double *rf, double *Jf) {
   SR_CHECK(r != nullptr, "sr_rays_download: NULL rays");
-  return download_rows(r, sf, rf, Jf, r->n, 0, nullptr);
-}
-
-__global__ void k_unpermute_f32(const float *__restrict__ src, float *__restrict__ dst, const uint32_t *__restrict__ perm, int64_t N) {
-  const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (j < N) dst[perm[j]] = src[j];
+  return sr::download_rows(r, sf, rf, Jf, r->n, 0, nullptr);
 }
 
 int sr_rays_error_bound(const sr_rays *r, float *bound) {
@@ -1756,42 +1730,12 @@ int sr_rays_get_bbox(const sr_rays *r, double *bbox, int *known) {
 
 int sr_volume_sample(const sr_volume *v, const double *pts, int64_t N, double *out) {
   SR_CHECK(v && N >= 0 && (N == 0 || (pts && out)), "sr_volume_sample: bad argument");
-  if (N == 0) return SR_OK;
-  hipStream_t st = sr::ctx().stream;
-  double *d = nullptr;
-  int rc = sr::dev_alloc(&d, (size_t)7 * N);
-  if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(d, pts, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_sample, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, vol_dev(v), v->axis, v->L != nullptr,
-                       (const double *)d, N, d + 3 * N);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * N, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  sr::dev_free(d);
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_volume_sample: %s", hipGetErrorString(e));
-  return SR_OK;
+  return sample_points(v, pts, N, out, false, "sr_volume_sample");
 }
 
 int sr_volume_sample_aux(const sr_volume *v, const double *pts, int64_t N, double *out) {
   SR_CHECK(v && N >= 0 && (N == 0 || (pts && out)), "sr_volume_sample_aux: bad argument");
-  if (N == 0) return SR_OK;
-  hipStream_t st = sr::ctx().stream;
-  double *d = nullptr;
-  int rc = sr::dev_alloc(&d, (size_t)8 * N);
-  if (rc) return rc;
-  hipError_t e = hipMemcpyAsync(d, pts, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_sample_aux, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, vol_dev(v), v->axis, (const double *)d, N,
-                       d + 3 * N);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * N, sizeof(double) * 5 * N, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  sr::dev_free(d);
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_volume_sample_aux: %s", hipGetErrorString(e));
-  return SR_OK;
+  return sample_points(v, pts, N, out, true, "sr_volume_sample_aux");
 }
 
 int sr_ray_to_jones(const double *sf, int64_t N, double extent, int probing_axis, int row_order, double *rf, double *Jf) {
@@ -1816,334 +1760,6 @@ int sr_ray_to_jones(const double *sf, int64_t N, double extent, int probing_axis
   sr::dev_free(d);
   if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_ray_to_jones: %s", hipGetErrorString(e));
   return SR_OK;
-}
-
-// The host-buffer entry point on a large bundle: the rays go through in chunks that alternate between the library's two
-// streams, so that the upload of chunk i+1 and the download of chunk i-1 (host-synchronous copies of pageable memory)
-// run while chunk i is traced (the traces themselves one after the other: see `serial` below).  Rays are independent and every output row is written at its own rays' columns: the
-// arrays are those of the single pass, bit for bit.  No hipMalloc / hipFree inside the loop after the first two chunks
-// (hipFree waits for every stream).
-static int64_t pipeline_chunk() {
-  const char *e = getenv("SYNTHRAY_TRACE_CHUNK");  // most rays per chunk; 0 = never pipeline
-  // 2.5 * 2^20: 1e7 rays in four chunks of 2.5e6, dense enough for the tile path's records kernel (15 rays per cell of a 4 mm
-  // beam on 512^3) -- 77.7 ms per call with page-locked result arrays; 2^20: 79.5, 1.5 * 2^20: 84 (chunks at the tile path's
-  // threshold, where it is no faster than the per-ray kernel), 2^21: 80, 3.4e6: 77.7, 5e6: 80.5 (profiles/r05_pcie_host_arrays.txt)
-  return e ? atoll(e) : (int64_t)5 << 19;
-}
-
-// Result arrays that are ordinary (pageable, never written) NumPy memory cost a page fault per 4 KB when the copy engine's
-// staging thread first writes them: 1.36 GB of sf / rf / Jf for 1e7 rays, more time than the trace.  MADV_POPULATE_WRITE
-// maps the pages WITHOUT touching their contents (safe beside copies already landing), and several threads do it side by
-// side while the first chunks are uploaded and traced.  Page-locked arrays (sr_host_alloc) are left alone.
-static void populate_pages(double *p, size_t bytes, std::vector<std::thread> &pool) {
-  if (!p || bytes < ((size_t)8 << 20)) return;
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type != hipMemoryTypeUnregistered) return;  // page-locked already
-  (void)hipGetLastError();
-  const uintptr_t page = 4096, lo = ((uintptr_t)p + page - 1) & ~(page - 1), hi = ((uintptr_t)p + bytes) & ~(page - 1);
-  if (hi <= lo) return;
-  const int n_thr = 4;
-  const uintptr_t per = (((hi - lo) / n_thr) + page - 1) & ~(page - 1);
-  for (int t = 0; t < n_thr; ++t) {
-    const uintptr_t a = lo + (uintptr_t)t * per, b = std::min(hi, a + per);
-    if (a < b) pool.emplace_back([a, b]() { (void)madvise((void *)a, b - a, 23 /* MADV_POPULATE_WRITE */); });
-  }
-}
-
-// The device side of trace_pipelined -- three chunk-sized ray bundles and two staging blocks, ~2.5 GB of HBM at the default
-// chunk -- is KEPT between calls (a loop of solve() calls: ~40 hipMalloc + ~40 hipFree, each of which waits for the device,
-// were 6 of a call's 85 ms).  Released by sr_release_caches(), by a call with another chunk size or device, and not kept at
-// all with SYNTHRAY_TRACE_CACHE=0.
-namespace {
-struct PipelineCache {
-  int64_t chunk = 0;
-  int device = -1;
-  sr_rays *ring[3] = {nullptr, nullptr, nullptr};
-  double *staging[2] = {nullptr, nullptr};
-} g_pipe;
-void release_pipeline_cache() {
-  for (auto &r : g_pipe.ring) {
-    if (r) sr_rays_destroy(r);
-    r = nullptr;
-  }
-  for (auto &q : g_pipe.staging) {
-    sr::dev_free(q);
-    q = nullptr;
-  }
-  g_pipe.chunk = 0;
-  g_pipe.device = -1;
-}
-}  // namespace
-
-int sr_release_caches(void) {
-  if (sr::ctx().stream) (void)sr_synchronize();
-  release_pipeline_cache();
-  sr::scratch_release();
-  return SR_OK;
-}
-
-static int trace_pipelined(const sr_volume *v, const double *s0, int64_t N, const sr_trace_params *p, double *sf, double *rf,
-                           double *Jf, sr_trace_stats *stats, int64_t cap) {
-  sr::Context &c = sr::ctx();
-  const int saved = c.current;
-  // `cap`: the most rays of a chunk (what the bundles, staging blocks and bounce buffers are sized for, and what the cache is
-  // kept by); the chunks themselves are EQUAL parts of this call's rays -- 1e7 rays: 4 x 2.5e6, not 3 x 2.62e6 and a rest at a
-  // lower ray density (the density chooses the kernel)
-  const int64_t n_chunks = std::max<int64_t>(2, (N + cap - 1) / cap);
-  int64_t chunk = std::min(cap, (N + n_chunks - 1) / n_chunks);
-  if ((n_chunks - 1) * chunk >= N) chunk = cap;  // (only chunks of a few rays: n_chunks^2 > N)
-  const int64_t last = N - (n_chunks - 1) * chunk;
-  constexpr int kRing = 3;  // bundles in flight: one being traced on each of the two streams, one being uploaded
-  sr_rays *ring[kRing] = {nullptr, nullptr, nullptr};
-  double *staging[2] = {nullptr, nullptr};
-  sr_trace_stats tot{0, 0, 0.0, 0.0};
-  int rc = SR_OK;
-  std::vector<std::thread> faulters;
-  populate_pages(sf, sizeof(double) * 9 * (size_t)N, faulters);
-  populate_pages(rf, sizeof(double) * 4 * (size_t)N, faulters);
-  populate_pages(Jf, sizeof(double) * 4 * (size_t)N, faulters);
-  const char *ce = getenv("SYNTHRAY_TRACE_CACHE");
-  const bool keep = !(ce && ce[0] == '0');
-  if (g_pipe.chunk != cap || g_pipe.device != c.device) release_pipeline_cache();
-  for (int q = 0; q < kRing; ++q) {  // from the cache (whole set or nothing)
-    ring[q] = g_pipe.ring[q];
-    g_pipe.ring[q] = nullptr;
-  }
-  for (int q = 0; q < 2; ++q) {
-    staging[q] = g_pipe.staging[q];
-    g_pipe.staging[q] = nullptr;
-  }
-  g_pipe.chunk = 0;
-  for (int q = 0; q < kRing && q < n_chunks && !rc; ++q)
-    if (!ring[q]) rc = sr_rays_create(&ring[q], cap);  // a chunk may use part of one
-  for (int q = 0; q < 2 && !rc; ++q) {
-    rc = sr_stream_select(q);
-    if (!rc && !staging[q]) rc = sr::dev_alloc(&staging[q], (size_t)17 * (size_t)cap);
-  }
-  // events: uploaded[ci] (recorded by the uploader on its own stream), traced[ci] (recorded after chunk ci's trace)
-  std::vector<hipEvent_t> uploaded((size_t)n_chunks, nullptr), traced((size_t)n_chunks, nullptr);
-  // per chunk: the launch positions' bounding box (min x, y, z, max x, y, z), written by the uploader's copier threads before the
-  // chunk is announced (n_uploaded, under the mutex); lo > hi: not known
-  std::vector<std::array<double, 6>> boxes((size_t)n_chunks, std::array<double, 6>{1, 1, 1, 0, 0, 0});
-  for (int64_t ci = 0; ci < n_chunks && !rc; ++ci) {
-    if (hipEventCreateWithFlags(&uploaded[ci], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&traced[ci], hipEventDisableTiming) != hipSuccess)
-      rc = sr::fail(SR_ERR_HIP, "sr_trace: hipEventCreate failed");
-  }
-  // ---- the uploader: a host thread of its own, because a copy FROM pageable memory holds the thread that asked for it
-  // (staged through the runtime's bounce buffers at ~15 GB/s): on the caller's thread every chunk's upload delayed the
-  // download of the chunk before it and the launch of the chunk after it.
-  std::mutex mu;
-  std::condition_variable cv;
-  int64_t n_uploaded = 0, n_traced = 0;  // chunks whose `uploaded` / `traced` event has been RECORDED (guarded by mu)
-  bool abort_upload = false;
-  hipError_t up_err = hipSuccess;
-  const int device = c.device;
-  // Page-locked bounce buffers of the library's own (two chunks' worth, allocated at the first large sr_trace and kept): the
-  // runtime's copy from pageable memory runs on ONE thread at ~8 GB/s -- 90 ms for the 0.72 GB of 1e7 rays, more than their
-  // trace; four threads copying into a page-locked buffer and a DMA from there move them in a quarter of that.
-  static double *bounce[2] = {nullptr, nullptr};
-  static size_t bounce_rays = 0;
-  if (!rc && bounce_rays < (size_t)cap) {
-    for (auto &b : bounce) {
-      if (b) (void)hipHostFree(b);
-      b = nullptr;
-    }
-    bounce_rays = 0;
-    if (hipHostMalloc(reinterpret_cast<void **>(&bounce[0]), sizeof(double) * 9 * (size_t)cap, hipHostMallocDefault) == hipSuccess &&
-        hipHostMalloc(reinterpret_cast<void **>(&bounce[1]), sizeof(double) * 9 * (size_t)cap, hipHostMallocDefault) == hipSuccess)
-      bounce_rays = (size_t)cap;
-    else
-      (void)hipGetLastError();  // no page-locked memory to be had: the runtime's own staging does (slower)
-  }
-  const bool use_bounce = bounce_rays >= (size_t)cap;
-  std::thread uploader;
-  if (!rc) uploader = std::thread([&]() {
-    hipStream_t us = nullptr;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&us, hipStreamNonBlocking);
-    hipEvent_t bounce_free[2] = {nullptr, nullptr};
-    for (auto &b : bounce_free)
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&b, hipEventDisableTiming);
-    for (int64_t ci = 0; ci < n_chunks && e == hipSuccess; ++ci) {
-      if (ci >= kRing) {  // the bundle is free again once the trace that read it is done
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          cv.wait(lk, [&] { return abort_upload || n_traced > ci - kRing; });
-          if (abort_upload) break;
-        }
-        e = hipEventSynchronize(traced[ci - kRing]);
-        if (e != hipSuccess) break;
-      }
-      sr_rays *r = ring[ci % kRing];
-      const int64_t off = ci * chunk, n = ci + 1 < n_chunks ? chunk : last;
-      if (use_bounce) {
-        double *bb = bounce[ci & 1];
-        if (ci >= 2) e = hipEventSynchronize(bounce_free[ci & 1]);  // the DMA that last read this buffer
-        std::thread copiers[3];
-        // the three position rows are read for their bounding box while they are copied (the chunk's rays per lateral cell of
-        // the BEAM choose its kernel, as for a bundle uploaded whole: tile_plan); NaN positions compare false and are left out
-        auto copy_rows = [&](int q0, int q1) {
-          for (int q = q0; q < q1; ++q) {
-            const double *src = s0 + (size_t)q * N + off;
-            double *dst = bb + (size_t)q * n;
-            if (q < 3) {
-              double lo = __builtin_inf(), hi = -__builtin_inf();
-              for (int64_t t = 0; t < n; ++t) {
-                const double x = src[t];
-                dst[t] = x;
-                lo = x < lo ? x : lo;
-                hi = x > hi ? x : hi;
-              }
-              boxes[(size_t)ci][q] = lo;
-              boxes[(size_t)ci][3 + q] = hi;
-            } else {
-              memcpy(dst, src, sizeof(double) * (size_t)n);
-            }
-          }
-        };
-        copiers[0] = std::thread(copy_rows, 2, 4);
-        copiers[1] = std::thread(copy_rows, 4, 6);
-        copiers[2] = std::thread(copy_rows, 6, 9);
-        copy_rows(0, 2);
-        for (auto &t : copiers) t.join();
-        if (e == hipSuccess) e = hipMemcpyAsync(r->s0, bb, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, us);  // rows at pitch n
-        if (e == hipSuccess) e = hipEventRecord(bounce_free[ci & 1], us);
-      } else {
-        for (int q = 0; q < 9 && e == hipSuccess; ++q)  // rows of n rays at pitch n: a shorter last chunk uses the front of a full-size bundle
-          e = hipMemcpyAsync(r->s0 + (size_t)q * n, s0 + (size_t)q * N + off, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, us);
-      }
-      if (e == hipSuccess) e = hipEventRecord(uploaded[ci], us);
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        if (e == hipSuccess) n_uploaded = ci + 1;
-      }
-      cv.notify_all();
-    }
-    if (us) {
-      (void)hipStreamSynchronize(us);
-      (void)hipStreamDestroy(us);
-    }
-    for (auto &b : bounce_free)
-      if (b) (void)hipEventDestroy(b);
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      up_err = e;
-      if (e != hipSuccess) abort_upload = true;
-    }
-    cv.notify_all();
-  });
-  struct Pending {
-    sr_rays *r;
-    int64_t off, n;
-    int sid;
-  } prev{nullptr, 0, 0, 0};
-  auto finish = [&](const Pending &q) -> int {  // waits for the chunk's trace (its stream), copies its rows out, adds its totals
-    int e = sr_stream_select(q.sid);
-    if (!e) e = download_rows(q.r, sf, rf, Jf, N, q.off, staging[q.sid]);
-    sr_trace_stats st{0, 0, 0.0, 0.0};
-    if (!e) e = sr_rays_trace_stats(q.r, &st);
-    tot.ray_steps += st.ray_steps;
-    tot.fallback_rays += st.fallback_rays;
-    tot.trace_kernel_ms += st.trace_kernel_ms;
-    tot.total_ms += st.total_ms;
-    return e;
-  };
-  const bool dbg = getenv("SYNTHRAY_TRACE_DEBUG") != nullptr;
-  // The chunks' TRACES run one after the other, each behind the one before (an event wait; the streams still alternate, so
-  // the download of chunk i runs beside the trace of chunk i+1): two traces side by side finish together, and the first one's
-  // download then overlaps nothing -- 104 -> 91 ms per 1e7 rays at 2^21-ray chunks, 119 -> 104 at 5e6.  SYNTHRAY_TRACE_SERIAL=0:
-  // side by side, as before.
-  const bool serial = getenv("SYNTHRAY_TRACE_SERIAL") ? atoi(getenv("SYNTHRAY_TRACE_SERIAL")) != 0 : true;
-  auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_begin = now_ms();
-  for (int64_t ci = 0; ci < n_chunks && !rc; ++ci) {
-    const int sid = (int)(ci & 1);
-    const int64_t off = ci * chunk, n = ci + 1 < n_chunks ? chunk : last;
-    rc = sr_stream_select(sid);
-    if (rc) break;
-    const double t_a = now_ms();
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return abort_upload || n_uploaded > ci; });
-      if (abort_upload) {
-        rc = sr::fail(SR_ERR_HIP, "sr_trace: upload of rays %lld..: %s", (long long)off, hipGetErrorString(up_err));
-        break;
-      }
-    }
-    sr_rays *r = ring[ci % kRing];
-    if (hipStreamWaitEvent(c.stream, uploaded[ci], 0) != hipSuccess ||
-        (serial && ci > 0 && hipStreamWaitEvent(c.stream, traced[ci - 1], 0) != hipSuccess)) {
-      rc = sr::fail(SR_ERR_HIP, "sr_trace: hipStreamWaitEvent failed");
-      break;
-    }
-    r->n = n;  // a shorter last chunk: the front of a full-size bundle (its rows were uploaded at pitch n)
-    r->have_bbox = true;   // found by the uploader's copier threads while they copied the position rows
-    for (int q = 0; q < 6; ++q) r->bbox[q] = boxes[(size_t)ci][q];
-    for (int q = 0; q < 3; ++q)
-      if (!(r->bbox[q] <= r->bbox[3 + q])) r->have_bbox = false;  // no bounce buffers (the runtime staged the rows), or every position NaN
-    r->have_s0 = true;
-    r->traced = false;
-    rc = sr_rays_trace(r, v, p, nullptr);  // queued; returns at once
-    if (!rc && hipEventRecord(traced[ci], c.stream) != hipSuccess) rc = sr::fail(SR_ERR_HIP, "sr_trace: hipEventRecord failed");
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      n_traced = ci + 1;
-    }
-    cv.notify_all();
-    if (rc) break;
-    const double t_b = now_ms();
-    if (prev.r) rc = finish(prev);  // the chunk before this one, on the other stream
-    if (dbg) fprintf(stderr, "sr_trace chunk %lld: at %.1f ms waited %.1f ms for its upload, queued in %.1f ms, finish(prev) %.1f ms\n", (long long)ci,
-                     t_a - t_begin, t_b - t_a, 0.0, now_ms() - t_b);
-    prev = Pending{r, off, n, sid};
-  }
-  {
-    const double t_b = now_ms();
-    if (!rc && prev.r) rc = finish(prev);
-    if (dbg) fprintf(stderr, "sr_trace last finish at %.1f ms: %.1f ms\n", t_b - t_begin, now_ms() - t_b);
-  }
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    if (rc) abort_upload = true;
-  }
-  cv.notify_all();
-  if (uploader.joinable()) uploader.join();
-  for (auto &t : faulters) t.join();
-  (void)sr_synchronize();
-  for (int q = 0; q < kRing; ++q)
-    if (ring[q]) ring[q]->n = cap;
-  if (keep && !rc) {  // for the next call
-    for (int q = 0; q < kRing; ++q) g_pipe.ring[q] = ring[q];
-    for (int q = 0; q < 2; ++q) g_pipe.staging[q] = staging[q];
-    g_pipe.chunk = cap;
-    g_pipe.device = c.device;
-  } else {
-    for (int q = 0; q < kRing; ++q) sr_rays_destroy(ring[q]);
-    for (int q = 0; q < 2; ++q) sr::dev_free(staging[q]);
-  }
-  for (auto e : uploaded)
-    if (e) (void)hipEventDestroy(e);
-  for (auto e : traced)
-    if (e) (void)hipEventDestroy(e);
-  (void)sr_stream_select(saved);
-  if (stats) *stats = tot;
-  return rc;
-}
-
-int sr_trace(const sr_volume *v, const double *s0, int64_t n_rays, const sr_trace_params *p, double *sf, double *rf,
-             double *Jf, sr_trace_stats *stats) {
-  SR_CHECK(v && s0 && p, "sr_trace: NULL argument");
-  const int64_t chunk = pipeline_chunk();
-  // from 1.2 chunks' worth of rays: two equal chunks (3.1e6 rays and more at the default, as before the chunks grew)
-  if (chunk > 0 && n_rays >= chunk + chunk / 5 && n_rays >= 2 && !p->handoff) return trace_pipelined(v, s0, n_rays, p, sf, rf, Jf, stats, chunk);
-  sr_rays *r = nullptr;
-  int rc = sr_rays_create(&r, n_rays);
-  if (rc) return rc;
-  rc = sr_rays_upload(r, s0);
-  if (!rc) rc = sr_rays_trace(r, v, p, stats);
-  if (!rc) rc = sr_rays_download(r, sf, rf, Jf);
-  sr_rays_destroy(r);
-  return rc;
 }
 
 }  // extern "C"

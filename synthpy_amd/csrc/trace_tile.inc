@@ -74,9 +74,9 @@ struct TileArgs {
   // the next slab (SR_HANDOFF_EXIT) instead of becoming sf / rf / Jf; slab: there are no further levels (a slab holds only its own
   // planes): a ray the plane form cannot finish comes out NaN, as from k_trace_f64 on a slab
   int exit_rec, slab;
-  int rot;          // 1: the producers' wavefront rotates with the workgroup index (see `producer` in the kernel)
-  // A launch may take a RANGE of the bundle's workgroups: block0 = the first one, A.n_blocks = how many (the last segment goes in
-  // two launches, so that the first part's stragglers are carried beside the second part: trace_tiled)
+  int rot;          // 1: the producers' wavefront rotates with the workgroup index (see `producer` in the kernel).  The host sets 0
+  // A launch may take a RANGE of the bundle's workgroups: block0 = the first one, A.n_blocks = how many.  The host always sets 0
+  // and every workgroup: both experiments were measured and ended (docs/HISTORY.md); the arguments stay until the kernel is next timed
   unsigned block0;
   // Not the first segment: the state comes from rec_in[row][order[j]] (the records the segment before wrote -- or a slab's
   // arrivals -- read through the order of the new binning); A.rec is the OTHER buffer, written in place j; perm_out[j] = the
