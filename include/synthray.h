@@ -411,6 +411,39 @@ int sr_rays_optics(const sr_rays *r, const sr_optic *chain, int n_ops, const sr_
 int sr_rays_refine(const sr_rays *r, int n_diag, const sr_optic *const *chains, const int *n_ops,
                    sr_image *const *imgs, int64_t *retraced);
 
+/* ---- polarimetry: analyser-weighted intensity images of the traced rays ---------
+ * None of these entries has a reference counterpart: the reference forms the exit Jones vector
+ * E = amp*exp(i*phase)*(-sin pol, cos pol) (full_solver.py:838-894) and shows it through counts and coherent sums only.
+ * An ANALYSER at angle beta (from the y axis, in the sense `pol` is measured) has the transmission axis
+ * (a, b) = (-sin beta, cos beta); a ray's weight in that channel is
+ *   w = |a E_x + b E_y|^2 = (a Re E_x + b Re E_y)^2 + (a Im E_x + b Im E_y)^2     (= amp^2 cos^2(pol - beta)),
+ * and a channel given as (NaN, NaN) has no analyser: w = |E_x|^2 + |E_y|^2 (the attenuation image).  a and b are formed
+ * by the caller in float64 and passed down, so host and device work with the same two numbers. */
+#define SR_IMG_INTENSITY 2 /* float64 [n_ch][ny][nx], A9 binning; nx, ny = number of bins */
+#define SR_MAX_ANALYSERS 4
+/* no reference counterpart: an image I[c][iy][ix] = sum of w_c over the rays of pixel (iy, ix), np.histogram2d's binning
+ * (the geometry of SR_IMG_COUNTS).  sr_image_zero / _download (float64 buffer) / _bytes / _destroy / _reduce (float64 sum)
+ * take it as they take the other kinds. */
+int sr_image_create_intensity(sr_image **out, int n_ch, int nx, int ny, double x_lo, double x_hi,
+                              double y_lo, double y_hi);
+/* no reference counterpart: I += sum of w over the bundle's rays the masks of the chain leave un-rejected; exit rays in
+ * HBM -> m_to_mm -> chain (masks and geometry only: the sum is incoherent, the field factors of its legs have modulus 1
+ * and no reference beam is added) -> np.histogram2d's bin -> up to SR_MAX_ANALYSERS channels in one pass.  lds_tiles as in
+ * sr_deposit_params.  No edge guard: intensities are floating-point sums, a mixed-precision bundle is binned as it is.
+ * Errors: bundle not traced, bundle traced without Jf, n_ch different from the image's. */
+int sr_rays_deposit_intensity(const sr_rays *r, const sr_optic *chain, int n_ops,
+                              const double *analyser_ab /* [n_ch][2] = (a, b); NaN, NaN = no analyser */, int n_ch,
+                              int lds_tiles, sr_image *img, sr_deposit_stats *stats);
+/* no reference counterpart: the host-array form of the same sums (as sr_hist2d is to the counts image): x, y are
+ * detector-plane coordinates (NaN: rejected), E (2, N) complex128, I [n_ch][ny_bins][nx_bins] float64 (overwritten). */
+int sr_intensity2d(const double *x, const double *y, const double *E, int64_t n_rays, const double *analyser_ab, int n_ch,
+                   int nx_bins, int ny_bins, double x_lo, double x_hi, double y_lo, double y_hi, double *I);
+/* no reference counterpart: the rotation map of two channels at +beta and -beta, 0 < beta < pi/2:
+ *   D = (I+ - I-)/(I+ + I-), R = hypot(sin 2beta, D cos 2beta), delta = atan2(D cos 2beta, sin 2beta),
+ *   alpha = (delta + asin(D/R))/2, NaN where I+ + I- == 0; unambiguous for |alpha| < min(beta, pi/2 - beta);
+ * beta = pi/4: alpha = asin(D)/2. */
+int sr_image_rotation(const sr_image *img, int ch_plus, int ch_minus, double beta, double *alpha /* [ny][nx] */);
+
 /* ---- ray-sharded multi-GPU: sum of the per-GPU images (RCCL over xGMI) ---------
  * replaces comm.reduce(sh.H, root=0, op=MPI.SUM): examples/jobs/run_scripts/pvti_trace_mpi.py:169-170,
  * interference_MPI.py:189.  The 128-byte id is made on rank 0 and handed to the other ranks by the

@@ -42,6 +42,7 @@ class FresnelParams(C.Structure):
 FRESNEL_STATS = 6  # SR_FRESNEL_STATS
 
 MAX_REF_BEAMS = 4  # SR_MAX_REF_BEAMS
+MAX_ANALYSERS = 4  # SR_MAX_ANALYSERS
 
 
 class DepositParams(C.Structure):
@@ -122,6 +123,10 @@ SYMBOLS = {
     "sr_image_destroy": (None, [_vp]),
     "sr_rays_deposit": (_i, [_vp, C.POINTER(Optic), _i, C.POINTER(DepositParams), _vp, C.POINTER(DepositStats)]),
     "sr_rays_refine": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
+    "sr_image_create_intensity": (_i, [_pp, _i, _i, _i, _d, _d, _d, _d]),
+    "sr_rays_deposit_intensity": (_i, [_vp, C.POINTER(Optic), _i, _vp, _i, _i, _vp, C.POINTER(DepositStats)]),
+    "sr_intensity2d": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _i, _d, _d, _d, _d, _vp]),
+    "sr_image_rotation": (_i, [_vp, _i, _i, _d, _vp]),
     "sr_comm_unique_id": (_i, [_vp]),
     "sr_comm_create": (_i, [_pp, _vp, _i, _i]),
     "sr_image_reduce": (_i, [_vp, _vp, _i]),

@@ -223,7 +223,8 @@ int download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int64_t 
 
 struct sr_image {
   int kind = 0;
-  int nx = 0, ny = 0;  // bins (counts) or edges (complex)
+  int nx = 0, ny = 0;  // bins (counts, intensity) or edges (complex)
+  int n_ch = 0;        // intensity: channels
   double x_lo = 0, x_hi = 0, y_lo = 0, y_hi = 0;
   void *d = nullptr;
   int64_t bytes = 0;

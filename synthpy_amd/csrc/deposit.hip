@@ -1,6 +1,7 @@
 // A7-A11 on the device: ray-transfer-matrix optics (rtm_solver.py:48-136 and the chains
 // :197-286, :376-422), Rays.histogram = np.histogram2d (:156-178), Interferometry.interferogram
-// (:424-453) and interfere_ref_beam (diagnostics.py:559-581).
+// (:424-453) and interfere_ref_beam (diagnostics.py:559-581).  Beyond the reference: analyser-weighted intensity images
+// of the same rays and the rotation map of an analyser pair (k_deposit_intensity, k_intensity2d, k_rotation).
 //
 // Detector arithmetic is integer work downstream of a float64 coordinate, so the coordinate
 // has to round exactly as the reference's: this file is compiled with -ffp-contract=off and
@@ -460,6 +461,137 @@ __global__ __launch_bounds__(256) void k_deposit_list(Chain C, int64_t N, const 
   if (hits) atomicAdd(sr::stripe(counter, 1), hits);
 }
 
+// ---- polarimetry: analyser-weighted intensity images (no reference counterpart) ------------------------------------
+// Channel c holds the analyser's transmission axis (a, b) = (-sin beta, cos beta); a ray's weight there is
+// |a E_x + b E_y|^2, or |E_x|^2 + |E_y|^2 for a channel without analyser (a NaN).  The sums are incoherent: the field
+// factors of a chain's legs have modulus 1 and drop out, so the masks-only chain is all a ray needs.
+struct Analysers {
+  double a[SR_MAX_ANALYSERS], b[SR_MAX_ANALYSERS];
+};
+
+__device__ __forceinline__ double analyser_weight(const Analysers &A, int c, double e0r, double e0i, double e1r, double e1i) {
+  const double a = A.a[c], b = A.b[c];
+  if (a != a) return (e0r * e0r + e0i * e0i) + (e1r * e1r + e1i * e1i);
+  const double re = a * e0r + b * e1r, im = a * e0i + b * e1i;
+  return re * re + im * im;
+}
+
+// host-array form (sr_intensity2d): x, y already through the chain, np.histogram2d's binning with weights
+template <int NCH>
+__global__ void k_intensity2d(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ E, int64_t N,
+                              Edges ex, Edges ey, Analysers A, double *__restrict__ I) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const double xv = x[i], yv = y[i];
+  if (xv != xv || yv != yv) return;
+  const int bx = bin_hist(ex, xv), by = bin_hist(ey, yv);
+  if (bx < 0 || by < 0) return;
+  const int64_t plane = (int64_t)ex.n * ey.n, p = (int64_t)by * ex.n + bx;
+  const double e0r = E[2 * i], e0i = E[2 * i + 1], e1r = E[2 * (N + i)], e1i = E[2 * (N + i) + 1];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const double w = analyser_weight(A, c, e0r, e0i, e1r, e1i);
+    if (w != 0.0) unsafeAtomicAdd(&I[c * plane + p], w);
+  }
+}
+
+// Fused intensity deposit: exit-plane rays in HBM (metres) -> m_to_mm -> masks-only chain -> bin_hist -> NCH weighted
+// float64 sums per ray in ONE pass.  Laid out as k_deposit: one ray per work-item, the workgroup's patch origin by LDS
+// atomicMin, and with TILED a [NCH][TH][TW] tile of doubles in LDS (16 KiB at four channels: the complex tile's known-good
+// size) that is flushed channel by channel, row by row, with one global atomic per non-zero (bin, channel).
+constexpr int kITileW = 32, kITileH = 16;
+
+template <int NCH, bool TILED>
+__global__ __launch_bounds__(256) void k_deposit_intensity(Chain C, int64_t N, const double *__restrict__ rf,
+                                                           const double *__restrict__ Jf, Edges ex, Edges ey, Analysers A,
+                                                           double *__restrict__ img, unsigned long long *__restrict__ counter) {
+  constexpr int TW = kITileW, TH = kITileH, TB = TW * TH;
+  __shared__ int org[2];
+  __shared__ double tile[TILED ? TB * NCH : 1];
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (TILED) {
+    if (threadIdx.x < 2) org[threadIdx.x] = 0x7fffffff;
+    for (int t = threadIdx.x; t < TB * NCH; t += blockDim.x) tile[t] = 0.0;
+    __syncthreads();
+  }
+  int bx = -1, by = -1;
+  double w[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) w[c] = 0.0;
+  if (i < N) {
+    Ray4 r{rf[i] * 1e3, rf[N + i], rf[2 * N + i] * 1e3, rf[3 * N + i], 0, 0, 0, 0};  // m_to_mm
+    apply_chain<false>(C, r);
+    if (r.x == r.x && r.y == r.y) {
+      bx = bin_hist(ex, r.x);
+      by = bin_hist(ey, r.y);
+    }
+    if (bx >= 0 && by >= 0) {
+      const double e0r = Jf[2 * i], e0i = Jf[2 * i + 1], e1r = Jf[2 * (N + i)], e1i = Jf[2 * (N + i) + 1];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) w[c] = analyser_weight(A, c, e0r, e0i, e1r, e1i);
+    }
+  }
+  const bool hit = bx >= 0 && by >= 0;
+  int tx = -1, ty = -1;
+  if (TILED) {
+    if (hit) {
+      atomicMin(&org[0], bx);
+      atomicMin(&org[1], by);
+    }
+    __syncthreads();
+    tx = bx - org[0];
+    ty = by - org[1];
+  }
+  const bool in_tile = TILED && hit && tx < TW && ty < TH;  // tx, ty >= 0 by construction of the origin
+  const int64_t plane = (int64_t)ex.n * ey.n;
+  if (hit) {
+    if (in_tile) {
+      double *t = tile + ty * TW + tx;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+        if (w[c] != 0.0) unsafeAtomicAdd(&t[c * TB], w[c]);
+    } else {
+      double *g = img + (int64_t)by * ex.n + bx;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+        if (w[c] != 0.0) unsafeAtomicAdd(&g[c * plane], w[c]);
+    }
+  }
+  if (TILED) {
+    __syncthreads();
+    const int ox = org[0], oy = org[1];
+    if (ox != 0x7fffffff) {  // at least one hit in this workgroup
+      for (int q = threadIdx.x; q < TB * NCH; q += blockDim.x) {
+        const int c = q / TB, t = q % TB;
+        const int gx = ox + t % TW, gy = oy + t / TW;
+        if (gx >= ex.n || gy >= ey.n) continue;
+        const double s = tile[q];
+        if (s != 0.0) unsafeAtomicAdd(&img[c * plane + (int64_t)gy * ex.n + gx], s);
+      }
+    }
+  }
+  unsigned long long tot = hit ? 1ull : 0ull;
+  for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
+  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(sr::stripe(counter, 1), tot);
+}
+
+// Rotation map of two analyser channels at +beta and -beta (sr_image_rotation): D = (I+ - I-)/(I+ + I-),
+// R = hypot(sin 2b, D cos 2b), delta = atan2(D cos 2b, sin 2b), alpha = (delta + asin(D/R))/2; NaN where I+ + I- == 0
+__global__ void k_rotation(const double *__restrict__ Ip, const double *__restrict__ Im, int64_t plane, double s2b, double c2b,
+                           double *__restrict__ alpha) {
+  const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (p >= plane) return;
+  const double tot = Ip[p] + Im[p];
+  if (tot == 0.0) {
+    alpha[p] = __builtin_nan("");
+    return;
+  }
+  const double D = (Ip[p] - Im[p]) / tot, dc = D * c2b;
+  const double R = hypot(s2b, dc);
+  const double q = fmin(1.0, fmax(-1.0, D / R));  // |D| <= R up to the rounding of the hypot
+  alpha[p] = 0.5 * (atan2(dc, s2b) + asin(q));
+}
+
 // Edge guard for SEVERAL counts diagnostics at once (sr_rays_refine): a ray is queued when its pixel or a mask's decision is
 // not certain for ANY of them; one float64 re-trace then serves every deposit that follows.
 struct GuardSet {
@@ -536,6 +668,20 @@ struct DevBuf {
     return SR_OK;
   }
 };
+
+// the device buffer of a new image, zeroed (sr_image_create, sr_image_create_intensity)
+int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi, int64_t bytes);
+
+int make_analysers(const double *ab, int n_ch, Analysers &A) {
+  SR_CHECK(ab != nullptr && n_ch >= 1 && n_ch <= SR_MAX_ANALYSERS, "analysers: %d channels (1..%d), or NULL", n_ch, SR_MAX_ANALYSERS);
+  for (int c = 0; c < SR_MAX_ANALYSERS; ++c) A.a[c] = A.b[c] = 0.0;
+  for (int c = 0; c < n_ch; ++c) {
+    A.a[c] = ab[2 * c];
+    A.b[c] = ab[2 * c + 1];
+    SR_CHECK((A.a[c] != A.a[c]) == (A.b[c] != A.b[c]), "analyser %d: (a, b) must both be NaN (no analyser) or both finite", c);
+  }
+  return SR_OK;
+}
 
 }  // namespace
 
@@ -669,17 +815,35 @@ int sr_image_create(sr_image **out, int kind, int nx, int ny, double x_lo, doubl
     SR_CHECK(nx >= 1 && ny >= 1, "sr_image_create: bins must be positive");
   else
     SR_CHECK(nx >= 2 && ny >= 2, "sr_image_create: need at least 2 edges per axis");
+  return image_alloc(out, kind, 0, nx, ny, x_lo, x_hi, y_lo, y_hi,
+                     kind == SR_IMG_COUNTS ? (int64_t)sizeof(uint32_t) * nx * ny : (int64_t)sizeof(double) * 4 * (nx - 1) * (ny - 1));
+}
+
+int sr_image_create_intensity(sr_image **out, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi) {
+  SR_CHECK(out != nullptr, "sr_image_create_intensity: NULL out");
+  *out = nullptr;
+  SR_CHECK(n_ch >= 1 && n_ch <= SR_MAX_ANALYSERS, "sr_image_create_intensity: %d channels (1..%d)", n_ch, SR_MAX_ANALYSERS);
+  SR_CHECK(x_hi > x_lo && y_hi > y_lo, "sr_image_create_intensity: empty range");
+  SR_CHECK(nx >= 1 && ny >= 1, "sr_image_create_intensity: bins must be positive");
+  return image_alloc(out, SR_IMG_INTENSITY, n_ch, nx, ny, x_lo, x_hi, y_lo, y_hi, (int64_t)sizeof(double) * n_ch * nx * ny);
+}
+
+}  // extern "C"
+
+namespace {
+int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi, int64_t bytes) {
   int rc = sr::ensure_init();
   if (rc) return rc;
   sr_image *img = new sr_image();
   img->kind = kind;
+  img->n_ch = n_ch;
   img->nx = nx;
   img->ny = ny;
   img->x_lo = x_lo;
   img->x_hi = x_hi;
   img->y_lo = y_lo;
   img->y_hi = y_hi;
-  img->bytes = kind == SR_IMG_COUNTS ? (int64_t)sizeof(uint32_t) * nx * ny : (int64_t)sizeof(double) * 4 * (nx - 1) * (ny - 1);
+  img->bytes = bytes;
   hipError_t e = hipMalloc(&img->d, (size_t)img->bytes);
   if (e != hipSuccess) {
     delete img;
@@ -693,6 +857,9 @@ int sr_image_create(sr_image **out, int kind, int nx, int ny, double x_lo, doubl
   *out = img;
   return SR_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int sr_image_zero(sr_image *img) {
   SR_CHECK(img != nullptr, "sr_image_zero: NULL image");
@@ -814,6 +981,7 @@ int sr_rays_deposit(const sr_rays *r, const sr_optic *chain, int n_ops, const sr
                     sr_deposit_stats *stats) {
   SR_CHECK(r && img, "sr_rays_deposit: NULL argument");
   if (!r->traced) return sr::fail(SR_ERR_STATE, "sr_rays_deposit: rays have not been traced");
+  SR_CHECK(img->kind != SR_IMG_INTENSITY, "sr_rays_deposit: an intensity image is filled by sr_rays_deposit_intensity");
   Chain C;
   int rc = make_chain(chain, n_ops, p ? p->kwave : 0.0, C);
   if (rc) return rc;
@@ -878,6 +1046,115 @@ int sr_rays_deposit(const sr_rays *r, const sr_optic *chain, int n_ops, const sr
     stats->deposited = (int64_t)h;
     stats->retraced = exact ? (int64_t)hw[4] : 0;
   }
+  return SR_OK;
+}
+
+// ---- polarimetry (no reference counterpart) ----------------------------------------------
+int sr_intensity2d(const double *x, const double *y, const double *E, int64_t N, const double *analyser_ab, int n_ch, int nxb,
+                   int nyb, double x_lo, double x_hi, double y_lo, double y_hi, double *I) {
+  SR_CHECK(N >= 0 && (N == 0 || (x && y && E)) && I, "sr_intensity2d: bad argument");
+  SR_CHECK(nxb >= 1 && nyb >= 1, "sr_intensity2d: bins must be positive");
+  SR_CHECK(x_hi > x_lo && y_hi > y_lo, "sr_intensity2d: empty range");
+  Analysers A;
+  int rc = make_analysers(analyser_ab, n_ch, A);
+  if (rc) return rc;
+  if ((rc = sr::ensure_init())) return rc;
+  hipStream_t st = sr::ctx().stream;
+  DevBuf dx, dy, dE, dI;
+  const size_t ib = sizeof(double) * (size_t)n_ch * nxb * nyb;
+  if ((rc = dI.alloc(ib))) return rc;
+  SR_HIP(hipMemsetAsync(dI.p, 0, ib, st));
+  if (N > 0) {
+    if ((rc = dx.alloc(sizeof(double) * N)) || (rc = dy.alloc(sizeof(double) * N)) || (rc = dE.alloc(sizeof(double) * 4 * N)))
+      return rc;
+    SR_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    SR_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice, st));
+    SR_HIP(hipMemcpyAsync(dE.p, E, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
+    const Edges ex = make_edges(x_lo, x_hi, nxb), ey = make_edges(y_lo, y_hi, nyb);
+#define SR_I2D(NCH) hipLaunchKernelGGL((k_intensity2d<NCH>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx.p, \
+                                       (const double *)dy.p, (const double *)dE.p, N, ex, ey, A, (double *)dI.p)
+    switch (n_ch) {
+      case 1: SR_I2D(1); break;
+      case 2: SR_I2D(2); break;
+      case 3: SR_I2D(3); break;
+      default: SR_I2D(4); break;
+    }
+#undef SR_I2D
+    SR_HIP(hipGetLastError());
+  }
+  SR_HIP(hipMemcpyAsync(I, dI.p, ib, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  return SR_OK;
+}
+
+int sr_rays_deposit_intensity(const sr_rays *r, const sr_optic *chain, int n_ops, const double *analyser_ab, int n_ch,
+                              int lds_tiles, sr_image *img, sr_deposit_stats *stats) {
+  SR_CHECK(r && img, "sr_rays_deposit_intensity: NULL argument");
+  if (!r->traced) return sr::fail(SR_ERR_STATE, "sr_rays_deposit_intensity: rays have not been traced");
+  if (!r->Jf) return sr::fail(SR_ERR_STATE, "sr_rays_deposit_intensity: the bundle was traced without the Jones vector Jf");
+  SR_CHECK(img->kind == SR_IMG_INTENSITY, "sr_rays_deposit_intensity: image does not hold intensities");
+  SR_CHECK(n_ch == img->n_ch, "sr_rays_deposit_intensity: %d analysers for an image of %d channels", n_ch, img->n_ch);
+  Chain C;
+  int rc = make_chain(chain, n_ops, 0.0, C);
+  if (rc) return rc;
+  Analysers A;
+  if ((rc = make_analysers(analyser_ab, n_ch, A))) return rc;
+  sr::Context &c = sr::ctx();
+  hipStream_t st = c.stream;
+  const int64_t N = r->n;
+  if (stats) *stats = sr_deposit_stats{0.0, 0, 0};
+  if (N == 0) return SR_OK;
+  unsigned long long *dep_stripes = r->counters + 16 + (size_t)sr::kStripes * sr::kStripeStride;
+  SR_HIP(hipMemsetAsync(dep_stripes, 0, sizeof(unsigned long long) * sr::kStripes * sr::kStripeStride, st));
+  SR_HIP(hipEventRecord(c.ev[0], st));
+  const unsigned grid = sr::grid_for(N, 256);
+  const Edges ex = make_edges(img->x_lo, img->x_hi, img->nx), ey = make_edges(img->y_lo, img->y_hi, img->ny);
+#define SR_DEPI(NCH)                                                                                                           \
+  do {                                                                                                                         \
+    if (lds_tiles)                                                                                                             \
+      hipLaunchKernelGGL((k_deposit_intensity<NCH, true>), dim3(grid), dim3(256), 0, st, C, N, (const double *)r->rf,          \
+                         (const double *)r->Jf, ex, ey, A, (double *)img->d, r->counters);                                     \
+    else                                                                                                                       \
+      hipLaunchKernelGGL((k_deposit_intensity<NCH, false>), dim3(grid), dim3(256), 0, st, C, N, (const double *)r->rf,         \
+                         (const double *)r->Jf, ex, ey, A, (double *)img->d, r->counters);                                     \
+  } while (0)
+  switch (n_ch) {
+    case 1: SR_DEPI(1); break;
+    case 2: SR_DEPI(2); break;
+    case 3: SR_DEPI(3); break;
+    default: SR_DEPI(4); break;
+  }
+#undef SR_DEPI
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], st));
+  if (stats) {
+    std::vector<unsigned long long> hw(sr::kCounterWords, 0ull);
+    SR_HIP(hipMemcpyAsync(hw.data(), r->counters, sizeof(unsigned long long) * sr::kCounterWords, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipStreamSynchronize(st));
+    float ms = 0.f;
+    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    stats->kernel_ms = ms;
+    stats->deposited = (int64_t)sr::stripe_sum(hw.data(), 1);
+  }
+  return SR_OK;
+}
+
+int sr_image_rotation(const sr_image *img, int ch_plus, int ch_minus, double beta, double *alpha) {
+  SR_CHECK(img && alpha, "sr_image_rotation: NULL argument");
+  SR_CHECK(img->kind == SR_IMG_INTENSITY, "sr_image_rotation: image does not hold intensities");
+  SR_CHECK(ch_plus >= 0 && ch_plus < img->n_ch && ch_minus >= 0 && ch_minus < img->n_ch && ch_plus != ch_minus,
+           "sr_image_rotation: channels %d, %d of an image of %d", ch_plus, ch_minus, img->n_ch);
+  SR_CHECK(beta > 0 && beta < M_PI / 2, "sr_image_rotation: beta must lie in (0, pi/2)");
+  hipStream_t st = sr::ctx().stream;
+  const int64_t plane = (int64_t)img->nx * img->ny;
+  double *dA = static_cast<double *>(sr::scratch(sizeof(double) * plane));
+  if (!dA) return SR_ERR_HIP;
+  const double *I = (const double *)img->d;
+  hipLaunchKernelGGL(k_rotation, dim3(sr::grid_for(plane, 256)), dim3(256), 0, st, I + ch_plus * plane, I + ch_minus * plane, plane,
+                     sin(2 * beta), cos(2 * beta), dA);
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipMemcpyAsync(alpha, dA, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
   return SR_OK;
 }
 

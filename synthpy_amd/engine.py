@@ -19,7 +19,7 @@ c = 299792458.0  # scipy.constants.c, as the reference uses (full_solver.py:93)
 # optic op codes (include/synthray.h)
 OP_DIST, OP_LENS, OP_CIRC_AP, OP_CIRC_STOP, OP_RECT_AP, OP_KNIFE, OP_SCALE, OP_PHASE = range(8)
 ROWS_LEGACY, ROWS_JAX = 0, 1
-IMG_COUNTS, IMG_COMPLEX = 0, 1
+IMG_COUNTS, IMG_COMPLEX, IMG_INTENSITY = 0, 1, 2
 VOL_PHASE = 1
 
 _AXES = {"x": 0, "y": 1, "z": 2}
@@ -137,7 +137,11 @@ def resolve_precision(precision, volume, *, resident=True, handoff=0, substeps=1
     * Where no guard can follow -- host arrays out (`resident=False`: trace(), ScalarDomain.solve: the caller bins rf
       itself), slab hand-offs (a slab holds neither the rays' start nor the other planes) -- "auto" is float64; so it is with
       sub-steps and the optional terms, which the mixed build has no kernel for ("mixed" asked for by name runs the float64
-      kernels there too)."""
+        kernels there too).
+    * Intensity images (RayBundle.deposit_intensity, Diagnostic.intensity, Polarimetry) need the Jones vector of a volume
+      with the optional terms, which "auto" already traces in float64.  On a bundle traced by the mixed build the intensity
+      deposit runs WITHOUT the edge guard: intensities are floating-point outputs, and the guard exists for the integer
+      equality of counts.  Nothing in this function's result depends on it."""
     if precision in (None, "auto"):
         if getattr(volume, "phase", False) or not resident or handoff or substeps != 1 or getattr(volume, "aux", False):
             return "f64"
@@ -574,6 +578,18 @@ class RayBundle:
         self.retraced = int(st.retraced)
         return st.kernel_ms, int(st.deposited)
 
+    def deposit_intensity(self, image: "DetectorImage", ops, analysers, lds_tiles=True, want_stats=True):
+        """m_to_mm -> chain (masks and geometry only) -> np.histogram2d's bin -> image[c] += |a_c . E|^2 per analyser channel
+        (sr_rays_deposit_intensity; no reference counterpart).  analysers: angles in radians from the y axis in the sense
+        `pol` is measured, None = no analyser (|E|^2); as many as the image has channels.  An incoherent sum: no reference
+        beam, no field propagation (its factors have modulus 1).  No edge guard on a mixed-precision bundle
+        (resolve_precision).  Returns (kernel_ms, deposited rays)."""
+        ab = analyser_ab(analysers)
+        st = _ffi.DepositStats()
+        check(lib.sr_rays_deposit_intensity(self._h, make_chain(ops), len(ops), ptr(ab), len(ab), 1 if lds_tiles else 0, image._h,
+                                            C.byref(st) if want_stats else None))
+        return st.kernel_ms, int(st.deposited)
+
     def optics(self, ops=(), *, kwave=0.0, ref_beam=None, with_E=False):
         """The deposit's front end without the detector (sr_rays_optics): exit-plane rays -> m_to_mm -> [reference beams] ->
         chain, as HOST arrays in the original ray order: (r (4, N) mm, E (2, N) | None).  ops == (): r0 = m_to_mm(rf)."""
@@ -617,13 +633,18 @@ class RayBundle:
 
 
 class DetectorImage:
-    """A detector image in HBM.  kind IMG_COUNTS: nx, ny are bins (A9); IMG_COMPLEX: edges (A10)."""
+    """A detector image in HBM.  kind IMG_COUNTS: nx, ny are bins (A9); IMG_COMPLEX: edges (A10); IMG_INTENSITY: bins, and
+    n_channels float64 planes (polarimetry)."""
 
-    def __init__(self, kind, nx, ny, x_lo, x_hi, y_lo, y_hi):
+    def __init__(self, kind, nx, ny, x_lo, x_hi, y_lo, y_hi, n_channels=0):
         self.kind, self.nx, self.ny = kind, int(nx), int(ny)
+        self.n_channels = int(n_channels) if kind == IMG_INTENSITY else 0
         self.range = (float(x_lo), float(x_hi), float(y_lo), float(y_hi))
         self._h = C.c_void_p()
-        check(lib.sr_image_create(C.byref(self._h), kind, self.nx, self.ny, *self.range))
+        if kind == IMG_INTENSITY:
+            check(lib.sr_image_create_intensity(C.byref(self._h), self.n_channels, self.nx, self.ny, *self.range))
+        else:
+            check(lib.sr_image_create(C.byref(self._h), kind, self.nx, self.ny, *self.range))
 
     @classmethod
     def counts(cls, bin_scale=1, pix_x=3448, pix_y=2574, Lx=18.0, Ly=13.5):
@@ -636,12 +657,27 @@ class DetectorImage:
         division as written in the reference (rtm_solver.py:436-437): x in [-9, 9], y in [-7, 6] for the defaults."""
         return cls(IMG_COMPLEX, pix_x // bin_scale, pix_y // bin_scale, -Lx // 2, Lx // 2, -Ly // 2, Ly // 2)
 
+    @classmethod
+    def intensity(cls, n_channels=1, bin_scale=1, pix_x=3448, pix_y=2574, Lx=18.0, Ly=13.5):
+        """n_channels analyser-weighted intensity planes on the detector of Rays.histogram (np.histogram2d's binning);
+        download() gives (n_channels, ny, nx) float64.  No reference counterpart."""
+        return cls(IMG_INTENSITY, pix_x // bin_scale, pix_y // bin_scale, -Lx / 2, Lx / 2, -Ly / 2, Ly / 2, n_channels=n_channels)
+
     def zero(self):
         check(lib.sr_image_zero(self._h))
+
+    def rotation(self, ch_plus, ch_minus, beta):
+        """IMG_INTENSITY: the rotation map alpha [ny][nx] of two channels whose analysers stand at +beta and -beta
+        (rotation_map's formula, evaluated on the device: sr_image_rotation); NaN where both channels are empty."""
+        a = pinned_empty((self.ny, self.nx))
+        check(lib.sr_image_rotation(self._h, int(ch_plus), int(ch_minus), float(beta), ptr(a)))
+        return a
 
     def download(self):
         if self.kind == IMG_COUNTS:
             H = np.empty((self.ny, self.nx), np.uint32)
+        elif self.kind == IMG_INTENSITY:
+            H = np.empty((self.n_channels, self.ny, self.nx))
         else:
             H = np.empty((2, self.ny - 1, self.nx - 1), np.complex128)
         check(lib.sr_image_download(self._h, ptr(H)))
@@ -697,6 +733,52 @@ def hist2d(x, y, nxb, nyb, xlo, xhi, ylo, yhi):
     H = np.empty((int(nyb), int(nxb)), np.uint32)
     check(lib.sr_hist2d(ptr(x), ptr(y), len(x), int(nxb), int(nyb), float(xlo), float(xhi), float(ylo), float(yhi), ptr(H)))
     return H
+
+
+def analyser_ab(analysers):
+    """[n_ch][2] float64 (a, b) = (-sin beta, cos beta) per analyser angle beta [rad], (NaN, NaN) for None (no analyser):
+    formed once here, in float64, so that the host and the device work with the same two numbers."""
+    if analysers is None or np.isscalar(analysers):
+        analysers = [analysers]
+    analysers = list(analysers)
+    if not 1 <= len(analysers) <= _ffi.MAX_ANALYSERS:
+        raise ValueError(f"1 to {_ffi.MAX_ANALYSERS} analyser channels per image, got {len(analysers)}")
+    ab = np.empty((len(analysers), 2))
+    for c, beta in enumerate(analysers):
+        ab[c] = (np.nan, np.nan) if beta is None else (-np.sin(float(beta)), np.cos(float(beta)))
+    return ab
+
+
+def intensity2d(x, y, E, analysers, nxb, nyb, xlo, xhi, ylo, yhi):
+    """I[c] = np.histogram2d(x, y, bins=[nxb, nyb], range=..., weights=|a_c . E|^2)[0].T per analyser channel, (n_ch, nyb,
+    nxb) float64 (sr_intensity2d: the host-array form of RayBundle.deposit_intensity; no reference counterpart)."""
+    x, y = f64(x), f64(y)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError("x and y must be 1-D arrays of equal length")
+    E = np.ascontiguousarray(E, dtype=np.complex128)
+    if E.shape != (2, len(x)):
+        raise ValueError(f"E must have shape (2, {len(x)}), got {E.shape}")
+    ab = analyser_ab(analysers)
+    out = np.empty((len(ab), int(nyb), int(nxb)))
+    check(lib.sr_intensity2d(ptr(x), ptr(y), ptr(E), len(x), ptr(ab), len(ab), int(nxb), int(nyb), float(xlo), float(xhi),
+                             float(ylo), float(yhi), ptr(out)))
+    return out
+
+
+def rotation_map(I_plus, I_minus, beta):
+    """The polarisation rotation alpha from two intensity images taken through analysers at +beta and -beta, 0 < beta < pi/2
+    (I = A^2 cos^2(alpha -+ beta)):  D = (I+ - I-)/(I+ + I-), R = hypot(sin 2beta, D cos 2beta),
+    delta = atan2(D cos 2beta, sin 2beta), alpha = (delta + asin(D/R))/2; NaN where I+ + I- == 0.  Unambiguous for
+    |alpha| < min(beta, pi/2 - beta); beta = pi/4 gives alpha = asin(D)/2.  Host NumPy: the formula DetectorImage.rotation
+    evaluates on the device (sr_image_rotation), for images that are already on the host."""
+    if not 0 < beta < np.pi / 2:
+        raise ValueError("beta must lie in (0, pi/2)")
+    Ip, Im = np.asarray(I_plus, dtype=np.float64), np.asarray(I_minus, dtype=np.float64)
+    tot = Ip + Im
+    with np.errstate(divide="ignore", invalid="ignore"):
+        D = np.where(tot == 0, np.nan, (Ip - Im) / tot)
+        s2, dc = np.sin(2 * beta), D * np.cos(2 * beta)
+        return 0.5 * (np.arctan2(dc, s2) + np.arcsin(np.clip(D / np.hypot(s2, dc), -1.0, 1.0)))
 
 
 def interferogram(x, y, E, nxe, nye, xlo, xhi, ylo, yhi, sums=False):

@@ -9,7 +9,8 @@ solve() mirrors) remembers which bundle an `rf` / `Jf` pair came from; `attach()
 Diagnostic.__init__) gives the bundle back when the arrays are THE arrays solve() returned and still hold what it wrote.
 The diagnostic then records its optic chain in *_solve() and histogram() / interferogram() run the fused deposit
 (sr_rays_deposit: m_to_mm -> reference beams -> chain -> LDS-tiled detector atomics) on the resident rays; `.r0`, `.rf`,
-`.rE` / `.Jf` are formed on the device and copied to the host only when somebody reads them (sr_rays_optics).
+`.rE` / `.Jf` are formed on the device and copied to the host only when somebody reads them (sr_rays_optics).  intensity() /
+Polarimetry.polarogram() deposit from the same rays under the same rule (sr_rays_deposit_intensity).
 
 The guard, in this order:
 
@@ -313,18 +314,18 @@ class DeviceRays:
         with_E = self.has_E if with_E is None else with_E
         return self.bundle.optics(ops, kwave=self.kwave if ops else 0.0, ref_beam=self.refs or None, with_E=with_E)
 
-    def _image(self, kind, nx, ny, rng):
+    def _image(self, kind, nx, ny, rng, n_channels=0):
         """The detector image of this geometry, kept with the bundle (a chunk loop asks for the same detector every time:
         no hipMalloc / hipFree per histogram) and zeroed for this deposit."""
         cache = self.bundle.__dict__.setdefault("_images", {})
-        key = (kind, int(nx), int(ny), tuple(float(v) for v in rng))
+        key = (kind, int(nx), int(ny), tuple(float(v) for v in rng), int(n_channels))
         img = cache.get(key)
         if img is None:
             if len(cache) >= 4:  # a caller sweeping bin_scale: do not pile detectors up
                 for old in cache.values():
                     old.close()
                 cache.clear()
-            img = cache[key] = engine.DetectorImage(kind, nx, ny, *rng)
+            img = cache[key] = engine.DetectorImage(kind, nx, ny, *rng, n_channels=n_channels)
         else:
             img.zero()
         return img
@@ -341,6 +342,13 @@ class DeviceRays:
         img = self._image(engine.IMG_COMPLEX, nxe, nye, (x_lo, x_hi, y_lo, y_hi))
         self.bundle.deposit(img, self.ops, kwave=self.kwave, ref_beam=self.refs or None, want_stats=False)
         return img.amplitude()
+
+    def intensity(self, analysers, nx, ny, x_lo, x_hi, y_lo, y_hi):
+        """Analyser-weighted intensities of the resident rays (RayBundle.deposit_intensity): (n_ch, ny, nx) float64 of the
+        bundle's own Jf through the masks of the recorded chain.  The caller has made sure no reference beam was added."""
+        img = self._image(engine.IMG_INTENSITY, nx, ny, (x_lo, x_hi, y_lo, y_hi), len(engine.analyser_ab(analysers)))
+        self.bundle.deposit_intensity(img, self.ops, analysers, want_stats=False)
+        return img.download()
 
     def drop(self, owner):
         if self.bundle is not None:

@@ -202,6 +202,30 @@ class Rays:
         if clear_mem:
             self.clear_rays()
 
+    def intensity(self, analyser=None, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
+        """Analyser-weighted intensity images of the detector-plane rays: I (n_ch, pix_y // bin_scale, pix_x // bin_scale),
+        I[c] = np.histogram2d(..., weights=w_c) on histogram()'s detector, xedges / yedges as histogram() sets them; .H is
+        left alone.  No reference counterpart (the reference shows amplitude and polarisation in no image).
+
+        analyser: None, one angle [rad], or a sequence of up to 4 angles, None among them = no analyser.  An analyser at
+        angle beta, measured from the y axis in the sense `pol` is, passes the component of E along (-sin beta, cos beta):
+        w = |(-sin beta) E_x + (cos beta) E_y|^2 = amp^2 cos^2(pol - beta); without analyser w = |E_x|^2 + |E_y|^2 (the
+        attenuation image).  The sum over a pixel's rays is incoherent, so the field factors of a chain's legs (modulus 1)
+        play no part: the weights come from E as given."""
+        if self.E is None:
+            raise ValueError("intensity needs the field E (the Jf returned by solve(..., return_E=True))")
+        nx, ny = pix_x // bin_scale, pix_y // bin_scale
+        rng = (-self.Lx / 2, self.Lx / 2, -self.Ly / 2, self.Ly / 2)
+        self._guard()
+        if self._deposits_from_device() and self._dev.has_E:
+            self.I = self._dev.intensity(analyser, nx, ny, *rng)
+        else:
+            self.I = engine.intensity2d(self.rf[0], self.rf[2], self.E, analyser, nx, ny, *rng)
+        self.xedges = np.linspace(-self.Lx / 2, self.Lx / 2, nx + 1)
+        self.yedges = np.linspace(-self.Ly / 2, self.Ly / 2, ny + 1)
+        if clear_mem:
+            self.clear_rays()
+
     def plot(self, ax, clim=None, cmap=None):
         ax.imshow(self.H, interpolation="nearest", origin="lower", clim=clim, cmap=cmap,
                   extent=[self.xedges[0], self.xedges[-1], self.yedges[0], self.yedges[-1]])
@@ -297,3 +321,31 @@ class Interferometry(Rays):
             self.H = engine.interferogram(self.rf[0], self.rf[2], self.rE, pix_x // bin_scale, pix_y // bin_scale, *rng)
         if clear_mem:
             self.clear_rays()
+
+
+class Polarimetry(Rays):
+    """Faraday-rotation imaging through a pair of analysers at +beta and -beta: Shadowgraphy's imaging chains, and intensity
+    images weighted by what each analyser passes of the rays' Jones vector.  No reference counterpart: the reference
+    carries the rotation (state row 8) into Jf and has no diagnostic that shows it.
+
+        po = Polarimetry(rf, Jf); po.two_lens_solve(); po.polarogram(); alpha = po.rotation()"""
+
+    def single_lens_solve(self):
+        self._run(engine.chain_shadow_single(self.L, self.R, self.focal_plane))
+
+    def two_lens_solve(self):
+        self._run(engine.chain_shadow_two(self.L, self.R, self.focal_plane))
+
+    def polarogram(self, beta=np.pi / 4, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
+        """One pass over the rays, three images: H_plus and H_minus through analysers at +beta and -beta (0 < beta < pi/2),
+        H_total without analyser; .beta keeps the angle for rotation()."""
+        if not 0 < beta < np.pi / 2:
+            raise ValueError("beta must lie in (0, pi/2)")
+        self.intensity((beta, -beta, None), bin_scale=bin_scale, pix_x=pix_x, pix_y=pix_y, clear_mem=clear_mem)
+        self.H_plus, self.H_minus, self.H_total = self.I
+        self.beta = beta
+
+    def rotation(self):
+        """The polarisation rotation alpha [rad] per pixel from H_plus and H_minus (engine.rotation_map): NaN where no ray
+        landed; unambiguous for |alpha| < min(beta, pi/2 - beta)."""
+        return engine.rotation_map(self.H_plus, self.H_minus, self.beta)

@@ -30,9 +30,10 @@ def demangle(names):
 def normalise(text, plain):
     text = re.sub(r"\.L(func_end|func_begin|JTI|tmp)\d+(_\d+)?", lambda m: ".L" + m.group(1) + (m.group(2) or ""), text)
     text = re.sub(r"BB\d+_(\d+)", r"BB_\1", text)  # .LBB<function>_<block>, in labels and in the loop comments
+    text = re.sub(r"[ \t]+;", " ;", text)  # a comment's column moves with the width of the function number in the label before it
     for sym, name in sorted(plain.items(), key=lambda kv: -len(kv[0])):  # a symbol's own spelling (namespace and all) is no difference
         text = text.replace(sym, "<" + name + ">")
-    return text
+    return text.strip()  # (the last metadata entry of a file ends without the blank line the others have)
 
 
 def parse(txt):
