@@ -122,6 +122,26 @@ int sr_volume_sample_aux(const sr_volume *v, const double *pts, int64_t n_pts, d
 int sr_volume_create_slab(sr_volume **out, const void *ne_slab, int ne_is_f64, int nx, int ny, int nz,
                           const float *x, const float *y, const float *z, double lwl, int probing_axis,
                           int flags, int k_lo, int k_hi);
+/* No reference counterpart: the line integrals of the volume along its probing axis, the thin-plasma predictions of what the
+ * tracer integrates along the true path (d(phase) = omega (n-1), d(v) = dndr, d(amp) = kappa amp, d(pol) = V n_e (B.v)):
+ *   phase = omega/c * NM1,  N_e = NE,  deflection = GRAD/c^2,  ln(amp) = KAPPA/c,  rotation = verdet * NEB.
+ * maps is a HOST array (SR_PROJ_MAPS, n_u, n_v), float64, C order; (n_u, n_v) is the domain's shape with the probing axis
+ * dropped -- for y-probing (nx, nz), although the device's lateral order there is (z, x).  Bit i of *have (may be NULL) says
+ * that map i exists; an absent map is filled with 0.0.  The integral is the trapezoid rule on the volume's own float64 node
+ * coordinates g of the probing axis, sum_k w_k f_k with w_0 = (g_1-g_0)/2, w_k = (g_{k+1}-g_{k-1})/2, w_{n-1} = (g_{n-1}-g_{n-2})/2;
+ * a slab volume (sr_volume_create_slab) integrates its own planes k_lo..k_hi by the same rule, so the sum over the slabs of a
+ * domain is the whole domain's integral.  A NaN node makes its column NaN and no other.  Each lane sums its plane of every
+ * octet in float64 and a fixed tree adds the eight planes of a column (project.hip): no atomics, a repeated call returns the
+ * identical bits.  Arguments are checked before the device is touched: NULL v or maps, a volume with fewer than 2 planes. */
+#define SR_PROJ_GRAD1 0  /* integral of dnd_u dl: u, v = the two lateral axes in x<y<z order           */
+#define SR_PROJ_GRAD2 1  /* integral of dnd_v dl                                                        */
+#define SR_PROJ_NM1   2  /* integral of (n-1) dl, n-1 = hi + lo                  needs SR_VOL_PHASE     */
+#define SR_PROJ_NE    3  /* integral of n_e dl, n_e = -m(2+m)*omega^2*1e6/5.64e4^2, m = n-1 (the n
+                            formula of sr_volume_create inverted)                needs SR_VOL_PHASE     */
+#define SR_PROJ_KAPPA 4  /* integral of kappa dl                                 needs attached kappa   */
+#define SR_PROJ_NEB   5  /* integral of n_e*B_a dl, a = probing axis             needs attached ne, B   */
+#define SR_PROJ_MAPS  6
+int sr_volume_project(const sr_volume *v, double *maps, uint32_t *have);
 double sr_volume_omega(const sr_volume *v);
 int64_t sr_volume_bytes(const sr_volume *v); /* HBM held by the handle */
 void sr_volume_destroy(sr_volume *v);

@@ -43,6 +43,7 @@ FRESNEL_STATS = 6  # SR_FRESNEL_STATS
 
 MAX_REF_BEAMS = 4  # SR_MAX_REF_BEAMS
 MAX_ANALYSERS = 4  # SR_MAX_ANALYSERS
+PROJ_GRAD1, PROJ_GRAD2, PROJ_NM1, PROJ_NE, PROJ_KAPPA, PROJ_NEB, PROJ_MAPS = range(7)  # SR_PROJ_*
 
 
 class DepositParams(C.Structure):
@@ -87,6 +88,7 @@ SYMBOLS = {
     "sr_rays_handoff_send": (_i, [_vp, _vp, _i]),
     "sr_rays_handoff_recv": (_i, [_vp, _vp, _i]),
     "sr_volume_sample_aux": (_i, [_vp, _vp, _i64, _vp]),
+    "sr_volume_project": (_i, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "sr_volume_omega": (_d, [_vp]),
     "sr_volume_bytes": (_i64, [_vp]),
     "sr_volume_destroy": (None, [_vp]),

@@ -104,6 +104,19 @@ def stream_wait(waiting: int, on: int) -> None:
     check(lib.sr_stream_wait(int(waiting), int(on)))
 
 
+def trapezoid_weights(g):
+    """The weights w of the trapezoid rule on the nodes g, sum(w * f) = np.trapz(f, g): w_0 = (g_1 - g_0)/2,
+    w_k = (g_{k+1} - g_{k-1})/2, w_{n-1} = (g_{n-1} - g_{n-2})/2 -- what sr_volume_project builds from the volume's float64
+    node coordinates of the probing axis."""
+    g = np.asarray(g, dtype=np.float64)
+    if g.ndim != 1 or len(g) < 2:
+        raise ValueError(f"the trapezoid rule needs at least 2 nodes on one axis, got shape {g.shape}")
+    w = np.empty_like(g)
+    w[0], w[-1] = (g[1] - g[0]) / 2, (g[-1] - g[-2]) / 2
+    w[1:-1] = (g[2:] - g[:-2]) / 2
+    return w
+
+
 def default_t_end(extent: float) -> float:
     """t = sqrt(8)*extent/c: long enough for every ray to leave the volume (full_solver.py:381)."""
     return float(np.sqrt(8.0) * extent / c)
@@ -198,6 +211,7 @@ class Volume:
         self.axis = axis
         self.phase = bool(phase)  # the n-1 field is resident: the trace integrates the phase (A5)
         self.aux = False          # attach_aux: kappa / Faraday fields resident
+        self.verdet = 0.0         # the VerdetConst attach_aux was given (Projection.rotation scales by it)
 
     @classmethod
     def from_ne(cls, ne, x, y, z, lwl, probing_direction="z", phaseshift=False):
@@ -288,7 +302,22 @@ class Volume:
                 raise ValueError(f"ne {ne.shape} / B {B.shape} do not match the volume {self.shape} (+ (3,))")
         check(lib.sr_volume_attach_aux(self._h, ptr(kappa), ptr(ne), ptr(B), float(verdet)))
         self.aux = kappa is not None or B is not None
+        self.verdet = float(verdet)
         return self
+
+    def project(self):
+        """The line integrals of the volume along its probing axis (sr_volume_project): the trapezoid rule on the volume's
+        own node coordinates, a slab over its own planes.  {"grad": (2, n_u, n_v) [u, v = the lateral axes in x < y < z
+        order], "nm1", "ne", "kappa", "neB": (n_u, n_v) | None where the volume does not hold the field}."""
+        if not getattr(self, "_h", None):
+            raise ValueError("the volume has been closed")
+        lateral = tuple(n for k, n in enumerate(self.shape) if k != self.axis)
+        maps = np.empty((_ffi.PROJ_MAPS,) + lateral)
+        have = C.c_uint32(0)
+        check(lib.sr_volume_project(self._h, ptr(maps), C.byref(have)))
+        pick = lambda k: maps[k] if have.value >> k & 1 else None
+        return {"grad": maps[_ffi.PROJ_GRAD1:_ffi.PROJ_GRAD2 + 1], "nm1": pick(_ffi.PROJ_NM1), "ne": pick(_ffi.PROJ_NE),
+                "kappa": pick(_ffi.PROJ_KAPPA), "neB": pick(_ffi.PROJ_NEB)}
 
     def sample_aux(self, pts):
         """Interpolated (kappa, ne, Bx, By, Bz) at pts (N,3): the gathers of atten / get_ne / get_B, shape (5, N)."""

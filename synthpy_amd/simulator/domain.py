@@ -127,6 +127,13 @@ class ScalarDomain:
     def external_Z(self, Z):
         self.Z = Z
 
+    def line_integrals(self, lwl=1064e-9, regions=None):
+        """The line integrals of the domain along its probing axis (no reference counterpart): a projection.Projection
+        with the phase, deflection, areal density, absorption and rotation maps a straight ray would gather."""
+        from ..projection import line_integrals
+
+        return line_integrals(self, lwl=lwl, regions=regions)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (domain.py:505-579), written without pyvista."""
         from ..utils.handle_filetypes import export_scalar_field

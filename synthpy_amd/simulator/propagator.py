@@ -167,32 +167,48 @@ def _regions(domain, lwl):
     return regions
 
 
-def _solve_by_regions(s0, domain, probing_depth, return_E, lwl, substeps, precision, regions):
-    """The region loop of propagator.py:366-452: one slab of node planes of the probing axis in HBM at a time, the
-    rays handed from slab to slab on the shared planes (engine.Volume.from_ne_slab, HANDOFF_*)."""
+def _slab_volumes(domain, lwl, regions):
+    """The slabs of the region loop: (cuts, iterator).  The iterator holds one slab in HBM at a time: it yields the device
+    volume of each range of node planes of the probing axis (cuts = engine.slab_cuts) with its own planes of the optional
+    terms' fields attached, and closes it when the caller comes back for the next (_solve_by_regions,
+    projection.line_integrals)."""
     if domain.ne is None:
         raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
     axis = "xyz".index(domain.probing_direction)
     ne = np.asarray(domain.ne)
     cuts = engine.slab_cuts(ne.shape[axis], regions)
     aux = _aux_fields(domain, lwl)  # the optional terms' fields: each slab gets its own node planes of them
+
+    def slabs():
+        for lo, hi in cuts:
+            vol = engine.Volume.from_ne_slab(engine.slab_source(ne, axis, lo, hi), domain.x, domain.y, domain.z, lwl,
+                                             domain.probing_direction, lo, hi, phaseshift=domain.phaseshift)
+            try:
+                if aux is not None:
+                    sl = [slice(None)] * 3
+                    sl[axis] = slice(lo, hi + 1)
+                    part = lambda a: None if a is None else np.ascontiguousarray(a[tuple(sl)])
+                    vol.attach_aux(part(aux[0]), part(aux[1]), part(aux[2]), aux[3])
+                yield vol
+            finally:
+                vol.close()
+
+    return cuts, slabs()
+
+
+def _solve_by_regions(s0, domain, probing_depth, return_E, lwl, substeps, precision, regions):
+    """The region loop of propagator.py:366-452: one slab of node planes of the probing axis in HBM at a time, the
+    rays handed from slab to slab on the shared planes (engine.Volume.from_ne_slab, HANDOFF_*)."""
+    cuts, slabs = _slab_volumes(domain, lwl, regions)
     start = time()
     t_end = np.sqrt(8.0) * probing_depth / c
     rays = resident.acquire(s0.shape[1], getattr(domain, "_rays", None)).upload(s0)
     domain._rays = rays
     steps = 0
-    for q, (lo, hi) in enumerate(cuts):
-        vol = engine.Volume.from_ne_slab(engine.slab_source(ne, axis, lo, hi), domain.x, domain.y, domain.z, lwl,
-                                         domain.probing_direction, lo, hi, phaseshift=domain.phaseshift)
-        if aux is not None:
-            sl = [slice(None)] * 3
-            sl[axis] = slice(lo, hi + 1)
-            part = lambda a: None if a is None else np.ascontiguousarray(a[tuple(sl)])
-            vol.attach_aux(part(aux[0]), part(aux[1]), part(aux[2]), aux[3])
+    for q, vol in enumerate(slabs):
         flags = (engine.HANDOFF_ENTER if q else 0) | (engine.HANDOFF_EXIT if q + 1 < len(cuts) else 0)
         st = rays.trace(vol, t_end, probing_depth, row_order=engine.ROWS_JAX, substeps=substeps, precision=precision, handoff=flags)
         steps += st.ray_steps
-        vol.close()
     _, rf, Jf = rays.download(sf=False, Jf=return_E)
     rf, Jf = resident.register(rays, rf, Jf)  # the same memory, write-tracked (resident.TrackedArray)
     duration = time() - start

@@ -132,6 +132,14 @@ class ScalarDomain:
                                               probing_direction=self.probing_direction, phaseshift=self.phaseshift)
         self._fields = None
 
+    def line_integrals(self):
+        """The line integrals of the volume calc_dndr (and set_up_interps) left on the GPU, along the probing axis (no
+        reference counterpart): a projection.Projection with the phase, deflection, areal density, absorption and rotation
+        maps a straight ray would gather."""
+        from ..projection import line_integrals
+
+        return line_integrals(self)
+
     def _field(self, k):
         if self._volume is None:
             raise RuntimeError("call calc_dndr(lwl) first")
