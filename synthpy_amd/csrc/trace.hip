@@ -43,6 +43,26 @@ constexpr int64_t kSC = 8;
 __device__ __forceinline__ int64_t col8(const VolDev &V, int ib, int ic) { return ((int64_t)ib * V.nc + ic) * 8; }
 __device__ __forceinline__ int64_t koff(const VolDev &V, int k) { return (int64_t)(k >> 3) * V.OS + (k & 7); }
 
+// LDS-DMA of one kilobyte: the wavefront's 64 lanes x 16 bytes from src + lane_off (src wave-uniform, lane_off the lane's own
+// 32 bits) into LDS at byte address dst + lane * 16 (dst wave-uniform), no register in between.  The caller waits (vmcnt) before
+// anybody reads the kilobyte.  In a loop that moves src on, the compiler keeps src + lane_off as a per-lane 64-bit pointer and
+// adds to it with one v_lshl_add_u64 per step.  SR_TILE_EXP_DMA_SADDR: the scalar-base + 32-bit-lane-offset form by an inline
+// statement instead, no vector instruction at all (M0, the destination, is the compiler's register: written in the statement
+// that reads it and put back, one wait state before the DMA) -- in the records kernel's step loop (trace_tile.inc) three vector
+// instructions fewer per step, 23 scalar ones more, and no faster (profiles/r06_step_loop.txt): not the default.
+__device__ __forceinline__ void lds_dma16(const char *src, unsigned lane_off, unsigned dst) {
+#ifdef SR_TILE_EXP_DMA_SADDR
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(lane_off), "s"(src), "s"(dst)
+               : "memory");
+#else
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + lane_off),
+                                   (__attribute__((address_space(3))) void *)(uintptr_t)dst, 16, 0, 0);
+#endif
+}
+
 // wave-uniform constants of one RK4 sub-step from node plane k (sub-interval m): index k*sub + m.
 // Built on the host with the oracle's formulas (trace_one_planes): dz = (g[k+1]-g[k])/sub, za = g[k] + m*dz,
 // zb = g[k+1] for the last sub-interval else g[k] + (m+1)*dz, h = zb - za, plane weights (z - g[k])/(g[k+1]-g[k]).

@@ -18,7 +18,7 @@
 //    node planes' records are ready-made in HBM (sr_volume::R: k_build_records forms them once per volume with
 //    coefs_from_corners -- 128 bytes per node plane and lateral cell, 17 GB for 512^3) and come into the ring by LDS-DMA: at a
 //    step's start each of the four wavefronts asks for two tile columns of node plane k+2 (2 x global_load_lds_dwordx4: one
-//    kilobyte each, no register, no conversion; the address is a scalar base + one 32-bit lane offset), at its end it adds them
+//    kilobyte each, no register, no conversion; the sources are running pointers, one node plane further per step), at its end it adds them
 //    to its own two columns of plane k+1 for the mid record (the same lane-linear kilobytes: 4 ds_read_b128 + 4 v_add_f64 + 2
 //    ds_write_b128, every lane busy).  No producer wavefront: the four wavefronts of a workgroup do the same work.  LDS
 //    layout: see kRecColD (piece-major column blocks 1104 bytes apart: the DMA writes a wavefront's 64 x 16 bytes contiguously, so
@@ -247,7 +247,8 @@ __global__ __launch_bounds__(256) void k_build_records(VolDev V, double *__restr
 
 // Diagnostic builds (tools/build_variant.sh <name> -DSR_TILE_EXP_...; wrong results, timing only; DESIGN.md round 3 has the numbers):
 // SR_TILE_EXP_NOBARRIER (no barrier in the step loop), SR_TILE_EXP_NOPRODUCE (no plane is loaded or built in the loop),
-// SR_TILE_EXP_NORELOC (a ray never changes its cell).
+// SR_TILE_EXP_NORELOC (a ray never changes its cell).  SR_TILE_EXP_DMA_SADDR (right results): the records kernel's LDS-DMA by an
+// inline statement in the scalar-base form (lds_dma16, trace.hip; profiles/r06_step_loop.txt).
 #ifndef SR_TILE_THREADS
 // 256 rays per workgroup with an 8 x 8 tile (46 KB of LDS): THREE workgroups share a CU -- 12 wavefronts, 3 per SIMD at 168
 // VGPRs as before, but a workgroup's barrier (four wavefronts, one per SIMD) and its start and end are the other two's issue
@@ -297,8 +298,9 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
                             : ((size_t)(2 * (TB + 1) + 2 * (TC + 1) + 4) + 1) & ~(size_t)1;
   double *recs = lds + tables;                       // 16-byte aligned (REC: 1 KiB)
   const int slot_d = REC ? TC * kRecColD : NC * kTileRec;  // doubles per slot
-  // where the record of tile cell (tb, tc) starts inside a slot, in doubles (REC: its piece 0; the others follow 128 bytes apart)
-  auto cell_off = [&](int b_, int c_) { return REC ? c_ * kRecColD + b_ * 2 : (c_ * TB + b_) * kTileRec; };
+  // where the record of tile cell (tb, tc) starts inside a slot, in doubles -- REC: in BYTES (its piece 0; the others follow 128
+  // bytes apart): the records kernel keeps every LDS address of the step loop as a byte address (see slot_h below)
+  auto cell_off = [&](int b_, int c_) { return REC ? c_ * (kRecColD * 8) + b_ * 16 : (c_ * TB + b_) * kTileRec; };
   // slots 0..2: node planes (k % 3); 3, 4: mid-step planes (3 + k % 2)
 
   const unsigned chunk = gridDim.x / 8;
@@ -549,42 +551,50 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   // record of cell (ob + l / 8, oc + column), and land at the slot's column + l * 16 -- the DMA's own lane-linear order
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int ln = (int)(threadIdx.x & 63);
-  typedef __attribute__((address_space(3))) void *lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void *glb_ptr_t;
   // Addresses: everything but the lane's place inside its kilobyte is wave-uniform -- the tile's first record, the node plane, the
   // column -- and is kept in scalar registers (ob, oc come out of LDS: readfirstlane tells the compiler); the lane adds ONE 32-bit
-  // offset, the same for the whole launch.  (Formed per lane in 64-bit integer arithmetic the two addresses were 15 vector
+  // offset, the same for the whole launch (what becomes of it in the step loop: see lds_dma16).  (Formed per lane in 64-bit integer arithmetic the two addresses were 15 vector
   // instructions per step: profiles/r05_pmc_c3_f64_first_layout.csv, INT32 + INT64 35 per wavefront-step against the producers' 27.)
   const int ob_u = __builtin_amdgcn_readfirstlane(ob), oc_u = __builtin_amdgcn_readfirstlane(oc);
   const unsigned lane_off = (unsigned)(ln & 7) * 128u + (unsigned)(ln >> 3) * 16u;  // piece ln / 8 of the record of row ln % 8
   const int64_t col_bytes = (int64_t)(V.nb - 1) * 128, plane_bytes = (int64_t)(V.nc - 1) * col_bytes;
   const char *tile_r = REC ? reinterpret_cast<const char *>(V.R) + ((int64_t)oc_u * (V.nb - 1) + ob_u) * 128 : nullptr;
-  auto dma_plane = [&](int k, int slot) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int col = 2 * wv + q;
-      if (col >= TC) break;  // (a tile of fewer than eight columns: the last wavefront has one, or none)
-      const char *src = tile_r + ((int64_t)k * plane_bytes + (int64_t)col * col_bytes) + lane_off;
-      double *dst = recs + slot * slot_d + col * kRecColD;  // wave-uniform: the hardware adds lane * 16 bytes
-      __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)dst, 16, 0, 0);
-    }
+  // A slot's HANDLE is what the step loop rotates and hands to request / dma_cols / mid_from.  REC: the LDS byte address of the
+  // slot's first record, wave-uniform, so that the loop holds no slot * slot_d multiply and an address is one add of a handle
+  // and a lane constant; otherwise the slot's index, as the producers' stores and the optional terms' reads take it.
+  const unsigned recs_lds = (unsigned)(uintptr_t)recs;  // LDS byte address of the records (low word of the flat address)
+  auto slot_h = [&](int slot) { return REC ? (int)(recs_lds + (unsigned)(slot * slot_d) * 8u) : slot; };
+  // the wavefront's first column: where its block starts inside a slot (bytes), and the node plane's records of it in HBM.  The
+  // records are plane-linear in the volume's -- or the slab's -- OWN planes (k_build_records: no koff() octets here)
+  const int wcol_b = 2 * wv * (kRecColD * 8);
+  const char *wcol_r = REC ? tile_r + (int64_t)(2 * wv) * col_bytes : nullptr;
+  // one kilobyte from src + lane_off into LDS at dst + lane * 16 (lds_dma16, trace.hip: the address forms are weighed there)
+  auto glds16 = [&](const char *src, int dst) { lds_dma16(src, lane_off, (unsigned)dst); };
+  // the wavefront's two columns of one node plane (src0, src1: their records in HBM) into the slot with handle `slot`
+  auto dma_cols = [&](const char *src0, const char *src1, int slot) {
+    if (2 * wv < TC) glds16(src0, slot + wcol_b);  // (a tile of fewer than eight columns: the last wavefront has one, or none)
+    if (2 * wv + 1 < TC) glds16(src1, slot + wcol_b + kRecColD * 8);
   };
-  // the mid record of the wavefront's own two columns: (plane in slot `lo`) + (plane in slot `hi`) -> slot `mid`, 16 bytes per lane
-  auto mid_from = [&](int lo, int hi, int mid) {
+  // the mid record of the wavefront's own two columns: (plane in slot `lo`) + (plane in slot `hi`) -> slot `mid`, 16 bytes per
+  // lane; the slots by their handles, the lane's place in the wavefront's block a constant of the launch
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) d2 *lds_d2_t;
+  const int mid_lane = wcol_b + ln * 16;
+  auto mid_from = [&](int lo, int hi, int mid, bool col0, bool col1) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      if (2 * wv + q >= TC) break;
-      const int off = (2 * wv + q) * kRecColD + ln * 2;
-      const double2 a = *reinterpret_cast<const double2 *>(recs + lo * slot_d + off);
-      const double2 b = *reinterpret_cast<const double2 *>(recs + hi * slot_d + off);
-      *reinterpret_cast<double2 *>(recs + mid * slot_d + off) = make_double2(a.x + b.x, a.y + b.y);
+      if (!(q ? col1 : col0)) break;
+      const d2 a = ((lds_d2_t)(uintptr_t)(unsigned)(lo + mid_lane))[q * (kRecColD / 2)];
+      const d2 b = ((lds_d2_t)(uintptr_t)(unsigned)(hi + mid_lane))[q * (kRecColD / 2)];
+      ((lds_d2_t)(uintptr_t)(unsigned)(mid + mid_lane))[q * (kRecColD / 2)] = a + b;
     }
   };
   if (REC && wg_live) {
-    dma_plane(T.k0, T.k0 % 3);
-    dma_plane(T.k0 + 1, (T.k0 + 1) % 3);
+    const char *p0 = wcol_r + (int64_t)T.k0 * plane_bytes;
+    dma_cols(p0, p0 + col_bytes, slot_h(T.k0 % 3));
+    dma_cols(p0 + plane_bytes, p0 + plane_bytes + col_bytes, slot_h((T.k0 + 1) % 3));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    mid_from(T.k0 % 3, (T.k0 + 1) % 3, 3 + T.k0 % 2);
+    mid_from(slot_h(T.k0 % 3), slot_h((T.k0 + 1) % 3), slot_h(3 + T.k0 % 2), 2 * wv < TC, 2 * wv + 1 < TC);
   }
   if (producer) {
     RawPlane r0, r1;
@@ -659,15 +669,15 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   // at the START of stage s, before its blend -- so stage s first places the ray for stage s+1, issues that record's reads,
   // and only then blends with its own record, requested a stage earlier.  Stages 2 and 3 share the mid record and stage 1
   // of the next step takes over stage 4's (the same node plane) when the cell is the same, which it almost always is.
-  typedef double d2 __attribute__((ext_vector_type(2)));
   struct Rec {
     d2 q[8];  // a01 a23 b01 b23 c01 c23 d01 d23
     int off;  // where the record sits in LDS, in doubles from `recs` (AUX: the optional terms' coefficients are 16 further on)
   };
-  const unsigned recs_lds = (unsigned)(uintptr_t)recs;  // LDS byte address of the records (low word of the flat address)
+  // slot: the slot's handle (slot_h), cell_d: the cell's place inside a slot as cell_off gives it.  REC: both are bytes, the
+  // address is their sum -- one vector add of a scalar
   auto request = [&](int slot, int cell_d, Rec &R) {
-    R.off = slot * slot_d + cell_d;
-    const unsigned addr = recs_lds + (unsigned)(slot * slot_d + cell_d) * 8u;
+    R.off = REC ? 0 : slot * slot_d + cell_d;
+    const unsigned addr = REC ? (unsigned)slot + (unsigned)cell_d : recs_lds + (unsigned)(slot * slot_d + cell_d) * 8u;
     if (REC)  // the record's pieces are 128 bytes apart (piece-major blocks)
       asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %8 offset:128\n\tds_read_b128 %2, %8 offset:256\n\tds_read_b128 %3, %8 offset:384\n\t"
                    "ds_read_b128 %4, %8 offset:512\n\tds_read_b128 %5, %8 offset:640\n\tds_read_b128 %6, %8 offset:768\n\tds_read_b128 %7, %8 offset:896"
@@ -684,9 +694,16 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
                : "+v"(R.q[0]), "+v"(R.q[1]), "+v"(R.q[2]), "+v"(R.q[3]), "+v"(R.q[4]), "+v"(R.q[5]), "+v"(R.q[6]), "+v"(R.q[7]))
 
   // slots rotate with the step: s_lo = k % 3, s_hi = (k + 1) % 3, s_nx = (k + 2) % 3, m_cur = 3 + k % 2, m_nx = 3 + (k + 1) % 2
-  int s_lo = T.k0 % 3, s_hi = (T.k0 + 1) % 3, s_nx = (T.k0 + 2) % 3, m_cur = 3 + T.k0 % 2, m_nx = 3 + (T.k0 + 1) % 2;
+  // -- held as HANDLES (slot_h; REC: five byte addresses in scalar registers, rotated as they are)
+  int s_lo = slot_h(T.k0 % 3), s_hi = slot_h((T.k0 + 1) % 3), s_nx = slot_h((T.k0 + 2) % 3);
+  int m_cur = slot_h(3 + T.k0 % 2), m_nx = slot_h(3 + (T.k0 + 1) % 2);
+  // REC: where the wavefront's two columns of node plane k + 2 sit in HBM: running pointers, one plane further with every step
+  // the last step at which the wavefront asks for its first / second column of node plane k + 2 (none: before every step).  One
+  // integer compare with the step stands for "a live workgroup, a column inside the tile, a plane inside the segment"
+  constexpr int kNever = -0x7fffffff - 1;
+  const int k_col0 = (wg_live && 2 * wv < TC) ? T.k1 - 2 : kNever, k_col1 = (wg_live && 2 * wv + 1 < TC) ? T.k1 - 2 : kNever;
+  const char *nx_r0 = REC ? wcol_r + (int64_t)(T.k0 + 2) * plane_bytes : nullptr, *nx_r1 = REC ? nx_r0 + col_bytes : nullptr;
   Rec RA, RB;           // RA: node-plane records (stage 1, stage 4), RB: the mid record
-  int cell_ra = cell;   // the cell RA was read for
   request(s_lo, cell, RA);
   // The NEXT step's constants {h, h/2, h/6, omega*h/6} by scalar loads, a step ahead: through a constant-address-space pointer,
   // which the compiler reads with s_load whatever else the loop holds (through the generic pointer it turns them into vector
@@ -696,15 +713,18 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   // uniform with eight v_readfirstlane per step: 0.8 % slower, 5.5 KB of LDS and three spilled registers more.)
   typedef const double __attribute__((address_space(4))) *cdbl_t;
   const cdbl_t ctab = (cdbl_t)(uintptr_t)A.tab64;  // StepTab64 = {h, hh, h6, wa0, waH, wa1, h6w, pad}: 8 doubles per step
-  double nh = ctab[8 * T.k0], nhh = ctab[8 * T.k0 + 1], nh6 = ctab[8 * T.k0 + 2], nh6w = ctab[8 * T.k0 + 6];
+  // a running pointer, 64 bytes further with every step; the last step reads the first one's again (there is no step k1)
+  const cdbl_t tab0 = ctab + 8 * (int64_t)T.k0;
+  cdbl_t tab = tab0;
+  double nh = tab[0], nhh = tab[1], nh6 = tab[2], nh6w = tab[6];
   for (int k = T.k0; k < T.k1; ++k) {
     const double Sh = nh, Shh = nhh, Sh6 = nh6, Sh6w = nh6w;
     {
-      const int kn = 8 * (k + 1 < T.k1 ? k + 1 : T.k0);
-      nh = ctab[kn];
-      nhh = ctab[kn + 1];
-      nh6 = ctab[kn + 2];
-      nh6w = ctab[kn + 6];
+      tab = k + 1 < T.k1 ? tab + 8 : tab0;
+      nh = tab[0];
+      nhh = tab[1];
+      nh6 = tab[2];
+      nh6w = tab[6];
     }
     RawPlane NX;
     // AUX: ONE buffer of 20 float64 for the plane on its way, whichever kind of producer the lane is -- the gradient producers'
@@ -712,9 +732,12 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     // kinds never share a lane, and two separate buffers would be 60 registers in every lane of the kernel
     double NXU[20];
     const bool more = k + 2 <= T.k1;  // node plane k + 2 is needed by the next step
+    // REC: ... and this wavefront brings a first / a second column of it (k_col0, k_col1: see there)
+    const bool more0 = k <= k_col0, more1 = k <= k_col1;
 #ifndef SR_TILE_EXP_NOPRODUCE
     if (REC) {
-      if (wg_live && more) dma_plane(k + 2, s_nx);
+      if (more0) glds16(nx_r0, s_nx + wcol_b);
+      if (more1) glds16(nx_r1, s_nx + wcol_b + kRecColD * 8);
     } else if (!AUX) {
       if (producer && more) issue_raw(k + 2, NX);
     } else {
@@ -744,18 +767,20 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
       double ap0, ap1, av0, av1, av2, aph, at;
       double k7 = 0, k8 = 0, a7 = 0, a8 = 0;  // AUX: slopes and sums of amp, pol
       bool ok = true;
-      // ---- stage 1 at (y0, y1): its record RA was requested by the step before (or before the loop) for cell_ra
+      // ---- stage 1 at (y0, y1): its record RA was requested by the step before (or before the loop) for the cell the ray was
+      // in then, and nothing but this region moves it on since
       double wb = (y0 - lo_b) * r_b, wc = (y1 - lo_c) * r_c;
       if (max(hi_word(wb), hi_word(wc)) >= kInside) {  // the rarely-taken region: an index change
+        const int was = cell;
         if (!relocate2(y0, y1, wb, wc)) ok = false;   // left the tile: lost to this kernel
         cell = cell_off(tb, tc);
         wb = (y0 - lo_b) * r_b;
         wc = (y1 - lo_c) * r_c;
+        if (cell != was) request(s_lo, cell, RA);  // the ray ended the step before in another cell than its last stage was in: read again
       }
-      if (cell != cell_ra) {  // the ray ended the step before in another cell than its last stage was in (rare): read again
-        request(s_lo, cell, RA);
-        cell_ra = cell;
-      }
+      // whether the stage just run moved the ray into another cell while placing the next one: set in the rarely-taken region only
+      // (a lane mask in scalar registers; a copy of `cell` to compare with afterwards was a vector move and a compare in every step)
+      bool moved = false;
       // One stage: (t2, t3, t4) = the stage's velocities, (wb, wc) its weights, R its record (already requested; `pending`
       // reads were issued after it).  Before blending, the NEXT stage's position, cell and weights are formed and (HASNEXT) its
       // record requested into NXT from `nslot`; without it the next stage uses R again unless its cell differs.
@@ -771,8 +796,10 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
           nwc = (qc - lo_c) * r_c;
           if (max(hi_word(nwb), hi_word(nwc)) >= kInside) {
             // this stage's weights (wb, wc) belong to the OLD cell: they are already in registers; the cell variables move on
+            const int was = cell;
             if (!relocate2(qb, qc, nwb, nwc)) ok = false;
             cell = cell_off(tb, tc);
+            moved = cell != was;
             nwb = (qb - lo_b) * r_b;
             nwc = (qc - lo_c) * r_c;
           }
@@ -836,18 +863,15 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
       double w1b, w1c, w2b, w2c, w3b, w3c;
       // stage 1 (record RA, node plane k); places stage 2 and requests the mid record for it
       stage(std::integral_constant<int, 0>{}, std::true_type{}, y2, y3, y4, y7, RA, RB, m_cur, w1b, w1c);
-      int cell_rb = cell;
       // stage 2 (mid record RB); places stage 3, which uses RB again when its cell is the same
       {
         const double t2 = fma(Shh, av2, y2), t3 = fma(Shh, av0, y3), t4 = fma(Shh, av1, y4);
         ok = ok && (t2 > 0);
         wb = w1b;
         wc = w1c;
+        moved = false;
         stage(std::integral_constant<int, 1>{}, std::false_type{}, t2, t3, t4, AUX ? fma(Shh, a7, y7) : 0.0, RB, RB, 0, w2b, w2c);
-        if (cell != cell_rb) {
-          request(m_cur, cell, RB);
-          cell_rb = cell;
-        }
+        if (moved) request(m_cur, cell, RB);
       }
       // stage 3 (mid record RB); places stage 4 and requests node plane k+1 for it into RA
       {
@@ -856,7 +880,6 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
         wb = w2b;
         wc = w2c;
         stage(std::integral_constant<int, 2>{}, std::true_type{}, t2, t3, t4, AUX ? fma(Shh, k7, y7) : 0.0, RB, RA, s_hi, w3b, w3c);
-        cell_ra = cell;
       }
       // stage 4 (record RA, node plane k+1); nothing to place: the next step starts from the updated state
       {
@@ -882,9 +905,9 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     }
 #ifndef SR_TILE_EXP_NOPRODUCE
     if (REC) {
-      if (wg_live && more) {
+      if (more0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's two kilobytes of node plane k + 2, asked for a step ago
-        mid_from(s_hi, s_nx, m_nx);
+        mid_from(s_hi, s_nx, m_nx, true, more1);
       }
     } else if (!AUX) {
       if (producer && more) produce(NX, s_nx, s_hi, m_nx);
@@ -917,6 +940,10 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
 #ifndef SR_TILE_EXP_NOBARRIER
     __syncthreads();
 #endif
+    if (REC) {
+      nx_r0 += plane_bytes;
+      nx_r1 += plane_bytes;
+    }
     const int t = s_lo;
     s_lo = s_hi;
     s_hi = s_nx;
