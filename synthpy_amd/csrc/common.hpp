@@ -117,6 +117,39 @@ inline unsigned long long stripe_sum(const unsigned long long *host_words, int w
   for (int s = 0; s < kStripes; ++s) t += host_words[16 + ((size_t)which * kStripes + s) * kStripeStride];
   return t;
 }
+// The counter words and striped totals by name.  [kGuardQueue]: length of the edge guard's queue, and after it the length of the
+// queue its float64 re-trace leaves (the two are reset together).  stripe_base: the first word of striped total `which`.
+constexpr int kGuardQueue = 4;
+constexpr int kStripeDeposited = 1, kStripeRetrace = 2;
+constexpr size_t kStripeBytes = sizeof(unsigned long long) * kStripes * kStripeStride;  // one striped total
+inline unsigned long long *counter_word(unsigned long long *counters, int word) { return counters + word; }
+inline unsigned long long *stripe_base(unsigned long long *counters, int which) {
+  return counters + 16 + (size_t)which * kStripes * kStripeStride;
+}
+
+// ---- runtime values -> template arguments --------------------------------------------------------------------------------
+// with_flags(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): every launch that picks a kernel
+// instantiation from runtime booleans is written once, as a generic lambda, and prunes the combinations that must not exist with
+// `if constexpr` (they are never instantiated).
+template <typename F>
+void with_flags(F &&f) {
+  f();
+}
+template <typename F, typename... Rest>
+void with_flags(F &&f, bool b, Rest... rest) {
+  if (b)
+    with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else
+    with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// with_count<MAX>(f, n) calls f(std::integral_constant<int, n>{}) for n in 1..MAX (n is clamped to that range)
+template <int MAX, typename F>
+void with_count(F &&f, int n) {
+  if constexpr (MAX > 1) {
+    if (n < MAX) return with_count<MAX - 1>(f, n);
+  }
+  f(std::integral_constant<int, MAX>{});
+}
 
 // ---- the packed node order of a volume ---------------------------------------------------------------------------
 // Node (ia, ib, ic) -- ia along the probing axis -- sits at

@@ -7,6 +7,12 @@
 // has to round exactly as the reference's: this file is compiled with -ffp-contract=off and
 // fuses only where OpenBLAS' dgemm does (distance: x' = fma(d, theta, x); see the oracle, A7).
 // Bin edges are numpy's linspace values i*step + lo (last edge = hi), recomputed per ray.
+//
+// Layout: the loaders and tests the kernels share (exit_ray, load_field / store_field, bin_hist2, guard_seed / guard_uncertain,
+// add_hits); ONE skeleton for the fused deposits, deposit_patch (one ray per work-item, the workgroup's patch of the detector
+// privatised in LDS), which a kernel gives a front end (bins ray i, says what it adds) and a patch type (tile shape and layout,
+// what a hit adds to a tile bin and an image bin, how a flush item goes to the image); host side: stage_in / stage_out,
+// read_out, deposit_begin / deposit_finish, guard_queue_reset, kernels picked by sr::with_flags / sr::with_count.
 #include <algorithm>
 
 #include "common.hpp"
@@ -194,7 +200,62 @@ __device__ __forceinline__ void apply_chain(const Chain &C, Ray4 &r, Err4 *g = n
   }
 }
 
+// ---- what the kernels of this file share ---------------------------------------------------------------------------
+// the exit ray of launch slot i of a resident bundle, m_to_mm (rtm_solver.py:48-51); xm, ym: its position still in metres
+__device__ __forceinline__ Ray4 exit_ray(const double *rf, int64_t N, int64_t i, double &xm, double &ym) {
+  xm = rf[i];
+  ym = rf[2 * N + i];
+  return Ray4{xm * 1e3, rf[N + i], ym * 1e3, rf[3 * N + i], 0, 0, 0, 0};
+}
+__device__ __forceinline__ Ray4 exit_ray(const double *rf, int64_t N, int64_t i) {
+  double xm, ym;
+  return exit_ray(rf, N, i, xm, ym);
+}
+// E (2, N) complex: the field of ray i
+__device__ __forceinline__ void load_field(const double *__restrict__ E, int64_t N, int64_t i, Ray4 &r) {
+  r.e0r = E[2 * i];
+  r.e0i = E[2 * i + 1];
+  r.e1r = E[2 * (N + i)];
+  r.e1i = E[2 * (N + i) + 1];
+}
+__device__ __forceinline__ void store_field(const Ray4 &r, double *__restrict__ E, int64_t N, int64_t i) {
+  E[2 * i] = r.e0r;
+  E[2 * i + 1] = r.e0i;
+  E[2 * (N + i)] = r.e1r;
+  E[2 * (N + i) + 1] = r.e1i;
+}
+// np.histogram2d's bins of (x, y): true for a hit; (bx, by) are left alone for a NaN coordinate
+__device__ __forceinline__ bool bin_hist2(const Edges &ex, const Edges &ey, double x, double y, int &bx, int &by) {
+  if (!(x == x && y == y)) return false;
+  bx = bin_hist(ex, x);
+  by = bin_hist(ey, y);
+  return bx >= 0 && by >= 0;
+}
+// the hits of a launch: one atomic per wavefront into the striped total (reached by the whole wavefront)
+__device__ __forceinline__ void add_hits(unsigned long long *__restrict__ counter, bool hit) {
+  unsigned long long tot = hit ? 1ull : 0ull;
+  for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
+  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(sr::stripe(counter, sr::kStripeDeposited), tot);
+}
+
+struct Guard {
+  const float *bound;         // per launch slot: angle bound of the mixed build [rad]; 0 = a float64 result
+  double len;                 // position bound = len * angle bound [m]
+  uint32_t *list;             // the slots to trace again
+  unsigned long long *count;
+};
+// the half-widths a ray with angle bound ea starts its chain with; 1.0000001: the few roundings of the half-widths themselves
+__device__ __forceinline__ Err4 guard_seed(const Guard &G, double ea) {
+  return Err4{1e3 * (G.len * ea) * 1.0000001, ea * 1.0000001, 1, 0, 0, 1, 1, 0, 0, 1, false};
+}
+// after apply_chain<false, true>(C, r, &g): could a mask's decision or the pixel differ from the float64 result's?
+__device__ __forceinline__ bool guard_uncertain(const Err4 &g, const Edges &ex, const Edges &ey, const Ray4 &r) {
+  return g.near || near_bin_edge(ex, r.x, g.hx()) || near_bin_edge(ey, r.y, g.hy());
+}
+
 // host-buffer optics: r (4,N) mm in/out, E (2,N) complex in/out
+// (the field rows are spelled out: with load_field / store_field the compiler keeps a second scaled index alive across the
+// chain, 51 VGPRs instead of 49)
 template <bool WITH_E>
 __global__ void k_optics(Chain C, int64_t N, const double *__restrict__ rin, const double *__restrict__ Ein,
                          double *__restrict__ rout, double *__restrict__ Eout) {
@@ -224,11 +285,8 @@ __global__ void k_hist2d(const double *__restrict__ x, const double *__restrict_
                          uint32_t *__restrict__ H) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const double xv = x[i], yv = y[i];
-  if (xv != xv || yv != yv) return;
-  const int bx = bin_hist(ex, xv), by = bin_hist(ey, yv);
-  if (bx < 0 || by < 0) return;
-  atomicAdd(&H[(int64_t)by * ex.n + bx], 1u);
+  int bx, by;
+  if (bin_hist2(ex, ey, x[i], y[i], bx, by)) atomicAdd(&H[(int64_t)by * ex.n + bx], 1u);
 }
 
 __global__ void k_interferogram(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ E,
@@ -270,13 +328,10 @@ __global__ __launch_bounds__(256) void k_rays_optics(Chain C, RefSet R, int64_t 
                                                      const uint32_t *__restrict__ perm, double *__restrict__ rout, double *__restrict__ Eout) {
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j >= N) return;
-  const double xm = rf[j], ym = rf[2 * N + j];
-  Ray4 r{xm * 1e3, rf[N + j], ym * 1e3, rf[3 * N + j], 0, 0, 0, 0};
+  double xm, ym;
+  Ray4 r = exit_ray(rf, N, j, xm, ym);
   if (WITH_E) {
-    r.e0r = Jf[2 * j];
-    r.e0i = Jf[2 * j + 1];
-    r.e1r = Jf[2 * (N + j)];
-    r.e1i = Jf[2 * (N + j) + 1];
+    load_field(Jf, N, j, r);
     R.add_to(xm, ym, r.e1r, r.e1i);
   }
   apply_chain<WITH_E>(C, r);
@@ -285,12 +340,7 @@ __global__ __launch_bounds__(256) void k_rays_optics(Chain C, RefSet R, int64_t 
   rout[N + i] = r.th;
   rout[2 * N + i] = r.y;
   rout[3 * N + i] = r.ph;
-  if (WITH_E) {
-    Eout[2 * i] = r.e0r;
-    Eout[2 * i + 1] = r.e0i;
-    Eout[2 * (N + i)] = r.e1r;
-    Eout[2 * (N + i) + 1] = r.e1i;
-  }
+  if (WITH_E) store_field(r, Eout, N, i);
 }
 
 __global__ void k_counts_f64(const uint32_t *__restrict__ cnt, int64_t n, double *__restrict__ H) {
@@ -298,83 +348,111 @@ __global__ void k_counts_f64(const uint32_t *__restrict__ cnt, int64_t n, double
   if (p < n) H[p] = (double)cnt[p];
 }
 
-// Fused deposit: exit-plane rays in HBM (metres) -> m_to_mm -> [reference beam] -> chain -> detector.
+// Fused deposits: exit-plane rays in HBM (metres) -> m_to_mm -> [reference beam] -> chain -> detector, one ray per work-item.
 //
 // The rays arrive in launch order, i.e. binned by entry cell, and the imaging chains map neighbouring rays
 // to neighbouring pixels, so the 256 hits of a workgroup fall in a compact patch of the detector.  With
 // TILED the workgroup privatises that patch in LDS: the patch origin is the minimum (bx, by) over the
 // workgroup (LDS atomicMin), hits inside the TW x TH tile are LDS atomics, the few outside it go straight
-// to HBM, and the tile is flushed with one global atomic per NON-EMPTY bin, row by row (coalesced).
-// Integer counts are order-independent, so the image is bit-identical with and without tiles; the complex
-// image sums in a different order (float64 atomics either way).
+// to HBM, and the tile is flushed with one global atomic per NON-EMPTY flush item, row by row (coalesced).
+// Integer counts are order-independent, so the image is bit-identical with and without tiles; the float64
+// images sum in a different order (float64 atomics either way).  A zero contribution is skipped everywhere (x + 0 = x).
+//
+// A PATCH TYPE says what is deposited: the tile's shape TW x TH, its LDS cells (kCells of Cell, kPlanes planes of TW*TH flush
+// items), what a hit carries (Val), and add_tile(tile, bin in the tile, v), add_image(bin in the image, v), flush(tile, plane,
+// bin in the tile, bin in the image).  Layout and flush order decide the LDS banks and the atomics' pattern: they are the
+// patch type's, not the skeleton's.
 constexpr int kTileW = 64, kTileH = 32;   // counts: 2048 bins, 8 KiB of LDS
 constexpr int kCTileW = 32, kCTileH = 16;  // complex: 512 bins x 4 doubles, 16 KiB of LDS
+constexpr int kITileW = 32, kITileH = 16;  // intensity: 512 bins x NCH doubles (16 KiB at four channels: the complex tile's known-good size)
 
-struct Guard {
-  const float *bound;         // per launch slot: angle bound of the mixed build [rad]; 0 = a float64 result
-  double len;                 // position bound = len * angle bound [m]
-  uint32_t *list;             // the slots to trace again
-  unsigned long long *count;
+struct CountsPatch {
+  static constexpr int TW = kTileW, TH = kTileH, kPlanes = 1, kCells = TW * TH;
+  using Cell = uint32_t;  // of the tile and of the image
+  struct Val {};
+  uint32_t *__restrict__ img;
+  __device__ __forceinline__ void add_tile(Cell *tile, int t, const Val &) const { atomicAdd(&tile[t], 1u); }
+  __device__ __forceinline__ void add_image(int64_t p, const Val &) const { atomicAdd(&img[p], 1u); }
+  __device__ __forceinline__ void flush(const Cell *tile, int, int t, int64_t p) const {
+    const uint32_t cnt = tile[t];
+    if (cnt) atomicAdd(&img[p], cnt);
+  }
 };
 
-template <int KIND, bool TILED, bool GUARD = false>
-__global__ __launch_bounds__(256) void k_deposit(Chain C, RefSet R, int64_t N, const double *__restrict__ rf,
-                                                 const double *__restrict__ Jf, Edges ex, Edges ey, void *__restrict__ img,
-                                                 unsigned long long *__restrict__ counter, Guard G) {
-  constexpr int TW = KIND == SR_IMG_COMPLEX ? kCTileW : kTileW, TH = KIND == SR_IMG_COMPLEX ? kCTileH : kTileH;
+// (2, ny, nx) complex image; the tile is [bin][4] interleaved: {Re Ex, Im Ex, Re Ey, Im Ey} of a bin side by side
+struct ComplexPatch {
+  static constexpr int TW = kCTileW, TH = kCTileH, kPlanes = 1, kCells = TW * TH * 4;
+  using Cell = double;
+  using Val = Ray4;  // the ray's field
+  double *__restrict__ img;
+  int64_t plane;
+  // E_x of an unrotated ray is exactly -0: skipping zeros saves half of the atomics
+  static __device__ __forceinline__ void add(double *x, double *y, double e0r, double e0i, double e1r, double e1i) {
+    if (e0r != 0.0) unsafeAtomicAdd(&x[0], e0r);
+    if (e0i != 0.0) unsafeAtomicAdd(&x[1], e0i);
+    if (e1r != 0.0) unsafeAtomicAdd(&y[0], e1r);
+    if (e1i != 0.0) unsafeAtomicAdd(&y[1], e1i);
+  }
+  __device__ __forceinline__ void add_tile(Cell *tile, int t, const Val &r) const {
+    double *s = tile + (size_t)t * 4;
+    add(s, s + 2, r.e0r, r.e0i, r.e1r, r.e1i);
+  }
+  __device__ __forceinline__ void add_image(int64_t p, const Val &r) const {
+    add(img + 2 * p, img + 2 * (plane + p), r.e0r, r.e0i, r.e1r, r.e1i);
+  }
+  __device__ __forceinline__ void flush(const Cell *tile, int, int t, int64_t p) const {
+    const double *s = tile + (size_t)t * 4;
+    if (s[0] != 0.0 || s[1] != 0.0 || s[2] != 0.0 || s[3] != 0.0) add(img + 2 * p, img + 2 * (plane + p), s[0], s[1], s[2], s[3]);
+  }
+};
+
+// (NCH, ny, nx) float64 image; the tile is [channel][bin] planar and flushed channel by channel
+template <int NCH>
+struct IntensityPatch {
+  static constexpr int TW = kITileW, TH = kITileH, kPlanes = NCH, kCells = TW * TH * NCH;
+  using Cell = double;
+  struct Val {
+    double w[NCH];
+  };
+  double *__restrict__ img;
+  int64_t plane;
+  __device__ __forceinline__ void add_tile(Cell *tile, int t, const Val &v) const {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (v.w[c] != 0.0) unsafeAtomicAdd(&tile[c * (TW * TH) + t], v.w[c]);
+  }
+  __device__ __forceinline__ void add_image(int64_t p, const Val &v) const {
+    double *g = img + p;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (v.w[c] != 0.0) unsafeAtomicAdd(&g[c * plane], v.w[c]);
+  }
+  __device__ __forceinline__ void flush(const Cell *tile, int c, int t, int64_t p) const {
+    const double s = tile[c * (TW * TH) + t];
+    if (s != 0.0) unsafeAtomicAdd(&img[c * plane + p], s);
+  }
+};
+
+template <int KIND>
+using ImagePatch = std::conditional_t<KIND == SR_IMG_COMPLEX, ComplexPatch, CountsPatch>;  // of an sr_image kind (k_deposit)
+
+// The skeleton.  front(i, bx, by, v) is called by EVERY work-item, out-of-range ones included (the edge guard's queue_push must
+// be reached by the whole wavefront); it leaves (bx, by) at (-1, -1) unless ray i hits the detector, and in v what the hit adds.
+template <bool TILED, typename Patch, typename Front>
+__device__ __forceinline__ void deposit_patch(const Edges &ex, const Edges &ey, const Patch &P, unsigned long long *__restrict__ counter,
+                                              Front &&front) {
+  constexpr int TW = Patch::TW, TH = Patch::TH, TB = TW * TH;
   __shared__ int org[2];
-  __shared__ double tile_store[TILED ? (KIND == SR_IMG_COMPLEX ? TW * TH * 4 : TW * TH / 2) : 1];
+  __shared__ typename Patch::Cell tile[TILED ? Patch::kCells : 1];
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (TILED) {
     if (threadIdx.x < 2) org[threadIdx.x] = 0x7fffffff;
-    if (KIND == SR_IMG_COMPLEX) {
-      for (int t = threadIdx.x; t < TW * TH * 4; t += blockDim.x) tile_store[t] = 0.0;
-    } else {
-      uint32_t *tc = reinterpret_cast<uint32_t *>(tile_store);
-      for (int t = threadIdx.x; t < TW * TH; t += blockDim.x) tc[t] = 0u;
-    }
+    for (int t = threadIdx.x; t < Patch::kCells; t += blockDim.x) tile[t] = 0;
     __syncthreads();
   }
   int bx = -1, by = -1;
-  bool again = false;
-  Ray4 r{0, 0, 0, 0, 0, 0, 0, 0};
-  if (i < N) {
-    const double xm = rf[i], ym = rf[2 * N + i];
-    r = Ray4{xm * 1e3, rf[N + i], ym * 1e3, rf[3 * N + i], 0, 0, 0, 0};  // m_to_mm (rtm_solver.py:48-51)
-    if (KIND == SR_IMG_COMPLEX) {
-      r.e0r = Jf[2 * i];
-      r.e0i = Jf[2 * i + 1];
-      r.e1r = Jf[2 * (N + i)];
-      r.e1i = Jf[2 * (N + i) + 1];
-      R.add_to(xm, ym, r.e1r, r.e1i);
-      apply_chain<true>(C, r);
-      bx = bin_digitize(ex, r.x);
-      by = bin_digitize(ey, r.y);
-    } else if (GUARD) {
-      const double ea = (double)G.bound[i];
-      if (!(ea < INFINITY)) {  // a kernel that keeps no bound (sub-steps, optional terms): every such ray is traced again
-        again = true;
-      } else if (ea > 0.0) {  // a mixed-precision result: is its pixel (and every mask's decision) the float64 result's as well?
-        // 1.0000001: the few roundings of the half-widths themselves
-        Err4 g{1e3 * (G.len * ea) * 1.0000001, ea * 1.0000001, 1, 0, 0, 1, 1, 0, 0, 1, false};
-        apply_chain<false, true>(C, r, &g);
-        again = g.near || near_bin_edge(ex, r.x, g.hx()) || near_bin_edge(ey, r.y, g.hy());
-      } else {
-        apply_chain<false>(C, r);
-      }
-      if (!again && r.x == r.x && r.y == r.y) {
-        bx = bin_hist(ex, r.x);
-        by = bin_hist(ey, r.y);
-      }
-    } else {
-      apply_chain<false>(C, r);
-      if (r.x == r.x && r.y == r.y) {
-        bx = bin_hist(ex, r.x);
-        by = bin_hist(ey, r.y);
-      }
-    }
-  }
-  if (GUARD) sr::queue_push(G.count, G.list, again, (uint32_t)i);  // counted after their float64 re-trace (k_deposit_list)
+  typename Patch::Val v{};
+  front(i, bx, by, v);
   const bool hit = bx >= 0 && by >= 0;
   int tx = -1, ty = -1;
   if (TILED) {
@@ -388,56 +466,64 @@ __global__ __launch_bounds__(256) void k_deposit(Chain C, RefSet R, int64_t N, c
   }
   const bool in_tile = TILED && hit && tx < TW && ty < TH;  // tx, ty >= 0 by construction of the origin
   if (hit) {
-    if (KIND == SR_IMG_COMPLEX) {
-      // a zero contribution is skipped (x + 0 = x): E_x of an unrotated ray is exactly -0, half of the atomics
-      if (in_tile) {
-        double *t = tile_store + (size_t)(ty * TW + tx) * 4;
-        if (r.e0r != 0.0) unsafeAtomicAdd(&t[0], r.e0r);
-        if (r.e0i != 0.0) unsafeAtomicAdd(&t[1], r.e0i);
-        if (r.e1r != 0.0) unsafeAtomicAdd(&t[2], r.e1r);
-        if (r.e1i != 0.0) unsafeAtomicAdd(&t[3], r.e1i);
-      } else {
-        double *amp = (double *)img;
-        const int64_t plane = (int64_t)ex.n * ey.n, p = (int64_t)by * ex.n + bx;
-        if (r.e0r != 0.0) unsafeAtomicAdd(&amp[2 * p], r.e0r);
-        if (r.e0i != 0.0) unsafeAtomicAdd(&amp[2 * p + 1], r.e0i);
-        if (r.e1r != 0.0) unsafeAtomicAdd(&amp[2 * (plane + p)], r.e1r);
-        if (r.e1i != 0.0) unsafeAtomicAdd(&amp[2 * (plane + p) + 1], r.e1i);
-      }
-    } else {
-      if (in_tile)
-        atomicAdd(&reinterpret_cast<uint32_t *>(tile_store)[ty * TW + tx], 1u);
-      else
-        atomicAdd(&((uint32_t *)img)[(int64_t)by * ex.n + bx], 1u);
-    }
+    if (in_tile)
+      P.add_tile(tile, ty * TW + tx, v);
+    else
+      P.add_image((int64_t)by * ex.n + bx, v);
   }
   if (TILED) {
     __syncthreads();
     const int ox = org[0], oy = org[1];
     if (ox != 0x7fffffff) {  // at least one hit in this workgroup
-      for (int t = threadIdx.x; t < TW * TH; t += blockDim.x) {
+      for (int q = threadIdx.x; q < TB * Patch::kPlanes; q += blockDim.x) {
+        const int c = q / TB, t = q % TB;
         const int gx = ox + t % TW, gy = oy + t / TW;
-        if (gx >= ex.n || gy >= ey.n) continue;
-        if (KIND == SR_IMG_COMPLEX) {
-          const double *s = tile_store + (size_t)t * 4;
-          if (s[0] != 0.0 || s[1] != 0.0 || s[2] != 0.0 || s[3] != 0.0) {
-            double *amp = (double *)img;
-            const int64_t plane = (int64_t)ex.n * ey.n, p = (int64_t)gy * ex.n + gx;
-            if (s[0] != 0.0) unsafeAtomicAdd(&amp[2 * p], s[0]);
-            if (s[1] != 0.0) unsafeAtomicAdd(&amp[2 * p + 1], s[1]);
-            if (s[2] != 0.0) unsafeAtomicAdd(&amp[2 * (plane + p)], s[2]);
-            if (s[3] != 0.0) unsafeAtomicAdd(&amp[2 * (plane + p) + 1], s[3]);
-          }
-        } else {
-          const uint32_t cnt = reinterpret_cast<const uint32_t *>(tile_store)[t];
-          if (cnt) atomicAdd(&((uint32_t *)img)[(int64_t)gy * ex.n + gx], cnt);
-        }
+        if (gx >= ex.n || gy >= ey.n) continue;  // the tile overhangs the detector
+        P.flush(tile, c, t, (int64_t)gy * ex.n + gx);
       }
     }
   }
-  unsigned long long tot = hit ? 1ull : 0ull;
-  for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(sr::stripe(counter, 1), tot);
+  add_hits(counter, hit);
+}
+
+// counts (np.histogram2d's binning; GUARD: the edge guard queues the rays whose pixel is not certain, which are counted after
+// their float64 re-trace by k_deposit_list) or the complex image (np.digitize's binning, reference beams, field factors)
+template <int KIND, bool TILED, bool GUARD = false>
+__global__ __launch_bounds__(256) void k_deposit(Chain C, RefSet R, int64_t N, const double *__restrict__ rf,
+                                                 const double *__restrict__ Jf, Edges ex, Edges ey,
+                                                 typename ImagePatch<KIND>::Cell *__restrict__ img,
+                                                 unsigned long long *__restrict__ counter, Guard G) {
+  if constexpr (KIND == SR_IMG_COMPLEX) {
+    deposit_patch<TILED>(ex, ey, ComplexPatch{img, (int64_t)ex.n * ey.n}, counter, [&](int64_t i, int &bx, int &by, Ray4 &r) {
+      if (i >= N) return;
+      double xm, ym;
+      r = exit_ray(rf, N, i, xm, ym);
+      load_field(Jf, N, i, r);
+      R.add_to(xm, ym, r.e1r, r.e1i);
+      apply_chain<true>(C, r);
+      bx = bin_digitize(ex, r.x);
+      by = bin_digitize(ey, r.y);
+    });
+  } else {
+    deposit_patch<TILED>(ex, ey, CountsPatch{img}, counter, [&](int64_t i, int &bx, int &by, CountsPatch::Val &) {
+      bool again = false;
+      if (i < N) {
+        Ray4 r = exit_ray(rf, N, i);
+        const double ea = GUARD ? (double)G.bound[i] : 0.0;
+        if (!(ea < INFINITY)) {  // a kernel that keeps no bound (sub-steps, optional terms): every such ray is traced again
+          again = true;
+        } else if (ea > 0.0) {  // a mixed-precision result: is its pixel (and every mask's decision) the float64 result's as well?
+          Err4 g = guard_seed(G, ea);
+          apply_chain<false, true>(C, r, &g);
+          again = guard_uncertain(g, ex, ey, r);
+        } else {
+          apply_chain<false>(C, r);
+        }
+        if (!again) bin_hist2(ex, ey, r.x, r.y, bx, by);
+      }
+      if (GUARD) sr::queue_push(G.count, G.list, again, (uint32_t)i);  // must be reached by the whole wavefront
+    });
+  }
 }
 
 // counts deposit of the launch slots list[0..*count): the rays the edge guard had traced again (few; global atomics)
@@ -447,18 +533,15 @@ __global__ __launch_bounds__(256) void k_deposit_list(Chain C, int64_t N, const 
   const unsigned long long n = *count;
   unsigned long long hits = 0;
   for (unsigned long long t = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; t < n; t += (unsigned long long)gridDim.x * blockDim.x) {
-    const int64_t i = list[t];
-    Ray4 r{rf[i] * 1e3, rf[N + i], rf[2 * N + i] * 1e3, rf[3 * N + i], 0, 0, 0, 0};
+    Ray4 r = exit_ray(rf, N, list[t]);
     apply_chain<false>(C, r);
-    if (r.x == r.x && r.y == r.y) {
-      const int bx = bin_hist(ex, r.x), by = bin_hist(ey, r.y);
-      if (bx >= 0 && by >= 0) {
-        atomicAdd(&img[(int64_t)by * ex.n + bx], 1u);
-        ++hits;
-      }
+    int bx, by;
+    if (bin_hist2(ex, ey, r.x, r.y, bx, by)) {
+      atomicAdd(&img[(int64_t)by * ex.n + bx], 1u);
+      ++hits;
     }
   }
-  if (hits) atomicAdd(sr::stripe(counter, 1), hits);
+  if (hits) atomicAdd(sr::stripe(counter, sr::kStripeDeposited), hits);
 }
 
 // ---- polarimetry: analyser-weighted intensity images (no reference counterpart) ------------------------------------
@@ -469,10 +552,10 @@ struct Analysers {
   double a[SR_MAX_ANALYSERS], b[SR_MAX_ANALYSERS];
 };
 
-__device__ __forceinline__ double analyser_weight(const Analysers &A, int c, double e0r, double e0i, double e1r, double e1i) {
+__device__ __forceinline__ double analyser_weight(const Analysers &A, int c, const Ray4 &r) {
   const double a = A.a[c], b = A.b[c];
-  if (a != a) return (e0r * e0r + e0i * e0i) + (e1r * e1r + e1i * e1i);
-  const double re = a * e0r + b * e1r, im = a * e0i + b * e1i;
+  if (a != a) return (r.e0r * r.e0r + r.e0i * r.e0i) + (r.e1r * r.e1r + r.e1i * r.e1i);
+  const double re = a * r.e0r + b * r.e1r, im = a * r.e0i + b * r.e1i;
   return re * re + im * im;
 }
 
@@ -482,97 +565,33 @@ __global__ void k_intensity2d(const double *__restrict__ x, const double *__rest
                               Edges ex, Edges ey, Analysers A, double *__restrict__ I) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const double xv = x[i], yv = y[i];
-  if (xv != xv || yv != yv) return;
-  const int bx = bin_hist(ex, xv), by = bin_hist(ey, yv);
-  if (bx < 0 || by < 0) return;
+  int bx, by;
+  if (!bin_hist2(ex, ey, x[i], y[i], bx, by)) return;
   const int64_t plane = (int64_t)ex.n * ey.n, p = (int64_t)by * ex.n + bx;
-  const double e0r = E[2 * i], e0i = E[2 * i + 1], e1r = E[2 * (N + i)], e1i = E[2 * (N + i) + 1];
+  Ray4 r{};
+  load_field(E, N, i, r);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    const double w = analyser_weight(A, c, e0r, e0i, e1r, e1i);
+    const double w = analyser_weight(A, c, r);
     if (w != 0.0) unsafeAtomicAdd(&I[c * plane + p], w);
   }
 }
 
-// Fused intensity deposit: exit-plane rays in HBM (metres) -> m_to_mm -> masks-only chain -> bin_hist -> NCH weighted
-// float64 sums per ray in ONE pass.  Laid out as k_deposit: one ray per work-item, the workgroup's patch origin by LDS
-// atomicMin, and with TILED a [NCH][TH][TW] tile of doubles in LDS (16 KiB at four channels: the complex tile's known-good
-// size) that is flushed channel by channel, row by row, with one global atomic per non-zero (bin, channel).
-constexpr int kITileW = 32, kITileH = 16;
-
+// Fused intensity deposit: masks-only chain -> bin_hist -> NCH weighted float64 sums per ray in ONE pass over the rays
 template <int NCH, bool TILED>
 __global__ __launch_bounds__(256) void k_deposit_intensity(Chain C, int64_t N, const double *__restrict__ rf,
                                                            const double *__restrict__ Jf, Edges ex, Edges ey, Analysers A,
                                                            double *__restrict__ img, unsigned long long *__restrict__ counter) {
-  constexpr int TW = kITileW, TH = kITileH, TB = TW * TH;
-  __shared__ int org[2];
-  __shared__ double tile[TILED ? TB * NCH : 1];
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (TILED) {
-    if (threadIdx.x < 2) org[threadIdx.x] = 0x7fffffff;
-    for (int t = threadIdx.x; t < TB * NCH; t += blockDim.x) tile[t] = 0.0;
-    __syncthreads();
-  }
-  int bx = -1, by = -1;
-  double w[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) w[c] = 0.0;
-  if (i < N) {
-    Ray4 r{rf[i] * 1e3, rf[N + i], rf[2 * N + i] * 1e3, rf[3 * N + i], 0, 0, 0, 0};  // m_to_mm
+  using Patch = IntensityPatch<NCH>;
+  deposit_patch<TILED>(ex, ey, Patch{img, (int64_t)ex.n * ey.n}, counter, [&](int64_t i, int &bx, int &by, typename Patch::Val &v) {
+    if (i >= N) return;
+    Ray4 r = exit_ray(rf, N, i);
     apply_chain<false>(C, r);
-    if (r.x == r.x && r.y == r.y) {
-      bx = bin_hist(ex, r.x);
-      by = bin_hist(ey, r.y);
-    }
-    if (bx >= 0 && by >= 0) {
-      const double e0r = Jf[2 * i], e0i = Jf[2 * i + 1], e1r = Jf[2 * (N + i)], e1i = Jf[2 * (N + i) + 1];
+    if (!bin_hist2(ex, ey, r.x, r.y, bx, by)) return;
+    load_field(Jf, N, i, r);
 #pragma unroll
-      for (int c = 0; c < NCH; ++c) w[c] = analyser_weight(A, c, e0r, e0i, e1r, e1i);
-    }
-  }
-  const bool hit = bx >= 0 && by >= 0;
-  int tx = -1, ty = -1;
-  if (TILED) {
-    if (hit) {
-      atomicMin(&org[0], bx);
-      atomicMin(&org[1], by);
-    }
-    __syncthreads();
-    tx = bx - org[0];
-    ty = by - org[1];
-  }
-  const bool in_tile = TILED && hit && tx < TW && ty < TH;  // tx, ty >= 0 by construction of the origin
-  const int64_t plane = (int64_t)ex.n * ey.n;
-  if (hit) {
-    if (in_tile) {
-      double *t = tile + ty * TW + tx;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (w[c] != 0.0) unsafeAtomicAdd(&t[c * TB], w[c]);
-    } else {
-      double *g = img + (int64_t)by * ex.n + bx;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (w[c] != 0.0) unsafeAtomicAdd(&g[c * plane], w[c]);
-    }
-  }
-  if (TILED) {
-    __syncthreads();
-    const int ox = org[0], oy = org[1];
-    if (ox != 0x7fffffff) {  // at least one hit in this workgroup
-      for (int q = threadIdx.x; q < TB * NCH; q += blockDim.x) {
-        const int c = q / TB, t = q % TB;
-        const int gx = ox + t % TW, gy = oy + t / TW;
-        if (gx >= ex.n || gy >= ey.n) continue;
-        const double s = tile[q];
-        if (s != 0.0) unsafeAtomicAdd(&img[c * plane + (int64_t)gy * ex.n + gx], s);
-      }
-    }
-  }
-  unsigned long long tot = hit ? 1ull : 0ull;
-  for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-  if ((threadIdx.x & 63) == 0 && tot) atomicAdd(sr::stripe(counter, 1), tot);
+    for (int c = 0; c < NCH; ++c) v.w[c] = analyser_weight(A, c, r);
+  });
 }
 
 // Rotation map of two analyser channels at +beta and -beta (sr_image_rotation): D = (I+ - I-)/(I+ + I-),
@@ -608,10 +627,10 @@ __global__ __launch_bounds__(256) void k_guard_flags(const GuardSet *__restrict_
       again = true;
     } else if (ea > 0.0) {
       for (int q = 0; q < S->n && !again; ++q) {
-        Ray4 r{rf[i] * 1e3, rf[N + i], rf[2 * N + i] * 1e3, rf[3 * N + i], 0, 0, 0, 0};
-        Err4 g{1e3 * (G.len * ea) * 1.0000001, ea * 1.0000001, 1, 0, 0, 1, 1, 0, 0, 1, false};
+        Ray4 r = exit_ray(rf, N, i);
+        Err4 g = guard_seed(G, ea);
         apply_chain<false, true>(S->C[q], r, &g);
-        again = g.near || near_bin_edge(S->ex[q], r.x, g.hx()) || near_bin_edge(S->ey[q], r.y, g.hy());
+        again = guard_uncertain(g, S->ex[q], S->ey[q], r);
       }
     }
   }
@@ -651,26 +670,8 @@ int make_refs(const sr_deposit_params *p, RefSet &R) {
 }
 
 Edges make_edges(double lo, double hi, int nbins) {
-  Edges e;
-  e.lo = lo;
-  e.hi = hi;
-  e.n = nbins;
-  e.step = (hi - lo) / nbins;  // np.linspace: delta / div
-  return e;
+  return Edges{lo, hi, (hi - lo) / nbins, nbins};  // step: np.linspace's delta / div
 }
-
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { sr::dev_free(p); }
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-    if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    return SR_OK;
-  }
-};
-
-// the device buffer of a new image, zeroed (sr_image_create, sr_image_create_intensity)
-int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi, int64_t bytes);
 
 int make_analysers(const double *ab, int n_ch, Analysers &A) {
   SR_CHECK(ab != nullptr && n_ch >= 1 && n_ch <= SR_MAX_ANALYSERS, "analysers: %d channels (1..%d), or NULL", n_ch, SR_MAX_ANALYSERS);
@@ -680,6 +681,117 @@ int make_analysers(const double *ab, int n_ch, Analysers &A) {
     A.b[c] = ab[2 * c + 1];
     SR_CHECK((A.a[c] != A.a[c]) == (A.b[c] != A.b[c]), "analyser %d: (a, b) must both be NaN (no analyser) or both finite", c);
   }
+  return SR_OK;
+}
+
+// ---- staging of the host-array entry points ----------------------------------------------------------------------------
+// a device buffer for the length of one call
+struct DevBuf {
+  void *p = nullptr;
+  ~DevBuf() { sr::dev_free(p); }
+  int alloc(size_t bytes) {
+    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    return SR_OK;
+  }
+  int zeroed(size_t bytes, hipStream_t st) {  // a result that kernels add into
+    int rc = alloc(bytes);
+    if (rc) return rc;
+    SR_HIP(hipMemsetAsync(p, 0, bytes, st));
+    return SR_OK;
+  }
+  template <typename T>
+  T *as() const {
+    return static_cast<T *>(p);
+  }
+};
+struct HostIn {
+  DevBuf &buf;
+  const void *host;
+  size_t bytes;
+};
+struct HostOut {
+  void *host;
+  const void *dev;
+  size_t bytes;
+};
+// host arrays into fresh device buffers: all are allocated, then all copies are queued on `st`; a NULL array is skipped and
+// its buffer stays NULL (sr_optics without E)
+int stage_in(hipStream_t st, std::initializer_list<HostIn> in) {
+  for (const HostIn &a : in)
+    if (a.host)
+      if (int rc = a.buf.alloc(a.bytes)) return rc;
+  for (const HostIn &a : in)
+    if (a.host) SR_HIP(hipMemcpyAsync(a.buf.p, a.host, a.bytes, hipMemcpyHostToDevice, st));
+  return SR_OK;
+}
+// after the launches: their error, the results to the host (a NULL destination is skipped), and the stream is waited for -- the
+// call is done with its buffers
+int stage_out(hipStream_t st, std::initializer_list<HostOut> out) {
+  SR_HIP(hipGetLastError());
+  for (const HostOut &a : out)
+    if (a.host) SR_HIP(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  return SR_OK;
+}
+// n doubles for the host: fill(d, grid, st) launches the kernel that writes them into the call's scratch block (256 per workgroup)
+template <typename Fill>
+int read_out(double *host, int64_t n, Fill &&fill) {
+  hipStream_t st = sr::ctx().stream;
+  double *d = static_cast<double *>(sr::scratch(sizeof(double) * n));
+  if (!d) return SR_ERR_HIP;
+  fill(d, dim3(sr::grid_for(n, 256)), st);
+  return stage_out(st, {{host, d, sizeof(double) * n}});
+}
+
+// ---- what the bundle deposits share --------------------------------------------------------------------------------------
+// the edge guard's queue of a bundle, emptied: its length (and the re-trace's own queue after it) and the re-trace's step total
+int guard_queue_reset(const sr_rays *r, hipStream_t st) {
+  SR_HIP(hipMemsetAsync(sr::counter_word(r->counters, sr::kGuardQueue), 0, 2 * sizeof(unsigned long long), st));
+  SR_HIP(hipMemsetAsync(sr::stripe_base(r->counters, sr::kStripeRetrace), 0, sr::kStripeBytes, st));
+  return SR_OK;
+}
+Guard guard_of(const sr_rays *r) { return Guard{r->guard, r->guard_len, r->fb_list, sr::counter_word(r->counters, sr::kGuardQueue)}; }
+
+// A timed bundle deposit: begin resets the stats and (unless the bundle is empty: nothing else happens then) the `deposited`
+// total and records the start; finish records the end and, when stats are asked for, waits and fills them in.
+int deposit_begin(const sr_rays *r, sr_deposit_stats *stats) {
+  if (stats) *stats = sr_deposit_stats{0.0, 0, 0};
+  if (r->n == 0) return SR_OK;
+  sr::Context &c = sr::ctx();
+  SR_HIP(hipMemsetAsync(sr::stripe_base(r->counters, sr::kStripeDeposited), 0, sr::kStripeBytes, c.stream));
+  SR_HIP(hipEventRecord(c.ev[0], c.stream));
+  return SR_OK;
+}
+int deposit_finish(const sr_rays *r, sr_deposit_stats *stats, bool guarded) {
+  sr::Context &c = sr::ctx();
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], c.stream));
+  if (!stats) return SR_OK;
+  std::vector<unsigned long long> hw(sr::kCounterWords, 0ull);
+  SR_HIP(hipMemcpyAsync(hw.data(), r->counters, sizeof(unsigned long long) * sr::kCounterWords, hipMemcpyDeviceToHost, c.stream));
+  SR_HIP(hipStreamSynchronize(c.stream));
+  float ms = 0.f;
+  SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+  stats->kernel_ms = ms;
+  stats->deposited = (int64_t)sr::stripe_sum(hw.data(), sr::kStripeDeposited);
+  stats->retraced = guarded ? (int64_t)hw[sr::kGuardQueue] : 0;
+  return SR_OK;
+}
+
+// the device buffer of a new image, zeroed (sr_image_create, sr_image_create_intensity)
+int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi, int64_t bytes) {
+  int rc = sr::ensure_init();
+  if (rc) return rc;
+  void *d = nullptr;
+  hipError_t e = hipMalloc(&d, (size_t)bytes);
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_image_create: hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
+  e = hipMemsetAsync(d, 0, (size_t)bytes, sr::ctx().stream);
+  if (e != hipSuccess) {
+    sr::dev_free(d);
+    return sr::fail(SR_ERR_HIP, "sr_image_create: memset failed: %s", hipGetErrorString(e));
+  }
+  *out = new sr_image{kind, nx, ny, n_ch, x_lo, x_hi, y_lo, y_hi, d, bytes};
   return SR_OK;
 }
 
@@ -698,22 +810,15 @@ int sr_optics(const sr_optic *chain, int n_ops, double kwave, int64_t N, const d
   if ((rc = sr::ensure_init())) return rc;
   hipStream_t st = sr::ctx().stream;
   DevBuf dr, dE;
-  if ((rc = dr.alloc(sizeof(double) * 4 * N))) return rc;
-  SR_HIP(hipMemcpyAsync(dr.p, r_in, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
-  if (E_in) {
-    if ((rc = dE.alloc(sizeof(double) * 4 * N))) return rc;
-    SR_HIP(hipMemcpyAsync(dE.p, E_in, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((k_optics<true>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N, (const double *)dr.p,
-                       (const double *)dE.p, (double *)dr.p, (double *)dE.p);
-  } else {
-    hipLaunchKernelGGL((k_optics<false>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N, (const double *)dr.p,
-                       (const double *)nullptr, (double *)dr.p, (double *)nullptr);
-  }
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(r_out, dr.p, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st));
-  if (E_out) SR_HIP(hipMemcpyAsync(E_out, dE.p, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  const size_t rb = sizeof(double) * 4 * N;
+  if ((rc = stage_in(st, {{dr, r_in, rb}, {dE, E_in, rb}}))) return rc;
+  sr::with_flags(
+      [&](auto with_e) {
+        hipLaunchKernelGGL((k_optics<with_e.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N, dr.as<const double>(),
+                           dE.as<const double>(), dr.as<double>(), dE.as<double>());
+      },
+      E_in != nullptr);
+  return stage_out(st, {{r_out, dr.p, rb}, {E_out, dE.p, rb}});
 }
 
 int sr_hist2d(const double *x, const double *y, int64_t N, int nxb, int nyb, double x_lo, double x_hi, double y_lo,
@@ -726,19 +831,13 @@ int sr_hist2d(const double *x, const double *y, int64_t N, int nxb, int nyb, dou
   hipStream_t st = sr::ctx().stream;
   DevBuf dx, dy, dH;
   const size_t hb = sizeof(uint32_t) * (size_t)nxb * nyb;
-  if ((rc = dH.alloc(hb))) return rc;
-  SR_HIP(hipMemsetAsync(dH.p, 0, hb, st));
+  if ((rc = dH.zeroed(hb, st))) return rc;
   if (N > 0) {
-    if ((rc = dx.alloc(sizeof(double) * N)) || (rc = dy.alloc(sizeof(double) * N))) return rc;
-    SR_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_hist2d, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx.p, (const double *)dy.p, N,
-                       make_edges(x_lo, x_hi, nxb), make_edges(y_lo, y_hi, nyb), (uint32_t *)dH.p);
-    SR_HIP(hipGetLastError());
+    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}}))) return rc;
+    hipLaunchKernelGGL(k_hist2d, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(), N,
+                       make_edges(x_lo, x_hi, nxb), make_edges(y_lo, y_hi, nyb), dH.as<uint32_t>());
   }
-  SR_HIP(hipMemcpyAsync(H, dH.p, hb, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return stage_out(st, {{H, dH.p, hb}});
 }
 
 int sr_interferogram(const double *x, const double *y, const double *E, int64_t N, int nxe, int nye, double x_lo,
@@ -750,33 +849,20 @@ int sr_interferogram(const double *x, const double *y, const double *E, int64_t 
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
   DevBuf dx, dy, dE, dA;
-  const size_t ab = sizeof(double) * 4 * (size_t)(nxe - 1) * (nye - 1);
-  if ((rc = dA.alloc(ab))) return rc;
-  SR_HIP(hipMemsetAsync(dA.p, 0, ab, st));
+  const int64_t plane = (int64_t)(nxe - 1) * (nye - 1);
+  const size_t ab = sizeof(double) * 4 * (size_t)plane;
+  if ((rc = dA.zeroed(ab, st))) return rc;
   if (N > 0) {
-    if ((rc = dx.alloc(sizeof(double) * N)) || (rc = dy.alloc(sizeof(double) * N)) || (rc = dE.alloc(sizeof(double) * 4 * N)))
-      return rc;
-    SR_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(dE.p, E, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_interferogram, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx.p,
-                       (const double *)dy.p, (const double *)dE.p, N, make_edges(x_lo, x_hi, nxe - 1),
-                       make_edges(y_lo, y_hi, nye - 1), (double *)dA.p);
-    SR_HIP(hipGetLastError());
+    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
+    hipLaunchKernelGGL(k_interferogram, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(),
+                       dE.as<const double>(), N, make_edges(x_lo, x_hi, nxe - 1), make_edges(y_lo, y_hi, nye - 1), dA.as<double>());
   }
+  if (!H) return stage_out(st, {{amp, dA.p, ab}});
+  SR_HIP(hipGetLastError());
   if (amp) SR_HIP(hipMemcpyAsync(amp, dA.p, ab, hipMemcpyDeviceToHost, st));
-  if (H) {
-    DevBuf dH;
-    const int64_t plane = (int64_t)(nxe - 1) * (nye - 1);
-    if ((rc = dH.alloc(sizeof(double) * plane))) return rc;
-    hipLaunchKernelGGL(k_amplitude, dim3(sr::grid_for(plane, 256)), dim3(256), 0, st, (const double *)dA.p, plane, (double *)dH.p);
-    SR_HIP(hipGetLastError());
-    SR_HIP(hipMemcpyAsync(H, dH.p, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-    return SR_OK;
-  }
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return read_out(H, plane, [&](double *dH, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_amplitude, grid, dim3(256), 0, s, dA.as<const double>(), plane, dH);
+  });
 }
 
 int sr_interfere_ref_beam(const double *x, const double *y, int64_t N, double n_fringes, double deg, double *E) {
@@ -786,17 +872,10 @@ int sr_interfere_ref_beam(const double *x, const double *y, int64_t N, double n_
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
   DevBuf dx, dy, dE;
-  if ((rc = dx.alloc(sizeof(double) * N)) || (rc = dy.alloc(sizeof(double) * N)) || (rc = dE.alloc(sizeof(double) * 4 * N)))
-    return rc;
-  SR_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * N, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(dE.p, E, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_ref_beam, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx.p, (const double *)dy.p, N,
-                     make_ref(n_fringes, deg), (double *)dE.p);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(E, dE.p, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
+  hipLaunchKernelGGL(k_ref_beam, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(), N,
+                     make_ref(n_fringes, deg), dE.as<double>());
+  return stage_out(st, {{E, dE.p, sizeof(double) * 4 * N}});
 }
 
 // ---- device-resident images -------------------------------------------------------------
@@ -828,39 +907,6 @@ int sr_image_create_intensity(sr_image **out, int n_ch, int nx, int ny, double x
   return image_alloc(out, SR_IMG_INTENSITY, n_ch, nx, ny, x_lo, x_hi, y_lo, y_hi, (int64_t)sizeof(double) * n_ch * nx * ny);
 }
 
-}  // extern "C"
-
-namespace {
-int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo, double x_hi, double y_lo, double y_hi, int64_t bytes) {
-  int rc = sr::ensure_init();
-  if (rc) return rc;
-  sr_image *img = new sr_image();
-  img->kind = kind;
-  img->n_ch = n_ch;
-  img->nx = nx;
-  img->ny = ny;
-  img->x_lo = x_lo;
-  img->x_hi = x_hi;
-  img->y_lo = y_lo;
-  img->y_hi = y_hi;
-  img->bytes = bytes;
-  hipError_t e = hipMalloc(&img->d, (size_t)img->bytes);
-  if (e != hipSuccess) {
-    delete img;
-    return sr::fail(SR_ERR_HIP, "sr_image_create: hipMalloc(%lld) failed: %s", (long long)img->bytes, hipGetErrorString(e));
-  }
-  e = hipMemsetAsync(img->d, 0, (size_t)img->bytes, sr::ctx().stream);
-  if (e != hipSuccess) {
-    sr_image_destroy(img);
-    return sr::fail(SR_ERR_HIP, "sr_image_create: memset failed: %s", hipGetErrorString(e));
-  }
-  *out = img;
-  return SR_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int sr_image_zero(sr_image *img) {
   SR_CHECK(img != nullptr, "sr_image_zero: NULL image");
   SR_HIP(hipMemsetAsync(img->d, 0, (size_t)img->bytes, sr::ctx().stream));
@@ -877,15 +923,10 @@ int sr_image_download(const sr_image *img, void *host) {
 int sr_image_amplitude(const sr_image *img, double *H) {
   SR_CHECK(img && H, "sr_image_amplitude: NULL argument");
   SR_CHECK(img->kind == SR_IMG_COMPLEX, "sr_image_amplitude: image does not hold a complex field");
-  hipStream_t st = sr::ctx().stream;
   const int64_t plane = (int64_t)(img->nx - 1) * (img->ny - 1);
-  double *dH = static_cast<double *>(sr::scratch(sizeof(double) * plane));
-  if (!dH) return SR_ERR_HIP;
-  hipLaunchKernelGGL(k_amplitude, dim3(sr::grid_for(plane, 256)), dim3(256), 0, st, (const double *)img->d, plane, dH);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(H, dH, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return read_out(H, plane, [&](double *dH, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_amplitude, grid, dim3(256), 0, st, (const double *)img->d, plane, dH);
+  });
 }
 
 int64_t sr_image_bytes(const sr_image *img) { return img ? img->bytes : 0; }
@@ -893,15 +934,10 @@ int64_t sr_image_bytes(const sr_image *img) { return img ? img->bytes : 0; }
 int sr_image_counts_f64(const sr_image *img, double *H) {
   SR_CHECK(img && H, "sr_image_counts_f64: NULL argument");
   SR_CHECK(img->kind == SR_IMG_COUNTS, "sr_image_counts_f64: image does not hold counts");
-  hipStream_t st = sr::ctx().stream;
   const int64_t n = (int64_t)img->nx * img->ny;
-  double *dH = static_cast<double *>(sr::scratch(sizeof(double) * n));
-  if (!dH) return SR_ERR_HIP;
-  hipLaunchKernelGGL(k_counts_f64, dim3(sr::grid_for(n, 256)), dim3(256), 0, st, (const uint32_t *)img->d, n, dH);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(H, dH, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return read_out(H, n, [&](double *dH, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_counts_f64, grid, dim3(256), 0, st, (const uint32_t *)img->d, n, dH);
+  });
 }
 
 int sr_rays_optics(const sr_rays *r, const sr_optic *chain, int n_ops, const sr_deposit_params *p, double *rf_out, double *E_out) {
@@ -918,16 +954,14 @@ int sr_rays_optics(const sr_rays *r, const sr_optic *chain, int n_ops, const sr_
   double *dr = static_cast<double *>(sr::scratch(sizeof(double) * (E_out ? 8 : 4) * (size_t)N));
   if (!dr) return SR_ERR_HIP;
   double *dE = E_out ? dr + 4 * (size_t)N : nullptr;
-  if (E_out)
-    hipLaunchKernelGGL((k_rays_optics<true>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, R, N, (const double *)r->rf,
-                       (const double *)r->Jf, (const uint32_t *)r->perm, dr, dE);
-  else
-    hipLaunchKernelGGL((k_rays_optics<false>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, R, N, (const double *)r->rf,
-                       (const double *)nullptr, (const uint32_t *)r->perm, dr, (double *)nullptr);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(rf_out, dr, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st));
-  if (E_out) SR_HIP(hipMemcpyAsync(E_out, dE, sizeof(double) * 4 * N, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
+  sr::with_flags(
+      [&](auto with_e) {
+        hipLaunchKernelGGL((k_rays_optics<with_e.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, R, N, (const double *)r->rf,
+                           with_e.value ? (const double *)r->Jf : nullptr, (const uint32_t *)r->perm, dr, dE);
+      },
+      E_out != nullptr);
+  rc = stage_out(st, {{rf_out, dr, sizeof(double) * 4 * N}, {E_out, dE, sizeof(double) * 4 * N}});
+  if (rc) return rc;
   sr::scratch_trim();
   return SR_OK;
 }
@@ -950,8 +984,7 @@ int sr_rays_refine(const sr_rays *r, int n_diag, const sr_optic *const *chains, 
     ++S.n;
   }
   if (S.n == 0) return SR_OK;
-  sr::Context &c = sr::ctx();
-  hipStream_t st = c.stream;
+  hipStream_t st = sr::ctx().stream;
   const int64_t N = r->n;
   // the set travels through a buffer that belongs to the bundle (device side) and a copy the bundle keeps (host side): no wait
   // is needed for either, so a chunked driver can queue refine + deposits without a host round trip (retraced == NULL)
@@ -959,18 +992,15 @@ int sr_rays_refine(const sr_rays *r, int n_diag, const sr_optic *const *chains, 
   if (!rw->guard_set) SR_HIP(hipMalloc(&rw->guard_set, sizeof(GuardSet)));
   rw->guard_set_host.assign(reinterpret_cast<const char *>(&S), reinterpret_cast<const char *>(&S) + sizeof(GuardSet));
   SR_HIP(hipMemcpyAsync(rw->guard_set, rw->guard_set_host.data(), sizeof(GuardSet), hipMemcpyHostToDevice, st));
-  int rc = SR_OK;
-  SR_HIP(hipMemsetAsync(r->counters + 4, 0, 2 * sizeof(unsigned long long), st));
-  SR_HIP(hipMemsetAsync(r->counters + 16 + 2 * (size_t)sr::kStripes * sr::kStripeStride, 0,
-                        sizeof(unsigned long long) * sr::kStripes * sr::kStripeStride, st));
-  Guard G{r->guard, r->guard_len, r->fb_list, r->counters + 4};
+  int rc = guard_queue_reset(r, st);
+  if (rc) return rc;
+  const Guard G = guard_of(r);
   hipLaunchKernelGGL(k_guard_flags, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const GuardSet *)rw->guard_set, N, (const double *)r->rf, G);
   SR_HIP(hipGetLastError());
-  rc = sr::retrace_f64(r, r->fb_list, r->counters + 4);
-  if (rc) return rc;
+  if ((rc = sr::retrace_f64(r, G.list, G.count))) return rc;
   if (retraced) {
     unsigned long long n_again = 0;
-    SR_HIP(hipMemcpyAsync(&n_again, r->counters + 4, sizeof n_again, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipMemcpyAsync(&n_again, G.count, sizeof n_again, hipMemcpyDeviceToHost, st));
     SR_HIP(hipStreamSynchronize(st));
     *retraced = (int64_t)n_again;
   }
@@ -990,63 +1020,34 @@ int sr_rays_deposit(const sr_rays *r, const sr_optic *chain, int n_ops, const sr
   sr::Context &c = sr::ctx();
   hipStream_t st = c.stream;
   const int64_t N = r->n;
-  if (stats) *stats = sr_deposit_stats{0.0, 0, 0};
-  if (N == 0) return SR_OK;
-  unsigned long long *dep_stripes = r->counters + 16 + (size_t)sr::kStripes * sr::kStripeStride;
-  SR_HIP(hipMemsetAsync(dep_stripes, 0, sizeof(unsigned long long) * sr::kStripes * sr::kStripeStride, st));
-  SR_HIP(hipEventRecord(c.ev[0], st));
+  if ((rc = deposit_begin(r, stats)) || N == 0) return rc;
   const unsigned grid = sr::grid_for(N, 256);
   const bool tiled = p ? p->lds_tiles != 0 : true;
   const bool cplx = img->kind == SR_IMG_COMPLEX;
   const Edges ex = make_edges(img->x_lo, img->x_hi, cplx ? img->nx - 1 : img->nx);
   const Edges ey = make_edges(img->y_lo, img->y_hi, cplx ? img->ny - 1 : img->ny);
   const double *rf = r->rf, *Jf = r->Jf;
-  unsigned long long *cnt = r->counters;
   // exact counts (the default): rays of a mixed-precision trace whose pixel or mask decision is not certain are traced
   // again in float64 and counted afterwards -- the image is the float64 build's, integer for integer
   const bool exact = !cplx && (p ? p->exact_counts != 0 : true) && r->guard_live;
-  Guard G{r->guard, r->guard_len, r->fb_list, r->counters + 4};
-#define SR_DEP(KIND, T, GD) hipLaunchKernelGGL((k_deposit<KIND, T, GD>), dim3(grid), dim3(256), 0, st, C, R, N, rf, Jf, ex, ey, img->d, cnt, G)
-  if (cplx) {
-    if (tiled)
-      SR_DEP(SR_IMG_COMPLEX, true, false);
-    else
-      SR_DEP(SR_IMG_COMPLEX, false, false);
-  } else if (exact) {
-    SR_HIP(hipMemsetAsync(r->counters + 4, 0, 2 * sizeof(unsigned long long), st));
-    SR_HIP(hipMemsetAsync(r->counters + 16 + 2 * (size_t)sr::kStripes * sr::kStripeStride, 0,
-                          sizeof(unsigned long long) * sr::kStripes * sr::kStripeStride, st));
-    if (tiled)
-      SR_DEP(SR_IMG_COUNTS, true, true);
-    else
-      SR_DEP(SR_IMG_COUNTS, false, true);
+  const Guard G = guard_of(r);
+  if (exact && (rc = guard_queue_reset(r, st))) return rc;
+  sr::with_flags(
+      [&](auto is_cplx, auto is_tiled, auto guarded) {
+        constexpr int KIND = is_cplx.value ? SR_IMG_COMPLEX : SR_IMG_COUNTS;
+        if constexpr (!(is_cplx.value && guarded.value))  // the guard is the counts image's
+          hipLaunchKernelGGL((k_deposit<KIND, is_tiled.value, guarded.value>), dim3(grid), dim3(256), 0, st, C, R, N, rf, Jf, ex, ey,
+                             static_cast<typename ImagePatch<KIND>::Cell *>(img->d), r->counters, G);
+      },
+      cplx, tiled, exact);
+  if (exact) {
     SR_HIP(hipGetLastError());
-    rc = sr::retrace_f64(r, r->fb_list, r->counters + 4);
-    if (rc) return rc;
+    if ((rc = sr::retrace_f64(r, G.list, G.count))) return rc;
     const unsigned lgrid = (unsigned)std::min<int64_t>(grid, (int64_t)c.n_cu * 8);
-    hipLaunchKernelGGL(k_deposit_list, dim3(lgrid), dim3(256), 0, st, C, N, rf, ex, ey, (uint32_t *)img->d, cnt,
-                       (const uint32_t *)r->fb_list, (const unsigned long long *)(r->counters + 4));
-  } else {
-    if (tiled)
-      SR_DEP(SR_IMG_COUNTS, true, false);
-    else
-      SR_DEP(SR_IMG_COUNTS, false, false);
+    hipLaunchKernelGGL(k_deposit_list, dim3(lgrid), dim3(256), 0, st, C, N, rf, ex, ey, (uint32_t *)img->d, r->counters,
+                       (const uint32_t *)G.list, (const unsigned long long *)G.count);
   }
-#undef SR_DEP
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipEventRecord(c.ev[1], st));
-  if (stats) {
-    std::vector<unsigned long long> hw(sr::kCounterWords, 0ull);
-    SR_HIP(hipMemcpyAsync(hw.data(), r->counters, sizeof(unsigned long long) * sr::kCounterWords, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-    const unsigned long long h = sr::stripe_sum(hw.data(), 1);
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    stats->kernel_ms = ms;
-    stats->deposited = (int64_t)h;
-    stats->retraced = exact ? (int64_t)hw[4] : 0;
-  }
-  return SR_OK;
+  return deposit_finish(r, stats, exact);
 }
 
 // ---- polarimetry (no reference counterpart) ----------------------------------------------
@@ -1062,29 +1063,18 @@ int sr_intensity2d(const double *x, const double *y, const double *E, int64_t N,
   hipStream_t st = sr::ctx().stream;
   DevBuf dx, dy, dE, dI;
   const size_t ib = sizeof(double) * (size_t)n_ch * nxb * nyb;
-  if ((rc = dI.alloc(ib))) return rc;
-  SR_HIP(hipMemsetAsync(dI.p, 0, ib, st));
+  if ((rc = dI.zeroed(ib, st))) return rc;
   if (N > 0) {
-    if ((rc = dx.alloc(sizeof(double) * N)) || (rc = dy.alloc(sizeof(double) * N)) || (rc = dE.alloc(sizeof(double) * 4 * N)))
-      return rc;
-    SR_HIP(hipMemcpyAsync(dx.p, x, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(dy.p, y, sizeof(double) * N, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(dE.p, E, sizeof(double) * 4 * N, hipMemcpyHostToDevice, st));
+    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
     const Edges ex = make_edges(x_lo, x_hi, nxb), ey = make_edges(y_lo, y_hi, nyb);
-#define SR_I2D(NCH) hipLaunchKernelGGL((k_intensity2d<NCH>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx.p, \
-                                       (const double *)dy.p, (const double *)dE.p, N, ex, ey, A, (double *)dI.p)
-    switch (n_ch) {
-      case 1: SR_I2D(1); break;
-      case 2: SR_I2D(2); break;
-      case 3: SR_I2D(3); break;
-      default: SR_I2D(4); break;
-    }
-#undef SR_I2D
-    SR_HIP(hipGetLastError());
+    sr::with_count<SR_MAX_ANALYSERS>(
+        [&](auto nch) {
+          hipLaunchKernelGGL((k_intensity2d<nch.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(),
+                             dy.as<const double>(), dE.as<const double>(), N, ex, ey, A, dI.as<double>());
+        },
+        n_ch);
   }
-  SR_HIP(hipMemcpyAsync(I, dI.p, ib, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return stage_out(st, {{I, dI.p, ib}});
 }
 
 int sr_rays_deposit_intensity(const sr_rays *r, const sr_optic *chain, int n_ops, const double *analyser_ab, int n_ch,
@@ -1099,44 +1089,21 @@ int sr_rays_deposit_intensity(const sr_rays *r, const sr_optic *chain, int n_ops
   if (rc) return rc;
   Analysers A;
   if ((rc = make_analysers(analyser_ab, n_ch, A))) return rc;
-  sr::Context &c = sr::ctx();
-  hipStream_t st = c.stream;
+  hipStream_t st = sr::ctx().stream;
   const int64_t N = r->n;
-  if (stats) *stats = sr_deposit_stats{0.0, 0, 0};
-  if (N == 0) return SR_OK;
-  unsigned long long *dep_stripes = r->counters + 16 + (size_t)sr::kStripes * sr::kStripeStride;
-  SR_HIP(hipMemsetAsync(dep_stripes, 0, sizeof(unsigned long long) * sr::kStripes * sr::kStripeStride, st));
-  SR_HIP(hipEventRecord(c.ev[0], st));
-  const unsigned grid = sr::grid_for(N, 256);
+  if ((rc = deposit_begin(r, stats)) || N == 0) return rc;
   const Edges ex = make_edges(img->x_lo, img->x_hi, img->nx), ey = make_edges(img->y_lo, img->y_hi, img->ny);
-#define SR_DEPI(NCH)                                                                                                           \
-  do {                                                                                                                         \
-    if (lds_tiles)                                                                                                             \
-      hipLaunchKernelGGL((k_deposit_intensity<NCH, true>), dim3(grid), dim3(256), 0, st, C, N, (const double *)r->rf,          \
-                         (const double *)r->Jf, ex, ey, A, (double *)img->d, r->counters);                                     \
-    else                                                                                                                       \
-      hipLaunchKernelGGL((k_deposit_intensity<NCH, false>), dim3(grid), dim3(256), 0, st, C, N, (const double *)r->rf,         \
-                         (const double *)r->Jf, ex, ey, A, (double *)img->d, r->counters);                                     \
-  } while (0)
-  switch (n_ch) {
-    case 1: SR_DEPI(1); break;
-    case 2: SR_DEPI(2); break;
-    case 3: SR_DEPI(3); break;
-    default: SR_DEPI(4); break;
-  }
-#undef SR_DEPI
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipEventRecord(c.ev[1], st));
-  if (stats) {
-    std::vector<unsigned long long> hw(sr::kCounterWords, 0ull);
-    SR_HIP(hipMemcpyAsync(hw.data(), r->counters, sizeof(unsigned long long) * sr::kCounterWords, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    stats->kernel_ms = ms;
-    stats->deposited = (int64_t)sr::stripe_sum(hw.data(), 1);
-  }
-  return SR_OK;
+  sr::with_count<SR_MAX_ANALYSERS>(
+      [&](auto nch) {
+        sr::with_flags(
+            [&](auto is_tiled) {
+              hipLaunchKernelGGL((k_deposit_intensity<nch.value, is_tiled.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N,
+                                 (const double *)r->rf, (const double *)r->Jf, ex, ey, A, (double *)img->d, r->counters);
+            },
+            lds_tiles != 0);
+      },
+      n_ch);
+  return deposit_finish(r, stats, false);
 }
 
 int sr_image_rotation(const sr_image *img, int ch_plus, int ch_minus, double beta, double *alpha) {
@@ -1145,17 +1112,11 @@ int sr_image_rotation(const sr_image *img, int ch_plus, int ch_minus, double bet
   SR_CHECK(ch_plus >= 0 && ch_plus < img->n_ch && ch_minus >= 0 && ch_minus < img->n_ch && ch_plus != ch_minus,
            "sr_image_rotation: channels %d, %d of an image of %d", ch_plus, ch_minus, img->n_ch);
   SR_CHECK(beta > 0 && beta < M_PI / 2, "sr_image_rotation: beta must lie in (0, pi/2)");
-  hipStream_t st = sr::ctx().stream;
   const int64_t plane = (int64_t)img->nx * img->ny;
-  double *dA = static_cast<double *>(sr::scratch(sizeof(double) * plane));
-  if (!dA) return SR_ERR_HIP;
   const double *I = (const double *)img->d;
-  hipLaunchKernelGGL(k_rotation, dim3(sr::grid_for(plane, 256)), dim3(256), 0, st, I + ch_plus * plane, I + ch_minus * plane, plane,
-                     sin(2 * beta), cos(2 * beta), dA);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipMemcpyAsync(alpha, dA, sizeof(double) * plane, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
+  return read_out(alpha, plane, [&](double *dA, dim3 grid, hipStream_t st) {
+    hipLaunchKernelGGL(k_rotation, grid, dim3(256), 0, st, I + ch_plus * plane, I + ch_minus * plane, plane, sin(2 * beta), cos(2 * beta), dA);
+  });
 }
 
 }  // extern "C"

@@ -734,22 +734,6 @@ __global__ void k_unpermute_f32(const float *__restrict__ src, float *__restrict
   if (j < N) dst[perm[j]] = src[j];
 }
 
-// ---- runtime flags -> template arguments ---------------------------------------------------------------------------------
-// with_flags(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): every launch that picks a kernel
-// instantiation from runtime booleans is written once, as a generic lambda, and prunes the combinations that must not exist with
-// `if constexpr` (they are never instantiated).
-template <typename F>
-void with_flags(F &&f) {
-  f();
-}
-template <typename F, typename... Rest>
-void with_flags(F &&f, bool b, Rest... rest) {
-  if (b)
-    with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-  else
-    with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-}
-
 // Threads per workgroup of k_trace_f64 / k_trace_mx: as FEW wavefronts as the LDS node tables allow at the kernel's
 // occupancy.  A workgroup's place on its CU (registers, LDS) is given to the next workgroup only when its slowest wavefront
 // is done, and wavefronts differ in how many cell changes their rays make: with one-wavefront workgroups a finished
@@ -920,7 +904,7 @@ int tile_records(const sr_volume *v, const TraceKnobs &knobs, hipStream_t st, bo
       return SR_OK;
     }
     const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(count / 16 + 255) / 256, (int64_t)sr::ctx().n_cu * 64);
-    with_flags([&](auto ph) { hipLaunchKernelGGL(k_build_records<ph.value>, dim3(grid), dim3(256), 0, st, vol_dev(v), R); }, v->L != nullptr);
+    sr::with_flags([&](auto ph) { hipLaunchKernelGGL(k_build_records<ph.value>, dim3(grid), dim3(256), 0, st, vol_dev(v), R); }, v->L != nullptr);
     hipError_t err = hipGetLastError();
     // The volume is shared by every stream that traces through it (the job driver alternates its bundles between the library's two
     // streams): the records must be COMPLETE before anybody can see the pointer.  Once per volume: 15 ms for 512^3.
@@ -1051,7 +1035,7 @@ int tile_buffers(sr_rays *r, size_t cap, int n_seg, bool second) {
 int launch_tile(const TileArgs &T, bool phase, bool aux, bool rec, size_t lds, hipStream_t st) {
   const unsigned grid = ((T.A.n_blocks + 7) / 8) * 8;
   hipError_t err = hipSuccess;
-  with_flags(
+  sr::with_flags(
       [&](auto ph, auto ax, auto rc) {
         if constexpr (!(ax.value && rc.value)) {  // the ready-made records hold the gradient fields only
           auto *kernel = &k_trace_tile<ph.value, ax.value, rc.value>;
@@ -1284,7 +1268,7 @@ void launch_planes64(const sr_volume *v, const sr_trace_params *p, const TraceKn
   TraceArgs L = A;
   L.n_blocks = sr::grid_for(A.N, block);
   const unsigned grid = ((L.n_blocks + 7) / 8) * 8;
-  with_flags(
+  sr::with_flags(
       [&](auto ph, auto ax, auto sb, auto sel) {  // SEL = 1 exists for <PHASE, true, false> only
         if constexpr (!sel.value || (ax.value && !sb.value))
           hipLaunchKernelGGL((k_trace_f64<ph.value, ax.value, sb.value, sel.value ? 1 : 0>), dim3(grid), dim3(block), lds, st, L);
@@ -1299,7 +1283,7 @@ void launch_mx(const sr_volume *v, const TraceArgs &A, hipStream_t st) {
   TraceArgs L = A;
   L.n_blocks = sr::grid_for(A.N, block);
   const unsigned grid = ((L.n_blocks + 7) / 8) * 8;
-  with_flags([&](auto ph) { hipLaunchKernelGGL((k_trace_mx<ph.value>), dim3(grid), dim3(block), ml, st, L); }, v->L != nullptr);
+  sr::with_flags([&](auto ph) { hipLaunchKernelGGL((k_trace_mx<ph.value>), dim3(grid), dim3(block), ml, st, L); }, v->L != nullptr);
 }
 
 // time-stepping form for what the plane form cannot take (the level before's rejects become its queue): fixed small grid,
@@ -1311,7 +1295,7 @@ void launch_time(const sr_volume *v, TraceArgs &A, hipStream_t st) {
   A.out_list = nullptr;
   A.out_count = nullptr;
   const unsigned fgrid = (unsigned)std::min<int64_t>(sr::grid_for(A.N, block), (int64_t)sr::ctx().n_cu * 4);
-  with_flags(
+  sr::with_flags(
       [&](auto ph, auto ax) { hipLaunchKernelGGL((k_trace_time<ph.value, ax.value>), dim3(fgrid), dim3(block), 0, st, A); },
       v->L != nullptr, v->K != nullptr || v->Q != nullptr);
 }

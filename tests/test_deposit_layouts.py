@@ -45,7 +45,7 @@ DET2 = (-8192 * U, 8192 * U, -4096 * U, 4096 * U)
 MASK = [(OP_CIRC_AP, 8.0)]
 BINS = [(1, 1), (8, 4), (63, 31), (64, 32), (65, 33), (344, 257)]
 BINS2 = BINS + [(32, 16), (33, 17)]  # complex and intensity tiles are 32 x 16
-ANALYSERS = {1: (None,), 3: (np.pi / 4, -np.pi / 4, None)}
+ANALYSERS = {1: (None,), 2: (0.7, None), 3: (np.pi / 4, -np.pi / 4, None), 4: (0.3, -0.3, 1.0, None)}
 KWAVE = 2 * np.pi / 532e-9
 
 
@@ -585,14 +585,15 @@ def test_complex_on_layout(eng, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n_ch", [1, 3])
-@pytest.mark.parametrize("name", list(LAYOUTS))
+@pytest.mark.parametrize("name, n_ch", [(name, n_ch) for name in LAYOUTS for n_ch in ((1, 2, 3, 4) if name == "scatter" else (1, 3))])
 def test_intensity_on_layout(eng, name, n_ch):
     """k_deposit_intensity<1> and <3> (a None analyser among them) with and without the LDS tile against np.histogram2d with
-    weights, under test_polarimetry's bound."""
+    weights, under test_polarimetry's bound; <2> and <4> on the scattered rays, so that every instantiation runs here."""
     rays, s0, rf, Jf = traced(eng, name)
     assert_claims(name, rays, s0, rf)
     rng, bins, chains = cases(eng, name)
+    if n_ch in (2, 4):
+        bins = BINS2  # with the detectors around the 32 x 16 tile
     an = ANALYSERS[n_ch]
     for cname, ops in chains.items():
         r = np.array(rays.optics(ops)[0])

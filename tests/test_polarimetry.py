@@ -236,7 +236,7 @@ def _chain_cases(eng):
     return {"empty": [], "shadow_two": eng.chain_shadow_two(), "schlieren": eng.chain_schlieren()}
 
 
-CHANNELS = {"total": (None,), "pair": (np.pi / 4, -np.pi / 4, None), "four": (0.3, -0.3, 1.0, None)}
+CHANNELS = {"total": (None,), "two": (0.7, None), "pair": (np.pi / 4, -np.pi / 4, None), "four": (0.3, -0.3, 1.0, None)}
 
 
 @pytest.mark.gpu
