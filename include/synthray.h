@@ -146,6 +146,45 @@ double sr_volume_omega(const sr_volume *v);
 int64_t sr_volume_bytes(const sr_volume *v); /* HBM held by the handle */
 void sr_volume_destroy(sr_volume *v);
 
+/* ---- oblique lines of sight: a field rotated onto a new grid ------------------------
+ * No reference counterpart (its users turn the cube with scipy.ndimage before they build the domain).  sr_field is a scalar or
+ * 3-vector field on a rectilinear grid, resident in HBM: data is (nx, ny, nz) or (nx, ny, nz, 3) (as B is), C order, float64
+ * (is_f64 != 0) or float32; x, y, z are its float32 node coordinates.  sr_field_resample evaluates it, trilinearly, at the
+ * nodes of a VIEW grid (mx, my, mz; float32 coordinates ox, oy, oz) whose node q sits at the lab position p = M q + t, and
+ * writes out, a HOST array (mx, my, mz[, n_comp]) in C order and the source's dtype.  Every output node follows one rule
+ * (resample.hip is compiled with -ffp-contract=off: every product and sum below rounds on its own, in float64):
+ *   positions  the coordinates are widened to float64, q = (ox[i], oy[j], oz[k]), and
+ *              p_a = ((M[a][0]*q0 + M[a][1]*q1) + M[a][2]*q2) + t[a]                          (M row-major).
+ *   cell       per source axis with float64-widened nodes g[0..n-1]: the largest i with g[i] <= p, clipped to n-2 -- so
+ *              p == g[n-1] lies in the last cell -- and w = (p - g[i]) / (g[i+1] - g[i]).  Axes may be non-uniform.
+ *   outside    p < g[0] or p > g[n-1] on any axis (or a NaN p): the output is fill[c] for component c.
+ *   blend      with u = 1 - w per axis, w00 = uy*uz, w01 = uy*wz, w10 = wy*uz, w11 = wy*wz and f(di, dj, dk) the corner
+ *              values widened to float64, for di = 0, 1 (node plane i + di of x):
+ *                  s_di = ((f(di,0,0)*w00 + f(di,0,1)*w01) + f(di,1,0)*w10) + f(di,1,1)*w11
+ *              and the value is ux*s_0 + wx*s_1: the corner order of sr_volume_sample's gather (the four corners of a node
+ *              plane, then the two planes), with (1 - w) and w as the factors -- weight 0 returns the low node and weight 1
+ *              the high node exactly.  A float32 source is blended in float64 and rounded once on store.  A NaN corner
+ *              makes NaN every output whose cell holds it, zero weights included, and no other output.
+ *   vectors    n_comp == 3: the three components are interpolated as above, b = (b0, b1, b2); with use_V the output
+ *              components are ((V[r][0]*b0 + V[r][1]*b1) + V[r][2]*b2), r = 0, 1, 2 (V row-major).
+ * No atomics: a repeated call returns the identical bits.  *kernel_ms (may be NULL) is the HIP-event time of the kernel alone.
+ * Arguments are checked before the device is touched -- sr_field_create: a NULL pointer, n_comp not 1 or 3, an axis with fewer
+ * than 2 nodes or not strictly ascending; sr_field_resample: a NULL pointer, a view axis without nodes, a non-finite entry of
+ * M, t or (with use_V) V. */
+typedef struct sr_field sr_field;
+int sr_field_create(sr_field **out, const void *data, int is_f64, int n_comp, int nx, int ny, int nz,
+                    const float *x, const float *y, const float *z);
+typedef struct {
+  double M[9], t[3];     /* row-major; lab position of view node q:  p = M q + t                         */
+  double V[9];           /* n_comp == 3 and use_V: out components = V * (interpolated components)        */
+  double fill[3];        /* value per component where p lies outside the source grid on any axis         */
+  int32_t use_V, reserved;
+} sr_resample_params;
+int sr_field_resample(const sr_field *f, const sr_resample_params *p, int mx, int my, int mz,
+                      const float *ox, const float *oy, const float *oz, void *out, double *kernel_ms);
+int64_t sr_field_bytes(const sr_field *f); /* HBM held by the handle */
+void sr_field_destroy(sr_field *f);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

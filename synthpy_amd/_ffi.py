@@ -51,6 +51,11 @@ class DepositParams(C.Structure):
                 ("ref_on", C.c_int32), ("lds_tiles", C.c_int32), ("exact_counts", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ResampleParams(C.Structure):
+    _fields_ = [("M", C.c_double * 9), ("t", C.c_double * 3), ("V", C.c_double * 9), ("fill", C.c_double * 3),
+                ("use_V", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -92,6 +97,10 @@ SYMBOLS = {
     "sr_volume_omega": (_d, [_vp]),
     "sr_volume_bytes": (_i64, [_vp]),
     "sr_volume_destroy": (None, [_vp]),
+    "sr_field_create": (_i, [_pp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_field_resample": (_i, [_vp, C.POINTER(ResampleParams), _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_bytes": (_i64, [_vp]),
+    "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),
     "sr_ray_to_jones": (_i, [_vp, _i64, _d, _i, _i, _vp, _vp]),
     "sr_rays_create": (_i, [_pp, _i64]),

@@ -338,6 +338,80 @@ class Volume:
             pass
 
 
+def resample_params(M, t=(0.0, 0.0, 0.0), V=None, fill=0.0):
+    """sr_resample_params: p = M q + t (M 3x3, t 3), the optional component matrix V (3x3) and the fill value (one, or one per
+    component)."""
+    M, t = f64(M), f64(t)
+    if M.shape != (3, 3) or t.shape != (3,):
+        raise ValueError(f"M must be 3x3 and t have 3 entries, got {M.shape} and {t.shape}")
+    p = _ffi.ResampleParams()
+    p.M[:], p.t[:] = M.ravel().tolist(), t.tolist()
+    if V is not None:
+        V = f64(V)
+        if V.shape != (3, 3):
+            raise ValueError(f"V must be 3x3, got {V.shape}")
+        p.V[:] = V.ravel().tolist()
+    p.fill[:] = np.broadcast_to(f64(fill), (3,)).tolist()
+    p.use_V, p.reserved = 0 if V is None else 1, 0
+    return p
+
+
+class Field:
+    """A scalar (nx, ny, nz) or 3-vector (nx, ny, nz, 3) field on a rectilinear grid, resident in HBM (sr_field): uploaded
+    once, resampled onto as many view grids as wanted."""
+
+    def __init__(self, data, x, y, z):
+        data = np.asarray(data)
+        if data.dtype != np.float32:
+            data = f64(data)
+        data = np.ascontiguousarray(data)
+        x, y, z = f32(x), f32(y), f32(z)
+        grid = (len(x), len(y), len(z))
+        if data.shape != grid and data.shape != grid + (3,):
+            raise ValueError(f"the field has shape {data.shape}, coordinates give {grid} (+ (3,) for a vector field)")
+        self.shape, self.dtype = data.shape, data.dtype
+        self.n_comp = 3 if data.ndim == 4 else 1
+        self.last_kernel_ms = 0.0
+        self._h = None
+        h = C.c_void_p()
+        check(lib.sr_field_create(C.byref(h), ptr(data), 0 if data.dtype == np.float32 else 1, self.n_comp, *grid,
+                                  ptr(x), ptr(y), ptr(z)))
+        self._h = h
+
+    @property
+    def nbytes(self) -> int:
+        return int(lib.sr_field_bytes(self._h))
+
+    def resample(self, M, t, coords_out, V=None, fill=0.0):
+        """The field at the nodes of the view grid coords_out = (ox, oy, oz), node q at the lab position p = M q + t:
+        trilinear inside the source grid, `fill` outside (sr_field_resample; include/synthray.h states the rule).  V (3x3,
+        vector fields): the output components are V times the interpolated ones.  An ndarray (mx, my, mz[, 3]) of the
+        field's dtype."""
+        if not getattr(self, "_h", None):
+            raise ValueError("the field has been closed")
+        ox, oy, oz = (f32(a) for a in coords_out)
+        if V is not None and self.n_comp != 3:
+            raise ValueError("V applies to a vector field (nx, ny, nz, 3)")
+        p = resample_params(M, t, V, fill)
+        out = np.empty((len(ox), len(oy), len(oz)) + ((3,) if self.n_comp == 3 else ()), self.dtype)
+        ms = C.c_double(0.0)
+        check(lib.sr_field_resample(self._h, C.byref(p), len(ox), len(oy), len(oz), ptr(ox), ptr(oy), ptr(oz), ptr(out),
+                                    C.byref(ms)))
+        self.last_kernel_ms = float(ms.value)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.sr_field_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

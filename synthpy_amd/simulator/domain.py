@@ -134,6 +134,13 @@ class ScalarDomain:
 
         return line_integrals(self, lwl=lwl, regions=regions)
 
+    def rotated(self, angle_deg=None, about="y", **kw):
+        """This domain seen from a frame turned by angle_deg about the lab axis `about` (or matrix=R): a new ScalarDomain whose
+        probing axis is an oblique line of sight of this one (no reference counterpart; orientation.rotated)."""
+        from ..orientation import rotated
+
+        return rotated(self, angle_deg, about, **kw)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (domain.py:505-579), written without pyvista."""
         from ..utils.handle_filetypes import export_scalar_field

@@ -140,6 +140,14 @@ class ScalarDomain:
 
         return line_integrals(self)
 
+    def rotated(self, angle_deg=None, about="y", **kw):
+        """This domain seen from a frame turned by angle_deg about the lab axis `about` (or matrix=R): a new ScalarDomain (call
+        calc_dndr on it) whose probing axis is an oblique line of sight of this one (no reference counterpart;
+        orientation.rotated)."""
+        from ..orientation import rotated
+
+        return rotated(self, angle_deg, about, **kw)
+
     def _field(self, k):
         if self._volume is None:
             raise RuntimeError("call calc_dndr(lwl) first")
