@@ -185,6 +185,48 @@ int sr_field_resample(const sr_field *f, const sr_resample_params *p, int mx, in
 int64_t sr_field_bytes(const sr_field *f); /* HBM held by the handle */
 void sr_field_destroy(sr_field *f);
 
+/* ---- self-emission: emission with self-absorption along a grid axis -------------------
+ * No reference counterpart.  The plasma's own light on a detector that looks along grid axis `axis`: per band (an angular
+ * frequency omega; up to SR_MAX_BANDS in one pass) and per lateral column, the formal solution of dI/ds = alpha (S - I) from
+ * the far plane to the plane nearest the detector.  ne [m^-3], Te [eV], Z are scalar sr_fields on ONE grid (the node
+ * coordinates are compared bit for bit) and of one dtype; Te or Z may be NULL: the field is then the uniform value p->Te / p->Z
+ * and is not read.  emission.hip is compiled with -ffp-contract=off: every operation below rounds on its own, in float64; max(a, b)
+ * is numpy's maximum (a NaN operand gives NaN).
+ *   node     ne, Te, Z are widened to float64.  Te <= 0 or ne <= 0: alpha = 0 and S = 0.  Otherwise, per band,
+ *              n = ne*1e-6;  w = max(5.64e4*sqrt(n), omega);  q = sqrt(Te)
+ *              L = max(Z*1.602176634e-19/Te, 2.760428269727312e-10/q)
+ *              lnL = max(2.0, log(4.19e5*q / (w*L)));  r = n/omega
+ *              alpha = (((((3.1e-5*Z)*c)*(r*r))*lnL) * (1.0/(Te*q))) / c           c = 299792458   [1/m]
+ *            -- propagator.kappa(ne, Te, Z, omega) / c in its order of operations, Te**-1.5 written 1/(Te*sqrt(Te)): the NRL
+ *            low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy for hbar*omega <~ Te -- and
+ *              S = c_omega / expm1(e_ph / Te)
+ *            the Planck function B_omega(Te): the host gives e_ph = hbar*omega/e [eV] and c_omega = hbar*omega^3/(4 pi^3 c^2)
+ *            per band.  The emissivity alpha*S (Kirchhoff) is never formed.  A NaN input stays NaN.
+ *   column   toward = +1 marches planes 0 -> n-1 (the direction the rays travel), toward = -1 the reverse.  Start from
+ *            I = backlight (0 when NULL), tau = 0; for each cell between consecutive planes k, k' of the march, on the float64
+ *            values g of the float32 node coordinates:
+ *              h = |g[k'] - g[k]|;  dtau = (0.5*(alpha_k + alpha_k'))*h
+ *              I <- I*exp(-dtau) + (0.5*(S_k + S_k'))*(-expm1(-dtau));   tau <- tau + dtau
+ *            A cell's update is an affine map I -> I*a + b with a in [0, 1] and b >= 0, and composing two of them,
+ *            (a1, b1) then (a2, b2) -> (a1*a2, b1*a2 + b2), is associative in exact arithmetic: the kernel may compose the
+ *            cells of a column (and add their dtau) in any FIXED order.  No atomics: a repeated call returns identical bits.
+ *            A NaN node makes its own column NaN and no other.
+ * I, tau and backlight are HOST arrays (n_band, n_u, n_v), float64, C order; (u, v) are the lateral axes in x < y < z order, as
+ * sr_volume_project lays its maps out.  *kernel_ms (may be NULL) is the HIP-event time of the kernel alone.
+ * Arguments are checked before the device is touched: a NULL p, I or tau, n_band outside 1..SR_MAX_BANDS, a non-finite or
+ * non-positive omega (or non-finite e_ph, c_omega), toward not +-1, axis outside 0..2, a NULL ne, a vector field, fields of
+ * different dtypes, grids that differ. */
+#define SR_MAX_BANDS 4
+typedef struct {
+  int32_t axis, toward, n_band, reserved;
+  double omega[SR_MAX_BANDS];   /* angular frequency [rad/s]                                             */
+  double e_ph[SR_MAX_BANDS];    /* hbar*omega/e [eV]                                                     */
+  double c_omega[SR_MAX_BANDS]; /* hbar*omega^3/(4 pi^3 c^2) [W m^-2 sr^-1 (rad/s)^-1]                   */
+  double Te, Z;                 /* the uniform field values where the handle is NULL                     */
+} sr_emission_params;
+int sr_field_emission(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p,
+                      const double *backlight, double *I, double *tau, double *kernel_ms);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

@@ -56,6 +56,15 @@ class ResampleParams(C.Structure):
                 ("use_V", C.c_int32), ("reserved", C.c_int32)]
 
 
+MAX_BANDS = 4  # SR_MAX_BANDS
+
+
+class EmissionParams(C.Structure):
+    _fields_ = [("axis", C.c_int32), ("toward", C.c_int32), ("n_band", C.c_int32), ("reserved", C.c_int32),
+                ("omega", C.c_double * MAX_BANDS), ("e_ph", C.c_double * MAX_BANDS), ("c_omega", C.c_double * MAX_BANDS),
+                ("Te", C.c_double), ("Z", C.c_double)]
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -99,6 +108,7 @@ SYMBOLS = {
     "sr_volume_destroy": (None, [_vp]),
     "sr_field_create": (_i, [_pp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_field_resample": (_i, [_vp, C.POINTER(ResampleParams), _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_emission": (_i, [_vp, _vp, _vp, C.POINTER(EmissionParams), _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),
     "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),

@@ -262,3 +262,14 @@ struct sr_image {
   void *d = nullptr;
   int64_t bytes = 0;
 };
+
+// A scalar or 3-vector field on a rectilinear grid (resample.hip creates and resamples it, emission.hip marches through it).
+struct sr_field {
+  int n[3] = {0, 0, 0};
+  int n_comp = 1;
+  bool is_f64 = false;
+  void *data = nullptr;                        // (nx, ny, nz[, n_comp]) C order, the caller's dtype
+  double *g[3] = {nullptr, nullptr, nullptr};  // node coordinates widened to float64
+  std::vector<double> hg[3];                   // host copies of g (grids are compared without touching the device)
+  double inv_h[3] = {0, 0, 0};                 // (n - 1) / (g[n-1] - g[0]): the first guess of a cell on a uniform axis
+};

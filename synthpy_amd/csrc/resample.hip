@@ -17,15 +17,6 @@
 
 #include "common.hpp"
 
-struct sr_field {
-  int n[3] = {0, 0, 0};
-  int n_comp = 1;
-  bool is_f64 = false;
-  void *data = nullptr;                        // (nx, ny, nz[, n_comp]) C order, the caller's dtype
-  double *g[3] = {nullptr, nullptr, nullptr};  // node coordinates widened to float64
-  double inv_h[3] = {0, 0, 0};                 // (n - 1) / (g[n-1] - g[0]): the first guess of a cell on a uniform axis
-};
-
 namespace {
 
 constexpr int kSuper = 4;  // bricks per supertile and axis
@@ -191,6 +182,7 @@ int sr_field_create(sr_field **out, const void *data, int is_f64, int n_comp, in
   for (int k = 0; k < 3 && !rc; ++k) {
     f->n[k] = n[k];
     std::vector<double> g(co[k], co[k] + n[k]);
+    f->hg[k] = g;
     f->inv_h[k] = (n[k] - 1) / (g[n[k] - 1] - g[0]);
     rc = sr::dev_alloc(&f->g[k], (size_t)n[k]);
     if (!rc) rc = sr::upload_sync(f->g[k], g.data(), sizeof(double) * g.size(), st);

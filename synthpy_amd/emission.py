@@ -1,0 +1,125 @@
+"""Self-emission images: the plasma's own light along the probing axis, emission with self-absorption.
+
+    em = self_emission(domain, [532e-9, 100e-9])          # or domain.self_emission(...), domain.rotated(30).self_emission(...)
+    em.intensity, em.optical_depth, em.transmission       # (n_band, n_u, n_v)
+    em.sample(p, q, "intensity")                          # at lateral positions
+
+No reference counterpart.  Every other image of the package is an image of the probe; this is the optical fast-framing / XUV
+pinhole channel.  Per band and lateral column the formal solution of dI/ds = alpha (S - I) is marched from the far plane to the
+plane nearest the detector on the GPU (engine.emission -> sr_field_emission; include/synthray.h states the rule): alpha is
+propagator.kappa(ne, Te, Z, omega) / c -- the NRL low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy
+for hbar*omega <~ Te -- and S is the Planck function B_omega(Te), so the emissivity follows from Kirchhoff's law.  Refraction of the
+emitted light, line emission, opacity tables and detector optics are not modelled.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import engine
+from .projection import _lateral, bilinear
+
+c = engine.c
+_QUANTITIES = ("intensity", "optical_depth", "transmission")
+
+
+class Emission:
+    """The self-emission maps of one line of sight.  `axes` names the two lateral axes in x < y < z order, `coords` holds their
+    node coordinates (float64); intensity [W m^-2 sr^-1 (rad/s)^-1, spectral radiance per unit angular frequency] and
+    optical_depth are (n_band, len(coords[0]), len(coords[1])), band b at wavelengths[b]."""
+
+    def __init__(self, intensity, optical_depth, axes, coords, wavelengths):
+        self.axes = (str(axes[0]), str(axes[1]))
+        self.coords = (np.asarray(coords[0], np.float64), np.asarray(coords[1], np.float64))
+        self.wavelengths = np.atleast_1d(np.asarray(wavelengths, np.float64))
+        want = (len(self.wavelengths), len(self.coords[0]), len(self.coords[1]))
+        self.intensity = np.asarray(intensity, np.float64)
+        self.optical_depth = np.asarray(optical_depth, np.float64)
+        for name in ("intensity", "optical_depth"):
+            if getattr(self, name).shape != want:
+                raise ValueError(f"{name} has shape {getattr(self, name).shape}, the bands and the lateral grid give {want}")
+
+    @property
+    def transmission(self):
+        """exp(-optical_depth): what a backlight keeps."""
+        return np.exp(-self.optical_depth)
+
+    def sample(self, p, q, what="intensity"):
+        """Bilinear interpolation of a quantity at the lateral positions (p along axes[0], q along axes[1]) -> (n_band, N);
+        NaN outside the grid (Projection.sample's rule)."""
+        if what not in _QUANTITIES:
+            raise ValueError(f"what must be one of {_QUANTITIES}, got {what!r}")
+        return bilinear(self.coords, getattr(self, what), p, q)
+
+    def after(self, other):
+        """This slab seen through nothing, with `other` behind it on the same line of sight: I = I_other * exp(-tau_self) + I_self,
+        the optical depths added -- what passing other.intensity as this slab's backlight gives.  A volume too large for HBM is
+        done slab by slab this way."""
+        if self.axes != other.axes or not np.array_equal(self.wavelengths, other.wavelengths) or any(
+                not np.array_equal(a, b) for a, b in zip(self.coords, other.coords)):
+            raise ValueError("the two slabs differ in lateral axes, coordinates or wavelengths")
+        return Emission(other.intensity * np.exp(-self.optical_depth) + self.intensity, other.optical_depth + self.optical_depth,
+                        self.axes, self.coords, self.wavelengths)
+
+
+def _toward(toward):
+    if toward in ("+", +1):
+        return +1
+    if toward in ("-", -1):
+        return -1
+    raise ValueError(f"toward must be '+' (the detector behind the last plane, where the rays leave) or '-', got {toward!r}")
+
+
+def _omegas(wavelengths):
+    lam = np.atleast_1d(np.asarray(wavelengths, np.float64))
+    if lam.ndim != 1 or not 1 <= len(lam) <= engine._ffi.MAX_BANDS:
+        raise ValueError(f"between 1 and {engine._ffi.MAX_BANDS} wavelengths go in one pass, got shape {lam.shape}")
+    if not np.all(np.isfinite(lam) & (lam > 0)):
+        raise ValueError(f"wavelengths must be finite and positive, got {lam.tolist()}")
+    return lam, 2 * np.pi * c / lam
+
+
+def _uniform(a):
+    """The one value of a scalar, or of an array broadcast from one; None for a real array."""
+    if np.ndim(a) == 0:
+        return float(a)
+    a = np.asarray(a)
+    if a.size == 1 or all(s == 0 for s in a.strides):
+        return float(a.reshape(-1)[0])
+    return None
+
+
+def self_emission(domain, wavelengths, toward="+", backlight=None):
+    """The Emission of a domain of either API generation along its probing_direction, at up to 4 wavelengths [m] in one pass
+    over the fields.  toward "+": the detector is where the rays leave (behind the last node plane of the axis), "-": where
+    they enter.  backlight: (n_band, n_u, n_v) spectral radiance behind the far plane, or None.  The domain needs external_Te()
+    and external_Z(); a Te or Z that is a scalar (or broadcast from one) is not uploaded."""
+    axis = engine.axis_index(domain.probing_direction)
+    sign = _toward(toward)
+    lam, omegas = _omegas(wavelengths)
+    ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
+    if ne is None:
+        raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
+    if Te is None or Z is None:
+        raise ValueError("self_emission needs external_Te() and external_Z()")
+    axes, coords = _lateral(domain, axis)
+    shape = (len(domain.x), len(domain.y), len(domain.z))
+    arrays = {"ne": np.asarray(ne)}
+    values = {}
+    for name, a in (("Te", Te), ("Z", Z)):
+        u = _uniform(a)
+        if u is None:
+            arrays[name] = np.asarray(a)
+        else:
+            values[name] = u
+    # one dtype for the uploads: float32 only when every array is (widening float32 is exact, so the image does not change)
+    dtype = np.float32 if all(a.dtype == np.float32 for a in arrays.values()) else np.float64
+    fields = {}
+    try:
+        for name, a in arrays.items():
+            fields[name] = engine.Field(np.ascontiguousarray(np.broadcast_to(a, shape), dtype), domain.x, domain.y, domain.z)
+        I, tau = engine.emission(fields["ne"], fields.get("Te", values.get("Te")), fields.get("Z", values.get("Z")), omegas, axis,
+                                 sign, backlight)
+    finally:
+        for f in fields.values():
+            f.close()
+    return Emission(I, tau, axes, coords, lam)

@@ -412,6 +412,61 @@ class Field:
             pass
 
 
+HBAR = 6.62607015e-34 / (2 * np.pi)  # J s, from the exact h of the SI
+E_CHARGE = 1.602176634e-19           # C
+
+
+def emission_params(omegas, axis, toward=+1, Te=0.0, Z=0.0):
+    """sr_emission_params for the bands `omegas` [rad/s]: per band E_ph = hbar*omega/e [eV] and C_omega = hbar*omega^3/(4 pi^3 c^2),
+    the Planck function's prefactor, B_omega(Te) = C_omega / expm1(E_ph / Te); Te, Z: the uniform values of absent fields."""
+    om = np.atleast_1d(f64(omegas))
+    if om.ndim != 1:
+        raise ValueError(f"omegas must be a scalar or one-dimensional, got shape {om.shape}")
+    p = _ffi.EmissionParams()
+    p.axis, p.toward, p.n_band, p.reserved = int(axis), int(toward), len(om), 0
+    for b, w in enumerate(om[:_ffi.MAX_BANDS].tolist()):
+        p.omega[b] = w
+        p.e_ph[b] = HBAR * w / E_CHARGE
+        p.c_omega[b] = HBAR * w ** 3 / (4 * np.pi ** 3 * c ** 2)
+    p.Te, p.Z = float(Te), float(Z)
+    return p
+
+
+def emission(ne, Te, Z, omegas, axis, toward=+1, backlight=None):
+    """Self-emission with self-absorption along grid axis `axis` (0 | 1 | 2) of the fields ne [m^-3], Te [eV], Z (sr_field_emission;
+    include/synthray.h states the rule): (I, tau), each (n_band, n_u, n_v) float64 with (u, v) the lateral axes in x < y < z order.
+    ne is a scalar Field; Te and Z are Fields on the same grid and of the same dtype, or floats (a uniform field, which is not read).
+    omegas: up to 4 angular frequencies, done in one pass over the fields.  toward = +1 puts the detector behind the last plane
+    (the direction the rays travel), -1 before the first.  backlight: (n_band, n_u, n_v) behind the far plane, or None.
+    I is the spectral radiance per unit angular frequency [W m^-2 sr^-1 (rad/s)^-1].  The absorption coefficient is
+    propagator.kappa / c -- the NRL low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy for
+    hbar*omega <~ Te; the source function is Planck's.  ne.last_kernel_ms keeps the kernel's time."""
+    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
+        raise ValueError("ne must be an open engine.Field")
+    handles, uniform = [], []
+    for name, a in (("Te", Te), ("Z", Z)):
+        if isinstance(a, Field):
+            if not getattr(a, "_h", None):
+                raise ValueError(f"the field {name} has been closed")
+            handles.append(a._h)
+            uniform.append(0.0)
+        else:
+            handles.append(None)
+            uniform.append(float(a))
+    p = emission_params(omegas, axis, toward, *uniform)
+    nb = p.n_band
+    lateral = tuple(n for k, n in enumerate(ne.shape[:3]) if k != p.axis) if 0 <= p.axis <= 2 else ne.shape[:2]
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != (nb,) + lateral:
+            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lateral grid give {(nb,) + lateral}")
+    I, tau = np.empty((nb,) + lateral), np.empty((nb,) + lateral)
+    ms = C.c_double(0.0)
+    check(lib.sr_field_emission(ne._h, handles[0], handles[1], C.byref(p), ptr(backlight), ptr(I), ptr(tau), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    return I, tau
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

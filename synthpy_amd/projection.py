@@ -104,21 +104,26 @@ class Projection:
         the grid.  `what` names one of the quantities above; "deflection" gives (2, N)."""
         if what not in _QUANTITIES:
             raise ValueError(f"what must be one of {_QUANTITIES}, got {what!r}")
-        m = getattr(self, what)
-        p, q = np.asarray(p, np.float64), np.asarray(q, np.float64)
-        if p.shape != q.shape:
-            raise ValueError(f"p has shape {p.shape}, q {q.shape}")
-        gu, gv = self.coords
-        with np.errstate(invalid="ignore"):
-            inside = (p >= gu[0]) & (p <= gu[-1]) & (q >= gv[0]) & (q <= gv[-1])
-        ps, qs = np.where(inside, p, gu[0]), np.where(inside, q, gv[0])
-        i = np.clip(np.searchsorted(gu, ps, side="right") - 1, 0, len(gu) - 2)
-        j = np.clip(np.searchsorted(gv, qs, side="right") - 1, 0, len(gv) - 2)
-        t = (ps - gu[i]) / (gu[i + 1] - gu[i])
-        s = (qs - gv[j]) / (gv[j + 1] - gv[j])
-        out = ((1 - t) * (1 - s) * m[..., i, j] + t * (1 - s) * m[..., i + 1, j]
-               + (1 - t) * s * m[..., i, j + 1] + t * s * m[..., i + 1, j + 1])
-        return np.where(inside, out, np.nan)
+        return bilinear(self.coords, getattr(self, what), p, q)
+
+
+def bilinear(coords, m, p, q):
+    """Bilinear interpolation of the maps m (..., n_u, n_v) on the node coordinates coords = (gu, gv) at the lateral positions
+    (p, q); NaN outside the grid.  Projection.sample's and Emission.sample's rule."""
+    p, q = np.asarray(p, np.float64), np.asarray(q, np.float64)
+    if p.shape != q.shape:
+        raise ValueError(f"p has shape {p.shape}, q {q.shape}")
+    gu, gv = coords
+    with np.errstate(invalid="ignore"):
+        inside = (p >= gu[0]) & (p <= gu[-1]) & (q >= gv[0]) & (q <= gv[-1])
+    ps, qs = np.where(inside, p, gu[0]), np.where(inside, q, gv[0])
+    i = np.clip(np.searchsorted(gu, ps, side="right") - 1, 0, len(gu) - 2)
+    j = np.clip(np.searchsorted(gv, qs, side="right") - 1, 0, len(gv) - 2)
+    t = (ps - gu[i]) / (gu[i + 1] - gu[i])
+    s = (qs - gv[j]) / (gv[j + 1] - gv[j])
+    out = ((1 - t) * (1 - s) * m[..., i, j] + t * (1 - s) * m[..., i + 1, j]
+           + (1 - t) * s * m[..., i, j + 1] + t * s * m[..., i + 1, j + 1])
+    return np.where(inside, out, np.nan)
 
 
 def _lateral(domain, axis):

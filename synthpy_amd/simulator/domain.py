@@ -141,6 +141,13 @@ class ScalarDomain:
 
         return rotated(self, angle_deg, about, **kw)
 
+    def self_emission(self, wavelengths, toward="+", backlight=None):
+        """The plasma's own light along the probing axis, emission with self-absorption (no reference counterpart): an
+        emission.Emission with the intensity and optical-depth maps per wavelength.  Needs external_Te() and external_Z()."""
+        from ..emission import self_emission
+
+        return self_emission(self, wavelengths, toward=toward, backlight=backlight)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (domain.py:505-579), written without pyvista."""
         from ..utils.handle_filetypes import export_scalar_field

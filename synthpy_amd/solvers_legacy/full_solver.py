@@ -148,6 +148,13 @@ class ScalarDomain:
 
         return rotated(self, angle_deg, about, **kw)
 
+    def self_emission(self, wavelengths, toward="+", backlight=None):
+        """The plasma's own light along the probing axis, emission with self-absorption (no reference counterpart): an
+        emission.Emission with the intensity and optical-depth maps per wavelength.  Needs external_Te() and external_Z()."""
+        from ..emission import self_emission
+
+        return self_emission(self, wavelengths, toward=toward, backlight=backlight)
+
     def _field(self, k):
         if self._volume is None:
             raise RuntimeError("call calc_dndr(lwl) first")
