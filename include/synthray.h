@@ -227,6 +227,45 @@ typedef struct {
 int sr_field_emission(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p,
                       const double *backlight, double *I, double *tau, double *kernel_ms);
 
+/* ---- self-emission from tabulated opacities ----------------------------------------------
+ * sr_field_emission with the node's absorption and emission taken from an opacity table over temperature x ion number density
+ * (PROPACEOS tables, or anything laid out that way) instead of the NRL coefficient: the bands where bound-free and line opacity
+ * dominate.  Fields, columns, outputs, units and layouts are sr_field_emission's; only the node differs.  float64 throughout,
+ * every operation rounds on its own (emission_table.hip is compiled with -ffp-contract=off); max and min are numpy's (a NaN
+ * operand gives NaN).
+ *   host     the table arrives as logarithms, float64, C order: LT[i] = log(temperature i [eV]), LD[j] = log(ion number density j
+ *            [cm^-3]), both strictly increasing, nT and nD nodes (2..512 each); per band b of p->n_band,
+ *            LA[b][i][j] = log(absorption opacity [cm^2/g]) and LE[b][i][j] = log(emission opacity [cm^2/g]); LE may be NULL:
+ *            LTE, emission opacity = absorption opacity.  p->e_ph[b] and p->c_omega[b] are sr_emission_params' (made from the
+ *            angular frequency of the band's photon energy); p->omega is ignored.  m_ion = A * 1.66053906660e-24 [g].
+ *   node     Te <= 0, ne <= 0 or Z <= 0: alpha = 0 and S = 0.  Otherwise
+ *              ni = (ne*1e-6)/Z;  lt = log(Te);  ld = log(ni)
+ *              i = the largest index with LT[i] <= lt, clamped to [0, nT-2];  ft = min(max((lt - LT[i])/(LT[i+1] - LT[i]), 0), 1)
+ *              j, fd the same from LD and ld
+ *            -- outside the table the edge value holds, there is no extrapolation -- and per band, on a table T (LA or LE),
+ *              p0 = T[i][j] + fd*(T[i][j+1] - T[i][j]);  p1 = T[i+1][j] + fd*(T[i+1][j+1] - T[i+1][j]);  l(T) = p0 + ft*(p1 - p0)
+ *              la = l(LA);  alpha = (exp(la)*(ni*m_ion))*100.0                                                       [1/m]
+ *              S = exp(l(LE) - la) * (c_omega/expm1(e_ph/Te))            LE NULL: S = c_omega/expm1(e_ph/Te), LE is not read
+ *            The interpolant is continuous across lattice nodes, so an lt within rounding of LT[i] may land in the cell on
+ *            either side.  A NaN input stays NaN.
+ *   column   sr_field_emission's, word for word: dtau = (0.5*(alpha_k + alpha_k'))*h,
+ *            I <- I*exp(-dtau) + (0.5*(S_k + S_k'))*(-expm1(-dtau)), tau <- tau + dtau, composed in any FIXED order; toward = +-1;
+ *            backlight, Te or Z may be NULL (0, or the uniform value p->Te / p->Z).  No atomics: a repeated call returns identical
+ *            bits.  A NaN node makes its own column NaN and no other.
+ * I is the spectral radiance per unit angular frequency at the band's photon energy [W m^-2 sr^-1 (rad/s)^-1].  Not modelled:
+ * Z from the table's own ionisation (the solve ne = ni*zf(T, ni)), group-integrated Planck functions, refraction, detector optics.
+ * Arguments are checked before the device is touched: everything sr_field_emission checks except omega, a NULL table or a NULL
+ * LT, LD or LA, nT or nD outside 2..512, a lattice that is not finite or not strictly increasing, a non-finite table entry, an
+ * m_ion that is not finite and positive. */
+typedef struct {
+  int32_t nT, nD;        /* lattice nodes: temperature, ion number density                              */
+  const double *LT, *LD; /* log of the lattice [eV], [cm^-3]: nT, nD values                             */
+  const double *LA, *LE; /* log opacities [cm^2/g], (n_band, nT, nD); LE NULL: LTE                      */
+  double m_ion;          /* ion mass [g]                                                                */
+} sr_emission_table;
+int sr_field_emission_table(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *t,
+                            const sr_emission_params *p, const double *backlight, double *I, double *tau, double *kernel_ms);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

@@ -65,6 +65,11 @@ class EmissionParams(C.Structure):
                 ("Te", C.c_double), ("Z", C.c_double)]
 
 
+class EmissionTable(C.Structure):
+    _fields_ = [("nT", C.c_int32), ("nD", C.c_int32), ("LT", C.c_void_p), ("LD", C.c_void_p), ("LA", C.c_void_p),
+                ("LE", C.c_void_p), ("m_ion", C.c_double)]
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -109,6 +114,8 @@ SYMBOLS = {
     "sr_field_create": (_i, [_pp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_field_resample": (_i, [_vp, C.POINTER(ResampleParams), _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_emission": (_i, [_vp, _vp, _vp, C.POINTER(EmissionParams), _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_emission_table": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(EmissionParams), _vp, _vp, _vp,
+                                     C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),
     "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),

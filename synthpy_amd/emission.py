@@ -9,7 +9,11 @@ pinhole channel.  Per band and lateral column the formal solution of dI/ds = alp
 plane nearest the detector on the GPU (engine.emission -> sr_field_emission; include/synthray.h states the rule): alpha is
 propagator.kappa(ne, Te, Z, omega) / c -- the NRL low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy
 for hbar*omega <~ Te -- and S is the Planck function B_omega(Te), so the emissivity follows from Kirchhoff's law.  Refraction of the
-emitted light, line emission, opacity tables and detector optics are not modelled.
+emitted light, line emission and detector optics are not modelled.  Where hbar*omega is above Te -- XUV and soft-X-ray bands, where
+bound-free and line opacity dominate -- the coefficient comes from an opacity table instead: table_emission below.
+
+    table = OpacityTable.from_propaceos(read_propaceos(path, need_abs_opacity=True, need_emiss_opacity=True), A=12.011)
+    em = table_emission(domain, table)                     # or domain.table_emission(table); a TableEmission
 """
 from __future__ import annotations
 
@@ -88,14 +92,12 @@ def _uniform(a):
     return None
 
 
-def self_emission(domain, wavelengths, toward="+", backlight=None):
-    """The Emission of a domain of either API generation along its probing_direction, at up to 4 wavelengths [m] in one pass
-    over the fields.  toward "+": the detector is where the rays leave (behind the last node plane of the axis), "-": where
-    they enter.  backlight: (n_band, n_u, n_v) spectral radiance behind the far plane, or None.  The domain needs external_Te()
-    and external_Z(); a Te or Z that is a scalar (or broadcast from one) is not uploaded."""
+def _march(domain, toward, run):
+    """What self_emission and table_emission share: the domain's fields uploaded by self_emission's rules -- a Te or Z that is a
+    scalar (or broadcast from one) goes as a value, float32 only when every array is float32 -- then run(ne, Te, Z, axis, sign)
+    -> (I, tau); returns (I, tau, axes, coords)."""
     axis = engine.axis_index(domain.probing_direction)
     sign = _toward(toward)
-    lam, omegas = _omegas(wavelengths)
     ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
     if ne is None:
         raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
@@ -117,9 +119,57 @@ def self_emission(domain, wavelengths, toward="+", backlight=None):
     try:
         for name, a in arrays.items():
             fields[name] = engine.Field(np.ascontiguousarray(np.broadcast_to(a, shape), dtype), domain.x, domain.y, domain.z)
-        I, tau = engine.emission(fields["ne"], fields.get("Te", values.get("Te")), fields.get("Z", values.get("Z")), omegas, axis,
-                                 sign, backlight)
+        I, tau = run(fields["ne"], fields.get("Te", values.get("Te")), fields.get("Z", values.get("Z")), axis, sign)
     finally:
         for f in fields.values():
             f.close()
+    return I, tau, axes, coords
+
+
+def self_emission(domain, wavelengths, toward="+", backlight=None):
+    """The Emission of a domain of either API generation along its probing_direction, at up to 4 wavelengths [m] in one pass
+    over the fields.  toward "+": the detector is where the rays leave (behind the last node plane of the axis), "-": where
+    they enter.  backlight: (n_band, n_u, n_v) spectral radiance behind the far plane, or None.  The domain needs external_Te()
+    and external_Z(); a Te or Z that is a scalar (or broadcast from one) is not uploaded."""
+    engine.axis_index(domain.probing_direction)
+    _toward(toward)
+    lam, omegas = _omegas(wavelengths)
+    I, tau, axes, coords = _march(domain, toward, lambda ne, Te, Z, axis, sign: engine.emission(ne, Te, Z, omegas, axis, sign, backlight))
     return Emission(I, tau, axes, coords, lam)
+
+
+class TableEmission(Emission):
+    """The Emission of a tabulated-opacity march: intensity is the spectral radiance per unit angular frequency at the table's
+    photon_energy [eV] per band (wavelengths = 2 pi hbar c / (e photon_energy)).  Where the table has band edges, `edges`
+    ((n_band, 2), eV) keeps them and band_radiance = intensity * (the band's width in angular frequency) [W m^-2 sr^-1]: the
+    Planck function is taken at photon_energy, not integrated over the group."""
+
+    def __init__(self, intensity, optical_depth, axes, coords, photon_energy, edges=None):
+        self.photon_energy = np.atleast_1d(np.asarray(photon_energy, np.float64))
+        super().__init__(intensity, optical_depth, axes, coords, 2 * np.pi * engine.HBAR * c / (engine.E_CHARGE * self.photon_energy))
+        self.edges = None if edges is None else np.asarray(edges, np.float64).reshape(len(self.photon_energy), 2)
+
+    @property
+    def band_radiance(self):
+        if self.edges is None:
+            raise ValueError("the table has no band edges: band_radiance needs the bands' widths")
+        d_omega = (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
+        return self.intensity * d_omega[:, None, None]
+
+
+def table_emission(domain, table, toward="+", backlight=None):
+    """self_emission with the opacities of `table` (utils.eos_opacity.OpacityTable, e.g. OpacityTable.from_propaceos(
+    read_propaceos(...), A)) in place of the NRL coefficient: a TableEmission, one band per band of the table
+    (engine.emission_table -> sr_field_emission_table; include/synthray.h states the rule).  A node's ion density is ne / Z with
+    the domain's Z; the opacities are interpolated bilinearly in (log Te, log ni) on their logarithms and held at the edge value
+    outside the table; the source function is Planck's at the band's photon_energy times emission / absorption opacity (1 for a
+    table without emission opacities: LTE).  toward, backlight and the upload rules are self_emission's.
+    Not modelled: Z from the table's own zf_table (it would need the solve ne = ni * zf(T, ni)), group-integrated Planck
+    functions, refraction of the emitted light, detector optics."""
+    engine.axis_index(domain.probing_direction)
+    _toward(toward)
+    for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
+        if not hasattr(table, name):
+            raise ValueError(f"table must be an OpacityTable (utils.eos_opacity): it has no {name}")
+    I, tau, axes, coords = _march(domain, toward, lambda ne, Te, Z, axis, sign: engine.emission_table(ne, Te, Z, table, axis, sign, backlight))
+    return TableEmission(I, tau, axes, coords, table.photon_energy, getattr(table, "edges", None))

@@ -467,6 +467,60 @@ def emission(ne, Te, Z, omegas, axis, toward=+1, backlight=None):
     return I, tau
 
 
+def emission_table_params(table):
+    """sr_emission_table for an utils.eos_opacity.OpacityTable (or anything with its members), and the arrays it points into
+    (keep them alive for the call): the logarithms of the lattice and of the opacities, float64."""
+    LT, LD = np.log(f64(table.temperatures)), np.log(f64(table.densities))
+    LA = np.ascontiguousarray(np.log(f64(table.absorption)))
+    LE = None if table.emission is None else np.ascontiguousarray(np.log(f64(table.emission)))
+    if LA.ndim != 3 or LA.shape[1:] != (len(LT), len(LD)) or (LE is not None and LE.shape != LA.shape):
+        raise ValueError(f"the table's opacities have shape {LA.shape}, its lattice gives (n_band, {len(LT)}, {len(LD)})")
+    t = _ffi.EmissionTable()
+    t.nT, t.nD = len(LT), len(LD)
+    t.LT, t.LD, t.LA, t.LE = ptr(LT), ptr(LD), ptr(LA), ptr(LE)
+    t.m_ion = float(table.A) * 1.66053906660e-24
+    return t, (LT, LD, LA, LE)
+
+
+def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
+    """engine.emission with the absorption and emission opacities of `table` (utils.eos_opacity.OpacityTable: a temperature x
+    ion-density lattice, up to 4 bands) in place of the NRL coefficient (sr_field_emission_table; include/synthray.h states the
+    rule): (I, tau), each (n_band, n_u, n_v) float64.  The ion density of a node is ne / Z; alpha = opacity * ni * m_ion, the
+    opacity interpolated bilinearly in (log Te, log ni) on its logarithm, the edge value outside the lattice; S is the Planck
+    function at the band's photon_energy times emission / absorption opacity.  I is the spectral radiance per unit angular
+    frequency at photon_energy.  Fields, uniform Te / Z, axis, toward and backlight are engine.emission's.  Not modelled: Z from
+    the table's own zf_table (the solve ne = ni * zf(T, ni)), group-integrated Planck functions, refraction, detector optics."""
+    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
+        raise ValueError("ne must be an open engine.Field")
+    handles, uniform = [], []
+    for name, a in (("Te", Te), ("Z", Z)):
+        if isinstance(a, Field):
+            if not getattr(a, "_h", None):
+                raise ValueError(f"the field {name} has been closed")
+            handles.append(a._h)
+            uniform.append(0.0)
+        else:
+            handles.append(None)
+            uniform.append(float(a))
+    t, keep = emission_table_params(table)
+    p = emission_params(np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR, axis, toward, *uniform)
+    nb = p.n_band
+    if nb != keep[2].shape[0]:
+        raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {nb} photon energies")
+    lateral = tuple(n for k, n in enumerate(ne.shape[:3]) if k != p.axis) if 0 <= p.axis <= 2 else ne.shape[:2]
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != (nb,) + lateral:
+            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lateral grid give {(nb,) + lateral}")
+    I, tau = np.empty((nb,) + lateral), np.empty((nb,) + lateral)
+    ms = C.c_double(0.0)
+    check(lib.sr_field_emission_table(ne._h, handles[0], handles[1], C.byref(t), C.byref(p), ptr(backlight), ptr(I), ptr(tau),
+                                      C.byref(ms)))
+    del keep
+    ne.last_kernel_ms = float(ms.value)
+    return I, tau
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

@@ -148,6 +148,14 @@ class ScalarDomain:
 
         return self_emission(self, wavelengths, toward=toward, backlight=backlight)
 
+    def table_emission(self, table, toward="+", backlight=None):
+        """self_emission with the opacities of an utils.eos_opacity.OpacityTable (PROPACEOS tables) in place of the NRL
+        coefficient (no reference counterpart): an emission.TableEmission, one band per band of the table.  Needs external_Te()
+        and external_Z().  Not modelled: Z from the table's zf_table, group-integrated Planck functions, refraction, detector optics."""
+        from ..emission import table_emission
+
+        return table_emission(self, table, toward=toward, backlight=backlight)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (domain.py:505-579), written without pyvista."""
         from ..utils.handle_filetypes import export_scalar_field

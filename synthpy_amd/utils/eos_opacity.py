@@ -1,0 +1,183 @@
+"""Equation-of-state and opacity tables (src/utils/eos_opacity.py of the reference): read_propaceos, the reference's reader of
+PROPACEOS text tables, and OpacityTable, what the tabulated self-emission consumes (emission.table_emission,
+engine.emission_table -> sr_field_emission_table; no reference counterpart).
+
+    d = read_propaceos("carbon.prp", need_emiss_opacity=True, need_abs_opacity=True)
+    table = OpacityTable.from_propaceos(d, A=12.011)
+    em = domain.table_emission(table)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+_HEADER_LINES = 38
+# (flag, key) in FILE order: each table follows one title line, so a table is found only by reading every table before it
+_TABLES = (("need_zf_table", "zf_table"), ("need_ross_opacity", "ross_opacity"), ("need_emiss_opacity", "emiss_opacity"),
+           ("need_abs_opacity", "abs_opacity"), ("need_en_table", "en_table"), ("need_eion", "eion_table"),
+           ("need_eele", "eele_table"), ("need_pion", "pion_table"), ("need_pele", "pele_table"))
+_KEYS = ("temperatures", "densities", "rad_groups") + tuple(key for _, key in _TABLES)
+
+
+class _Lines:
+    """The file's lines one after another: skip() as next() on a file does (StopIteration at the end), line() as readline()
+    (an empty string at the end)."""
+
+    def __init__(self, fh):
+        self._it = iter(fh)
+
+    def skip(self, n=1):
+        for _ in range(n):
+            next(self._it)
+
+    def line(self):
+        return next(self._it, "")
+
+    def values(self, n_lines):
+        out = []
+        for _ in range(n_lines):
+            out.extend(float(v) for v in self.line().strip().split())
+        return out
+
+
+def read_propaceos(file_name, need_zf_table=False, need_en_table=False, need_eion=False, need_eele=False, need_pion=False,
+                   need_pele=False, need_ross_opacity=False, need_emiss_opacity=False, need_abs_opacity=False):
+    """The reference's read_propaceos: a dict with "temperatures" [eV], "densities" [ion number density, cm^-3], "rad_groups"
+    (the photon-energy group edges [eV]) and, for every need_* flag set, the (n_temperature, n_density) table -- "zf_table"
+    (mean ionisation), "ross_opacity", "emiss_opacity", "abs_opacity" [cm^2/g], "en_table", "eion_table", "eele_table" [J/g],
+    "pion_table", "pele_table" [dyne/cm^2]; a table that was not asked for is None.
+
+    The file is read as the reference reads it, quirks included:
+    * 38 header lines are skipped; then a count line and the temperature grid, a count line and the density grid.  A grid of n
+      values is read as n // 10 lines (of ten values): a count that is no multiple of ten loses its last, short line -- the grid
+      comes back short and every later block is read from the wrong line (usually a ValueError from a title line or from a row
+      of the wrong length), exactly as in the reference.
+    * the same two grids again and 5 more lines are skipped (n_T // 10 + n_D // 10 + 2 + 5 lines), then the group count, one
+      skipped line and ngroups // 10 + 1 lines of group edges.
+    * the tables follow in FILE order -- zf, Rosseland, emission, absorption, en, eion, eele, pion, pele -- each after ONE skipped
+      title line, n_D // 10 lines per temperature.  A table is only skipped over when it is asked for: asking for a later table
+      without every earlier one reads an earlier table's block under the later name (or fails on its rows).
+    A count <= 0 raises ValueError; a file that ends early raises StopIteration or ValueError, whichever the reference's
+    next() / readline() at that place gives."""
+    wanted = dict(need_zf_table=need_zf_table, need_en_table=need_en_table, need_eion=need_eion, need_eele=need_eele,
+                  need_pion=need_pion, need_pele=need_pele, need_ross_opacity=need_ross_opacity,
+                  need_emiss_opacity=need_emiss_opacity, need_abs_opacity=need_abs_opacity)
+    data = dict.fromkeys(_KEYS)
+    with open(file_name, "r") as fh:
+        src = _Lines(fh)
+        src.skip(_HEADER_LINES)
+        n_t = int(src.line().strip())
+        if n_t <= 0:
+            raise ValueError("No temperature grid found in the PROPACEOS file.")
+        temperatures = src.values(n_t // 10)
+        n_d = int(src.line().strip())
+        if n_d <= 0:
+            raise ValueError("No density grid found in the PROPACEOS file.")
+        densities = src.values(n_d // 10)
+        data["temperatures"] = np.array(temperatures)
+        data["densities"] = np.array(densities)
+        src.skip(n_t // 10 + n_d // 10 + 2 + 5)
+        n_groups = int(src.line().strip())
+        src.skip()
+        data["rad_groups"] = np.array(src.values(n_groups // 10 + 1))
+        for flag, key in _TABLES:
+            if not wanted[flag]:
+                continue
+            if key == "en_table":
+                src.line()  # the reference skips this one title with readline(): no StopIteration at the end of the file
+            else:
+                src.skip()
+            table = np.zeros((n_t, n_d))
+            for t in range(n_t):
+                table[t, :] = src.values(n_d // 10)
+            data[key] = table
+    return data
+
+
+MAX_LATTICE = 512  # sr_field_emission_table: 2..512 nodes per lattice axis
+ATOMIC_MASS_G = 1.66053906660e-24  # u [g]
+
+
+class OpacityTable:
+    """Absorption (and emission) opacities on a temperature x ion-density lattice, for up to 4 bands: what
+    sr_field_emission_table interpolates (bilinearly in log T, log n_i, on the logarithm of the opacity; outside the lattice the
+    edge value holds).
+
+    temperatures [eV] and densities [ion number density, cm^-3]: strictly increasing, finite, positive, 2 to 512 entries each.
+    absorption, emission [cm^2/g]: (n_band, nT, nD) (a 2-D array is one band), finite and positive; emission=None is LTE
+    (emission opacity = absorption opacity).  photon_energy [eV] per band: where the Planck function is taken.  edges: optional
+    (n_band, 2) band edges [eV].  A: the atomic mass [u] that turns n_i into a mass density.  ValueError names the offending member."""
+
+    def __init__(self, temperatures, densities, absorption, photon_energy, A, emission=None, edges=None):
+        from .._ffi import MAX_BANDS
+
+        self.temperatures = np.array(temperatures, np.float64, ndmin=1)
+        self.densities = np.array(densities, np.float64, ndmin=1)
+        for name in ("temperatures", "densities"):
+            a = getattr(self, name)
+            if a.ndim != 1 or not 2 <= len(a) <= MAX_LATTICE:
+                raise ValueError(f"{name} must hold 2 to {MAX_LATTICE} values in one dimension, got shape {a.shape}")
+            if not np.all(np.isfinite(a) & (a > 0)):
+                raise ValueError(f"{name} must be finite and positive")
+            if not np.all(a[1:] > a[:-1]):
+                raise ValueError(f"{name} must be strictly increasing")
+        lattice = (len(self.temperatures), len(self.densities))
+        self.absorption = self._opacity("absorption", absorption, lattice)
+        n_band = len(self.absorption)
+        if not 1 <= n_band <= MAX_BANDS:
+            raise ValueError(f"absorption must hold 1 to {MAX_BANDS} bands, got {n_band}")
+        self.emission = None if emission is None else self._opacity("emission", emission, lattice)
+        if self.emission is not None and self.emission.shape != self.absorption.shape:
+            raise ValueError(f"emission has shape {self.emission.shape}, absorption {self.absorption.shape}")
+        self.photon_energy = np.array(photon_energy, np.float64, ndmin=1)
+        if self.photon_energy.shape != (n_band,) or not np.all(np.isfinite(self.photon_energy) & (self.photon_energy > 0)):
+            raise ValueError(f"photon_energy must be {n_band} finite positive value(s), got {self.photon_energy.tolist()}")
+        self.edges = None
+        if edges is not None:
+            self.edges = np.array(edges, np.float64, ndmin=2)
+            if self.edges.shape != (n_band, 2) or not np.all(np.isfinite(self.edges) & (self.edges >= 0)) or not np.all(
+                    self.edges[:, 1] > self.edges[:, 0]):
+                raise ValueError(f"edges must be ({n_band}, 2), finite, non-negative and increasing per band, got {self.edges.tolist()}")
+        self.A = float(A)
+        if not (np.isfinite(self.A) and self.A > 0):
+            raise ValueError(f"A must be a finite positive atomic mass [u], got {A!r}")
+
+    @staticmethod
+    def _opacity(name, values, lattice):
+        a = np.array(values, np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != lattice:
+            raise ValueError(f"{name} has shape {a.shape}, the lattice gives (n_band, {lattice[0]}, {lattice[1]})")
+        if not np.all(np.isfinite(a) & (a > 0)):
+            raise ValueError(f"{name} must be finite and positive")
+        return np.ascontiguousarray(a)
+
+    @property
+    def n_band(self):
+        return len(self.absorption)
+
+    @property
+    def m_ion(self):
+        """The ion mass [g]."""
+        return self.A * ATOMIC_MASS_G
+
+    def logs(self):
+        """(LT, LD, LA, LE): the float64 logarithms sr_field_emission_table takes; LE is None for LTE."""
+        return (np.log(self.temperatures), np.log(self.densities), np.ascontiguousarray(np.log(self.absorption)),
+                None if self.emission is None else np.ascontiguousarray(np.log(self.emission)))
+
+    @classmethod
+    def from_propaceos(cls, data, A, photon_energy=None):
+        """A one-band table from read_propaceos' dict (the reader yields group MEANS only; multi-band tables come from arrays):
+        absorption from "abs_opacity", emission from "emiss_opacity" when it was read, edges = the first and the last entry of
+        "rad_groups", photon_energy = their geometric mean unless given."""
+        if data.get("abs_opacity") is None:
+            raise ValueError("abs_opacity is missing: call read_propaceos(..., need_abs_opacity=True)")
+        groups = np.asarray(data["rad_groups"], np.float64)
+        if groups.ndim != 1 or len(groups) < 2:
+            raise ValueError(f"rad_groups must hold at least 2 edges, got shape {groups.shape}")
+        edges = np.array([[groups[0], groups[-1]]])
+        if photon_energy is None:
+            photon_energy = np.sqrt(groups[0] * groups[-1])
+        return cls(data["temperatures"], data["densities"], data["abs_opacity"], photon_energy, A,
+                   emission=data.get("emiss_opacity"), edges=edges)
