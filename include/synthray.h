@@ -304,7 +304,8 @@ int sr_power_spectrum(const double *field, int ndim, const int64_t *shape, const
  * amp[i] and phase[i]; node (j, i) of the (ny, nx) grid sits at (gx[i], gy[j]) (np.meshgrid(x, y)).  A node inside the
  * rays' convex hull gets the linear interpolation of amp and phase in the Delaunay triangle of all rays that holds it
  * (barycentric weights, float64), a node outside gets 0 -- scipy's LinearNDInterpolator(..., fill_value=0) evaluated at
- * every node, without building the triangulation.  tri_out (may be NULL): the triangle's three ray indices per node,
+ * every node, without building the triangulation.  Nodes on the hull's boundary, its vertices included, are inside, as
+ * scipy treats them.  tri_out (may be NULL): the triangle's three ray indices per node,
  * ascending, (ny, nx, 3), -1 outside.  stats (may be NULL): SR_FRESNEL_STATS values (hull vertices, rays left by the hull
  * pre-filter, bins along x and y, nodes outside, nodes the second pass resolved).  Rays must have finite positions and be
  * at least 3 (checked before the device is touched); collinear rays span no triangle: every node is outside. */

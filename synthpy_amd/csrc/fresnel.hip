@@ -309,7 +309,8 @@ __device__ int locate(const Bins &B, const Team<NT> &tm, double px, double py, i
       grow = v.slot < 0;
     }
     if (!grow) {
-      if (orient(u.x, u.y, v.x, v.y, 0.0, 0.0) < 0.0) {
+      const double o0 = orient(u.x, u.y, v.x, v.y, 0.0, 0.0);
+      if (o0 < 0.0) {
         const Cand s = u;
         u = v;
         v = s;
@@ -317,6 +318,14 @@ __device__ int locate(const Bins &B, const Team<NT> &tm, double px, double py, i
       for (int step = 0;; ++step) {
         if (step == max_steps) return -1;
         c = mate(B, w, tm, px, py, u, v);
+        // The node on the line of the starting pair (on a ray, on an edge, on the hull's boundary): its triangle may lie
+        // on either side.  No ray on this one (the pair runs clockwise along the hull): the other one.
+        if (c.slot < 0 && step == 0 && o0 == 0.0) {
+          const Cand s = u;
+          u = v;
+          v = s;
+          c = mate(B, w, tm, px, py, u, v);
+        }
         if (c.slot < 0) {  // (u, v) is a hull edge of the candidates and the node lies beyond it
           grow = true;
           break;

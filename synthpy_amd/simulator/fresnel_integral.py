@@ -35,6 +35,7 @@ Decided here:
     go to the lower ray index.  Rays at the same position: the lowest index is the vertex.  Four or more co-circular
     rays: the triangle the search reaches, a valid Delaunay triangle, which may differ from qhull's inside that polygon
     (both are linear interpolants of the same rays).  Nodes exactly on a triangle edge may take either neighbour.
+    Nodes on the hull's boundary, its vertices included, are inside, as scipy treats them.
 """
 from __future__ import annotations
 
