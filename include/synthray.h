@@ -266,6 +266,61 @@ typedef struct {
 int sr_field_emission_table(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *t,
                             const sr_emission_params *p, const double *backlight, double *I, double *tau, double *kernel_ms);
 
+/* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
+ * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
+ * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be
+ * equal), with a fixed step dt, until they leave the grid box or have made max_steps steps, and are then projected ballistically
+ * onto a detector plane.  E or B may be NULL: that field is zero, it is never read, and its line of the rule is skipped (um = u
+ * and u = up without E; up = um without B).  The state is x [m] and u = gamma*v [m/s]; s0 and sf are HOST arrays (6, n): rows
+ * x y z ux uy uz.  push.hip is compiled with -ffp-contract=off: every operation below rounds on its own, in float64; sqrt is the
+ * correctly rounded one.
+ * With c = 299792458.0, ic2 = 1.0/(c*c), hq = (qm*dt)*0.5, hd = dt*0.5 and |a|^2 = (a0*a0 + a1*a1) + a2*a2, per particle:
+ *   do {
+ *     g  = sqrt(1.0 + |u|^2*ic2);  d = hd/g;          xm_a = x_a + u_a*d                (half drift)
+ *     (E, B) at xm: sr_field_resample's cell / outside / blend rule with fill 0 (same corner order, u = 1 - w factors)
+ *     um_a = u_a + hq*E_a                                                               (half kick)
+ *     gm = sqrt(1.0 + |um|^2*ic2);  k = hq/gm;  t_a = k*B_a;  f = 2.0/(1.0 + |t|^2);  s_a = t_a*f
+ *     w  = um + um x t;   up = um + w x s            (cross: (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0))
+ *     u_a = up_a + hq*E_a                                                               (half kick)
+ *     gn = sqrt(1.0 + |u|^2*ic2);   x_a = xm_a + u_a*(hd/gn)                            (half drift)
+ *     steps += 1
+ *   } while (x inside the grid box on every axis: g[0] <= x_a <= g[n-1]; a NaN is outside) && steps < max_steps
+ * -- the Boris push in its relativistic, position-centred form.  The test is made after a step, never before the first.  A
+ * particle whose midpoint xm lies outside the box on any axis sees E = B = 0 (these zeros go through the arithmetic above), so a
+ * step taken outside the box is a free flight; moving a particle to the entry plane of the box is the caller's job.  A step's gn
+ * is the next step's g (same inputs, same operations).  SR_PUSH_UNFINISHED is set when the loop ends by steps == max_steps with x
+ * still inside.
+ *   detector  a = axis: tau = (det_pos - x_a)/u_a; SR_PUSH_MISSED is set unless tau is finite and > 0.  For the two other axes
+ *             b in x < y < z order (sr_volume_project's (u, v) convention), hits[j] = (x_b + u_b*tau)*hit_scale, whatever the flags.
+ *   image     a particle with flags == 0 is binned into img (SR_IMG_COUNTS; x = hits[0], y = hits[1]) by the A9 binning of sr_hist2d;
+ *             the counts are ADDED to what the image holds.  With img given and every host output NULL nothing but the stats
+ *             comes back.
+ * Counts are integer atomics and nothing else is atomic: a repeated call returns identical bits everywhere.  sf (6, n), hits
+ * (2, n), steps (n) and flags (n) are HOST arrays in the order of s0; each may be NULL.  stats (may be NULL): kernel_ms is the
+ * HIP-event time of the push kernel alone; finished + unfinished == n; missed counts SR_PUSH_MISSED; deposited the particles
+ * binned inside img.
+ * Validity: prescribed fields only (no self-fields), no scattering or stopping in the plasma, a fixed step, trilinear fields (div B
+ * is only as good as the input's).
+ * Arguments are checked before the device is touched: a NULL p or s0, n < 0, a non-finite or non-positive dt, a non-finite qm,
+ * det_pos or hit_scale, max_steps < 1, an axis outside 0..2, an img of another kind, E and B both NULL, a field with n_comp != 3,
+ * E and B of different dtypes or on grids that differ.  n == 0 succeeds. */
+typedef struct {
+  double qm;            /* charge / mass [C/kg] */
+  double dt;            /* step [s], > 0, finite */
+  int32_t max_steps;    /* >= 1 */
+  int32_t axis;         /* 0,1,2: the detector plane is  coordinate[axis] == det_pos */
+  double det_pos;       /* [m] */
+  double hit_scale;     /* hits are multiplied by this (1e3: mm, the detector's unit elsewhere in the project) */
+} sr_push_params;
+typedef struct { double kernel_ms; int64_t finished, unfinished, missed, deposited; } sr_push_stats;
+#define SR_PUSH_UNFINISHED 1   /* still inside the grid after max_steps */
+#define SR_PUSH_MISSED     2   /* does not reach the detector plane */
+int sr_particles_push(const sr_field *E, const sr_field *B, const sr_push_params *p, int64_t n,
+                      const double *s0 /* host (6, n): x y z [m], ux uy uz = gamma*v [m/s] */,
+                      double *sf /* host (6, n) or NULL */, double *hits /* host (2, n) or NULL */,
+                      int32_t *steps /* host (n) or NULL */, uint8_t *flags /* host (n) or NULL */,
+                      sr_image *img /* SR_IMG_COUNTS or NULL */, sr_push_stats *stats /* or NULL */);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

@@ -70,6 +70,19 @@ class EmissionTable(C.Structure):
                 ("LE", C.c_void_p), ("m_ion", C.c_double)]
 
 
+class PushParams(C.Structure):
+    _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("max_steps", C.c_int32), ("axis", C.c_int32),
+                ("det_pos", C.c_double), ("hit_scale", C.c_double)]
+
+
+class PushStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("finished", C.c_int64), ("unfinished", C.c_int64), ("missed", C.c_int64),
+                ("deposited", C.c_int64)]
+
+
+PUSH_UNFINISHED, PUSH_MISSED = 1, 2  # SR_PUSH_*
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -116,6 +129,7 @@ SYMBOLS = {
     "sr_field_emission": (_i, [_vp, _vp, _vp, C.POINTER(EmissionParams), _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_emission_table": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(EmissionParams), _vp, _vp, _vp,
                                      C.POINTER(C.c_double)]),
+    "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_bytes": (_i64, [_vp]),
     "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),

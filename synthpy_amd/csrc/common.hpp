@@ -112,6 +112,37 @@ __device__ __forceinline__ void queue_push(unsigned long long *count, uint32_t *
   if (want) list[base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull))] = slot;
 }
 #endif
+// The cell of p on one axis of an sr_field (the `cell` / `outside` lines of sr_field_resample's rule, include/synthray.h; shared by
+// resample.hip and push.hip): the largest i with g[i] <= p, clipped to n - 2; false when p lies outside (or is NaN).
+#ifdef __HIPCC__
+// BOUNDS: g0 = g[0] and gL = g[n - 1] come from the caller (push.hip holds them as kernel arguments for its own inside test);
+// otherwise they are read here (resample.hip).
+template <bool BOUNDS>
+__device__ __forceinline__ bool locate_in(const double *__restrict__ g, int n, double inv_h, double lo_in, double hi_in, double p,
+                                          int &cell, double &w) {
+  const double g0 = BOUNDS ? lo_in : g[0], gL = BOUNDS ? hi_in : g[n - 1];
+  if (!(p >= g0 && p <= gL)) return false;
+  int i = (int)((p - g0) * inv_h);
+  i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
+  if (!(g[i] <= p && (i == n - 2 || p < g[i + 1]))) {  // a non-uniform axis, or a guess one cell off: bisect
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (g[mid] <= p)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    i = lo;
+  }
+  cell = i;
+  w = (p - g[i]) / (g[i + 1] - g[i]);
+  return true;
+}
+__device__ __forceinline__ bool locate(const double *__restrict__ g, int n, double inv_h, double p, int &cell, double &w) {
+  return locate_in<false>(g, n, inv_h, 0.0, 0.0, p, cell, w);
+}
+#endif
 inline unsigned long long stripe_sum(const unsigned long long *host_words, int which) {
   unsigned long long t = 0;
   for (int s = 0; s < kStripes; ++s) t += host_words[16 + ((size_t)which * kStripes + s) * kStripeStride];
@@ -252,6 +283,11 @@ struct sr_rays {
 namespace sr {
 int retrace_f64(const sr_rays *r, const uint32_t *list, const unsigned long long *count);  // trace.hip (edge guard)
 int download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int64_t ld, int64_t off, double *staging);  // trace.hip
+// deposit.hip: the A9 counts binning of DEVICE coordinates (x[i], y[i]) into a SR_IMG_COUNTS image (added to what it holds), the
+// entries with skip[i] != 0 left out (skip may be NULL); *deposited (a device word the caller has zeroed) gets the number binned.
+// Queued on `st`, not waited for.
+int counts_deposit_device(const double *x, const double *y, const uint8_t *skip, int64_t n, sr_image *img,
+                          unsigned long long *deposited, hipStream_t st);
 }
 
 struct sr_image {

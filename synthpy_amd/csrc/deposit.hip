@@ -288,6 +288,22 @@ __global__ void k_hist2d(const double *__restrict__ x, const double *__restrict_
   int bx, by;
   if (bin_hist2(ex, ey, x[i], y[i], bx, by)) atomicAdd(&H[(int64_t)by * ex.n + bx], 1u);
 }
+// the same binning of coordinates that are already on the device, entries with skip[i] != 0 left out (sr::counts_deposit_device);
+// a grid-stride loop, so the hits of a launch are one atomic per wavefront of a bounded grid
+__global__ __launch_bounds__(256) void k_hist2d_device(const double *__restrict__ x, const double *__restrict__ y,
+                                                       const uint8_t *__restrict__ skip, int64_t N, Edges ex, Edges ey,
+                                                       uint32_t *__restrict__ H, unsigned long long *__restrict__ deposited) {
+  unsigned long long mine = 0ull;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+    int bx, by;
+    if ((skip == nullptr || skip[i] == 0) && bin_hist2(ex, ey, x[i], y[i], bx, by)) {
+      atomicAdd(&H[(int64_t)by * ex.n + bx], 1u);
+      ++mine;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(deposited, mine);
+}
 
 __global__ void k_interferogram(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ E,
                                 int64_t N, Edges ex, Edges ey, double *__restrict__ amp) {
@@ -796,6 +812,17 @@ int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo,
 }
 
 }  // namespace
+
+int sr::counts_deposit_device(const double *x, const double *y, const uint8_t *skip, int64_t n, sr_image *img,
+                              unsigned long long *deposited, hipStream_t st) {
+  SR_CHECK(img != nullptr && img->kind == SR_IMG_COUNTS, "counts_deposit_device: needs a counts image");
+  if (n <= 0) return SR_OK;
+  const unsigned grid = (unsigned)std::min<int64_t>(sr::grid_for(n, 256), 1024);
+  hipLaunchKernelGGL(k_hist2d_device, dim3(grid), dim3(256), 0, st, x, y, skip, n, make_edges(img->x_lo, img->x_hi, img->nx),
+                     make_edges(img->y_lo, img->y_hi, img->ny), static_cast<uint32_t *>(img->d), deposited);
+  SR_HIP(hipGetLastError());
+  return SR_OK;
+}
 
 extern "C" {
 

@@ -1,0 +1,259 @@
+// Proton radiography: independent charged particles pushed through prescribed E and B fields (sr_particles_push; include/synthray.h
+// states the rule every particle follows, operation for operation).  No reference counterpart.
+//
+// One particle per lane, 256-lane workgroups, the state (x, u, the step count and the last sqrt) in registers for the whole loop; no
+// LDS, no scratch, no atomics.  k_push is instantiated per (E given, B given, float32 / float64 source), so an absent field costs no
+// gather and none of its arithmetic.  A step's only memory traffic is the trilinear gather at the midpoint: per field four corner
+// ROWS of 2 nodes x 3 components, contiguous in the (nx, ny, nz, 3) layout (48 B in float64, 24 B in float32), each read as one run.
+// Lanes that have left the box idle until their wavefront ends (tools/push_rate.py measures how many lane-steps that is).
+// Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_radiography.py).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "common.hpp"
+
+namespace {
+
+struct PushArgs {
+  const void *E, *B;   // (nx, ny, nz, 3), or nullptr
+  const double *g[3];  // node coordinates
+  int n[3];
+  double inv_h[3], lo[3], hi[3];  // lo = g[0], hi = g[n-1] per axis: the box
+  double hq, hd, ic2, det_pos, hit_scale;
+  int max_steps, axis;
+  int64_t np;
+  const double *s0;  // (6, np)
+  double *sf;        // (6, np)
+  double *hits;      // (2, np)
+  int32_t *steps;
+  uint8_t *flags;
+};
+
+template <typename T>
+struct Row {  // one corner row: nodes k, k + 1 of z, three components each
+  T v[6];
+};
+
+// the three components of one field at the cell (ci, cj, ck) with the blend of sr_field_resample's rule
+template <typename T>
+__device__ __forceinline__ void blend(const T *__restrict__ src, int64_t sx, int64_t sy, int ci, int cj, int ck, double ux, double wx,
+                                      double w00, double w01, double w10, double w11, double (&val)[3]) {
+  const T *p = src + ((int64_t)ci * sx + (int64_t)cj * sy + (int64_t)ck * 3);
+  const Row<T> a0 = *reinterpret_cast<const Row<T> *>(p), a1 = *reinterpret_cast<const Row<T> *>(p + sy);
+  const Row<T> b0 = *reinterpret_cast<const Row<T> *>(p + sx), b1 = *reinterpret_cast<const Row<T> *>(p + sx + sy);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double s0 = (((double)a0.v[c] * w00 + (double)a0.v[3 + c] * w01) + (double)a1.v[c] * w10) + (double)a1.v[3 + c] * w11;
+    const double s1 = (((double)b0.v[c] * w00 + (double)b0.v[3 + c] * w01) + (double)b1.v[c] * w10) + (double)b1.v[3 + c] * w11;
+    val[c] = ux * s0 + wx * s1;
+  }
+}
+
+__device__ __forceinline__ double norm2(double a0, double a1, double a2) { return (a0 * a0 + a1 * a1) + a2 * a2; }
+
+template <bool HAS_E, bool HAS_B, typename T>
+__global__ void __launch_bounds__(256) k_push(PushArgs A) {
+  const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
+  if (i >= A.np) return;
+  const int64_t N = A.np;
+  double x0 = A.s0[i], x1 = A.s0[N + i], x2 = A.s0[2 * N + i];
+  double u0 = A.s0[3 * N + i], u1 = A.s0[4 * N + i], u2 = A.s0[5 * N + i];
+  const T *__restrict__ fE = static_cast<const T *>(A.E);
+  const T *__restrict__ fB = static_cast<const T *>(A.B);
+  const int64_t sy = (int64_t)A.n[2] * 3, sx = (int64_t)A.n[1] * sy;
+  const double hq = A.hq, hd = A.hd, ic2 = A.ic2;
+  int steps = 0;
+  bool inside;
+  double g = sqrt(1.0 + norm2(u0, u1, u2) * ic2);
+  do {
+    const double d = hd / g;
+    const double m0 = x0 + u0 * d, m1 = x1 + u1 * d, m2 = x2 + u2 * d;
+    double E[3] = {0.0, 0.0, 0.0}, B[3] = {0.0, 0.0, 0.0};
+    int ci = 0, cj = 0, ck = 0;
+    double wx = 0, wy = 0, wz = 0;
+    const bool in_x = sr::locate_in<true>(A.g[0], A.n[0], A.inv_h[0], A.lo[0], A.hi[0], m0, ci, wx);
+    const bool in_y = sr::locate_in<true>(A.g[1], A.n[1], A.inv_h[1], A.lo[1], A.hi[1], m1, cj, wy);
+    const bool in_z = sr::locate_in<true>(A.g[2], A.n[2], A.inv_h[2], A.lo[2], A.hi[2], m2, ck, wz);
+    if (in_x && in_y && in_z) {
+      const double ux = 1.0 - wx, uy = 1.0 - wy, uz = 1.0 - wz;
+      const double w00 = uy * uz, w01 = uy * wz, w10 = wy * uz, w11 = wy * wz;
+      if (HAS_E) blend<T>(fE, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11, E);
+      if (HAS_B) blend<T>(fB, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11, B);
+    }
+    double p0 = u0, p1 = u1, p2 = u2;  // um, then up
+    if (HAS_E) {
+      p0 = u0 + hq * E[0];
+      p1 = u1 + hq * E[1];
+      p2 = u2 + hq * E[2];
+    }
+    if (HAS_B) {
+      const double gm = sqrt(1.0 + norm2(p0, p1, p2) * ic2);
+      const double k = hq / gm;
+      const double t0 = k * B[0], t1 = k * B[1], t2 = k * B[2];
+      const double f = 2.0 / (1.0 + norm2(t0, t1, t2));
+      const double s0 = t0 * f, s1 = t1 * f, s2 = t2 * f;
+      const double w0 = p0 + (p1 * t2 - p2 * t1), w1 = p1 + (p2 * t0 - p0 * t2), w2 = p2 + (p0 * t1 - p1 * t0);
+      p0 = p0 + (w1 * s2 - w2 * s1);
+      p1 = p1 + (w2 * s0 - w0 * s2);
+      p2 = p2 + (w0 * s1 - w1 * s0);
+    }
+    if (HAS_E) {
+      u0 = p0 + hq * E[0];
+      u1 = p1 + hq * E[1];
+      u2 = p2 + hq * E[2];
+    } else {
+      u0 = p0;
+      u1 = p1;
+      u2 = p2;
+    }
+    g = sqrt(1.0 + norm2(u0, u1, u2) * ic2);  // gn: this step's second half drift, and the next step's g (same inputs, same operations)
+    const double dn = hd / g;
+    x0 = m0 + u0 * dn;
+    x1 = m1 + u1 * dn;
+    x2 = m2 + u2 * dn;
+    ++steps;
+    inside = x0 >= A.lo[0] && x0 <= A.hi[0] && x1 >= A.lo[1] && x1 <= A.hi[1] && x2 >= A.lo[2] && x2 <= A.hi[2];
+  } while (inside && steps < A.max_steps);
+
+  // the detector plane: coordinate[axis] == det_pos; (b, c) the two other axes in x < y < z order
+  const int a = A.axis;
+  const double xa = a == 0 ? x0 : (a == 1 ? x1 : x2), ua = a == 0 ? u0 : (a == 1 ? u1 : u2);
+  const double xb = a == 0 ? x1 : x0, ub = a == 0 ? u1 : u0;
+  const double xc = a == 2 ? x1 : x2, uc = a == 2 ? u1 : u2;
+  const double tau = (A.det_pos - xa) / ua;
+  const bool reaches = tau > 0.0 && tau <= 1.7976931348623157e308;  // finite and positive (a NaN fails both)
+  A.sf[i] = x0;
+  A.sf[N + i] = x1;
+  A.sf[2 * N + i] = x2;
+  A.sf[3 * N + i] = u0;
+  A.sf[4 * N + i] = u1;
+  A.sf[5 * N + i] = u2;
+  A.hits[i] = (xb + ub * tau) * A.hit_scale;
+  A.hits[N + i] = (xc + uc * tau) * A.hit_scale;
+  A.steps[i] = steps;
+  A.flags[i] = (uint8_t)((inside ? SR_PUSH_UNFINISHED : 0) | (reaches ? 0 : SR_PUSH_MISSED));
+}
+
+// [0] UNFINISHED, [1] MISSED over the flags of a call: a grid-stride count, one atomic per wavefront of a bounded grid
+__global__ void __launch_bounds__(256) k_push_flags(const uint8_t *__restrict__ flags, int64_t n, unsigned long long *__restrict__ out) {
+  unsigned long long unfinished = 0ull, missed = 0ull;
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const unsigned f = flags[i];
+    unfinished += (f & SR_PUSH_UNFINISHED) ? 1u : 0u;
+    missed += (f & SR_PUSH_MISSED) ? 1u : 0u;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    unfinished += __shfl_down(unfinished, off, 64);
+    missed += __shfl_down(missed, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (unfinished) atomicAdd(&out[0], unfinished);
+    if (missed) atomicAdd(&out[1], missed);
+  }
+}
+
+template <typename T>
+void launch(bool has_e, bool has_b, unsigned grid, hipStream_t st, const PushArgs &A) {
+  sr::with_flags(
+      [&](auto e, auto b) {
+        if constexpr (e.value || b.value) hipLaunchKernelGGL((k_push<e.value, b.value, T>), dim3(grid), dim3(256), 0, st, A);
+      },
+      has_e, has_b);
+}
+
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_push_params *p, int64_t n, const double *s0,
+                                 double *sf, double *hits, int32_t *steps, uint8_t *flags, sr_image *img, sr_push_stats *stats) {
+  SR_CHECK(p != nullptr && s0 != nullptr, "sr_particles_push: NULL argument (p or s0)");
+  SR_CHECK(n >= 0, "sr_particles_push: n must not be negative, got %lld", (long long)n);
+  SR_CHECK(std::isfinite(p->dt) && p->dt > 0.0, "sr_particles_push: dt must be finite and positive");
+  SR_CHECK(std::isfinite(p->qm), "sr_particles_push: non-finite qm");
+  SR_CHECK(std::isfinite(p->det_pos), "sr_particles_push: non-finite det_pos");
+  SR_CHECK(std::isfinite(p->hit_scale), "sr_particles_push: non-finite hit_scale");
+  SR_CHECK(p->max_steps >= 1, "sr_particles_push: max_steps must be at least 1, got %d", p->max_steps);
+  SR_CHECK(p->axis >= 0 && p->axis <= 2, "sr_particles_push: axis must be 0, 1 or 2, got %d", p->axis);
+  SR_CHECK(img == nullptr || img->kind == SR_IMG_COUNTS, "sr_particles_push: the image must be of kind SR_IMG_COUNTS");
+  SR_CHECK(E != nullptr || B != nullptr, "sr_particles_push: E and B are both NULL");
+  const sr_field *F = E ? E : B;
+  SR_CHECK(E == nullptr || E->n_comp == 3, "sr_particles_push: E is not a vector field (n_comp == 3)");
+  SR_CHECK(B == nullptr || B->n_comp == 3, "sr_particles_push: B is not a vector field (n_comp == 3)");
+  if (E && B) {
+    SR_CHECK(E->is_f64 == B->is_f64, "sr_particles_push: E and B differ in dtype");
+    for (int k = 0; k < 3; ++k)
+      SR_CHECK(E->n[k] == B->n[k] && memcmp(E->hg[k].data(), B->hg[k].data(), sizeof(double) * E->n[k]) == 0,
+               "sr_particles_push: the grids of E and B differ on axis %d", k);
+  }
+  if (stats) *stats = sr_push_stats{0.0, 0, 0, 0, 0};
+  if (n == 0) return SR_OK;
+  if (int rc = sr::ensure_init()) return rc;
+  sr::Context &c = sr::ctx();
+  hipStream_t st = c.stream;
+
+  // one scratch block: s0 | sf | hits | steps | flags | counters {unfinished, missed, deposited}
+  const size_t b6 = up256(sizeof(double) * 6 * (size_t)n), b2 = up256(sizeof(double) * 2 * (size_t)n);
+  const size_t bs = up256(sizeof(int32_t) * (size_t)n), bf = up256((size_t)n);
+  char *block = static_cast<char *>(sr::scratch(2 * b6 + b2 + bs + bf + 256));
+  if (!block) return SR_ERR_HIP;
+  PushArgs A{};
+  A.s0 = reinterpret_cast<const double *>(block);
+  A.sf = reinterpret_cast<double *>(block + b6);
+  A.hits = reinterpret_cast<double *>(block + 2 * b6);
+  A.steps = reinterpret_cast<int32_t *>(block + 2 * b6 + b2);
+  A.flags = reinterpret_cast<uint8_t *>(block + 2 * b6 + b2 + bs);
+  unsigned long long *counters = reinterpret_cast<unsigned long long *>(block + 2 * b6 + b2 + bs + bf);
+  A.E = E ? E->data : nullptr;
+  A.B = B ? B->data : nullptr;
+  for (int k = 0; k < 3; ++k) {
+    A.g[k] = F->g[k];
+    A.n[k] = F->n[k];
+    A.inv_h[k] = F->inv_h[k];
+    A.lo[k] = F->hg[k].front();
+    A.hi[k] = F->hg[k].back();
+  }
+  A.hq = (p->qm * p->dt) * 0.5;
+  A.hd = p->dt * 0.5;
+  A.ic2 = 1.0 / (sr::kC * sr::kC);
+  A.det_pos = p->det_pos;
+  A.hit_scale = p->hit_scale;
+  A.max_steps = p->max_steps;
+  A.axis = p->axis;
+  A.np = n;
+
+  if (int rc = sr::upload_sync(block, s0, sizeof(double) * 6 * (size_t)n, st)) return rc;
+  SR_HIP(hipMemsetAsync(counters, 0, 3 * sizeof(unsigned long long), st));
+  SR_HIP(hipEventRecord(c.ev[0], st));
+  if (F->is_f64)
+    launch<double>(E != nullptr, B != nullptr, sr::grid_for(n, 256), st, A);
+  else
+    launch<float>(E != nullptr, B != nullptr, sr::grid_for(n, 256), st, A);
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], st));
+  if (stats) {
+    hipLaunchKernelGGL(k_push_flags, dim3(std::min<unsigned>(sr::grid_for(n, 256), 1024u)), dim3(256), 0, st, A.flags, n, counters);
+    SR_HIP(hipGetLastError());
+  }
+  if (img)
+    if (int rc = sr::counts_deposit_device(A.hits, A.hits + n, A.flags, n, img, counters + 2, st)) return rc;
+  if (sf) SR_HIP(hipMemcpyAsync(sf, A.sf, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (hits) SR_HIP(hipMemcpyAsync(hits, A.hits, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (steps) SR_HIP(hipMemcpyAsync(steps, A.steps, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (flags) SR_HIP(hipMemcpyAsync(flags, A.flags, (size_t)n, hipMemcpyDeviceToHost, st));
+  unsigned long long hc[3] = {0, 0, 0};
+  if (stats) SR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  if (stats) {
+    float ms = 0.f;
+    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    stats->kernel_ms = ms;
+    stats->unfinished = (int64_t)hc[0];
+    stats->finished = n - (int64_t)hc[0];
+    stats->missed = (int64_t)hc[1];
+    stats->deposited = (int64_t)hc[2];
+  }
+  sr::scratch_trim();
+  return SR_OK;
+}

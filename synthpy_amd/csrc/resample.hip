@@ -35,27 +35,7 @@ struct ResampleArgs {
   int64_t nvb;  // ns[0] * ns[1] * ns[2] * kSuper^3: numbered bricks, the padded ones included
 };
 
-// The cell of p on one source axis: the largest i with g[i] <= p, clipped to n - 2; false when p lies outside (or is NaN).
-__device__ __forceinline__ bool locate(const double *__restrict__ g, int n, double inv_h, double p, int &cell, double &w) {
-  const double g0 = g[0], gL = g[n - 1];
-  if (!(p >= g0 && p <= gL)) return false;
-  int i = (int)((p - g0) * inv_h);
-  i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
-  if (!(g[i] <= p && (i == n - 2 || p < g[i + 1]))) {  // a non-uniform axis, or a guess one cell off: bisect
-    int lo = 0, hi = n - 1;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (g[mid] <= p)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    i = lo;
-  }
-  cell = i;
-  w = (p - g[i]) / (g[i + 1] - g[i]);
-  return true;
-}
+using sr::locate;  // the cell of p on one source axis (common.hpp)
 
 template <typename T, int NC, int BX, int BY, int BZ>
 __global__ void __launch_bounds__(256) k_resample(ResampleArgs A) {

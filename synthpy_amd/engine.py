@@ -521,6 +521,63 @@ def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
     return I, tau
 
 
+PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
+_PUSH_WANT = ("sf", "hits", "steps", "flags")
+
+
+@dataclass
+class PushStats:
+    kernel_ms: float   # HIP-event time of the push kernel alone
+    finished: int      # particles that left the grid box
+    unfinished: int    # still inside after max_steps (PUSH_UNFINISHED)
+    missed: int        # do not reach the detector plane (PUSH_MISSED)
+    deposited: int     # binned inside the image
+
+
+def push_params(qm, dt, max_steps, axis, det_pos, hit_scale=1e3):
+    """sr_push_params."""
+    p = _ffi.PushParams()
+    p.qm, p.dt, p.max_steps, p.axis, p.det_pos, p.hit_scale = float(qm), float(dt), int(max_steps), int(axis), float(det_pos), float(hit_scale)
+    return p
+
+
+def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, image=None, want=_PUSH_WANT):
+    """Push the particles s0 (6, n: x y z [m], ux uy uz = gamma*v [m/s]) of charge/mass qm [C/kg] through the vector Fields E [V/m]
+    and B [T] (either may be None: zero) with the fixed step dt until they leave the grid box or have made max_steps steps, and
+    project them onto the plane coordinate[axis] == det_pos (sr_particles_push; include/synthray.h states the rule).  Returns a
+    dict with the arrays named in `want` -- "sf" (6, n), "hits" (2, n; times hit_scale), "steps" (n) int32, "flags" (n) uint8
+    (PUSH_UNFINISHED | PUSH_MISSED) -- and "stats" (PushStats).  image: a counts DetectorImage the particles with flags == 0 are
+    added to on the device."""
+    for name, f in (("E", E), ("B", B)):
+        if f is not None and (not isinstance(f, Field) or not getattr(f, "_h", None)):
+            raise ValueError(f"{name} must be an open engine.Field or None")
+    s0 = f64(s0)
+    if s0.ndim != 2 or s0.shape[0] != 6:
+        raise ValueError(f"s0 must have shape (6, n), got {s0.shape}")
+    unknown = set(want) - set(_PUSH_WANT)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_PUSH_WANT}")
+    if image is not None and not isinstance(image, DetectorImage):
+        raise ValueError("image must be an engine.DetectorImage of counts")
+    n = s0.shape[1]
+    out = {}
+    if "sf" in want:
+        out["sf"] = np.empty((6, n))
+    if "hits" in want:
+        out["hits"] = np.empty((2, n))
+    if "steps" in want:
+        out["steps"] = np.empty(n, np.int32)
+    if "flags" in want:
+        out["flags"] = np.empty(n, np.uint8)
+    p = push_params(qm, dt, max_steps, axis, det_pos, hit_scale)
+    st = _ffi.PushStats()
+    check(lib.sr_particles_push(None if E is None else E._h, None if B is None else B._h, C.byref(p), n, ptr(s0),
+                                ptr(out.get("sf")), ptr(out.get("hits")), ptr(out.get("steps")), ptr(out.get("flags")),
+                                None if image is None else image._h, C.byref(st)))
+    out["stats"] = PushStats(float(st.kernel_ms), int(st.finished), int(st.unfinished), int(st.missed), int(st.deposited))
+    return out
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

@@ -25,7 +25,7 @@ class ScalarDomain:
             dims (int | 3 ints): number of nodes per axis
             ne_type (str): 'test_null' | 'test_slab' | 'test_linear_cos' | 'test_exponential_cos' | None
         """
-        self.ne = self.B = self.Te = self.Z = None
+        self.ne = self.B = self.Te = self.Z = self.E = None
         self.inv_brems, self.phaseshift, self.B_on = inv_brems, phaseshift, B_on
         if probing_direction not in ("x", "y", "z"):
             raise ValueError(f"probing_direction must be 'x', 'y' or 'z', got {probing_direction!r}")
@@ -120,6 +120,22 @@ class ScalarDomain:
 
     def external_B(self, B):
         self.B = B
+
+    def external_E(self, E):
+        """Load an (x_n, y_n, z_n, 3) grid of the electric field in V/m (no reference counterpart): what proton_radiograph
+        pushes its particles through beside B.  The tracer does not read it."""
+        E = np.asarray(E)
+        if E.shape != tuple(self.dims) + (3,):
+            raise ValueError(f"E has shape {E.shape}, the domain needs {tuple(self.dims) + (3,)}")
+        self.E = E
+
+    def proton_radiograph(self, source, det_pos, **kw):
+        """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
+        particles have crossed this domain's B (external_B / test_B) and E (external_E) (no reference counterpart): a
+        radiography.Radiograph.  Keywords: radiography.radiograph's."""
+        from ..radiography import radiograph
+
+        return radiograph(self, source, det_pos, **kw)
 
     def external_Te(self, Te, Te_min=1.0):
         self.Te = np.maximum(Te_min, Te)

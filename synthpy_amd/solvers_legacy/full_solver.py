@@ -78,6 +78,23 @@ class ScalarDomain:
         self.B = B
         self._aux_ready = False
 
+    def external_E(self, E):
+        """(nx, ny, nz, 3) grid of the electric field in V/m (no reference counterpart): what proton_radiograph pushes its
+        particles through beside B.  The tracer does not read it."""
+        E = np.asarray(E)
+        shape = (len(self.x), len(self.y), len(self.z), 3)
+        if E.shape != shape:
+            raise ValueError(f"E has shape {E.shape}, the domain needs {shape}")
+        self.E = E
+
+    def proton_radiograph(self, source, det_pos, **kw):
+        """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
+        particles have crossed this domain's B (external_B / test_B) and E (external_E) (no reference counterpart): a
+        radiography.Radiograph.  Keywords: radiography.radiograph's."""
+        from ..radiography import radiograph
+
+        return radiograph(self, source, det_pos, **kw)
+
     def external_Te(self, Te, Te_min=1.0):
         """(nx, ny, nz) grid of T_e in eV, floored at Te_min."""
         self.Te = np.maximum(Te_min, Te)
