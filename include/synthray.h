@@ -321,6 +321,67 @@ int sr_particles_push(const sr_field *E, const sr_field *B, const sr_push_params
                       int32_t *steps /* host (n) or NULL */, uint8_t *flags /* host (n) or NULL */,
                       sr_image *img /* SR_IMG_COUNTS or NULL */, sr_push_stats *stats /* or NULL */);
 
+/* ---- optical Thomson scattering: the spectral density function summed over scattering volumes ----------------
+ * No reference counterpart.  n_vol scattering volumes, each a quadrature of n_quad points p_q [m] with weights w_q [m] along the
+ * probe inside the collection cone, scatter a probe of wavelength lambda_i from unit direction ki (per volume) into the unit
+ * direction ks (per volume); the scattered power is evaluated at n_lambda wavelengths.  The model is non-relativistic and
+ * unmagnetised: Maxwellian electrons and ONE Maxwellian ion species (charge Z, mass number A) that share the flow V, vacuum
+ * wavenumbers -- valid for ne << n_crit (Sheffield; Froula et al.).  ne [m^-3], Te [eV], Ti [eV], Z are scalar sr_fields and V
+ * [m/s] a 3-vector sr_field on ONE grid (node coordinates compared bit for bit) and of one dtype.  Ti NULL: Ti = Te.  Z NULL: the
+ * uniform p->Z.  V NULL: no flow, nothing of V is read and the Doppler line reads wp = w.  thomson.hip is compiled with
+ * -ffp-contract=off: every operation below rounds on its own, in float64; sqrt and / are the correctly rounded ones, rint rounds
+ * half to even, exp is the device library's.
+ * Constants, each formed in float64 on the host exactly as written: c = 299792458.0, e = 1.602176634e-19, m_e = 9.1093837015e-31,
+ * m_p = 1.67262192369e-27, eps0 = 8.8541878128e-12, pi = 3.141592653589793; tpc = (2.0*pi)*c, ce = (2.0*e)/m_e,
+ * ci = (2.0*e)/(A*m_p), ee0 = e/eps0, SP = 1.7724538509055159 (sqrt(pi)), TSP = 3.5449077018110318, ISP = 0.5641895835477563.
+ *   volume m      cth = (ki0*ks0 + ki1*ks1) + ki2*ks2;  wi = tpc/lambda_i;  kin = wi/c
+ *   wavelength l  ws = tpc/lambda_l;  w = ws - wi;  ksc = ws/c;  k2 = (ksc*ksc + kin*kin) - ((2.0*ksc)*kin)*cth
+ *                 k = sqrt(k2);  rk = 1.0/k;  rk2 = 1.0/k2;  f_l = (1.0 + (2.0*w)/wi) * (c/(lambda_l*lambda_l))
+ *   point q       ne, Te, Ti, Z and the three components of V at p_q: sr_field_resample's cell / outside / blend rule (same corner
+ *                 order, u = 1 - w factors).  The point is DROPPED -- it adds nothing to P or to weight -- when p_q lies outside
+ *                 the box on any axis (a point on a face is inside; a NaN coordinate is outside), when ne <= 0, Te <= 0 or Ti <= 0,
+ *                 or when any gathered value is NaN.  Otherwise
+ *                   wn = w_q*ne;  ivte = 1.0/sqrt(ce*Te);  ivti = 1.0/sqrt(ci*Ti);  pe = (ne*ee0)/Te;  zt = (Z*Te)/Ti
+ *                   vs = (V0*ks0 + V1*ks1) + V2*ks2;  vi = (V0*ki0 + V1*ki1) + V2*ki2
+ *   sample (l, q) wp = w - (ksc*vs - kin*vi);  a = wp*rk;  xe = a*ivte;  xi = a*ivti;  al = pe*rk2;  az = al*zt
+ *                 (Fe, Ee) = D(xe);  (Fi, Ei) = D(xi)                                       (below)
+ *                 cer = al*(1.0 - (2.0*xe)*Fe);  cei = al*((SP*xe)*Ee);  cir = az*(1.0 - (2.0*xi)*Fi);  cii = az*((SP*xi)*Ei)
+ *                 er = (1.0 + cer) + cir;  ei = cei + cii;  ie2 = 1.0/(er*er + ei*ei)
+ *                 n1 = (1.0 + cir)*(1.0 + cir) + cii*cii;  n2 = cer*cer + cei*cei
+ *                 S = (TSP*rk) * (((n1*ie2)*Ee)*ivte + ((Z*(n2*ie2))*Ei)*ivti)
+ *               -- chi_e = alpha^2 W(xi_e), chi_i = alpha^2 (Z Te/Ti) W(xi_i), eps = 1 + chi_e + chi_i with alpha^2 = al and
+ *               W(x) = 1 - 2x F(x) + i sqrt(pi) x exp(-x^2), F Dawson's function.
+ *   D(x)          Dawson's function by Rybicki's sampling form with h = 0.25, and exp(-x^2):
+ *                   n0 = 2.0*rint(2.0*x);  xp = x - 0.25*n0;  g = exp(-(xp*xp));  p = exp(0.5*xp);  m = 1.0/p;  p2 = p*p;  m2 = m*m
+ *                   d0 = n0*n0;  s = 0;  for n = 1, 3, 5, ..., 25 in this order:
+ *                       s = s + C[n]*((p*(n0 - n) + m*(n0 + n))/(d0 - n*n));   p = p*p2;   m = m*m2
+ *                   F = (g*s)*ISP;   E = exp(-(x*x))
+ *                 -- the terms n and -n of sum_{n odd} C[n] e^{2 xp h n}/(n0 + n) over one denominator, the powers by repeated
+ *                 multiplication; C[n] = exp(-(n h)^2): 0.9394130628134758, 0.569782824730923, 0.2096113871510978,
+ *                 0.04677062238395898, 0.006329715427485747, 0.0005195746821548384, 2.586810022265412e-05, 7.811489408304491e-07,
+ *                 1.4307241918567688e-08, 1.5893910094516368e-10, 1.0709232382508077e-12, 4.37661850287085e-15,
+ *                 1.0848552640429378e-17.  Truncation at |n| <= 25 leaves less than 1e-16; three exp per D.
+ *   output        P[m][l] = (sum over the kept q, ascending, of wn*S) * f_l;   weight[m] = sum over the kept q, ascending, of wn
+ *                 -- P is (1/2pi) int ne S(k, w) dl (1 + 2w/wi) |dw/dlambda|; the caller multiplies by r_e^2 and the polarisation
+ *                 factor.  A volume whose points are all dropped gives exact zeros.  No atomics: a repeated call returns identical
+ *                 bits.
+ * pts (n_vol, n_quad, 3), wts (n_vol, n_quad), ki and ks (n_vol, 3), lambda (n_lambda), P (n_vol, n_lambda) and weight (n_vol) are
+ * HOST arrays, float64, C order.  *kernel_ms (may be NULL) is the HIP-event time of the kernel alone.
+ * Arguments are checked before the device is touched: a NULL p, pts, wts, ki, ks, lambda, P or weight; n_vol, n_quad or n_lambda
+ * below 0; lambda_i, A or an entry of lambda not finite and positive; a non-finite p->Z where the Z field is NULL; a direction
+ * that is not finite or whose squared length is further than 1e-12 from 1; ki == ks exactly, or cth >= 1 (k can then be 0); more
+ * than 2^31 - 1 workgroups; a NULL ne or Te; a field of the wrong n_comp; fields of differing dtypes or on grids that differ.
+ * n_vol == 0 or n_lambda == 0 succeeds and writes nothing; with n_quad == 0 every output is 0. */
+typedef struct {
+  double lambda_i;      /* probe wavelength [m] */
+  double A;             /* ion mass number (m_i = A*m_p) */
+  double Z;             /* the uniform ion charge where the Z field is NULL */
+} sr_thomson_params;
+int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *Z /* or NULL */,
+                     const sr_field *V /* or NULL */, const sr_thomson_params *p, int64_t n_vol, int32_t n_quad,
+                     const double *pts, const double *wts, const double *ki, const double *ks, int32_t n_lambda,
+                     const double *lambda, double *P, double *weight, double *kernel_ms);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

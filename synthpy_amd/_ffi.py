@@ -83,6 +83,10 @@ class PushStats(C.Structure):
 PUSH_UNFINISHED, PUSH_MISSED = 1, 2  # SR_PUSH_*
 
 
+class ThomsonParams(C.Structure):
+    _fields_ = [("lambda_i", C.c_double), ("A", C.c_double), ("Z", C.c_double)]
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -130,6 +134,8 @@ SYMBOLS = {
     "sr_field_emission_table": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(EmissionParams), _vp, _vp, _vp,
                                      C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
+    "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
+                              _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),
     "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),

@@ -1,0 +1,296 @@
+// Optical Thomson scattering: the spectral density function of a Maxwellian plasma summed over the quadrature points of each
+// scattering volume (sr_field_thomson; include/synthray.h states the rule every sample follows, operation for operation).  No
+// reference counterpart.
+//
+// One workgroup of 256 lanes per (volume, tile of 256 wavelengths); a lane owns one wavelength and keeps its sum in a register.
+// The volume's quadrature points are taken in chunks of up to 64.  Per chunk the first wavefront gathers -- one point per lane,
+// the trilinear blend of ne, Te, Ti, Z and V -- reduces the point to the numbers that do not depend on the wavelength (w*ne,
+// 1/v_te, 1/v_ti, ne e/(eps0 Te), Z Te/Ti, Z, V.ks, V.ki, a kept flag) and puts them in LDS; after a barrier every lane walks the
+// chunk from LDS, all lanes at the same address (a broadcast), and evaluates the sample: two plasma-dispersion values, 6 exp and
+// 31 divisions of float64 arithmetic with no memory traffic.  The gathers therefore happen once per point, not once per sample.
+// No atomics; the points are summed in ascending order, so a repeated call returns identical bits.  k_thomson is instantiated per
+// (V given, float32 / float64 source).  Compiled with -ffp-contract=off: products and sums round separately, as the NumPy
+// restatement's do (tests/test_thomson.py).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int kChunk = 64;   // quadrature points staged in LDS at a time: one wavefront gathers them
+constexpr int kTile = 256;   // wavelengths per workgroup, one per lane
+
+constexpr double kE = 1.602176634e-19, kMe = 9.1093837015e-31, kMp = 1.67262192369e-27, kEps0 = 8.8541878128e-12;
+constexpr double kPi = 3.141592653589793;
+constexpr double kSP = 1.7724538509055159, kTSP = 3.5449077018110318, kISP = 0.5641895835477563;
+
+struct ThomsonArgs {
+  const void *ne, *Te, *Ti, *Z, *V;  // Ti, Z, V may be nullptr
+  const double *g[3];                // node coordinates
+  int n[3];
+  double inv_h[3], lo[3], hi[3];
+  const double *pts;     // (n_vol, nq, 3)
+  const double *wts;     // (n_vol, nq)
+  const double *ki, *ks; // (n_vol, 3)
+  const double *lam;     // (n_lambda)
+  double *P;             // (n_vol, n_lambda)
+  double *weight;        // (n_vol)
+  int nq, n_lambda, n_tiles;
+  double Zu;             // the uniform Z
+  double tpc, ce, ci, ee0, wi, kin;
+};
+
+// one scalar at the cell (ci, cj, ck) with the blend of sr_field_resample's rule; nc: components per node, c: the one wanted
+template <typename T>
+__device__ __forceinline__ double blend(const T *__restrict__ src, int nc, int c, int64_t sx, int64_t sy, int ci, int cj, int ck,
+                                        double ux, double wx, double w00, double w01, double w10, double w11) {
+  const T *lo = src + (((int64_t)ci * sx + (int64_t)cj * sy + (int64_t)ck) * nc + c);
+  const T *hi = lo + sx * nc;
+  const int64_t ry = sy * nc;
+  const double s0 = (((double)lo[0] * w00 + (double)lo[nc] * w01) + (double)lo[ry] * w10) + (double)lo[ry + nc] * w11;
+  const double s1 = (((double)hi[0] * w00 + (double)hi[nc] * w01) + (double)hi[ry] * w10) + (double)hi[ry + nc] * w11;
+  return ux * s0 + wx * s1;
+}
+
+// D(x) of the rule: Dawson's function F and E = exp(-x^2)
+__device__ __forceinline__ void dawson(double x, double &F, double &E) {
+  constexpr double C[13] = {0.9394130628134758,     0.569782824730923,      0.2096113871510978,     0.04677062238395898,
+                            0.006329715427485747,   0.0005195746821548384,  2.586810022265412e-05,  7.811489408304491e-07,
+                            1.4307241918567688e-08, 1.5893910094516368e-10, 1.0709232382508077e-12, 4.37661850287085e-15,
+                            1.0848552640429378e-17};
+  const double n0 = 2.0 * rint(2.0 * x);
+  const double xp = x - 0.25 * n0;
+  const double g = exp(-(xp * xp));
+  double p = exp(0.5 * xp);
+  double m = 1.0 / p;
+  const double p2 = p * p, m2 = m * m, d0 = n0 * n0;
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < 13; ++j) {
+    const double n = (double)(2 * j + 1);
+    s = s + C[j] * ((p * (n0 - n) + m * (n0 + n)) / (d0 - n * n));
+    p = p * p2;
+    m = m * m2;
+  }
+  F = (g * s) * kISP;
+  E = exp(-(x * x));
+}
+
+template <bool HAS_V, typename T>
+__global__ void __launch_bounds__(256) k_thomson(ThomsonArgs A) {
+  __shared__ double s_wn[kChunk], s_ivte[kChunk], s_ivti[kChunk], s_pe[kChunk], s_zt[kChunk], s_z[kChunk], s_vs[kChunk], s_vi[kChunk];
+  __shared__ int s_keep[kChunk];
+  const int64_t vol = blockIdx.x / (unsigned)A.n_tiles;
+  const int tile = (int)(blockIdx.x % (unsigned)A.n_tiles);
+  const int l = tile * kTile + (int)threadIdx.x;
+  const bool active = l < A.n_lambda;
+  const double ki0 = A.ki[vol * 3], ki1 = A.ki[vol * 3 + 1], ki2 = A.ki[vol * 3 + 2];
+  const double ks0 = A.ks[vol * 3], ks1 = A.ks[vol * 3 + 1], ks2 = A.ks[vol * 3 + 2];
+  const double cth = (ki0 * ks0 + ki1 * ks1) + ki2 * ks2;
+  const double wi = A.wi, kin = A.kin;
+  // the wavelength's constants; an idle lane of the last tile takes the probe's own wavelength and stores nothing
+  const double lam = active ? A.lam[l] : A.tpc / wi;
+  const double ws = A.tpc / lam;
+  const double w = ws - wi;
+  const double ksc = ws / sr::kC;
+  const double k2 = (ksc * ksc + kin * kin) - ((2.0 * ksc) * kin) * cth;
+  const double k = sqrt(k2);
+  const double rk = 1.0 / k, rk2 = 1.0 / k2;
+  const double pre = kTSP * rk;
+
+  const int64_t sy = A.n[2], sx = (int64_t)A.n[1] * sy;
+  double acc = 0.0, wsum = 0.0;
+  for (int q0 = 0; q0 < A.nq; q0 += kChunk) {
+    const int cnt = min(kChunk, A.nq - q0);
+    __syncthreads();  // the chunk before this one has been read by every lane
+    if ((int)threadIdx.x < cnt) {
+      const int j = (int)threadIdx.x;
+      const int64_t q = vol * A.nq + q0 + j;
+      const double px = A.pts[q * 3], py = A.pts[q * 3 + 1], pz = A.pts[q * 3 + 2];
+      int ci = 0, cj = 0, ck = 0;
+      double wx = 0, wy = 0, wz = 0;
+      const bool in_x = sr::locate_in<true>(A.g[0], A.n[0], A.inv_h[0], A.lo[0], A.hi[0], px, ci, wx);
+      const bool in_y = sr::locate_in<true>(A.g[1], A.n[1], A.inv_h[1], A.lo[1], A.hi[1], py, cj, wy);
+      const bool in_z = sr::locate_in<true>(A.g[2], A.n[2], A.inv_h[2], A.lo[2], A.hi[2], pz, ck, wz);
+      bool keep = false;
+      if (in_x && in_y && in_z) {
+        const double ux = 1.0 - wx, uy = 1.0 - wy, uz = 1.0 - wz;
+        const double w00 = uy * uz, w01 = uy * wz, w10 = wy * uz, w11 = wy * wz;
+        const double ne = blend<T>(static_cast<const T *>(A.ne), 1, 0, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11);
+        const double Te = blend<T>(static_cast<const T *>(A.Te), 1, 0, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11);
+        const double Ti = A.Ti ? blend<T>(static_cast<const T *>(A.Ti), 1, 0, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11) : Te;
+        const double Z = A.Z ? blend<T>(static_cast<const T *>(A.Z), 1, 0, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11) : A.Zu;
+        double vs = 0.0, vi = 0.0;
+        if (HAS_V) {
+          const T *fV = static_cast<const T *>(A.V);
+          const double V0 = blend<T>(fV, 3, 0, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11);
+          const double V1 = blend<T>(fV, 3, 1, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11);
+          const double V2 = blend<T>(fV, 3, 2, sx, sy, ci, cj, ck, ux, wx, w00, w01, w10, w11);
+          vs = (V0 * ks0 + V1 * ks1) + V2 * ks2;
+          vi = (V0 * ki0 + V1 * ki1) + V2 * ki2;
+        }
+        // ne, Te, Ti > 0 is false for a NaN; a NaN component of V makes vs and vi NaN (the directions are finite)
+        keep = ne > 0.0 && Te > 0.0 && Ti > 0.0 && Z == Z && vs == vs && vi == vi;
+        if (keep) {
+          s_wn[j] = A.wts[q] * ne;
+          s_ivte[j] = 1.0 / sqrt(A.ce * Te);
+          s_ivti[j] = 1.0 / sqrt(A.ci * Ti);
+          s_pe[j] = (ne * A.ee0) / Te;
+          s_zt[j] = (Z * Te) / Ti;
+          s_z[j] = Z;
+          s_vs[j] = vs;
+          s_vi[j] = vi;
+        }
+      }
+      s_keep[j] = keep ? 1 : 0;
+    }
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) {
+      if (!s_keep[j]) continue;  // the same for every lane
+      const double wn = s_wn[j];
+      wsum = wsum + wn;
+      if (!active) continue;  // the last tile's idle lanes: a wavefront made of them skips the arithmetic
+      double wp = w;
+      if (HAS_V) wp = w - (ksc * s_vs[j] - kin * s_vi[j]);
+      const double ivte = s_ivte[j], ivti = s_ivti[j];
+      const double a = wp * rk;
+      const double xe = a * ivte, xi = a * ivti;
+      const double al = s_pe[j] * rk2;
+      const double az = al * s_zt[j];
+      double Fe, Ee, Fi, Ei;
+      dawson(xe, Fe, Ee);
+      dawson(xi, Fi, Ei);
+      const double cer = al * (1.0 - (2.0 * xe) * Fe), cei = al * ((kSP * xe) * Ee);
+      const double cir = az * (1.0 - (2.0 * xi) * Fi), cii = az * ((kSP * xi) * Ei);
+      const double er = (1.0 + cer) + cir, ei = cei + cii;
+      const double ie2 = 1.0 / (er * er + ei * ei);
+      const double n1 = (1.0 + cir) * (1.0 + cir) + cii * cii;
+      const double n2 = cer * cer + cei * cei;
+      const double S = pre * (((n1 * ie2) * Ee) * ivte + ((s_z[j] * (n2 * ie2)) * Ei) * ivti);
+      acc = acc + wn * S;
+    }
+  }
+  if (active) A.P[vol * A.n_lambda + l] = acc * ((1.0 + (2.0 * w) / wi) * (sr::kC / (lam * lam)));
+  if (tile == 0 && threadIdx.x == 0) A.weight[vol] = wsum;
+}
+
+template <typename T>
+void launch(bool has_v, unsigned grid, hipStream_t st, const ThomsonArgs &A) {
+  sr::with_flags([&](auto v) { hipLaunchKernelGGL((k_thomson<v.value, T>), dim3(grid), dim3(256), 0, st, A); }, has_v);
+}
+
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+bool positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+}  // namespace
+
+extern "C" int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr_field *Ti, const sr_field *Z, const sr_field *V,
+                                const sr_thomson_params *p, int64_t n_vol, int32_t n_quad, const double *pts, const double *wts,
+                                const double *ki, const double *ks, int32_t n_lambda, const double *lambda, double *P,
+                                double *weight, double *kernel_ms) {
+  SR_CHECK(p != nullptr && pts != nullptr && wts != nullptr && ki != nullptr && ks != nullptr && lambda != nullptr && P != nullptr &&
+               weight != nullptr,
+           "sr_field_thomson: NULL argument (p, pts, wts, ki, ks, lambda, P or weight)");
+  SR_CHECK(n_vol >= 0 && n_quad >= 0 && n_lambda >= 0, "sr_field_thomson: counts must not be negative, got n_vol %lld, n_quad %d, n_lambda %d",
+           (long long)n_vol, n_quad, n_lambda);
+  SR_CHECK(positive(p->lambda_i), "sr_field_thomson: lambda_i must be finite and positive");
+  SR_CHECK(positive(p->A), "sr_field_thomson: A must be finite and positive");
+  SR_CHECK(Z != nullptr || std::isfinite(p->Z), "sr_field_thomson: non-finite uniform Z");
+  for (int32_t l = 0; l < n_lambda; ++l)
+    SR_CHECK(positive(lambda[l]), "sr_field_thomson: lambda[%d] must be finite and positive", l);
+  for (int64_t m = 0; m < n_vol; ++m) {
+    const double *a = ki + 3 * m, *b = ks + 3 * m;
+    const double na = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], nb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    SR_CHECK(std::fabs(na - 1.0) <= 1e-12, "sr_field_thomson: ki of volume %lld is not a finite unit vector", (long long)m);
+    SR_CHECK(std::fabs(nb - 1.0) <= 1e-12, "sr_field_thomson: ks of volume %lld is not a finite unit vector", (long long)m);
+    const double cth = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+    SR_CHECK(!(a[0] == b[0] && a[1] == b[1] && a[2] == b[2]) && cth < 1.0,
+             "sr_field_thomson: ki equals ks in volume %lld (no scattering wavevector)", (long long)m);
+  }
+  const int64_t n_tiles = ((int64_t)n_lambda + kTile - 1) / kTile;
+  SR_CHECK(n_tiles == 0 || n_vol <= (int64_t)2147483647 / n_tiles, "sr_field_thomson: n_vol x wavelength tiles exceeds 2^31 - 1 workgroups");
+  SR_CHECK(ne != nullptr && Te != nullptr, "sr_field_thomson: NULL field (ne or Te)");
+  const sr_field *fs[5] = {ne, Te, Ti, Z, V};
+  const char *names[5] = {"ne", "Te", "Ti", "Z", "V"};
+  for (int f = 0; f < 5; ++f) {
+    if (!fs[f]) continue;
+    SR_CHECK(fs[f]->n_comp == (f == 4 ? 3 : 1), "sr_field_thomson: %s must have n_comp == %d", names[f], f == 4 ? 3 : 1);
+    SR_CHECK(fs[f]->is_f64 == ne->is_f64, "sr_field_thomson: ne and %s differ in dtype", names[f]);
+    for (int k = 0; k < 3; ++k)
+      SR_CHECK(fs[f]->n[k] == ne->n[k] && memcmp(fs[f]->hg[k].data(), ne->hg[k].data(), sizeof(double) * ne->n[k]) == 0,
+               "sr_field_thomson: the grids of ne and %s differ on axis %d", names[f], k);
+  }
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n_vol == 0 || n_lambda == 0) return SR_OK;
+  if (int rc = sr::ensure_init()) return rc;
+  sr::Context &c = sr::ctx();
+  hipStream_t st = c.stream;
+
+  // one scratch block: pts | wts | ki | ks | lambda | P | weight
+  const size_t nv = (size_t)n_vol, nq = (size_t)n_quad, nl = (size_t)n_lambda;
+  const size_t b_pts = up256(sizeof(double) * 3 * nv * nq), b_wts = up256(sizeof(double) * nv * nq), b_dir = up256(sizeof(double) * 3 * nv);
+  const size_t b_lam = up256(sizeof(double) * nl), b_P = up256(sizeof(double) * nv * nl), b_w = up256(sizeof(double) * nv);
+  char *block = static_cast<char *>(sr::scratch(b_pts + b_wts + 2 * b_dir + b_lam + b_P + b_w));
+  if (!block) return SR_ERR_HIP;
+  char *d_pts = block, *d_wts = d_pts + b_pts, *d_ki = d_wts + b_wts, *d_ks = d_ki + b_dir, *d_lam = d_ks + b_dir;
+  char *d_P = d_lam + b_lam, *d_w = d_P + b_P;
+  ThomsonArgs A{};
+  A.ne = ne->data;
+  A.Te = Te->data;
+  A.Ti = Ti ? Ti->data : nullptr;
+  A.Z = Z ? Z->data : nullptr;
+  A.V = V ? V->data : nullptr;
+  for (int k = 0; k < 3; ++k) {
+    A.g[k] = ne->g[k];
+    A.n[k] = ne->n[k];
+    A.inv_h[k] = ne->inv_h[k];
+    A.lo[k] = ne->hg[k].front();
+    A.hi[k] = ne->hg[k].back();
+  }
+  A.pts = reinterpret_cast<const double *>(d_pts);
+  A.wts = reinterpret_cast<const double *>(d_wts);
+  A.ki = reinterpret_cast<const double *>(d_ki);
+  A.ks = reinterpret_cast<const double *>(d_ks);
+  A.lam = reinterpret_cast<const double *>(d_lam);
+  A.P = reinterpret_cast<double *>(d_P);
+  A.weight = reinterpret_cast<double *>(d_w);
+  A.nq = n_quad;
+  A.n_lambda = n_lambda;
+  A.n_tiles = (int)n_tiles;
+  A.Zu = Z ? 0.0 : p->Z;
+  A.tpc = (2.0 * kPi) * sr::kC;
+  A.ce = (2.0 * kE) / kMe;
+  A.ci = (2.0 * kE) / (p->A * kMp);
+  A.ee0 = kE / kEps0;
+  A.wi = A.tpc / p->lambda_i;
+  A.kin = A.wi / sr::kC;
+
+  if (nq) {
+    if (int rc = sr::upload_sync(d_pts, pts, sizeof(double) * 3 * nv * nq, st)) return rc;
+    if (int rc = sr::upload_sync(d_wts, wts, sizeof(double) * nv * nq, st)) return rc;
+  }
+  SR_HIP(hipMemcpyAsync(d_ki, ki, sizeof(double) * 3 * nv, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_ks, ks, sizeof(double) * 3 * nv, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_lam, lambda, sizeof(double) * nl, hipMemcpyHostToDevice, st));
+  SR_HIP(hipEventRecord(c.ev[0], st));
+  const unsigned grid = (unsigned)(n_vol * n_tiles);
+  if (ne->is_f64)
+    launch<double>(V != nullptr, grid, st, A);
+  else
+    launch<float>(V != nullptr, grid, st, A);
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], st));
+  SR_HIP(hipMemcpyAsync(P, d_P, sizeof(double) * nv * nl, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(weight, d_w, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  if (kernel_ms) {
+    float ms = 0.f;
+    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    *kernel_ms = ms;
+  }
+  sr::scratch_trim();
+  return SR_OK;
+}

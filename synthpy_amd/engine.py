@@ -578,6 +578,49 @@ def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, im
     return out
 
 
+def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavelengths):
+    """The Thomson-scattering spectral density summed over the quadrature of each scattering volume (sr_field_thomson;
+    include/synthray.h states the rule): (P (M, n_lambda), weight (M)) float64, P = (1/2pi) sum_q w_q ne_q S_q (1 + 2w/wi)
+    |dw/dlambda| and weight = sum_q w_q ne_q over the points that lie inside the grid with ne, Te, Ti > 0.  ne [m^-3] and Te [eV]
+    are scalar Fields; Ti [eV] a Field or None (Ti = Te); Z a Field or a float (a uniform charge, which is not read); V [m/s] a
+    vector Field or None (no flow) -- all on one grid and of one dtype.  lambda_i: the probe's wavelength [m]; ion_mass: the mass
+    number A; points (M, Nq, 3) [m] and weights (M, Nq) [m]; ki, ks: the unit probe and collection directions, (3,) or (M, 3);
+    wavelengths (n_lambda) [m].  ne.last_kernel_ms keeps the kernel's time."""
+    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
+        raise ValueError("ne must be an open engine.Field")
+    handles = [ne._h]
+    for name, a, other in (("Te", Te, ""), ("Ti", Ti, " or None"), ("Z", Z, " or a number"), ("V", V, " or None")):
+        if isinstance(a, Field):
+            if not getattr(a, "_h", None):
+                raise ValueError(f"the field {name} has been closed")
+            handles.append(a._h)
+        elif (other == " or None" and a is None) or (name == "Z" and a is not None and np.ndim(a) == 0):
+            handles.append(None)
+        else:
+            raise ValueError(f"{name} must be an open engine.Field{other}")
+    points, weights = f64(points), f64(weights)
+    if points.ndim != 3 or points.shape[2] != 3 or weights.shape != points.shape[:2]:
+        raise ValueError(f"points must be (M, Nq, 3) and weights (M, Nq), got {points.shape} and {weights.shape}")
+    M, nq = weights.shape
+    dirs = []
+    for name, d in (("ki", ki), ("ks", ks)):
+        d = f64(d)
+        if d.shape not in ((3,), (M, 3)):
+            raise ValueError(f"{name} must have shape (3,) or ({M}, 3), got {d.shape}")
+        dirs.append(np.ascontiguousarray(np.broadcast_to(d, (M, 3))))
+    lam = f64(wavelengths)
+    if lam.ndim != 1:
+        raise ValueError(f"wavelengths must be one-dimensional, got shape {lam.shape}")
+    p = _ffi.ThomsonParams()
+    p.lambda_i, p.A, p.Z = float(lambda_i), float(ion_mass), 0.0 if isinstance(Z, Field) else float(Z)
+    P, weight = np.zeros((M, len(lam))), np.zeros(M)
+    ms = C.c_double(0.0)
+    check(lib.sr_field_thomson(*handles, C.byref(p), M, nq, ptr(points), ptr(weights), ptr(dirs[0]), ptr(dirs[1]), len(lam), ptr(lam),
+                               ptr(P), ptr(weight), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    return P, weight
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

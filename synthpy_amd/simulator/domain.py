@@ -25,7 +25,7 @@ class ScalarDomain:
             dims (int | 3 ints): number of nodes per axis
             ne_type (str): 'test_null' | 'test_slab' | 'test_linear_cos' | 'test_exponential_cos' | None
         """
-        self.ne = self.B = self.Te = self.Z = self.E = None
+        self.ne = self.B = self.Te = self.Z = self.E = self.Ti = self.V = None
         self.inv_brems, self.phaseshift, self.B_on = inv_brems, phaseshift, B_on
         if probing_direction not in ("x", "y", "z"):
             raise ValueError(f"probing_direction must be 'x', 'y' or 'z', got {probing_direction!r}")
@@ -142,6 +142,24 @@ class ScalarDomain:
 
     def external_Z(self, Z):
         self.Z = Z
+
+    def external_Ti(self, Ti, Ti_min=1.0):
+        """Load the ion temperature in eV, floored at Ti_min (no reference counterpart): what thomson_scattering reads beside
+        Te.  Without it Ti = Te.  The tracer does not read it."""
+        self.Ti = np.maximum(Ti_min, Ti)
+
+    def external_V(self, V):
+        """Load an (x_n, y_n, z_n, 3) grid of the flow velocity in m/s (no reference counterpart): the Doppler shift of
+        thomson_scattering.  The tracer does not read it."""
+        self.V = V
+
+    def thomson_scattering(self, probe, collection, wavelengths, ion_mass, **kw):
+        """The optical Thomson-scattering spectra of this domain's ne, Te (external_Te), Z (external_Z), Ti (external_Ti) and V
+        (external_V) for a thomson.Probe and a thomson.Collection at `wavelengths` [m], the ion's mass number ion_mass (no
+        reference counterpart): a thomson.ThomsonSpectra.  Keywords: thomson.spectra's."""
+        from ..thomson import spectra
+
+        return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
 
     def line_integrals(self, lwl=1064e-9, regions=None):
         """The line integrals of the domain along its probing axis (no reference counterpart): a projection.Projection

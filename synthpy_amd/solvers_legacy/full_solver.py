@@ -105,6 +105,24 @@ class ScalarDomain:
         self.Z = Z
         self._aux_ready = False
 
+    def external_Ti(self, Ti, Ti_min=1.0):
+        """(nx, ny, nz) grid of T_i in eV, floored at Ti_min (no reference counterpart): what thomson_scattering reads beside Te.
+        Without it Ti = Te.  The tracer does not read it."""
+        self.Ti = np.maximum(Ti_min, Ti)
+
+    def external_V(self, V):
+        """(nx, ny, nz, 3) grid of the flow velocity in m/s (no reference counterpart): the Doppler shift of thomson_scattering.
+        The tracer does not read it."""
+        self.V = V
+
+    def thomson_scattering(self, probe, collection, wavelengths, ion_mass, **kw):
+        """The optical Thomson-scattering spectra of this domain's ne, Te (external_Te), Z (external_Z), Ti (external_Ti) and V
+        (external_V) for a thomson.Probe and a thomson.Collection at `wavelengths` [m], the ion's mass number ion_mass (no
+        reference counterpart): a thomson.ThomsonSpectra.  Keywords: thomson.spectra's."""
+        from ..thomson import spectra
+
+        return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
+
     def test_B(self, Bmax=1.0):
         self.B = np.zeros((len(self.x), len(self.y), len(self.z), 3))
         self.B[:, :, :, 2] = self._full(Bmax * self.XX / self.extent)

@@ -1,0 +1,244 @@
+"""Optical Thomson scattering spectra of a domain (no reference counterpart).
+
+    probe = thomson.Probe(532e-9, origin=(0, 0, -5e-3), direction=(0, 0, 1), polarisation=(1, 0, 0))
+    coll = thomson.Collection(points, direction=(0, 1, 0), length=100e-6, n_quad=8, beam_radius=50e-6)
+    sp = domain.thomson_scattering(probe, coll, wavelengths, ion_mass=12)      # or thomson.spectra(domain, probe, coll, ...)
+    sp.power, sp.weight, sp.theta, sp.alpha
+
+Each scattering volume is a quadrature along the probe (and across it) about one of the collection's points; the GPU gathers
+ne, Te, Ti, Z and the flow V at every quadrature point and sums the spectral density function S(k, w) of a Maxwellian plasma over
+them, per wavelength (engine.thomson -> sr_field_thomson; include/synthray.h states the rule).  Validity: non-relativistic,
+unmagnetised, Maxwellian electrons and one Maxwellian ion species sharing the flow, vacuum wavenumbers (ne << n_crit), no probe
+absorption or refraction, no collection optics beyond one direction per volume.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import engine
+
+E_CHARGE = engine.E_CHARGE    # C
+EPS0 = 8.8541878128e-12       # F/m (CODATA 2018)
+R_E = 2.8179403262e-15        # m, the classical electron radius (CODATA 2018)
+
+# the 7-point rule of degree 5 on the unit disc (Abramowitz & Stegun 25.4.61): the centre and a hexagon of radius sqrt(2/3);
+# the weights are fractions of the disc's area
+_DISC = np.array([[0.0, 0.0]] + [[np.sqrt(2.0 / 3.0) * np.cos(k * np.pi / 3), np.sqrt(2.0 / 3.0) * np.sin(k * np.pi / 3)]
+                                 for k in range(6)])
+_DISC_W = np.array([0.25] + [0.125] * 6)
+
+
+def _unit(v, name):
+    v = np.asarray(v, np.float64)
+    if v.shape[-1:] != (3,) or v.ndim > 2 or not np.all(np.isfinite(v)):
+        raise ValueError(f"{name} must be finite and of shape (3,) or (M, 3), got shape {v.shape}")
+    n = np.sqrt(np.sum(v * v, axis=-1, keepdims=True))
+    if np.any(n == 0.0):
+        raise ValueError(f"{name} has zero length")
+    return v / n
+
+
+class Probe:
+    """The probe beam: wavelength [m], a point `origin` [m] on its axis, its direction (normalised here) and, optionally, its
+    linear polarisation (a vector perpendicular to the direction to 1e-6, normalised here; None: the polarisation factor is 1)."""
+
+    def __init__(self, wavelength, origin, direction, polarisation=None):
+        self.wavelength = float(wavelength)
+        if not (np.isfinite(self.wavelength) and self.wavelength > 0):
+            raise ValueError(f"wavelength must be finite and positive, got {wavelength!r}")
+        self.origin = np.asarray(origin, np.float64)
+        if self.origin.shape != (3,) or not np.all(np.isfinite(self.origin)):
+            raise ValueError("origin must be three finite numbers")
+        self.direction = _unit(direction, "direction")
+        if self.direction.shape != (3,):
+            raise ValueError("a probe has one direction (3,)")
+        self.polarisation = None
+        if polarisation is not None:
+            e = _unit(polarisation, "polarisation")
+            if e.shape != (3,) or abs(float(e @ self.direction)) > 1e-6:
+                raise ValueError("polarisation must be one vector perpendicular to the probe's direction")
+            self.polarisation = e
+
+
+class Collection:
+    """The scattering volumes: `points` (M, 3) [m], their centres, seen along the unit `direction` (3,) or (M, 3) (from the
+    plasma to the collection optic).  The quadrature of a volume is n_quad Gauss-Legendre nodes along the probe's direction over
+    `length` [m] centred on the point, weights in metres (they sum to `length`); with beam_radius > 0 [m] times the 7-point
+    disc rule of degree 5 across the beam, weights as fractions of the disc (7 n_quad points, a top-hat beam).  quadrature =
+    (points (M, Nq, 3), weights (M, Nq)) gives the points and weights [m] of every volume directly instead."""
+
+    def __init__(self, points, direction, length=None, n_quad=None, beam_radius=0.0, *, quadrature=None):
+        self.points = np.asarray(points, np.float64)
+        if self.points.ndim != 2 or self.points.shape[1] != 3 or not np.all(np.isfinite(self.points)):
+            raise ValueError(f"points must be finite and of shape (M, 3), got {self.points.shape}")
+        M = len(self.points)
+        d = _unit(direction, "direction")
+        if d.shape not in ((3,), (M, 3)):
+            raise ValueError(f"direction must have shape (3,) or ({M}, 3), got {d.shape}")
+        self.direction = np.ascontiguousarray(np.broadcast_to(d, (M, 3)))
+        self._given = None
+        if quadrature is not None:
+            if length is not None or n_quad is not None or beam_radius:
+                raise ValueError("give either quadrature or length, n_quad and beam_radius")
+            pts, wts = (np.asarray(a, np.float64) for a in quadrature)
+            if pts.ndim != 3 or pts.shape[0] != M or pts.shape[2] != 3 or wts.shape != pts.shape[:2]:
+                raise ValueError(f"quadrature must be (points ({M}, Nq, 3), weights ({M}, Nq)), got {pts.shape} and {wts.shape}")
+            if not np.all(np.isfinite(wts)):
+                raise ValueError("quadrature weights must be finite")
+            self._given = (np.ascontiguousarray(pts), np.ascontiguousarray(wts))
+            return
+        if length is None or n_quad is None:
+            raise ValueError("length and n_quad are needed (or quadrature)")
+        self.length, self.n_quad, self.beam_radius = float(length), int(n_quad), float(beam_radius)
+        if not (np.isfinite(self.length) and self.length > 0):
+            raise ValueError(f"length must be finite and positive, got {length!r}")
+        if self.n_quad < 1:
+            raise ValueError(f"n_quad must be at least 1, got {n_quad!r}")
+        if not (np.isfinite(self.beam_radius) and self.beam_radius >= 0):
+            raise ValueError(f"beam_radius must be finite and not negative, got {beam_radius!r}")
+
+    def quadrature(self, probe):
+        """(points (M, Nq, 3), weights (M, Nq)) for `probe`."""
+        if self._given is not None:
+            return self._given
+        t, w = np.polynomial.legendre.leggauss(self.n_quad)
+        d = probe.direction
+        along = (0.5 * self.length * t)[:, None] * d[None, :]                      # (n_quad, 3)
+        wts = 0.5 * self.length * w
+        if self.beam_radius > 0:
+            a = np.eye(3)[int(np.argmin(np.abs(d)))]
+            e1 = np.cross(d, a)
+            e1 /= np.sqrt(e1 @ e1)
+            e2 = np.cross(d, e1)
+            across = self.beam_radius * (_DISC[:, :1] * e1[None, :] + _DISC[:, 1:] * e2[None, :])   # (7, 3)
+            along = (along[:, None, :] + across[None, :, :]).reshape(-1, 3)
+            wts = (wts[:, None] * _DISC_W[None, :]).ravel()
+        pts = self.points[:, None, :] + along[None, :, :]
+        return np.ascontiguousarray(pts), np.ascontiguousarray(np.broadcast_to(wts, pts.shape[:2]))
+
+
+@dataclass
+class ThomsonSpectra:
+    wavelengths: np.ndarray   # (n_lambda) [m]
+    power: np.ndarray         # (M, n_lambda): scattered energy per incident energy, per steradian and per metre of wavelength
+    weight: np.ndarray        # (M): sum_q w_q ne_q over the points that scatter [m^-2]
+    theta: np.ndarray         # (M): the scattering angle [rad]
+    alpha: np.ndarray         # (M): 1/(k lambda_D) at the volume's centre and the probe's wavelength; NaN outside the plasma
+    kernel_ms: float = 0.0    # HIP-event time of the kernel
+
+
+def instrument_convolve(power, wavelengths, fwhm):
+    """`power` (..., n_lambda) with a Gaussian instrument function of full width at half maximum `fwhm` [m] applied along the
+    last axis: a normalised kernel on the wavelength grid, which must be uniform (ValueError otherwise).  What a sample spreads
+    onto the grid adds up to the sample, also next to the ends, so the sum over the grid is kept."""
+    lam = np.asarray(wavelengths, np.float64)
+    power = np.asarray(power, np.float64)
+    fwhm = float(fwhm)
+    if not (np.isfinite(fwhm) and fwhm > 0):
+        raise ValueError(f"instrument_fwhm must be finite and positive, got {fwhm!r}")
+    n = len(lam)
+    if n < 2:
+        return power.copy()
+    d = np.diff(lam)
+    if not np.all(np.abs(d - d[0]) <= 1e-9 * abs(d[0])) or d[0] == 0:
+        raise ValueError("the instrument function needs a uniform wavelength grid")
+    sigma = fwhm / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+    J = int(min(n - 1, np.ceil(8.5 * sigma / abs(d[0]))))  # beyond 8.5 sigma the kernel is below 2^-52 of its peak
+    g = np.exp(-0.5 * (np.arange(-J, J + 1) * d[0] / sigma) ** 2)
+    norm = np.convolve(np.ones(n), g, "full")[J:J + n]
+    flat = power.reshape(-1, n)
+    out = np.stack([np.convolve(row / norm, g, "full")[J:J + n] for row in flat]) if len(flat) else flat.copy()
+    return out.reshape(power.shape)
+
+
+def _at(domain, arrays, points):
+    """The trilinear values of the 3-D `arrays` at `points` (M, 3) on the host (NaN outside the grid): the volume centres."""
+    g = [np.float64(np.float32(a)) for a in (domain.x, domain.y, domain.z)]
+    inside = np.ones(len(points), bool)
+    cells, ws = [], []
+    for k in range(3):
+        p = points[:, k]
+        inside &= (p >= g[k][0]) & (p <= g[k][-1])
+        i = np.clip(np.searchsorted(g[k], p, side="right") - 1, 0, len(g[k]) - 2)
+        cells.append(i)
+        ws.append((np.clip(p, g[k][0], g[k][-1]) - g[k][i]) / (g[k][i + 1] - g[k][i]))
+    out = []
+    for a in arrays:
+        v = np.zeros(len(points))
+        for di in (0, 1):
+            for dj in (0, 1):
+                for dk in (0, 1):
+                    wgt = (ws[0] if di else 1 - ws[0]) * (ws[1] if dj else 1 - ws[1]) * (ws[2] if dk else 1 - ws[2])
+                    v += wgt * np.float64(a[cells[0] + di, cells[1] + dj, cells[2] + dk])
+        out.append(np.where(inside, v, np.nan))
+    return out
+
+
+def spectra(domain, probe, collection, wavelengths, ion_mass, instrument_fwhm=None, fields=None):
+    """The Thomson-scattering spectra of `domain` -- ne, Te (external_Te), Z (external_Z; an array or a number), Ti
+    (external_Ti; without it Ti = Te) and the flow V (external_V; without it none) -- for `probe` and the scattering volumes of
+    `collection` at `wavelengths` [m], the ion's mass number ion_mass: a ThomsonSpectra with
+        power = r_e^2 (1 - (ks . e)^2) P        (the polarisation factor is 1 when the probe has no polarisation)
+    P engine.thomson's, in scattered energy per incident energy, per steradian and per metre of wavelength.  instrument_fwhm
+    [m]: a Gaussian instrument function applied on the host (instrument_convolve; a uniform grid).  fields: an
+    orientation.SourceFields of the domain whose uploads are reused across calls (a fit loop, a sweep)."""
+    from .orientation import SourceFields
+
+    if not isinstance(probe, Probe) or not isinstance(collection, Collection):
+        raise ValueError("probe must be a thomson.Probe and collection a thomson.Collection")
+    ne, Te, Z = getattr(domain, "ne", None), getattr(domain, "Te", None), getattr(domain, "Z", None)
+    if ne is None or Te is None or Z is None:
+        raise ValueError("the domain needs ne, Te (external_Te) and Z (external_Z)")
+    Ti, V = getattr(domain, "Ti", None), getattr(domain, "V", None)
+    if fields is not None and fields.domain is not domain:
+        raise ValueError("fields holds the fields of another domain")
+    lam = np.asarray(wavelengths, np.float64)
+    if lam.ndim != 1 or not np.all(np.isfinite(lam)) or np.any(lam <= 0):
+        raise ValueError("wavelengths must be one-dimensional, finite and positive")
+    ion_mass = float(ion_mass)
+    if not (np.isfinite(ion_mass) and ion_mass > 0):
+        raise ValueError(f"ion_mass must be finite and positive, got {ion_mass!r}")
+    ks, ki = collection.direction, probe.direction
+    if np.any(np.all(ks == ki[None, :], axis=1)):
+        raise ValueError("a collection direction equals the probe's direction: no scattering wavevector")
+    shape = np.shape(ne)
+    named = {"ne": np.asarray(ne), "Te": np.asarray(Te) if np.ndim(Te) == 3 else np.full(shape, float(Te)),
+             "Ti": None if Ti is None else (np.asarray(Ti) if np.ndim(Ti) == 3 else np.full(shape, float(Ti))),
+             "Z": np.asarray(Z) if np.ndim(Z) == 3 else None, "V": None if V is None else np.asarray(V)}
+    if named["V"] is not None and named["V"].shape != tuple(shape) + (3,):
+        raise ValueError(f"V has shape {named['V'].shape}, the domain needs {tuple(shape) + (3,)}")
+    # the kernel reads every field in one dtype: float32 when all are, else float64 (uploaded under a name of its own)
+    single = all(a.dtype == np.float32 for a in named.values() if a is not None)
+    pts, wts = collection.quadrature(probe)
+    own = fields is None
+    src = SourceFields(domain) if own else fields
+
+    def field(name):
+        a = named[name]
+        if a is None:
+            return None
+        if single or a.dtype == np.float64:
+            return src.get(name, a)
+        return src.get(name + ":float64", np.asarray(a, np.float64))
+
+    try:
+        f_ne = field("ne")
+        P, weight = engine.thomson(f_ne, field("Te"), field("Ti"), field("Z") if named["Z"] is not None else float(Z), field("V"),
+                                   probe.wavelength, ion_mass, pts, wts, ki, ks, lam)
+        kernel_ms = f_ne.last_kernel_ms
+    finally:
+        if own:
+            src.close()
+    pol = 1.0 if probe.polarisation is None else 1.0 - (ks @ probe.polarisation) ** 2
+    power = (R_E * R_E * pol * np.ones(len(ks)))[:, None] * P
+    if instrument_fwhm is not None:
+        power = instrument_convolve(power, lam, instrument_fwhm)
+    cth = np.clip(ks @ ki, -1.0, 1.0)
+    theta = np.arccos(cth)
+    k = 2.0 * (2.0 * np.pi / probe.wavelength) * np.sin(0.5 * theta)
+    ne_c, Te_c = _at(domain, (named["ne"], named["Te"]), collection.points)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        alpha = np.where((ne_c > 0) & (Te_c > 0), np.sqrt(ne_c * E_CHARGE / (EPS0 * Te_c)) / k, np.nan)
+    return ThomsonSpectra(lam, power, weight, theta, alpha, kernel_ms)
