@@ -382,6 +382,88 @@ int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr_field *Ti 
                      const double *pts, const double *wts, const double *ki, const double *ks, int32_t n_lambda,
                      const double *lambda, double *P, double *weight, double *kernel_ms);
 
+/* ---- wave optics: a paraxial split-step march of a complex field through a domain ----------
+ * No counterpart in the reference's sources (its authors compare the tracer with a CPU beam-propagation library,
+ * evaluation/c.f._diffraction).  A complex scalar field U on a uniform lateral FRAME of mu x mv pixels is carried through the
+ * electron density of a domain along grid axis `axis`: a thin phase (and absorption) screen per cell between two node planes and a
+ * free-space (Fresnel) step between the screens' mid-planes, by 2-D transforms on the frame.  The field varies as
+ * exp(+i(kz - wt)), the carrier exp(i k0 z) is dropped, so a plasma screen (n < 1) has NEGATIVE phase.  Paraxial and scalar; the
+ * frame is periodic (leave a guard band, or absorb at the edges with wu, wv); nothing is reflected where ne approaches critical.
+ * ne [m^-3], and optionally Te [eV] and Z, are scalar sr_fields on ONE grid (node coordinates compared bit for bit) and of one
+ * dtype.  Te NULL: no absorption, Z is not looked at.  Z NULL: the uniform p->Z.  wave.hip is compiled with -ffp-contract=off:
+ * every operation below rounds on its own, in float64; the transforms are hipFFT's (Z2Z, unnormalised), cos, sin, exp and log the
+ * device library's.
+ *   frame     pixel (i, j), i < mu, j < mv, sits at (pu, pv) = (u0 + i*du, v0 + j*dv) on the two lateral axes (u, v) in x < y < z
+ *             order (axis 0: y, z; 1: x, z; 2: x, y), i*du and j*dv being float64 products.  U is (mu, mv) complex128, C order.
+ *   planes    g = the float64 values of the float32 nodes on `axis`; toward = +1 marches planes 0 -> n-1, -1 the reverse.  Cell c,
+ *             c = 0 .. n_c - 1 with n_c = n - 1, lies between consecutive planes k, k' of the march, h_c = |g[k'] - g[k]|.
+ *             d_0 = 0.5*h_0;  d_c = 0.5*(h_{c-1} + h_c);  d_{n_c} = 0.5*h_{n_c - 1}.
+ *   sequence  for c = 0 .. n_c - 1: D(d_c), then S_c; finally D(d_{n_c}).  U_out is the field on the last plane of the march.
+ *   D(d)      forward transform; per mode (i, j), with pd = pi_l*d formed once:
+ *               th = -(pd * (fu[i]*fu[i] + fv[j]*fv[j]));  co = cos(th);  si = sin(th)
+ *               (re, im) <- ((re*co - im*si) * s, (re*si + im*co) * s),   s = 1.0/((double)mu*(double)mv)
+ *             -- four products, two sums, then the scale; inverse transform.  fu, fv: the frame's spatial frequencies [1/m]
+ *             (np.fft.fftfreq(mu, du), np.fft.fftfreq(mv, dv)); pi_l = pi*lambda.
+ *   S_c       per pixel: on each lateral axis sr_field_resample's `cell` rule gives the cell (iu | iv) and the weight (wu_ | wv_)
+ *             of pu | pv; a pixel with pu or pv below the first or above the last node of its axis is VACUUM (ne = 0, alpha = 0
+ *             on both planes; no field is read); a pixel exactly on the last node is inside.  With uu = 1 - wu_, uv = 1 - wv_,
+ *             w00 = uu*uv, w01 = uu*wv_, w10 = wu_*uv, w11 = wu_*wv_ and f(a, b) the node (iu + a, iv + b) of a node plane
+ *             widened to float64, a field's value on that plane is sr_field_resample's blend of ONE node plane,
+ *               ((f(0,0)*w00 + f(0,1)*w01) + f(1,0)*w10) + f(1,1)*w11                       (ne, and with Te given: Te, Z).
+ *             index   ne <= 0: m = 0.  Otherwise wp = 5.64e4*sqrt(ne*1e-6);  r = wp/omega;  q = r*r;  q >= 1.0 on either plane:
+ *                     the pixel is OPAQUE for this screen, U <- (0, 0).  Otherwise m = -q/(1.0 + sqrt(1.0 - q))  ( = n - 1 ).
+ *             phase   ph = (k0*h_c) * (0.5*(m_k + m_k'))
+ *             absorb  with Te: alpha per plane by sr_field_emission's `node` rule on the plane's (ne, Te, Z) and this omega;
+ *                     dtau = (0.5*(alpha_k + alpha_k'))*h_c;  a = exp(-(0.5*dtau)).  Without Te: a = 1.0.
+ *             update  co = cos(ph);  si = sin(ph);  t = (a*wu[i])*wv[j];  (re, im) <- ((re*co - im*si)*t, (re*si + im*co)*t)
+ *             -- wu, wv: the edge absorber's windows (NULL: 1.0).  A NaN node makes NaN the pixels whose cell holds it, and after
+ *             the next transform the whole field: it is not guarded against.
+ *   power[c]  (may be NULL; n_c values) the sum of re*re + im*im over the pixels after S_c, in a FIXED order: pixels in C order
+ *             in groups of 1024, a group's sum by one fixed tree (per lane four pixels 256 apart, a shuffle tree over each
+ *             wavefront, the four wavefronts in order), the groups' sums added in ascending order.  No atomics: a repeated call
+ *             returns identical bits, U_out included.
+ * fu (mu), fv (mv), wu (mu), wv (mv), U_in and U_out (mu, mv, 2) are HOST arrays, float64.  kernel_ms (may be NULL) points to
+ * THREE values: the HIP-event time of the whole march [ms], and -- only with p->time_parts != 0, which puts an event between all
+ * the launches; 0 otherwise -- the part of it spent in hipFFT and the part in the library's own two kernels.
+ * Arguments are checked before the device is touched: a NULL p, fu, fv, U_in or U_out; mu or mv below 2, or mu*mv above 2^30;
+ * lambda, omega, k0, pi_l, du or dv not finite and positive; a non-finite u0 or v0; toward not +-1; axis outside 0..2; a NULL ne;
+ * a vector field; fields of differing dtypes or on grids that differ; with Te given and Z NULL, a non-finite p->Z. */
+typedef struct {
+  int32_t axis, toward;           /* 0 | 1 | 2;  +1 | -1 */
+  int32_t mu, mv;                 /* the frame */
+  double u0, du, v0, dv;          /* pixel (i, j) at (u0 + i*du, v0 + j*dv) [m] */
+  double lambda;                  /* vacuum wavelength [m] */
+  double omega, k0, pi_l;         /* 2 pi c/lambda, omega/c, pi*lambda: formed by the host */
+  double Z;                       /* the uniform ion charge where Te is given and the Z field is NULL */
+  int32_t time_parts, reserved;   /* != 0: kernel_ms[1], [2] are measured */
+} sr_wave_params;
+int sr_field_wave(const sr_field *ne, const sr_field *Te /* or NULL */, const sr_field *Z /* or NULL */, const sr_wave_params *p,
+                  const double *fu, const double *fv, const double *wu /* or NULL */, const double *wv /* or NULL */,
+                  const double *U_in, double *U_out, double *power /* or NULL */, double *kernel_ms /* [3] or NULL */);
+/* The exit field on the detector of an ideal one-to-one relay with a mask in the Fourier plane of a lens of focal length f and a
+ * defocus: forward transform; per mode (i, j), with pd = pi_l*defocus and s = 1.0/((double)mu*(double)mv),
+ *     th = -(pd * (fu[i]*fu[i] + fv[j]*fv[j]));  (re, im) <- ((re*cos(th) - im*sin(th))*s, (re*sin(th) + im*cos(th))*s)
+ *     xf = lf*fu[i];  yf = lf*fv[j];  r2 = xf*xf + yf*yf                 (lf = lambda*f: the mode's place in the focal plane)
+ *     (re, im) <- (0.0, 0.0) where a mask that is switched on rejects (xf, yf), as the ray optics do (SR_OP_CIRC_AP, _CIRC_STOP,
+ *     _KNIFE):  SR_WAVE_APERTURE: r2 > Ra*Ra;  SR_WAVE_STOP: r2 < Rs*Rs;  SR_WAVE_KNIFE: with x = xf (knife_axis 0) or yf (1),
+ *     x > knife_offset where knife_dir > 0, x < knife_offset where knife_dir < 0
+ * -- inverse transform.  Without a mask and with defocus 0 the output is the input to the transforms' rounding; defocus = d on its
+ * own is D(d) of sr_field_wave.  U_in, U_out: HOST (mu, mv, 2) float64.  *kernel_ms (may be NULL): the HIP-event time.  Checked
+ * before the device is touched: a NULL p, fu, fv, U_in or U_out; mu or mv below 2, or mu*mv above 2^30; non-finite pi_l, defocus
+ * or lf; flags outside the three bits; with its mask on, a non-finite Ra, Rs or knife_offset, knife_axis not 0 | 1, knife_dir 0
+ * or NaN. */
+#define SR_WAVE_APERTURE 1
+#define SR_WAVE_STOP 2
+#define SR_WAVE_KNIFE 4
+typedef struct {
+  int32_t mu, mv, flags, knife_axis;
+  double pi_l, defocus, lf;       /* pi*lambda [m], defocus [m], lambda*f [m^2] */
+  double Ra, Rs;                  /* aperture and stop radii in the focal plane [m] */
+  double knife_offset, knife_dir; /* [m]; > 0 rejects above the offset, < 0 below */
+} sr_wave_image_params;
+int sr_wave_image(const sr_wave_image_params *p, const double *fu, const double *fv, const double *U_in, double *U_out,
+                  double *kernel_ms);
+
 /* ---- the step before the path: volume synthesis ------------------------------------
  * gaussian3D.domain_fft (src/field_generator/gaussian3D.py:215-271): out = Re(ifftn(noise * amp)) [/ max|.| when
  * normalise], noise complex128 (n0, n1, n2) interleaved (the caller's seeded np.random draws), amp = sqrt(S(k))

@@ -87,6 +87,21 @@ class ThomsonParams(C.Structure):
     _fields_ = [("lambda_i", C.c_double), ("A", C.c_double), ("Z", C.c_double)]
 
 
+class WaveParams(C.Structure):
+    _fields_ = [("axis", C.c_int32), ("toward", C.c_int32), ("mu", C.c_int32), ("mv", C.c_int32), ("u0", C.c_double),
+                ("du", C.c_double), ("v0", C.c_double), ("dv", C.c_double), ("lambda_", C.c_double), ("omega", C.c_double),
+                ("k0", C.c_double), ("pi_l", C.c_double), ("Z", C.c_double), ("time_parts", C.c_int32), ("reserved", C.c_int32)]
+
+
+WAVE_APERTURE, WAVE_STOP, WAVE_KNIFE = 1, 2, 4  # SR_WAVE_*
+
+
+class WaveImageParams(C.Structure):
+    _fields_ = [("mu", C.c_int32), ("mv", C.c_int32), ("flags", C.c_int32), ("knife_axis", C.c_int32), ("pi_l", C.c_double),
+                ("defocus", C.c_double), ("lf", C.c_double), ("Ra", C.c_double), ("Rs", C.c_double), ("knife_offset", C.c_double),
+                ("knife_dir", C.c_double)]
+
+
 class DepositStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("deposited", C.c_int64), ("retraced", C.c_int64)]
 
@@ -136,6 +151,8 @@ SYMBOLS = {
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_wave": (_i, [_vp, _vp, _vp, C.POINTER(WaveParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_wave_image": (_i, [C.POINTER(WaveImageParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),
     "sr_field_destroy": (None, [_vp]),
     "sr_trace": (_i, [_vp, _vp, _i64, C.POINTER(TraceParams), _vp, _vp, _vp, C.POINTER(TraceStats)]),

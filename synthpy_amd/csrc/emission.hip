@@ -1,37 +1,12 @@
 // Self-emission images: emission with self-absorption along a grid axis (sr_field_emission; include/synthray.h states the rule
 // every node, cell and column follows, operation for operation).  The march -- k_emission_z, k_emission_xy, the cell, the host's
-// staging -- is emission_march.inc, shared with emission_table.hip; this unit holds the NRL node and the entry.  No LDS.
+// staging -- is emission_march.inc, shared with emission_table.hip; the NRL node is nrl_node.inc, shared with wave.hip; this unit
+// holds the node's policy and the entry.  No LDS.
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_emission.py).
 #include "emission_march.inc"
 
 namespace {
 
-// alpha [1/m] and S of one node: what every band shares, then one band.  A dark node's zeros are selected at the end; an early
-// return here left the callers' per-band arrays in scratch.
-struct NodeTerms {
-  bool dark;  // Te <= 0 or ne <= 0: alpha = S = 0
-  double Te, n, wp, L, num, zc, it;
-};
-__device__ __forceinline__ NodeTerms node_terms(double ne, double Te, double Z) {
-  NodeTerms t;
-  const double q = sqrt(Te);
-  t.dark = Te <= 0.0 || ne <= 0.0;
-  t.Te = Te;
-  t.n = ne * 1e-6;
-  t.wp = 5.64e4 * sqrt(t.n);
-  t.L = nmax(Z * 1.602176634e-19 / Te, 2.760428269727312e-10 / q);
-  t.num = 4.19e5 * q;
-  t.zc = (3.1e-5 * Z) * sr::kC;
-  t.it = 1.0 / (Te * q);
-  return t;
-}
-__device__ __forceinline__ void node_band(const NodeTerms &t, double omega, double e_ph, double c_omega, double &al, double &S) {
-  const double w = nmax(t.wp, omega);
-  const double lnL = nmax(2.0, log(t.num / (w * t.L)));
-  const double r = t.n / omega;
-  al = t.dark ? 0.0 : (((t.zc * (r * r)) * lnL) * t.it) / sr::kC;
-  S = t.dark ? 0.0 : c_omega / expm1(e_ph / t.Te);
-}
 struct NrlNode {
   struct Args {};
   static constexpr int kXYBlock = 64;

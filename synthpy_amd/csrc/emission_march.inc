@@ -38,8 +38,7 @@ struct EmArgs {
   double uTe, uZ;
 };
 
-// numpy's maximum: a NaN operand gives NaN
-__device__ __forceinline__ double nmax(double a, double b) { return (a > b || a != a) ? a : b; }
+#include "nrl_node.inc"  // nmax and the NRL node (shared with wave.hip)
 
 template <typename T, bool HAS_TE, bool HAS_Z, int NB>
 __device__ __forceinline__ void load_node(const EmArgs &A, int64_t at, double &ne, double &Te, double &Z) {

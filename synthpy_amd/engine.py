@@ -621,6 +621,100 @@ def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavel
     return P, weight
 
 
+def wave_params(frame, shape, lambda_, axis, toward=+1, Z=0.0, time_parts=False):
+    """sr_wave_params for a frame (u0, du, v0, dv) [m] of shape (mu, mv) and the vacuum wavelength lambda_ [m]: omega = 2 pi c /
+    lambda, k0 = omega / c and pi_l = pi * lambda are formed here, as emission_params forms its constants."""
+    u0, du, v0, dv = (float(a) for a in frame)
+    p = _ffi.WaveParams()
+    p.axis, p.toward, p.mu, p.mv = int(axis), int(toward), int(shape[0]), int(shape[1])
+    p.u0, p.du, p.v0, p.dv = u0, du, v0, dv
+    lam = float(lambda_)
+    p.lambda_ = lam
+    p.omega = 2 * np.pi * c / lam if lam != 0 else np.inf
+    p.k0 = p.omega / c
+    p.pi_l = np.pi * lam
+    p.Z, p.time_parts, p.reserved = float(Z), 1 if time_parts else 0, 0
+    return p
+
+
+def _complex_field(U, name="U"):
+    U = np.ascontiguousarray(U, dtype=np.complex128)
+    if U.ndim != 2:
+        raise ValueError(f"{name} must be a two-dimensional complex array (mu, mv), got shape {U.shape}")
+    return U
+
+
+def wave(ne, Te, Z, U, frame, lambda_, axis, toward=+1, absorber=None, want_power=True, time_parts=False):
+    """The paraxial split-step march of the complex field U (mu, mv) through the electron density `ne` along grid axis `axis`
+    (sr_field_wave; include/synthray.h states the rule): (U_out (mu, mv) complex128 on the last plane of the march, power (n_cells)
+    float64 = sum |U|^2 after every screen, or None).  ne [m^-3] is a scalar Field; Te [eV] a Field on the same grid and of the same
+    dtype, or None (no absorption); Z a Field or a number (a uniform charge, which is not read), looked at only with Te.  frame =
+    (u0, du, v0, dv) [m]: pixel (i, j) sits at (u0 + i du, v0 + j dv) on the lateral axes in x < y < z order.  lambda_: the vacuum
+    wavelength [m].  toward = +1 marches from the first node plane to the last.  absorber: (wu (mu), wv (mv)) windows applied with
+    every screen (wave.edge_absorber), or None.  The field varies as exp(+i(kz - wt)) without its carrier: plasma retards the phase.
+    ne.last_kernel_ms keeps the march's HIP-event time.  time_parts=True puts an event between all the launches and returns a
+    third value, (hipFFT ms, own kernels ms): a measurement mode (tools/wave_rate.py)."""
+    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
+        raise ValueError("ne must be an open engine.Field")
+    handles = []
+    for name, a in (("Te", Te), ("Z", Z)):
+        if isinstance(a, Field):
+            if not getattr(a, "_h", None):
+                raise ValueError(f"the field {name} has been closed")
+            handles.append(a._h)
+        elif a is None or np.ndim(a) == 0:
+            handles.append(None)
+        else:
+            raise ValueError(f"{name} must be an open engine.Field, a number or None")
+    U = _complex_field(U)
+    mu, mv = U.shape
+    p = wave_params(frame, U.shape, lambda_, axis, toward, 0.0 if isinstance(Z, Field) or Z is None else float(Z), time_parts)
+    fu, fv = np.fft.fftfreq(mu, p.du if p.du else 1.0), np.fft.fftfreq(mv, p.dv if p.dv else 1.0)
+    wu = wv = None
+    if absorber is not None:
+        wu, wv = f64(absorber[0]), f64(absorber[1])
+        if wu.shape != (mu,) or wv.shape != (mv,):
+            raise ValueError(f"absorber must be (wu ({mu},), wv ({mv},)), got {wu.shape} and {wv.shape}")
+    out = np.empty_like(U)
+    n_cells = ne.shape[p.axis] - 1 if 0 <= p.axis <= 2 else 1
+    power = np.zeros(n_cells) if want_power else None
+    ms = (C.c_double * 3)(0.0, 0.0, 0.0)
+    check(lib.sr_field_wave(ne._h, handles[0], handles[1], C.byref(p), ptr(fu), ptr(fv), ptr(wu), ptr(wv), ptr(U), ptr(out), ptr(power), ms))
+    ne.last_kernel_ms = float(ms[0])
+    if time_parts:
+        return out, power, (float(ms[1]), float(ms[2]))
+    return out, power
+
+
+def wave_image(U, du, dv, lambda_, f=1.0, defocus=0.0, aperture=None, stop=None, knife=None):
+    """The field U (mu, mv) on a frame of pitch (du, dv) [m] relayed one-to-one to the detector through a mask in the Fourier plane
+    of a lens of focal length f [m], with a defocus [m] (sr_wave_image; include/synthray.h states the rule): (mu, mv) complex128.
+    aperture: radius [m] outside which the focal plane is blocked; stop: radius [m] inside which it is; knife: (axis 0 | 1 -- u | v
+    --, offset [m], direction > 0: blocked above the offset, < 0: below).  The inequalities are the ray optics' (strict)."""
+    U = _complex_field(U)
+    mu, mv = U.shape
+    p = _ffi.WaveImageParams()
+    p.mu, p.mv, p.flags, p.knife_axis = mu, mv, 0, 0
+    p.pi_l, p.defocus, p.lf = np.pi * float(lambda_), float(defocus), float(lambda_) * float(f)
+    if aperture is not None:
+        p.flags |= _ffi.WAVE_APERTURE
+        p.Ra = float(aperture)
+    if stop is not None:
+        p.flags |= _ffi.WAVE_STOP
+        p.Rs = float(stop)
+    if knife is not None:
+        p.flags |= _ffi.WAVE_KNIFE
+        p.knife_axis, p.knife_offset, p.knife_dir = int(knife[0]), float(knife[1]), float(knife[2])
+    du, dv = float(du), float(dv)
+    if not (du > 0 and dv > 0 and np.isfinite(du) and np.isfinite(dv)):
+        raise ValueError(f"du and dv must be finite and positive, got {du!r} and {dv!r}")
+    fu, fv = np.fft.fftfreq(mu, du), np.fft.fftfreq(mv, dv)
+    out = np.empty_like(U)
+    ms = C.c_double(0.0)
+    check(lib.sr_wave_image(C.byref(p), ptr(fu), ptr(fv), ptr(U), ptr(out), C.byref(ms)))
+    return out, float(ms.value)
+
+
 class _PinnedBlock:
     """One page-locked host block (sr_host_alloc) under a NumPy array: the array's base; goes back to the pool when the
     last array over it is collected."""

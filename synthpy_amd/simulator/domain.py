@@ -161,6 +161,13 @@ class ScalarDomain:
 
         return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
 
+    def wave_propagate(self, source, **kw):
+        """The wave-optics march of a wave.Source through this domain's ne along its probing_direction (no reference
+        counterpart): a wave.WaveField on the exit plane.  Keywords: wave.propagate's."""
+        from ..wave import propagate
+
+        return propagate(self, source, **kw)
+
     def line_integrals(self, lwl=1064e-9, regions=None):
         """The line integrals of the domain along its probing axis (no reference counterpart): a projection.Projection
         with the phase, deflection, areal density, absorption and rotation maps a straight ray would gather."""

@@ -123,6 +123,13 @@ class ScalarDomain:
 
         return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
 
+    def wave_propagate(self, source, **kw):
+        """The wave-optics march of a wave.Source through this domain's ne along its probing_direction (no reference
+        counterpart): a wave.WaveField on the exit plane.  Keywords: wave.propagate's."""
+        from ..wave import propagate
+
+        return propagate(self, source, **kw)
+
     def test_B(self, Bmax=1.0):
         self.B = np.zeros((len(self.x), len(self.y), len(self.z), 3))
         self.B[:, :, :, 2] = self._full(Bmax * self.XX / self.extent)
