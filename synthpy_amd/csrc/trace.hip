@@ -45,11 +45,14 @@ __device__ __forceinline__ int64_t koff(const VolDev &V, int k) { return (int64_
 
 // LDS-DMA of one kilobyte: the wavefront's 64 lanes x 16 bytes from src + lane_off (src wave-uniform, lane_off the lane's own
 // 32 bits) into LDS at byte address dst + lane * 16 (dst wave-uniform), no register in between.  The caller waits (vmcnt) before
-// anybody reads the kilobyte.  In a loop that moves src on, the compiler keeps src + lane_off as a per-lane 64-bit pointer and
-// adds to it with one v_lshl_add_u64 per step.  SR_TILE_EXP_DMA_SADDR: the scalar-base + 32-bit-lane-offset form by an inline
-// statement instead, no vector instruction at all (M0, the destination, is the compiler's register: written in the statement
-// that reads it and put back, one wait state before the DMA) -- in the records kernel's step loop (trace_tile.inc) three vector
-// instructions fewer per step, 23 scalar ones more, and no faster (profiles/r06_step_loop.txt): not the default.
+// anybody reads the kilobyte.  The builtin takes the scalar-base + 32-bit-lane-offset form (global_load_lds_dwordx4 v, s[n:n+1],
+// no vector instruction) where the instruction selection sees `uniform pointer + zero-extended 32-bit value` in the DMA's own
+// block.  In a loop that moves src on it does not by itself: strength reduction folds lane_off into a per-lane 64-bit pointer
+// (one v_lshl_add_u64 per step and source), and a lane_off hoisted out of the loop arrives already widened.  The records
+// kernel's step loop (trace_tile.inc) therefore passes src and lane_off through an empty asm statement next to the call.
+// SR_TILE_EXP_DMA_SADDR: the same form by an inline statement (M0, the destination, is the compiler's register: written in the
+// statement that reads it and put back, one wait state before the DMA) -- 23 scalar instructions more per step than the builtin
+// needs (profiles/r06_step_loop.txt): a diagnostic, not the default.
 __device__ __forceinline__ void lds_dma16(const char *src, unsigned lane_off, unsigned dst) {
 #ifdef SR_TILE_EXP_DMA_SADDR
   unsigned keep;

@@ -18,7 +18,7 @@
 //    node planes' records are ready-made in HBM (sr_volume::R: k_build_records forms them once per volume with
 //    coefs_from_corners -- 128 bytes per node plane and lateral cell, 17 GB for 512^3) and come into the ring by LDS-DMA: at a
 //    step's start each of the four wavefronts asks for two tile columns of node plane k+2 (2 x global_load_lds_dwordx4: one
-//    kilobyte each, no register, no conversion; the sources are running pointers, one node plane further per step), at its end it adds them
+//    kilobyte each, no register, no conversion; the sources are running pointers in scalar registers, one node plane further per step), at its end it adds them
 //    to its own two columns of plane k+1 for the mid record (the same lane-linear kilobytes: 4 ds_read_b128 + 4 v_add_f64 + 2
 //    ds_write_b128, every lane busy).  No producer wavefront: the four wavefronts of a workgroup do the same work.  LDS
 //    layout: see kRecColD (piece-major column blocks 1104 bytes apart: the DMA writes a wavefront's 64 x 16 bytes contiguously, so
@@ -104,8 +104,20 @@ struct TileArgs {
 constexpr int kRecColD = (1024 + 80) / 8;  // doubles from one column block to the next
 __host__ __device__ constexpr int tile_rec(bool aux, bool rec = false) { return aux ? 38 : (rec ? 16 : 18); }
 
+// The tile's node tables, one per lateral axis: entry n = {g[n], 1 / (g[n+1] - g[n])} of the tile's n-th node, 16 bytes, so that a
+// cell's g[n], r[n] and g[n+1] are ONE address with immediate offsets.  Entries kTabLo below node 0 and kTabHi from node T on are
+// SENTINELS that make the cell search's acceptance test g[n] <= q < g[n+1] fail without a clamp of the index (relocate2):
+//   n < 0: {+inf, 1} -- q - g[n] is negative (or NaN);   n = T: {g[T], 1}, and n > T: {-inf, 1} -- q < g[n+1] is false.
+// A ray that failed the test is lost to the launch, but finishes its step: each of the step's further searches may move its index
+// on by one (three more at the most), so there are four sentinels on either side and every read stays inside the table.
+constexpr int kTabLo = 4, kTabHi = 5;
+__host__ __device__ constexpr int tile_tab_entries(int t) { return kTabLo + t + kTabHi; }
+// REC: the tables lie where those of the largest tile (8 x 8) would, so that their LDS addresses are constants of the kernel
+__host__ __device__ constexpr int tile_tab_doubles(int tb, int tc) { return 2 * tile_tab_entries(tb) + 2 * tile_tab_entries(tc) + 4; }  // + 8 words for the placement
+static_assert(tile_tab_doubles(8, 8) * sizeof(double) <= 1024, "the records kernel's table head is one KiB");
+
 __host__ __device__ inline size_t tile_lds_bytes(const TileGeom &g, int seg_steps, bool aux = false, bool rec = false) {
-  const size_t tables = (size_t)(2 * (g.tb + 1) + 2 * (g.tc + 1) + 4);  // node coordinates and reciprocal widths of the tile, + 8 words for its placement
+  const size_t tables = (size_t)(rec ? tile_tab_doubles(8, 8) : tile_tab_doubles(g.tb, g.tc));
   (void)seg_steps;  // (the step table was in LDS until the constants came by scalar loads)
   // REC: the records start on a 1 KiB boundary of the workgroup's LDS (a tile column of one slot = one DMA's kilobyte)
   const size_t head = rec ? (((tables * sizeof(double)) + 1023) & ~(size_t)1023) / sizeof(double) : ((tables + 1) & ~(size_t)1);
@@ -291,16 +303,22 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   const TraceArgs &A = T.A;
   const VolDev &V = A.V;
   const int TB = T.G.tb, TC = T.G.tc, NC = TB * TC;
-  // LDS: [tgb TB+1][trb TB+1][tgc TC+1][trc TC+1][placement: 8 ints][records: 5 slots x NC x kTileRec]
-  double *tgb = lds, *trb = tgb + (TB + 1), *tgc = trb + (TB + 1), *trc = tgc + (TC + 1);
-  int *org = reinterpret_cast<int *>(trc + (TC + 1));
-  const size_t tables = REC ? ((((size_t)(2 * (TB + 1) + 2 * (TC + 1) + 4) * sizeof(double)) + 1023) & ~(size_t)1023) / sizeof(double)
-                            : ((size_t)(2 * (TB + 1) + 2 * (TC + 1) + 4) + 1) & ~(size_t)1;
+  // LDS: [node table b: {g, r} x (TB + 9)][node table c: {g, r} x (TC + 9)][placement: 8 ints][records: 5 slots x NC x kTileRec]
+  // (tile_tab_entries: sentinels on both sides; REC: laid out for 8 x 8, so that both tables' addresses are constants)
+  const int tab_nb = tile_tab_entries(REC ? 8 : TB), tab_nc = tile_tab_entries(REC ? 8 : TC);
+  int *org = reinterpret_cast<int *>(lds + 2 * (tab_nb + tab_nc));
+  const size_t tables = REC ? 1024 / sizeof(double) : ((size_t)tile_tab_doubles(TB, TC) + 1) & ~(size_t)1;
+  // LDS byte addresses of the two tables' entries of node 0 (low word of the flat address)
+  // (taken from the LDS pointer itself: the flat pointer's low word comes with a null check that the compiler folds late)
+  const unsigned tab_b = (unsigned)(uintptr_t)(__attribute__((address_space(3))) double *)lds + kTabLo * 16u;
+  const unsigned tab_c = tab_b + (unsigned)tab_nb * 16u;
   double *recs = lds + tables;                       // 16-byte aligned (REC: 1 KiB)
   const int slot_d = REC ? TC * kRecColD : NC * kTileRec;  // doubles per slot
   // where the record of tile cell (tb, tc) starts inside a slot, in doubles -- REC: in BYTES (its piece 0; the others follow 128
   // bytes apart): the records kernel keeps every LDS address of the step loop as a byte address (see slot_h below)
-  auto cell_off = [&](int b_, int c_) { return REC ? c_ * (kRecColD * 8) + b_ * 16 : (c_ * TB + b_) * kTileRec; };
+  // (REC: the column pitch is a constant and the indices are small: a 24-bit multiply-add, where the full 32-bit product is a
+  // quarter-rate instruction)
+  auto cell_off = [&](int b_, int c_) { return REC ? __mul24(c_, kRecColD * 8) + b_ * 16 : (c_ * TB + b_) * kTileRec; };
   // slots 0..2: node planes (k % 3); 3, 4: mid-step planes (3 + k % 2)
 
   const unsigned chunk = gridDim.x / 8;
@@ -415,19 +433,32 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     return min(max(lo - (t - (hi - lo + 1)) / 2, 0), cells - t);
   };
   const int ob = place(org[0], org[2], org[4], org[6], TB, V.nb - 1), oc = place(org[1], org[3], org[5], org[7], TC, V.nc - 1);
-  for (int t = threadIdx.x; t <= TB; t += blockDim.x) {
-    tgb[t] = V.g[1][ob + t];
-    trb[t] = t < TB ? V.rg[1][ob + t] : 0.0;
-  }
-  for (int t = threadIdx.x; t <= TC; t += blockDim.x) {
-    tgc[t] = V.g[2][oc + t];
-    trc[t] = t < TC ? V.rg[2][oc + t] : 0.0;
-  }
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef __attribute__((address_space(3))) d2 *lds_d2_t;
+  // the node tables: nodes 0 .. t of the tile between their sentinels (tile_tab_entries)
+  auto fill_table = [&](unsigned tab, int t_cells, const double *g, const double *rg, int o) {
+    for (int t = threadIdx.x; t < tile_tab_entries(t_cells); t += blockDim.x) {
+      const int n = t - kTabLo;
+      d2 e = {n < 0 ? __builtin_inf() : -__builtin_inf(), 1.0};
+      if (n >= 0 && n <= t_cells) e.x = g[o + n];
+      if (n >= 0 && n < t_cells) e.y = rg[o + n];
+      ((lds_d2_t)(uintptr_t)tab)[n] = e;
+    }
+  };
+  fill_table(tab_b, TB, V.g[1], V.rg[1], ob);
+  fill_table(tab_c, TC, V.g[2], V.rg[2], oc);
   __syncthreads();
   int tb = cb - ob, tc = cc - oc;
   if (alive && !(tb >= 0 && tb < TB && tc >= 0 && tc < TC)) alive = false;  // the workgroup's rays span more than a tile
   if (!alive) tb = tc = 0;
-  double lo_b = tgb[tb], r_b = trb[tb], lo_c = tgc[tc], r_c = trc[tc];
+  double lo_b, r_b, lo_c, r_c;
+  {
+    const d2 eb = ((lds_d2_t)(uintptr_t)tab_b)[tb], ec = ((lds_d2_t)(uintptr_t)tab_c)[tc];
+    lo_b = eb.x;
+    r_b = eb.y;
+    lo_c = ec.x;
+    r_c = ec.y;
+  }
   int cell = cell_off(tb, tc);  // record offset inside a slot, in doubles: column-major (see the banks note below)
 
   // ---- producers: NC consecutive lanes, one cell each.  WHICH lanes rotates with the workgroup index: a CU holds three
@@ -553,10 +584,10 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   const int ln = (int)(threadIdx.x & 63);
   // Addresses: everything but the lane's place inside its kilobyte is wave-uniform -- the tile's first record, the node plane, the
   // column -- and is kept in scalar registers (ob, oc come out of LDS: readfirstlane tells the compiler); the lane adds ONE 32-bit
-  // offset, the same for the whole launch (what becomes of it in the step loop: see lds_dma16).  (Formed per lane in 64-bit integer arithmetic the two addresses were 15 vector
+  // offset, the same for the whole launch (how the step loop keeps it that way: see lds_dma16 and the loop's DMA).  (Formed per lane in 64-bit integer arithmetic the two addresses were 15 vector
   // instructions per step: profiles/r05_pmc_c3_f64_first_layout.csv, INT32 + INT64 35 per wavefront-step against the producers' 27.)
   const int ob_u = __builtin_amdgcn_readfirstlane(ob), oc_u = __builtin_amdgcn_readfirstlane(oc);
-  const unsigned lane_off = (unsigned)(ln & 7) * 128u + (unsigned)(ln >> 3) * 16u;  // piece ln / 8 of the record of row ln % 8
+  unsigned lane_off = (unsigned)(ln & 7) * 128u + (unsigned)(ln >> 3) * 16u;  // piece ln / 8 of the record of row ln % 8
   const int64_t col_bytes = (int64_t)(V.nb - 1) * 128, plane_bytes = (int64_t)(V.nc - 1) * col_bytes;
   const char *tile_r = REC ? reinterpret_cast<const char *>(V.R) + ((int64_t)oc_u * (V.nb - 1) + ob_u) * 128 : nullptr;
   // A slot's HANDLE is what the step loop rotates and hands to request / dma_cols / mid_from.  REC: the LDS byte address of the
@@ -577,8 +608,6 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   };
   // the mid record of the wavefront's own two columns: (plane in slot `lo`) + (plane in slot `hi`) -> slot `mid`, 16 bytes per
   // lane; the slots by their handles, the lane's place in the wavefront's block a constant of the launch
-  typedef double d2 __attribute__((ext_vector_type(2)));
-  typedef __attribute__((address_space(3))) d2 *lds_d2_t;
   const int mid_lane = wcol_b + ln * 16;
   auto mid_from = [&](int lo, int hi, int mid, bool col0, bool col1) {
 #pragma unroll
@@ -617,49 +646,44 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
 #else
   constexpr unsigned kInside = 0x3FEFFFFFu;  // hi32(w) <u this  <=>  0 <= w < 1 - 2^-21  (k_trace_f64)
 #endif
-  // The cell search inside the tile at position (qb, qc), given the weights that failed the test in the cached cell: the
+  // The cell search inside the tile at position (qb, qc), given the weights (wb, wc) that failed the test in the cached cell: the
   // neighbour each weight points at (the only way out of a cell within one stage: a stage moves a ray by a hundredth of a
-  // cell), accepted when the node table says g[i] <= q < g[i+1]; the six table entries of both axes are read BEFORE any
-  // branch: ONE LDS round trip (as k_trace_f64's locate2).  false: not there (the tile's edge, NaN, or a weight within 2^-21
-  // of 1 whose ray is still in its cell: one stage in two million) -- the ray is lost to this launch and k_trace_f64 carries
-  // it through the segment; a general walk along the table here cost 1.3 % of the kernel for nothing.
-  auto relocate2 = [&](double qb, double qc, double wb, double wc) -> bool {
-    const int nb_ = min(max(tb + (wb < 0.0 ? -1 : (hi_word(wb) >= kInside ? 1 : 0)), 0), TB - 1);
-    const int nc_ = min(max(tc + (wc < 0.0 ? -1 : (hi_word(wc) >= kInside ? 1 : 0)), 0), TC - 1);
-    double lb = tgb[nb_], ub = tgb[nb_ + 1], rb = trb[nb_], lc = tgc[nc_], uc = tgc[nc_ + 1], rc = trc[nc_];
-    asm("" : "+v"(lb), "+v"(ub), "+v"(rb), "+v"(lc), "+v"(uc), "+v"(rc));  // keeps the six reads together, ahead of the branches
-#ifdef SR_TILE_RELOC_SELECT
-    // (until round 5: each axis moved on only when the table accepted it -- five selects per axis, on 64-bit values two
-    // instructions each, in a region that runs for the whole wavefront when ONE ray changes its cell)
-    bool in = true;
-    if ((qb >= lb) & (qb < ub)) {
-      tb = nb_;
-      lo_b = lb;
-      r_b = rb;
-    } else {
-      in = false;
-    }
-    if ((qc >= lc) & (qc < uc)) {
-      tc = nc_;
-      lo_c = lc;
-      r_c = rc;
-    } else {
-      in = false;
-    }
-    return in;
-#else
-    // Both axes move on UNCONDITIONALLY: an axis whose weight passed the test gets its own cell again (index + 0: the same
-    // table entries, the same bits), and a ray the table does not accept is lost to this launch whatever its cell variables
-    // hold from here on (they stay inside the tile: the indices are clamped) -- its straggler entry is formed from the state it
-    // entered the segment with, not from this one.
-    tb = nb_;
-    lo_b = lb;
-    r_b = rb;
-    tc = nc_;
-    lo_c = lc;
-    r_c = rc;
-    return (qb >= lb) & (qb < ub) & (qc >= lc) & (qc < uc);
-#endif
+  // cell), accepted when the node table says g[n] <= q < g[n+1] (k_trace_f64's locate2); the weights come back formed in the new
+  // cell.  The region this is runs for the whole wavefront when ONE of its rays changes its cell, so it is written to be short:
+  //  * the step is integer arithmetic on the weight's high word h: (h >> 31) + (h >= kInside as signed) = -1 for a set sign, +1
+  //    from kInside on, else 0 -- a shift, a compare and an add with carry per axis.  (-0.0 and a NaN with the sign set step down
+  //    where `w < 0.0` did not: the acceptance test below decides, as it always did.)
+  //  * no clamp: the index may become -1 or T, where the table holds sentinels that fail the test (tile_tab_entries).
+  //  * one address per axis: g[n], r[n] and g[n+1] are 0, 8 and 16 bytes from tab + n * 16; both axes' six reads are one LDS
+  //    round trip, and there is no branch in here to keep them ahead of.  They are written as asm, one float64 each, with their
+  //    wait (which also ends the wait for any record still in flight: the counted waits that follow only become conservative).
+  //    Read through the compiler as {g, r} vectors of 16 bytes, the vectors reach the state: the SLP vectoriser pairs (y0, y1) into
+  //    one as well, and the common path pays two 64-bit copies per step; read as two float64 of one 16-byte load, g and r have to
+  //    be moved out of the load's register tuple -- six to nine v_mov_b32 per region.
+  //  * both axes move on UNCONDITIONALLY: an axis whose weight passed the test gets its own cell again (index + 0: the same
+  //    table entries, the same bits), and a ray the table does not accept is lost to this launch whatever its cell variables
+  //    hold from here on -- its straggler entry is formed from the state it entered the segment with, not from this one.  (Until
+  //    its step ends it reads records at whatever cell_off makes of its index, at most four cells off the tile: LDS reads, of
+  //    another slot's bytes or, outside the workgroup's allocation, of zeros.)
+  //  * g[n] <= q is the sign of the new weight (q - g[n]) * r[n]: the subtraction's sign is exact, r > 0, and a product that
+  //    underflows keeps its sign.  q < g[n+1] is asked of the table itself: the rounded reciprocal could say otherwise.
+  // false: not there (the tile's edge, NaN, or a weight within 2^-21 of 1 whose ray is still in its cell: one stage in two
+  // million) -- the ray is lost to this launch and k_trace_f64 carries it through the segment; a general walk along the table
+  // here cost 1.3 % of the kernel for nothing.
+  auto relocate2 = [&](double qb, double qc, double &wb, double &wc) -> bool {
+    const int hb = (int)hi_word(wb), hc = (int)hi_word(wc);
+    tb += (hb >> 31) + (hb >= (int)kInside ? 1 : 0);
+    tc += (hc >> 31) + (hc >= (int)kInside ? 1 : 0);
+    const unsigned ab = tab_b + ((unsigned)tb << 4), ac = tab_c + ((unsigned)tc << 4);
+    double ub, uc;
+    asm volatile("ds_read_b64 %0, %6\n\tds_read_b64 %1, %6 offset:8\n\tds_read_b64 %2, %6 offset:16\n\t"
+                 "ds_read_b64 %3, %7\n\tds_read_b64 %4, %7 offset:8\n\tds_read_b64 %5, %7 offset:16\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(lo_b), "=&v"(r_b), "=&v"(ub), "=&v"(lo_c), "=&v"(r_c), "=&v"(uc)
+                 : "v"(ab), "v"(ac));
+    wb = (qb - lo_b) * r_b;
+    wc = (qc - lo_c) * r_c;
+    // (the unsigned maximum has its top bit set when either weight's sign is; an OR of the two the compiler widens to 64 bits)
+    return ((int)max(hi_word(wb), hi_word(wc)) >= 0) & (qb < ub) & (qc < uc);
   };
 
   // ---- records in registers.  A record is read by eight ds_read_b128 written as asm: the compiler does not know them to be
@@ -736,8 +760,18 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     const bool more0 = k <= k_col0, more1 = k <= k_col1;
 #ifndef SR_TILE_EXP_NOPRODUCE
     if (REC) {
-      if (more0) glds16(nx_r0, s_nx + wcol_b);
-      if (more1) glds16(nx_r1, s_nx + wcol_b + kRecColD * 8);
+      // the two sources stay wave-uniform pointers in scalar registers: the empty statement hides from the loop's strength
+      // reduction that they are induction variables, which would fold lane_off into them (two per-lane 64-bit pointers, moved on
+      // by a v_lshl_add_u64 each per step); as they are, the DMA takes the scalar base + 32-bit lane offset form (lds_dma16)
+      // (and hide lane_off where it is used: hoisted out of the loop as a 64-bit value it no longer looks like a 32-bit offset)
+      if (more0) {
+        asm volatile("" : "+s"(nx_r0), "+v"(lane_off));
+        glds16(nx_r0, s_nx + wcol_b);
+      }
+      if (more1) {
+        asm volatile("" : "+s"(nx_r1), "+v"(lane_off));
+        glds16(nx_r1, s_nx + wcol_b + kRecColD * 8);
+      }
     } else if (!AUX) {
       if (producer && more) issue_raw(k + 2, NX);
     } else {
@@ -774,8 +808,6 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
         const int was = cell;
         if (!relocate2(y0, y1, wb, wc)) ok = false;   // left the tile: lost to this kernel
         cell = cell_off(tb, tc);
-        wb = (y0 - lo_b) * r_b;
-        wc = (y1 - lo_c) * r_c;
         if (cell != was) request(s_lo, cell, RA);  // the ray ended the step before in another cell than its last stage was in: read again
       }
       // whether the stage just run moved the ray into another cell while placing the next one: set in the rarely-taken region only
@@ -800,8 +832,6 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
             if (!relocate2(qb, qc, nwb, nwc)) ok = false;
             cell = cell_off(tb, tc);
             moved = cell != was;
-            nwb = (qb - lo_b) * r_b;
-            nwc = (qc - lo_c) * r_c;
           }
           if (has_next) request(nslot, cell, NXT);
         }
