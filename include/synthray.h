@@ -616,6 +616,23 @@ int sr_rays_tile_segments(const sr_rays *r);
  * workgroups per CU), 0 for the producers' kernel (records that do not fit in HBM, SYNTHRAY_TILE_RECORDS=0, the optional terms) or
  * when the tile path did not run.  Same results either way, bit for bit. */
 int sr_rays_tile_records(const sr_rays *r);
+/* The launch order of the bundle's last trace, read-only (for tests of the ray binning; never on a timed path): waits for the
+ * library's stream and copies N uint32 to the host, order[j] = index (as uploaded) of the ray in launch slot j.  What it holds:
+ *   - after a trace with sort_rays = 0: the identity;
+ *   - after a trace with sort_rays = 1 on the per-ray kernels: the rays by the Morton key of their entry cell, rays outside the
+ *     lateral grid and NaN rays last; on the tile path with ONE segment: by the band key of their entry cell;
+ *   - after a tile-path trace of several segments: the order of the LAST segment's re-binning -- by the band key of the cell a ray
+ *     is in on that segment's first node plane; rays the tiles have lost by then, and dead rays, last;
+ *   - after a slab entry (SR_HANDOFF_ENTER): on the per-ray kernels the sender's order (row 9 of the records as they arrived); on
+ *     the tile path the arrivals binned by the band key of the cell they arrive in (then as above when the slab has several segments).
+ * The order of the rays inside one cell (one key) is not defined.  SR_ERR_STATE before any trace (a slab entry is one) has been
+ * queued for the bundle; N = 0 copies nothing. */
+int sr_rays_launch_order(const sr_rays *r, uint32_t *order);
+/* The bundle holds n rays from now on, 0 <= n <= the count it was created with (its capacity; SR_ERR_INVALID otherwise): what
+ * sr_trace's pipeline does for a shorter last chunk.  Every device buffer keeps its size; the rows of s0 and of the results are at
+ * pitch n afterwards, so whatever the bundle held (rays, results, hand-off records, bounding box, launch order) is forgotten:
+ * upload or generate again. */
+int sr_rays_set_count(sr_rays *r, int64_t n);
 /* The density from which sr_rays_trace takes the tile path: rays per lateral cell of the beam's bounding box (sr_rays_get_bbox).
  * What a job that cuts its rays into chunks sizes them by (distributed.plan_chunks: the slab pipeline's chunk is the smallest
  * that every rank still traces with the tile kernel; the reference's drivers use a fixed 5e5, pvti_trace_mpi.py:27). */

@@ -264,6 +264,7 @@ struct sr_rays {
   unsigned long long *strag_snap = nullptr;
   int strag_snap_cap = 0;
   bool have_s0 = false, traced = false, sorted = false, have_rec = false;
+  bool have_order = false;  // a trace has been queued since the bundle was made / resized: perm[] is its launch order (sr_rays_launch_order)
   bool counters_carry = false;  // the step / fallback totals of earlier traces have not been read yet: keep adding
   int tile_segs = 0;  // the last trace ran the tile path in this many timed segments (0: not the tile path, or more than kMaxTileSegs)
   int tile_segs_run = 0;  // ... in this many segments, timed or not (sr_rays_tile_segments)

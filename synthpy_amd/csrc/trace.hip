@@ -1514,6 +1514,7 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   if (stats) *stats = sr_trace_stats{0, 0, 0.0, 0.0};
   if (N == 0) {
     r->traced = true;
+    r->have_order = true;
     return SR_OK;
   }
   const int block = 256;
@@ -1605,6 +1606,7 @@ int sr_rays_trace(sr_rays *r, const sr_volume *v, const sr_trace_params *p, sr_t
   r->traced = (p->handoff & SR_HANDOFF_EXIT) == 0;
   r->have_rec = (p->handoff & SR_HANDOFF_EXIT) != 0;
   r->sorted = p->sort_rays != 0 || ho_enter;
+  r->have_order = true;
   // what an exact-counts deposit needs to refine this trace (deposit.hip): only a mixed-precision trace of a WHOLE volume
   // from s0 can be repeated in float64 (a slab holds neither the other planes nor the rays' start)
   r->last_vol = v;
@@ -1650,6 +1652,29 @@ int sr_rays_trace_stats(sr_rays *r, sr_trace_stats *stats) {
 int sr_rays_tile_segments(const sr_rays *r) { return r ? r->tile_segs_run : 0; }
 
 int sr_rays_tile_records(const sr_rays *r) { return r && r->tile_rec ? 1 : 0; }
+
+int sr_rays_launch_order(const sr_rays *r, uint32_t *order) {
+  SR_CHECK(r && order, "sr_rays_launch_order: NULL argument");
+  if (!r->have_order) return sr::fail(SR_ERR_STATE, "sr_rays_launch_order: no trace has been queued for these rays");
+  if (r->n == 0) return SR_OK;
+  hipStream_t st = sr::ctx().stream;
+  SR_HIP(hipMemcpyAsync(order, r->perm, sizeof(uint32_t) * (size_t)r->n, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  return SR_OK;
+}
+
+int sr_rays_set_count(sr_rays *r, int64_t n) {
+  SR_CHECK(r != nullptr, "sr_rays_set_count: NULL rays");
+  SR_CHECK(n >= 0 && n <= r->cap, "sr_rays_set_count: %lld rays in a bundle made for %lld", (long long)n, (long long)r->cap);
+  r->n = n;  // every buffer keeps its size (by cap); rows are at pitch n from now on, so what the bundle held is gone
+  r->have_s0 = r->traced = r->sorted = r->have_rec = r->have_order = false;
+  r->have_bbox = r->bbox_given = false;
+  r->guard_live = false;
+  r->last_vol = nullptr;
+  r->tile_segs = r->tile_segs_run = 0;
+  r->tile_rec = false;
+  return SR_OK;
+}
 
 double sr_tile_min_density(void) { return kTileMinDensity; }
 

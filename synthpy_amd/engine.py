@@ -918,6 +918,21 @@ class RayBundle:
         """True when the last trace's tile path ran the records kernel (sr_rays_tile_records)."""
         return bool(lib.sr_rays_tile_records(self._h))
 
+    def launch_order(self):
+        """(N,) uint32: order[j] = index of the ray in launch slot j of the last trace (sr_rays_launch_order: the identity after
+        sort_rays=False, the Morton / band order of the binning otherwise).  Waits for the stream; for tests of the binning."""
+        out = np.empty(self.n, np.uint32)
+        check(lib.sr_rays_launch_order(self._h, ptr(out)))
+        return out
+
+    def resize(self, n_rays: int):
+        """The bundle holds n_rays <= its capacity (the count it was created with) from now on, in the same device buffers; what
+        it held is forgotten: upload again (sr_rays_set_count)."""
+        check(lib.sr_rays_set_count(self._h, int(n_rays)))
+        self.n = int(n_rays)
+        self.generation += 1
+        return self
+
     @property
     def bbox(self):
         """(min x, y, z, max x, y, z) of the launch positions of the beam these rays belong to [m], or None: what the library

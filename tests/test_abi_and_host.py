@@ -32,6 +32,7 @@ def _declared_symbols():
 def test_library_exports_every_declared_symbol(built):
     declared = _declared_symbols()
     assert len(declared) >= 30
+    assert {"sr_rays_launch_order", "sr_rays_set_count"} <= set(declared)  # what tests/test_ray_order.py reads the binning through
     lib = ctypes.CDLL(built.LIB_PATH)
     missing = [s for s in declared if not hasattr(lib, s)]
     assert not missing, f"declared in synthray.h but not exported: {missing}"
