@@ -3,9 +3,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <type_traits>
@@ -310,3 +312,50 @@ struct sr_field {
   std::vector<double> hg[3];                   // host copies of g (grids are compared without touching the device)
   double inv_h[3] = {0, 0, 0};                 // (n - 1) / (g[n-1] - g[0]): the first guess of a cell on a uniform axis
 };
+
+// ---- what the entry points of the field diagnostics share on the host (runtime.hip) ----------------------------------------
+namespace sr {
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline bool positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+// The grid of a field as a kernel takes it (push.hip, thomson.hip): what sr::locate_in<true> reads, per axis.
+struct FieldGrid {
+  const double *g[3];  // node coordinates
+  int n[3];
+  double inv_h[3], lo[3], hi[3];  // lo = g[0], hi = g[n-1]: the box
+};
+FieldGrid grid_of(const sr_field *f);
+
+// Every field given (f != NULL) has its n_comp, and the dtype and the grid of `ref` (one of them, named ref_name); before the
+// device is touched.
+struct FieldSpec {
+  const char *name;
+  const sr_field *f;
+  int n_comp;
+};
+int check_fields(const char *who, const sr_field *ref, const char *ref_name, std::initializer_list<FieldSpec> fields);
+
+// The pieces of one call's scratch block: take() them in order, each aligned to 256 bytes, then alloc() gets the block
+// (sr::scratch) and sets every pointer taken; false + error text on failure.  A piece of 0 elements shares the next one's address.
+class Carve {
+ public:
+  template <typename T>
+  void take(T **p, size_t count) {
+    slots_.push_back({(void **)p, bytes_});
+    bytes_ += up256(sizeof(T) * count);
+  }
+  bool alloc();
+
+ private:
+  struct Slot {
+    void **p;
+    size_t at;
+  };
+  std::vector<Slot> slots_;
+  size_t bytes_ = 0;
+};
+
+// The end of a timed call: the stream is waited for, *kernel_ms (may be NULL) gets the time between c.ev[0] and c.ev[1], the
+// scratch block is trimmed.
+int finish_timed(Context &c, double *kernel_ms);
+}  // namespace sr

@@ -20,7 +20,6 @@
 //   template <int NB> void eval(A, ne, Te, Z, al, S) const     alpha [1/m] and S of one node for the NB bands
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "common.hpp"
 
@@ -217,20 +216,10 @@ inline int check_fields(const char *who, const sr_field *ne, const sr_field *Te,
   SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
   SR_CHECK(p->axis >= 0 && p->axis <= 2, "%s: axis must be 0, 1 or 2, got %d", who, p->axis);
   SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
-  const sr_field *all[3] = {ne, Te, Z};
-  const char *names[3] = {"ne", "Te", "Z"};
-  for (int f = 0; f < 3; ++f) {
-    if (!all[f]) continue;
-    SR_CHECK(all[f]->n_comp == 1, "%s: %s is a vector field", who, names[f]);
-    SR_CHECK(all[f]->is_f64 == ne->is_f64, "%s: %s and ne differ in dtype", who, names[f]);
-    for (int k = 0; k < 3; ++k)
-      SR_CHECK(all[f]->n[k] == ne->n[k] && memcmp(all[f]->hg[k].data(), ne->hg[k].data(), sizeof(double) * ne->n[k]) == 0,
-               "%s: the grids of %s and ne differ on axis %d", who, names[f], k);
-  }
-  return SR_OK;
+  return sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}});
 }
 
-// Scratch for the maps (+ `extra` bytes behind them, 8-byte aligned: *extra_at), the kernel's arguments, the backlight's upload.
+// Scratch for the maps (+ `extra` bytes behind them: *extra_at), the kernel's arguments, the backlight's upload.
 inline int prepare(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p, const double *backlight,
                    size_t extra, EmArgs &A, size_t &map_bytes, char **extra_at) {
   sr::Context &c = sr::ctx();
@@ -238,17 +227,18 @@ inline int prepare(const sr_field *ne, const sr_field *Te, const sr_field *Z, co
   const int64_t ny = ne->n[1], nz = ne->n[2];
   const int64_t ncol = (int64_t)ne->n[0] * ny * nz / ne->n[axis];
   map_bytes = sizeof(double) * (size_t)nb * (size_t)ncol;
-  double *block = static_cast<double *>(sr::scratch(map_bytes * (backlight ? 3 : 2) + extra));
-  if (!block) return SR_ERR_HIP;
   A = EmArgs{};
+  char *behind;
+  sr::Carve carve;
+  carve.take(&A.I, (size_t)nb * ncol);
+  carve.take(&A.tau, (size_t)nb * ncol);
+  if (backlight) carve.take(&A.back, (size_t)nb * ncol);
+  carve.take(extra_at ? extra_at : &behind, extra);
+  if (!carve.alloc()) return SR_ERR_HIP;
   A.ne = ne->data;
   A.Te = Te ? Te->data : nullptr;
   A.Z = Z ? Z->data : nullptr;
   A.g = ne->g[axis];
-  A.I = block;
-  A.tau = block + (size_t)nb * ncol;
-  A.back = backlight ? block + 2 * (size_t)nb * ncol : nullptr;
-  if (extra_at) *extra_at = reinterpret_cast<char *>(block) + map_bytes * (backlight ? 3 : 2);
   A.n = ne->n[axis];
   A.toward = p->toward;
   A.ncol = ncol;
@@ -274,14 +264,7 @@ inline int finish(const EmArgs &A, size_t map_bytes, double *I, double *tau, dou
   SR_HIP(hipEventRecord(c.ev[1], st));
   SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
   SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    *kernel_ms = ms;
-  }
-  sr::scratch_trim();
-  return SR_OK;
+  return sr::finish_timed(c, kernel_ms);
 }
 
 }  // namespace

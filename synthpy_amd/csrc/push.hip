@@ -9,7 +9,6 @@
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_radiography.py).
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "common.hpp"
 
@@ -17,9 +16,7 @@ namespace {
 
 struct PushArgs {
   const void *E, *B;   // (nx, ny, nz, 3), or nullptr
-  const double *g[3];  // node coordinates
-  int n[3];
-  double inv_h[3], lo[3], hi[3];  // lo = g[0], hi = g[n-1] per axis: the box
+  sr::FieldGrid f;     // lo, hi: the box
   double hq, hd, ic2, det_pos, hit_scale;
   int max_steps, axis;
   int64_t np;
@@ -61,7 +58,7 @@ __global__ void __launch_bounds__(256) k_push(PushArgs A) {
   double u0 = A.s0[3 * N + i], u1 = A.s0[4 * N + i], u2 = A.s0[5 * N + i];
   const T *__restrict__ fE = static_cast<const T *>(A.E);
   const T *__restrict__ fB = static_cast<const T *>(A.B);
-  const int64_t sy = (int64_t)A.n[2] * 3, sx = (int64_t)A.n[1] * sy;
+  const int64_t sy = (int64_t)A.f.n[2] * 3, sx = (int64_t)A.f.n[1] * sy;
   const double hq = A.hq, hd = A.hd, ic2 = A.ic2;
   int steps = 0;
   bool inside;
@@ -72,9 +69,9 @@ __global__ void __launch_bounds__(256) k_push(PushArgs A) {
     double E[3] = {0.0, 0.0, 0.0}, B[3] = {0.0, 0.0, 0.0};
     int ci = 0, cj = 0, ck = 0;
     double wx = 0, wy = 0, wz = 0;
-    const bool in_x = sr::locate_in<true>(A.g[0], A.n[0], A.inv_h[0], A.lo[0], A.hi[0], m0, ci, wx);
-    const bool in_y = sr::locate_in<true>(A.g[1], A.n[1], A.inv_h[1], A.lo[1], A.hi[1], m1, cj, wy);
-    const bool in_z = sr::locate_in<true>(A.g[2], A.n[2], A.inv_h[2], A.lo[2], A.hi[2], m2, ck, wz);
+    const bool in_x = sr::locate_in<true>(A.f.g[0], A.f.n[0], A.f.inv_h[0], A.f.lo[0], A.f.hi[0], m0, ci, wx);
+    const bool in_y = sr::locate_in<true>(A.f.g[1], A.f.n[1], A.f.inv_h[1], A.f.lo[1], A.f.hi[1], m1, cj, wy);
+    const bool in_z = sr::locate_in<true>(A.f.g[2], A.f.n[2], A.f.inv_h[2], A.f.lo[2], A.f.hi[2], m2, ck, wz);
     if (in_x && in_y && in_z) {
       const double ux = 1.0 - wx, uy = 1.0 - wy, uz = 1.0 - wz;
       const double w00 = uy * uz, w01 = uy * wz, w10 = wy * uz, w11 = wy * wz;
@@ -113,7 +110,7 @@ __global__ void __launch_bounds__(256) k_push(PushArgs A) {
     x1 = m1 + u1 * dn;
     x2 = m2 + u2 * dn;
     ++steps;
-    inside = x0 >= A.lo[0] && x0 <= A.hi[0] && x1 >= A.lo[1] && x1 <= A.hi[1] && x2 >= A.lo[2] && x2 <= A.hi[2];
+    inside = x0 >= A.f.lo[0] && x0 <= A.f.hi[0] && x1 >= A.f.lo[1] && x1 <= A.f.hi[1] && x2 >= A.f.lo[2] && x2 <= A.f.hi[2];
   } while (inside && steps < A.max_steps);
 
   // the detector plane: coordinate[axis] == det_pos; (b, c) the two other axes in x < y < z order
@@ -162,8 +159,6 @@ void launch(bool has_e, bool has_b, unsigned grid, hipStream_t st, const PushArg
       has_e, has_b);
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_push_params *p, int64_t n, const double *s0,
@@ -179,14 +174,7 @@ extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_
   SR_CHECK(img == nullptr || img->kind == SR_IMG_COUNTS, "sr_particles_push: the image must be of kind SR_IMG_COUNTS");
   SR_CHECK(E != nullptr || B != nullptr, "sr_particles_push: E and B are both NULL");
   const sr_field *F = E ? E : B;
-  SR_CHECK(E == nullptr || E->n_comp == 3, "sr_particles_push: E is not a vector field (n_comp == 3)");
-  SR_CHECK(B == nullptr || B->n_comp == 3, "sr_particles_push: B is not a vector field (n_comp == 3)");
-  if (E && B) {
-    SR_CHECK(E->is_f64 == B->is_f64, "sr_particles_push: E and B differ in dtype");
-    for (int k = 0; k < 3; ++k)
-      SR_CHECK(E->n[k] == B->n[k] && memcmp(E->hg[k].data(), B->hg[k].data(), sizeof(double) * E->n[k]) == 0,
-               "sr_particles_push: the grids of E and B differ on axis %d", k);
-  }
+  if (int rc = sr::check_fields("sr_particles_push", F, E ? "E" : "B", {{"E", E, 3}, {"B", B, 3}})) return rc;
   if (stats) *stats = sr_push_stats{0.0, 0, 0, 0, 0};
   if (n == 0) return SR_OK;
   if (int rc = sr::ensure_init()) return rc;
@@ -194,26 +182,19 @@ extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_
   hipStream_t st = c.stream;
 
   // one scratch block: s0 | sf | hits | steps | flags | counters {unfinished, missed, deposited}
-  const size_t b6 = up256(sizeof(double) * 6 * (size_t)n), b2 = up256(sizeof(double) * 2 * (size_t)n);
-  const size_t bs = up256(sizeof(int32_t) * (size_t)n), bf = up256((size_t)n);
-  char *block = static_cast<char *>(sr::scratch(2 * b6 + b2 + bs + bf + 256));
-  if (!block) return SR_ERR_HIP;
   PushArgs A{};
-  A.s0 = reinterpret_cast<const double *>(block);
-  A.sf = reinterpret_cast<double *>(block + b6);
-  A.hits = reinterpret_cast<double *>(block + 2 * b6);
-  A.steps = reinterpret_cast<int32_t *>(block + 2 * b6 + b2);
-  A.flags = reinterpret_cast<uint8_t *>(block + 2 * b6 + b2 + bs);
-  unsigned long long *counters = reinterpret_cast<unsigned long long *>(block + 2 * b6 + b2 + bs + bf);
+  unsigned long long *counters = nullptr;
+  sr::Carve carve;
+  carve.take(&A.s0, 6 * (size_t)n);
+  carve.take(&A.sf, 6 * (size_t)n);
+  carve.take(&A.hits, 2 * (size_t)n);
+  carve.take(&A.steps, (size_t)n);
+  carve.take(&A.flags, (size_t)n);
+  carve.take(&counters, 3);
+  if (!carve.alloc()) return SR_ERR_HIP;
   A.E = E ? E->data : nullptr;
   A.B = B ? B->data : nullptr;
-  for (int k = 0; k < 3; ++k) {
-    A.g[k] = F->g[k];
-    A.n[k] = F->n[k];
-    A.inv_h[k] = F->inv_h[k];
-    A.lo[k] = F->hg[k].front();
-    A.hi[k] = F->hg[k].back();
-  }
+  A.f = sr::grid_of(F);
   A.hq = (p->qm * p->dt) * 0.5;
   A.hd = p->dt * 0.5;
   A.ic2 = 1.0 / (sr::kC * sr::kC);
@@ -223,7 +204,7 @@ extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_
   A.axis = p->axis;
   A.np = n;
 
-  if (int rc = sr::upload_sync(block, s0, sizeof(double) * 6 * (size_t)n, st)) return rc;
+  if (int rc = sr::upload_sync(const_cast<double *>(A.s0), s0, sizeof(double) * 6 * (size_t)n, st)) return rc;
   SR_HIP(hipMemsetAsync(counters, 0, 3 * sizeof(unsigned long long), st));
   SR_HIP(hipEventRecord(c.ev[0], st));
   if (F->is_f64)
@@ -244,16 +225,12 @@ extern "C" int sr_particles_push(const sr_field *E, const sr_field *B, const sr_
   if (flags) SR_HIP(hipMemcpyAsync(flags, A.flags, (size_t)n, hipMemcpyDeviceToHost, st));
   unsigned long long hc[3] = {0, 0, 0};
   if (stats) SR_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
+  if (int rc = sr::finish_timed(c, stats ? &stats->kernel_ms : nullptr)) return rc;
   if (stats) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    stats->kernel_ms = ms;
     stats->unfinished = (int64_t)hc[0];
     stats->finished = n - (int64_t)hc[0];
     stats->missed = (int64_t)hc[1];
     stats->deposited = (int64_t)hc[2];
   }
-  sr::scratch_trim();
   return SR_OK;
 }

@@ -192,13 +192,15 @@ int sr_field_resample(const sr_field *f, const sr_resample_params *p, int mx, in
   const float *oc[3] = {ox, oy, oz};
   const size_t elem = f->is_f64 ? sizeof(double) : sizeof(float);
   const size_t out_bytes = (size_t)mx * my * mz * f->n_comp * elem;
-  const size_t out_room = (out_bytes + 255) & ~(size_t)255;
   std::vector<double> o((size_t)mx + my + mz);
   for (int k = 0, at = 0; k < 3; at += m[k], ++k)
     for (int i = 0; i < m[k]; ++i) o[at + i] = (double)oc[k][i];
-  char *block = static_cast<char *>(sr::scratch(out_room + sizeof(double) * o.size()));
-  if (!block) return SR_ERR_HIP;
-  double *d_o = reinterpret_cast<double *>(block + out_room);
+  char *block;
+  double *d_o;
+  sr::Carve carve;
+  carve.take(&block, out_bytes);
+  carve.take(&d_o, o.size());
+  if (!carve.alloc()) return SR_ERR_HIP;
 
   ResampleArgs A{};
   A.src = f->data;
@@ -240,14 +242,7 @@ int sr_field_resample(const sr_field *f, const sr_resample_params *p, int mx, in
   SR_HIP(hipGetLastError());
   SR_HIP(hipEventRecord(c.ev[1], st));
   SR_HIP(hipMemcpyAsync(out, block, out_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    *kernel_ms = ms;
-  }
-  sr::scratch_trim();
-  return SR_OK;
+  return sr::finish_timed(c, kernel_ms);
 }
 
 int64_t sr_field_bytes(const sr_field *f) {

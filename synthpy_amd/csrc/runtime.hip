@@ -94,6 +94,50 @@ void scratch_release() {
   }
 }
 
+bool Carve::alloc() {
+  char *block = static_cast<char *>(scratch(bytes_));
+  if (!block) return false;
+  for (const Slot &s : slots_) *s.p = block + s.at;
+  return true;
+}
+
+int finish_timed(Context &c, double *kernel_ms) {
+  SR_HIP(hipStreamSynchronize(c.stream));
+  if (kernel_ms) {
+    float ms = 0.f;
+    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    *kernel_ms = ms;
+  }
+  scratch_trim();
+  return SR_OK;
+}
+
+// ---- the fields of one call ---------------------------------------------------------------------------------------------
+FieldGrid grid_of(const sr_field *f) {
+  FieldGrid G{};
+  for (int k = 0; k < 3; ++k) {
+    G.g[k] = f->g[k];
+    G.n[k] = f->n[k];
+    G.inv_h[k] = f->inv_h[k];
+    G.lo[k] = f->hg[k].front();
+    G.hi[k] = f->hg[k].back();
+  }
+  return G;
+}
+
+int check_fields(const char *who, const sr_field *ref, const char *ref_name, std::initializer_list<FieldSpec> fields) {
+  for (const FieldSpec &s : fields) {
+    if (!s.f) continue;
+    SR_CHECK(s.f->n_comp == s.n_comp, "%s: %s must have n_comp == %d (a %s, not a %s field)", who, s.name, s.n_comp,
+             s.n_comp == 3 ? "vector" : "scalar", s.n_comp == 3 ? "scalar" : "vector");
+    SR_CHECK(s.f->is_f64 == ref->is_f64, "%s: %s and %s differ in dtype", who, ref_name, s.name);
+    for (int k = 0; k < 3; ++k)
+      SR_CHECK(s.f->n[k] == ref->n[k] && memcmp(s.f->hg[k].data(), ref->hg[k].data(), sizeof(double) * ref->n[k]) == 0,
+               "%s: the grids of %s and %s differ on axis %d", who, ref_name, s.name, k);
+  }
+  return SR_OK;
+}
+
 // ---- host -> device from pageable memory ----------------------------------------------------------------------------------
 namespace {
 constexpr int kUpThreads = 6;

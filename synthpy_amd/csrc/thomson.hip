@@ -13,7 +13,6 @@
 // restatement's do (tests/test_thomson.py).
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "common.hpp"
 
@@ -28,9 +27,7 @@ constexpr double kSP = 1.7724538509055159, kTSP = 3.5449077018110318, kISP = 0.5
 
 struct ThomsonArgs {
   const void *ne, *Te, *Ti, *Z, *V;  // Ti, Z, V may be nullptr
-  const double *g[3];                // node coordinates
-  int n[3];
-  double inv_h[3], lo[3], hi[3];
+  sr::FieldGrid f;
   const double *pts;     // (n_vol, nq, 3)
   const double *wts;     // (n_vol, nq)
   const double *ki, *ks; // (n_vol, 3)
@@ -100,7 +97,7 @@ __global__ void __launch_bounds__(256) k_thomson(ThomsonArgs A) {
   const double rk = 1.0 / k, rk2 = 1.0 / k2;
   const double pre = kTSP * rk;
 
-  const int64_t sy = A.n[2], sx = (int64_t)A.n[1] * sy;
+  const int64_t sy = A.f.n[2], sx = (int64_t)A.f.n[1] * sy;
   double acc = 0.0, wsum = 0.0;
   for (int q0 = 0; q0 < A.nq; q0 += kChunk) {
     const int cnt = min(kChunk, A.nq - q0);
@@ -111,9 +108,9 @@ __global__ void __launch_bounds__(256) k_thomson(ThomsonArgs A) {
       const double px = A.pts[q * 3], py = A.pts[q * 3 + 1], pz = A.pts[q * 3 + 2];
       int ci = 0, cj = 0, ck = 0;
       double wx = 0, wy = 0, wz = 0;
-      const bool in_x = sr::locate_in<true>(A.g[0], A.n[0], A.inv_h[0], A.lo[0], A.hi[0], px, ci, wx);
-      const bool in_y = sr::locate_in<true>(A.g[1], A.n[1], A.inv_h[1], A.lo[1], A.hi[1], py, cj, wy);
-      const bool in_z = sr::locate_in<true>(A.g[2], A.n[2], A.inv_h[2], A.lo[2], A.hi[2], pz, ck, wz);
+      const bool in_x = sr::locate_in<true>(A.f.g[0], A.f.n[0], A.f.inv_h[0], A.f.lo[0], A.f.hi[0], px, ci, wx);
+      const bool in_y = sr::locate_in<true>(A.f.g[1], A.f.n[1], A.f.inv_h[1], A.f.lo[1], A.f.hi[1], py, cj, wy);
+      const bool in_z = sr::locate_in<true>(A.f.g[2], A.f.n[2], A.f.inv_h[2], A.f.lo[2], A.f.hi[2], pz, ck, wz);
       bool keep = false;
       if (in_x && in_y && in_z) {
         const double ux = 1.0 - wx, uy = 1.0 - wy, uz = 1.0 - wz;
@@ -181,9 +178,7 @@ void launch(bool has_v, unsigned grid, hipStream_t st, const ThomsonArgs &A) {
   sr::with_flags([&](auto v) { hipLaunchKernelGGL((k_thomson<v.value, T>), dim3(grid), dim3(256), 0, st, A); }, has_v);
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-bool positive(double v) { return std::isfinite(v) && v > 0.0; }
+using sr::positive;
 
 }  // namespace
 
@@ -213,16 +208,8 @@ extern "C" int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr
   const int64_t n_tiles = ((int64_t)n_lambda + kTile - 1) / kTile;
   SR_CHECK(n_tiles == 0 || n_vol <= (int64_t)2147483647 / n_tiles, "sr_field_thomson: n_vol x wavelength tiles exceeds 2^31 - 1 workgroups");
   SR_CHECK(ne != nullptr && Te != nullptr, "sr_field_thomson: NULL field (ne or Te)");
-  const sr_field *fs[5] = {ne, Te, Ti, Z, V};
-  const char *names[5] = {"ne", "Te", "Ti", "Z", "V"};
-  for (int f = 0; f < 5; ++f) {
-    if (!fs[f]) continue;
-    SR_CHECK(fs[f]->n_comp == (f == 4 ? 3 : 1), "sr_field_thomson: %s must have n_comp == %d", names[f], f == 4 ? 3 : 1);
-    SR_CHECK(fs[f]->is_f64 == ne->is_f64, "sr_field_thomson: ne and %s differ in dtype", names[f]);
-    for (int k = 0; k < 3; ++k)
-      SR_CHECK(fs[f]->n[k] == ne->n[k] && memcmp(fs[f]->hg[k].data(), ne->hg[k].data(), sizeof(double) * ne->n[k]) == 0,
-               "sr_field_thomson: the grids of ne and %s differ on axis %d", names[f], k);
-  }
+  if (int rc = sr::check_fields("sr_field_thomson", ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Ti", Ti, 1}, {"Z", Z, 1}, {"V", V, 3}}))
+    return rc;
   if (kernel_ms) *kernel_ms = 0.0;
   if (n_vol == 0 || n_lambda == 0) return SR_OK;
   if (int rc = sr::ensure_init()) return rc;
@@ -231,32 +218,28 @@ extern "C" int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr
 
   // one scratch block: pts | wts | ki | ks | lambda | P | weight
   const size_t nv = (size_t)n_vol, nq = (size_t)n_quad, nl = (size_t)n_lambda;
-  const size_t b_pts = up256(sizeof(double) * 3 * nv * nq), b_wts = up256(sizeof(double) * nv * nq), b_dir = up256(sizeof(double) * 3 * nv);
-  const size_t b_lam = up256(sizeof(double) * nl), b_P = up256(sizeof(double) * nv * nl), b_w = up256(sizeof(double) * nv);
-  char *block = static_cast<char *>(sr::scratch(b_pts + b_wts + 2 * b_dir + b_lam + b_P + b_w));
-  if (!block) return SR_ERR_HIP;
-  char *d_pts = block, *d_wts = d_pts + b_pts, *d_ki = d_wts + b_wts, *d_ks = d_ki + b_dir, *d_lam = d_ks + b_dir;
-  char *d_P = d_lam + b_lam, *d_w = d_P + b_P;
   ThomsonArgs A{};
+  double *d_pts, *d_wts, *d_ki, *d_ks, *d_lam;
+  sr::Carve carve;
+  carve.take(&d_pts, 3 * nv * nq);
+  carve.take(&d_wts, nv * nq);
+  carve.take(&d_ki, 3 * nv);
+  carve.take(&d_ks, 3 * nv);
+  carve.take(&d_lam, nl);
+  carve.take(&A.P, nv * nl);
+  carve.take(&A.weight, nv);
+  if (!carve.alloc()) return SR_ERR_HIP;
   A.ne = ne->data;
   A.Te = Te->data;
   A.Ti = Ti ? Ti->data : nullptr;
   A.Z = Z ? Z->data : nullptr;
   A.V = V ? V->data : nullptr;
-  for (int k = 0; k < 3; ++k) {
-    A.g[k] = ne->g[k];
-    A.n[k] = ne->n[k];
-    A.inv_h[k] = ne->inv_h[k];
-    A.lo[k] = ne->hg[k].front();
-    A.hi[k] = ne->hg[k].back();
-  }
-  A.pts = reinterpret_cast<const double *>(d_pts);
-  A.wts = reinterpret_cast<const double *>(d_wts);
-  A.ki = reinterpret_cast<const double *>(d_ki);
-  A.ks = reinterpret_cast<const double *>(d_ks);
-  A.lam = reinterpret_cast<const double *>(d_lam);
-  A.P = reinterpret_cast<double *>(d_P);
-  A.weight = reinterpret_cast<double *>(d_w);
+  A.f = sr::grid_of(ne);
+  A.pts = d_pts;
+  A.wts = d_wts;
+  A.ki = d_ki;
+  A.ks = d_ks;
+  A.lam = d_lam;
   A.nq = n_quad;
   A.n_lambda = n_lambda;
   A.n_tiles = (int)n_tiles;
@@ -283,14 +266,7 @@ extern "C" int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr
     launch<float>(V != nullptr, grid, st, A);
   SR_HIP(hipGetLastError());
   SR_HIP(hipEventRecord(c.ev[1], st));
-  SR_HIP(hipMemcpyAsync(P, d_P, sizeof(double) * nv * nl, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(weight, d_w, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    *kernel_ms = ms;
-  }
-  sr::scratch_trim();
-  return SR_OK;
+  SR_HIP(hipMemcpyAsync(P, A.P, sizeof(double) * nv * nl, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(weight, A.weight, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+  return sr::finish_timed(c, kernel_ms);
 }

@@ -216,9 +216,7 @@ void launch_screen(bool has_te, bool has_z, bool power, unsigned grid, hipStream
       has_te, has_te && has_z, power);
 }
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-bool positive(double v) { return std::isfinite(v) && v > 0.0; }
+using sr::positive;
 
 // sr_field_resample's `cell` rule for the pixels x0 + i*dx of one lateral axis; cell -1: outside
 void lateral_table(const std::vector<double> &g, int m, double x0, double dx, int *cell, double *w) {
@@ -285,16 +283,7 @@ extern "C" int sr_field_wave(const sr_field *ne, const sr_field *Te, const sr_fi
   SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
   SR_CHECK(p->axis >= 0 && p->axis <= 2, "%s: axis must be 0, 1 or 2, got %d", who, p->axis);
   SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
-  const sr_field *all[3] = {ne, Te, Z};
-  const char *names[3] = {"ne", "Te", "Z"};
-  for (int f = 0; f < 3; ++f) {
-    if (!all[f]) continue;
-    SR_CHECK(all[f]->n_comp == 1, "%s: %s is a vector field", who, names[f]);
-    SR_CHECK(all[f]->is_f64 == ne->is_f64, "%s: %s and ne differ in dtype", who, names[f]);
-    for (int k = 0; k < 3; ++k)
-      SR_CHECK(all[f]->n[k] == ne->n[k] && memcmp(all[f]->hg[k].data(), ne->hg[k].data(), sizeof(double) * ne->n[k]) == 0,
-               "%s: the grids of %s and ne differ on axis %d", who, names[f], k);
-  }
+  if (int rc = sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}})) return rc;
   SR_CHECK(Te == nullptr || Z != nullptr || std::isfinite(p->Z), "%s: non-finite uniform Z", who);
   if (int rc = sr::ensure_init()) return rc;
   sr::Context &c = sr::ctx();
@@ -327,18 +316,19 @@ extern "C" int sr_field_wave(const sr_field *ne, const sr_field *Te, const sr_fi
   memcpy(frq + mu, fv, sizeof(double) * mv);
 
   // one scratch block: U | tables | cells | partial sums | power | the slab buffers of a z march
-  const size_t b_U = up256(sizeof(double2) * (size_t)npix), b_tab = up256(sizeof(double) * tab.size());
-  const size_t b_cell = up256(sizeof(int) * cells.size());
-  const size_t b_part = power ? up256(sizeof(double) * (size_t)n_groups * n_cells) : 0, b_pow = power ? up256(sizeof(double) * n_cells) : 0;
-  const size_t b_slab = axis == 2 ? up256(elem * (size_t)kSlab * (size_t)ncol) : 0;
-  char *block = static_cast<char *>(sr::scratch(b_U + b_tab + b_cell + b_part + b_pow + b_slab * 2 * n_fields));
-  if (!block) return SR_ERR_HIP;
-  double2 *d_U = reinterpret_cast<double2 *>(block);
-  double *d_tab = reinterpret_cast<double *>(block + b_U);
-  int *d_cell = reinterpret_cast<int *>(block + b_U + b_tab);
-  double *d_part = reinterpret_cast<double *>(block + b_U + b_tab + b_cell);
-  double *d_pow = reinterpret_cast<double *>(block + b_U + b_tab + b_cell + b_part);
-  char *d_slab = block + b_U + b_tab + b_cell + b_part + b_pow;  // [field][parity]
+  const size_t b_slab = axis == 2 ? sr::up256(elem * (size_t)kSlab * (size_t)ncol) : 0;
+  double2 *d_U;
+  double *d_tab, *d_part, *d_pow;
+  int *d_cell;
+  char *d_slab;  // [field][parity]
+  sr::Carve carve;
+  carve.take(&d_U, (size_t)npix);
+  carve.take(&d_tab, tab.size());
+  carve.take(&d_cell, cells.size());
+  carve.take(&d_part, power ? (size_t)n_groups * n_cells : 0);
+  carve.take(&d_pow, power ? (size_t)n_cells : 0);
+  carve.take(&d_slab, b_slab * 2 * n_fields);
+  if (!carve.alloc()) return SR_ERR_HIP;
   const double *d_fu = d_tab + 2 * ((size_t)mu + mv), *d_fv = d_fu + mu;
 
   if (int rc = sr::upload_sync(d_U, U_in, sizeof(double2) * (size_t)npix, st)) return rc;
@@ -437,16 +427,11 @@ extern "C" int sr_field_wave(const sr_field *ne, const sr_field *Te, const sr_fi
   SR_HIP(hipEventRecord(c.ev[1], st));
   SR_HIP(hipMemcpyAsync(U_out, d_U, sizeof(double2) * (size_t)npix, hipMemcpyDeviceToHost, st));
   if (power) SR_HIP(hipMemcpyAsync(power, d_pow, sizeof(double) * n_cells, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
+  if (int rc = sr::finish_timed(c, kernel_ms)) return rc;
   if (kernel_ms) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    kernel_ms[0] = ms;
     kernel_ms[1] = kernel_ms[2] = 0.0;
-    if (parts.on)
-      if (int rc = parts.sums(kernel_ms + 1)) return rc;
+    if (parts.on) return parts.sums(kernel_ms + 1);
   }
-  sr::scratch_trim();
   return SR_OK;
 }
 
@@ -473,11 +458,12 @@ extern "C" int sr_wave_image(const sr_wave_image_params *p, const double *fu, co
   const int mu = p->mu, mv = p->mv;
   if (int rc = sr::fft_plan(F, 2, mu, mv, 0, &plan)) return rc;
   const int64_t npix = (int64_t)mu * mv;
-  const size_t b_U = up256(sizeof(double2) * (size_t)npix);
-  char *block = static_cast<char *>(sr::scratch(b_U + sizeof(double) * ((size_t)mu + mv)));
-  if (!block) return SR_ERR_HIP;
-  double2 *d_U = reinterpret_cast<double2 *>(block);
-  double *d_f = reinterpret_cast<double *>(block + b_U);
+  double2 *d_U;
+  double *d_f;
+  sr::Carve carve;
+  carve.take(&d_U, (size_t)npix);
+  carve.take(&d_f, (size_t)mu + mv);
+  if (!carve.alloc()) return SR_ERR_HIP;
   if (int rc = sr::upload_sync(d_U, U_in, sizeof(double2) * (size_t)npix, st)) return rc;
   SR_HIP(hipMemcpyAsync(d_f, fu, sizeof(double) * mu, hipMemcpyHostToDevice, st));
   SR_HIP(hipMemcpyAsync(d_f + mu, fv, sizeof(double) * mv, hipMemcpyHostToDevice, st));
@@ -502,12 +488,5 @@ extern "C" int sr_wave_image(const sr_wave_image_params *p, const double *fu, co
   if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: inverse FFT: hipfftResult %d", who, (int)fr);
   SR_HIP(hipEventRecord(c.ev[1], st));
   SR_HIP(hipMemcpyAsync(U_out, d_U, sizeof(double2) * (size_t)npix, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0.f;
-    SR_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-    *kernel_ms = ms;
-  }
-  sr::scratch_trim();
-  return SR_OK;
+  return sr::finish_timed(c, kernel_ms);
 }

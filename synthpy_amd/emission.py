@@ -3,6 +3,7 @@
     em = self_emission(domain, [532e-9, 100e-9])          # or domain.self_emission(...), domain.rotated(30).self_emission(...)
     em.intensity, em.optical_depth, em.transmission       # (n_band, n_u, n_v)
     em.sample(p, q, "intensity")                          # at lateral positions
+    self_emission(domain, lam, fields=fields.SourceFields(domain))   # a sweep: the fields are uploaded once and kept
 
 No reference counterpart.  Every other image of the package is an image of the probe; this is the optical fast-framing / XUV
 pinhole channel.  Per band and lateral column the formal solution of dI/ds = alpha (S - I) is marched from the far plane to the
@@ -20,6 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
+from .fields import staged, uniform
 from .projection import _lateral, bilinear
 
 c = engine.c
@@ -82,20 +84,10 @@ def _omegas(wavelengths):
     return lam, 2 * np.pi * c / lam
 
 
-def _uniform(a):
-    """The one value of a scalar, or of an array broadcast from one; None for a real array."""
-    if np.ndim(a) == 0:
-        return float(a)
-    a = np.asarray(a)
-    if a.size == 1 or all(s == 0 for s in a.strides):
-        return float(a.reshape(-1)[0])
-    return None
-
-
-def _march(domain, toward, run):
+def _march(domain, toward, fields, run):
     """What self_emission and table_emission share: the domain's fields uploaded by self_emission's rules -- a Te or Z that is a
-    scalar (or broadcast from one) goes as a value, float32 only when every array is float32 -- then run(ne, Te, Z, axis, sign)
-    -> (I, tau); returns (I, tau, axes, coords)."""
+    scalar (or broadcast from one) goes as a value, float32 only when every array is float32 (fields.SourceFields.get_all) --
+    then run(ne, Te, Z, axis, sign) -> (I, tau); returns (I, tau, axes, coords)."""
     axis = engine.axis_index(domain.probing_direction)
     sign = _toward(toward)
     ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
@@ -105,36 +97,24 @@ def _march(domain, toward, run):
         raise ValueError("self_emission needs external_Te() and external_Z()")
     axes, coords = _lateral(domain, axis)
     shape = (len(domain.x), len(domain.y), len(domain.z))
-    arrays = {"ne": np.asarray(ne)}
-    values = {}
-    for name, a in (("Te", Te), ("Z", Z)):
-        u = _uniform(a)
-        if u is None:
-            arrays[name] = np.asarray(a)
-        else:
-            values[name] = u
-    # one dtype for the uploads: float32 only when every array is (widening float32 is exact, so the image does not change)
-    dtype = np.float32 if all(a.dtype == np.float32 for a in arrays.values()) else np.float64
-    fields = {}
-    try:
-        for name, a in arrays.items():
-            fields[name] = engine.Field(np.ascontiguousarray(np.broadcast_to(a, shape), dtype), domain.x, domain.y, domain.z)
-        I, tau = run(fields["ne"], fields.get("Te", values.get("Te")), fields.get("Z", values.get("Z")), axis, sign)
-    finally:
-        for f in fields.values():
-            f.close()
+    values = {"Te": uniform(Te), "Z": uniform(Z)}
+    named = {name: np.broadcast_to(np.asarray(a), shape) for name, a in (("ne", ne), ("Te", Te), ("Z", Z)) if values.get(name) is None}
+    with staged(domain, fields) as src:
+        f = src.get_all(named)
+        I, tau = run(f["ne"], f.get("Te", values["Te"]), f.get("Z", values["Z"]), axis, sign)
     return I, tau, axes, coords
 
 
-def self_emission(domain, wavelengths, toward="+", backlight=None):
+def self_emission(domain, wavelengths, toward="+", backlight=None, fields=None):
     """The Emission of a domain of either API generation along its probing_direction, at up to 4 wavelengths [m] in one pass
     over the fields.  toward "+": the detector is where the rays leave (behind the last node plane of the axis), "-": where
     they enter.  backlight: (n_band, n_u, n_v) spectral radiance behind the far plane, or None.  The domain needs external_Te()
-    and external_Z(); a Te or Z that is a scalar (or broadcast from one) is not uploaded."""
+    and external_Z(); a Te or Z that is a scalar (or broadcast from one) is not uploaded.  fields: a fields.SourceFields of the
+    domain whose uploads are reused across calls."""
     engine.axis_index(domain.probing_direction)
     _toward(toward)
     lam, omegas = _omegas(wavelengths)
-    I, tau, axes, coords = _march(domain, toward, lambda ne, Te, Z, axis, sign: engine.emission(ne, Te, Z, omegas, axis, sign, backlight))
+    I, tau, axes, coords = _march(domain, toward, fields, lambda ne, Te, Z, axis, sign: engine.emission(ne, Te, Z, omegas, axis, sign, backlight))
     return Emission(I, tau, axes, coords, lam)
 
 
@@ -157,13 +137,13 @@ class TableEmission(Emission):
         return self.intensity * d_omega[:, None, None]
 
 
-def table_emission(domain, table, toward="+", backlight=None):
+def table_emission(domain, table, toward="+", backlight=None, fields=None):
     """self_emission with the opacities of `table` (utils.eos_opacity.OpacityTable, e.g. OpacityTable.from_propaceos(
     read_propaceos(...), A)) in place of the NRL coefficient: a TableEmission, one band per band of the table
     (engine.emission_table -> sr_field_emission_table; include/synthray.h states the rule).  A node's ion density is ne / Z with
     the domain's Z; the opacities are interpolated bilinearly in (log Te, log ni) on their logarithms and held at the edge value
     outside the table; the source function is Planck's at the band's photon_energy times emission / absorption opacity (1 for a
-    table without emission opacities: LTE).  toward, backlight and the upload rules are self_emission's.
+    table without emission opacities: LTE).  toward, backlight, fields and the upload rules are self_emission's.
     Not modelled: Z from the table's own zf_table (it would need the solve ne = ni * zf(T, ni)), group-integrated Planck
     functions, refraction of the emitted light, detector optics."""
     engine.axis_index(domain.probing_direction)
@@ -171,5 +151,5 @@ def table_emission(domain, table, toward="+", backlight=None):
     for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
         if not hasattr(table, name):
             raise ValueError(f"table must be an OpacityTable (utils.eos_opacity): it has no {name}")
-    I, tau, axes, coords = _march(domain, toward, lambda ne, Te, Z, axis, sign: engine.emission_table(ne, Te, Z, table, axis, sign, backlight))
+    I, tau, axes, coords = _march(domain, toward, fields, lambda ne, Te, Z, axis, sign: engine.emission_table(ne, Te, Z, table, axis, sign, backlight))
     return TableEmission(I, tau, axes, coords, table.photon_energy, getattr(table, "edges", None))

@@ -432,6 +432,38 @@ def emission_params(omegas, axis, toward=+1, Te=0.0, Z=0.0):
     return p
 
 
+def _handle(name, a, *, number=False, none=False):
+    """The sr_field handle of the open Field `a`, or None for what the entry takes in a field's place: a number (a uniform value,
+    which the caller passes on) and / or None."""
+    if isinstance(a, Field):
+        if not getattr(a, "_h", None):
+            raise ValueError(f"the field {name} has been closed")
+        return a._h
+    if (none and a is None) or (number and a is not None and np.ndim(a) == 0):
+        return None
+    other = {(False, False): "", (True, False): " or a number", (False, True): " or None", (True, True): ", a number or None"}
+    raise ValueError(f"{name} must be an open engine.Field{other[number, none]}")
+
+
+def _emission(entry, ne, Te, Z, omegas, axis, toward, backlight, *table):
+    """What emission and emission_table share: the handles, the uniform Te / Z, the backlight's shape, the maps and ne's kernel
+    time; entry: the library call, table: its arguments between the fields and the params."""
+    h_ne = _handle("ne", ne)
+    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
+    p = emission_params(omegas, axis, toward, *(0.0 if h else float(a) for h, a in zip(handles, (Te, Z))))
+    nb = p.n_band
+    lateral = tuple(n for k, n in enumerate(ne.shape[:3]) if k != p.axis) if 0 <= p.axis <= 2 else ne.shape[:2]
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != (nb,) + lateral:
+            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lateral grid give {(nb,) + lateral}")
+    I, tau = np.empty((nb,) + lateral), np.empty((nb,) + lateral)
+    ms = C.c_double(0.0)
+    check(entry(h_ne, *handles, *table, C.byref(p), ptr(backlight), ptr(I), ptr(tau), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    return I, tau
+
+
 def emission(ne, Te, Z, omegas, axis, toward=+1, backlight=None):
     """Self-emission with self-absorption along grid axis `axis` (0 | 1 | 2) of the fields ne [m^-3], Te [eV], Z (sr_field_emission;
     include/synthray.h states the rule): (I, tau), each (n_band, n_u, n_v) float64 with (u, v) the lateral axes in x < y < z order.
@@ -441,30 +473,7 @@ def emission(ne, Te, Z, omegas, axis, toward=+1, backlight=None):
     I is the spectral radiance per unit angular frequency [W m^-2 sr^-1 (rad/s)^-1].  The absorption coefficient is
     propagator.kappa / c -- the NRL low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy for
     hbar*omega <~ Te; the source function is Planck's.  ne.last_kernel_ms keeps the kernel's time."""
-    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
-        raise ValueError("ne must be an open engine.Field")
-    handles, uniform = [], []
-    for name, a in (("Te", Te), ("Z", Z)):
-        if isinstance(a, Field):
-            if not getattr(a, "_h", None):
-                raise ValueError(f"the field {name} has been closed")
-            handles.append(a._h)
-            uniform.append(0.0)
-        else:
-            handles.append(None)
-            uniform.append(float(a))
-    p = emission_params(omegas, axis, toward, *uniform)
-    nb = p.n_band
-    lateral = tuple(n for k, n in enumerate(ne.shape[:3]) if k != p.axis) if 0 <= p.axis <= 2 else ne.shape[:2]
-    if backlight is not None:
-        backlight = f64(backlight)
-        if backlight.shape != (nb,) + lateral:
-            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lateral grid give {(nb,) + lateral}")
-    I, tau = np.empty((nb,) + lateral), np.empty((nb,) + lateral)
-    ms = C.c_double(0.0)
-    check(lib.sr_field_emission(ne._h, handles[0], handles[1], C.byref(p), ptr(backlight), ptr(I), ptr(tau), C.byref(ms)))
-    ne.last_kernel_ms = float(ms.value)
-    return I, tau
+    return _emission(lib.sr_field_emission, ne, Te, Z, omegas, axis, toward, backlight)
 
 
 def emission_table_params(table):
@@ -490,35 +499,12 @@ def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
     function at the band's photon_energy times emission / absorption opacity.  I is the spectral radiance per unit angular
     frequency at photon_energy.  Fields, uniform Te / Z, axis, toward and backlight are engine.emission's.  Not modelled: Z from
     the table's own zf_table (the solve ne = ni * zf(T, ni)), group-integrated Planck functions, refraction, detector optics."""
-    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
-        raise ValueError("ne must be an open engine.Field")
-    handles, uniform = [], []
-    for name, a in (("Te", Te), ("Z", Z)):
-        if isinstance(a, Field):
-            if not getattr(a, "_h", None):
-                raise ValueError(f"the field {name} has been closed")
-            handles.append(a._h)
-            uniform.append(0.0)
-        else:
-            handles.append(None)
-            uniform.append(float(a))
-    t, keep = emission_table_params(table)
-    p = emission_params(np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR, axis, toward, *uniform)
-    nb = p.n_band
-    if nb != keep[2].shape[0]:
-        raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {nb} photon energies")
-    lateral = tuple(n for k, n in enumerate(ne.shape[:3]) if k != p.axis) if 0 <= p.axis <= 2 else ne.shape[:2]
-    if backlight is not None:
-        backlight = f64(backlight)
-        if backlight.shape != (nb,) + lateral:
-            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lateral grid give {(nb,) + lateral}")
-    I, tau = np.empty((nb,) + lateral), np.empty((nb,) + lateral)
-    ms = C.c_double(0.0)
-    check(lib.sr_field_emission_table(ne._h, handles[0], handles[1], C.byref(t), C.byref(p), ptr(backlight), ptr(I), ptr(tau),
-                                      C.byref(ms)))
-    del keep
-    ne.last_kernel_ms = float(ms.value)
-    return I, tau
+    _handle("ne", ne)
+    t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
+    omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
+    if len(omegas) != keep[2].shape[0]:
+        raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
+    return _emission(lib.sr_field_emission_table, ne, Te, Z, omegas, axis, toward, backlight, C.byref(t))
 
 
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
@@ -548,9 +534,7 @@ def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, im
     dict with the arrays named in `want` -- "sf" (6, n), "hits" (2, n; times hit_scale), "steps" (n) int32, "flags" (n) uint8
     (PUSH_UNFINISHED | PUSH_MISSED) -- and "stats" (PushStats).  image: a counts DetectorImage the particles with flags == 0 are
     added to on the device."""
-    for name, f in (("E", E), ("B", B)):
-        if f is not None and (not isinstance(f, Field) or not getattr(f, "_h", None)):
-            raise ValueError(f"{name} must be an open engine.Field or None")
+    h_E, h_B = _handle("E", E, none=True), _handle("B", B, none=True)
     s0 = f64(s0)
     if s0.ndim != 2 or s0.shape[0] != 6:
         raise ValueError(f"s0 must have shape (6, n), got {s0.shape}")
@@ -571,7 +555,7 @@ def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, im
         out["flags"] = np.empty(n, np.uint8)
     p = push_params(qm, dt, max_steps, axis, det_pos, hit_scale)
     st = _ffi.PushStats()
-    check(lib.sr_particles_push(None if E is None else E._h, None if B is None else B._h, C.byref(p), n, ptr(s0),
+    check(lib.sr_particles_push(h_E, h_B, C.byref(p), n, ptr(s0),
                                 ptr(out.get("sf")), ptr(out.get("hits")), ptr(out.get("steps")), ptr(out.get("flags")),
                                 None if image is None else image._h, C.byref(st)))
     out["stats"] = PushStats(float(st.kernel_ms), int(st.finished), int(st.unfinished), int(st.missed), int(st.deposited))
@@ -586,18 +570,8 @@ def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavel
     vector Field or None (no flow) -- all on one grid and of one dtype.  lambda_i: the probe's wavelength [m]; ion_mass: the mass
     number A; points (M, Nq, 3) [m] and weights (M, Nq) [m]; ki, ks: the unit probe and collection directions, (3,) or (M, 3);
     wavelengths (n_lambda) [m].  ne.last_kernel_ms keeps the kernel's time."""
-    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
-        raise ValueError("ne must be an open engine.Field")
-    handles = [ne._h]
-    for name, a, other in (("Te", Te, ""), ("Ti", Ti, " or None"), ("Z", Z, " or a number"), ("V", V, " or None")):
-        if isinstance(a, Field):
-            if not getattr(a, "_h", None):
-                raise ValueError(f"the field {name} has been closed")
-            handles.append(a._h)
-        elif (other == " or None" and a is None) or (name == "Z" and a is not None and np.ndim(a) == 0):
-            handles.append(None)
-        else:
-            raise ValueError(f"{name} must be an open engine.Field{other}")
+    handles = [_handle("ne", ne), _handle("Te", Te), _handle("Ti", Ti, none=True), _handle("Z", Z, number=True),
+               _handle("V", V, none=True)]
     points, weights = f64(points), f64(weights)
     if points.ndim != 3 or points.shape[2] != 3 or weights.shape != points.shape[:2]:
         raise ValueError(f"points must be (M, Nq, 3) and weights (M, Nq), got {points.shape} and {weights.shape}")
@@ -654,18 +628,7 @@ def wave(ne, Te, Z, U, frame, lambda_, axis, toward=+1, absorber=None, want_powe
     every screen (wave.edge_absorber), or None.  The field varies as exp(+i(kz - wt)) without its carrier: plasma retards the phase.
     ne.last_kernel_ms keeps the march's HIP-event time.  time_parts=True puts an event between all the launches and returns a
     third value, (hipFFT ms, own kernels ms): a measurement mode (tools/wave_rate.py)."""
-    if not isinstance(ne, Field) or not getattr(ne, "_h", None):
-        raise ValueError("ne must be an open engine.Field")
-    handles = []
-    for name, a in (("Te", Te), ("Z", Z)):
-        if isinstance(a, Field):
-            if not getattr(a, "_h", None):
-                raise ValueError(f"the field {name} has been closed")
-            handles.append(a._h)
-        elif a is None or np.ndim(a) == 0:
-            handles.append(None)
-        else:
-            raise ValueError(f"{name} must be an open engine.Field, a number or None")
+    handles = [_handle("ne", ne)] + [_handle(name, a, number=True, none=True) for name, a in (("Te", Te), ("Z", Z))]
     U = _complex_field(U)
     mu, mv = U.shape
     p = wave_params(frame, U.shape, lambda_, axis, toward, 0.0 if isinstance(Z, Field) or Z is None else float(Z), time_parts)
@@ -679,7 +642,7 @@ def wave(ne, Te, Z, U, frame, lambda_, axis, toward=+1, absorber=None, want_powe
     n_cells = ne.shape[p.axis] - 1 if 0 <= p.axis <= 2 else 1
     power = np.zeros(n_cells) if want_power else None
     ms = (C.c_double * 3)(0.0, 0.0, 0.0)
-    check(lib.sr_field_wave(ne._h, handles[0], handles[1], C.byref(p), ptr(fu), ptr(fv), ptr(wu), ptr(wv), ptr(U), ptr(out), ptr(power), ms))
+    check(lib.sr_field_wave(*handles, C.byref(p), ptr(fu), ptr(fv), ptr(wu), ptr(wv), ptr(U), ptr(out), ptr(power), ms))
     ne.last_kernel_ms = float(ms[0])
     if time_parts:
         return out, power, (float(ms[1]), float(ms[2]))

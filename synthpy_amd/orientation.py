@@ -13,13 +13,14 @@ frame's axes are the lab's turned by R (its axis k is column k of R, so node q o
 the source's generation and flags: solve, the region loop, line_integrals and export_scalar_field work on it unchanged, and
 probing it along z looks along the lab direction R e_z.  The resampling is trilinear and runs on the GPU
 (engine.Field.resample -> sr_field_resample, include/synthray.h states its rule); each source field is uploaded once, and
-views() keeps the uploads in HBM across the angles.  engine.Field takes the general affine form p = M q + t.
+views() keeps the uploads in HBM across the angles (fields.SourceFields, which the other field diagnostics stage through as well;
+it is importable from here too).  engine.Field takes the general affine form p = M q + t.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from . import engine
+from .fields import SourceFields, staged
 
 _ABOUT = {"x": 0, "y": 1, "z": 2}
 _QUARTER = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}  # angle -> (cos, sin), exactly
@@ -67,29 +68,6 @@ def check_orthonormal(R, tol=1e-12):
     return R
 
 
-class SourceFields:
-    """The fields of one domain as engine.Field handles, each uploaded at its first use and kept until close()."""
-
-    def __init__(self, domain):
-        self.domain = domain
-        self.fields = {}
-
-    def get(self, name, array):
-        if name not in self.fields:
-            d = self.domain
-            self.fields[name] = engine.Field(array, d.x, d.y, d.z)
-        return self.fields[name]
-
-    @property
-    def nbytes(self):
-        return sum(f.nbytes for f in self.fields.values())
-
-    def close(self):
-        for f in self.fields.values():
-            f.close()
-        self.fields = {}
-
-
 def _new_domain(domain, dims, lengths):
     """An empty domain of the source's generation and flags, and its grid."""
     if hasattr(domain, "_volume_cache"):  # simulator.ScalarDomain(lengths, dims, ...)
@@ -135,14 +113,10 @@ def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=N
     ne = getattr(domain, "ne", None)
     if ne is None:
         raise ValueError("the domain holds no ne yet")
-    if source is not None and source.domain is not domain:
-        raise ValueError("source holds the fields of another domain")
-    own = source is None
-    src = SourceFields(domain) if own else source
     new = _new_domain(domain, dims, lengths)
     grid = (new.x, new.y, new.z)
     zero = (0.0, 0.0, 0.0)
-    try:
+    with staged(domain, source, "source") as src:
         new.external_ne(src.get("ne", ne).resample(R, zero, grid, fill=fills["ne"]))
         for name in ("Te", "Z", "Ti"):
             a = getattr(domain, name, None)
@@ -158,22 +132,12 @@ def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=N
         V = getattr(domain, "V", None)
         if V is not None:
             new.V = src.get("V", V).resample(R, zero, grid, V=R.T, fill=fills.get("V", _EXTRA_FILL["V"]))
-    finally:
-        if own:
-            src.close()
     return new
 
 
 def views(domain, angles_deg, about="y", **kw):
     """A generator of rotated(domain, angle, about, **kw) over angles_deg that uploads each source field once and keeps it in
     HBM across the angles; the uploads are released when the generator ends or is closed."""
-    src = kw.pop("source", None)
-    own = src is None
-    if own:
-        src = SourceFields(domain)
-    try:
+    with staged(domain, kw.pop("source", None), "source") as src:
         for angle in angles_deg:
             yield rotated(domain, angle, about, source=src, **kw)
-    finally:
-        if own:
-            src.close()

@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
+from .fields import locate
 
 c = engine.c
 
@@ -116,11 +117,7 @@ def bilinear(coords, m, p, q):
     gu, gv = coords
     with np.errstate(invalid="ignore"):
         inside = (p >= gu[0]) & (p <= gu[-1]) & (q >= gv[0]) & (q <= gv[-1])
-    ps, qs = np.where(inside, p, gu[0]), np.where(inside, q, gv[0])
-    i = np.clip(np.searchsorted(gu, ps, side="right") - 1, 0, len(gu) - 2)
-    j = np.clip(np.searchsorted(gv, qs, side="right") - 1, 0, len(gv) - 2)
-    t = (ps - gu[i]) / (gu[i + 1] - gu[i])
-    s = (qs - gv[j]) / (gv[j + 1] - gv[j])
+    (i, t, _), (j, s, _) = locate(gu, np.where(inside, p, gu[0])), locate(gv, np.where(inside, q, gv[0]))
     out = ((1 - t) * (1 - s) * m[..., i, j] + t * (1 - s) * m[..., i + 1, j]
            + (1 - t) * s * m[..., i, j + 1] + t * s * m[..., i + 1, j + 1])
     return np.where(inside, out, np.nan)

@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
+from .fields import grid_f64, locate, staged
 
 c = engine.c
 M_P = 1.67262192369e-27      # kg (CODATA 2018)
@@ -143,7 +144,7 @@ def entry(s0, lo, hi):
 def entry_cell_order(s, g):
     """The stable order of the states s (6, n) by the cell (x slowest, z fastest: the fields' memory order) their positions lie in;
     g: the three float64 node arrays.  Neighbouring lanes of the push kernel then gather neighbouring nodes."""
-    cell = [np.clip(np.searchsorted(g[k], s[k], side="right") - 1, 0, len(g[k]) - 2) for k in range(3)]
+    cell = [locate(g[k], s[k])[0] for k in range(3)]
     key = (cell[0] * (len(g[1]) - 1) + cell[1]) * (len(g[2]) - 1) + cell[2]
     return np.argsort(key, kind="stable")
 
@@ -186,7 +187,7 @@ class Radiograph:
 
 def default_steps(domain, source, dt=None):
     """(dt, max_steps): dt, or a quarter of the smallest cell width over |v|; twice the box diagonal over |v| dt."""
-    g = [np.float64(np.float32(a)) for a in (domain.x, domain.y, domain.z)]
+    g = grid_f64(domain)
     h = min(float(np.min(np.diff(a))) for a in g)
     diag = float(np.sqrt(sum((a[-1] - a[0]) ** 2 for a in g)))
     dt = 0.25 * h / source.speed if dt is None else float(dt)
@@ -199,16 +200,14 @@ def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sor
     coordinate[source.axis] == det_pos [m].  dt, max_steps: default_steps.  image: an engine.DetectorImage of counts the pushed
     particles are added to on the device (zero it first if it is reused), or None for a detector of `bins` over the shadow of
     the box's centre plane.  sort: order the particles by entry cell before the upload (neighbouring lanes gather neighbouring
-    nodes) and undo the order on the outputs; the per-particle results are the same bits either way.  fields: an
-    orientation.SourceFields of the domain whose uploads are reused.  Returns a Radiograph."""
-    from .orientation import SourceFields
-
+    nodes) and undo the order on the outputs; the per-particle results are the same bits either way.  fields: a
+    fields.SourceFields of the domain whose uploads are reused.  Returns a Radiograph."""
     a = source.axis
     B, E = getattr(domain, "B", None), getattr(domain, "E", None)
     if B is None and E is None:
         raise ValueError("the domain holds neither B (external_B / test_B) nor E (external_E)")
     det_pos = float(det_pos)
-    g = [np.float64(np.float32(v)) for v in (domain.x, domain.y, domain.z)]
+    g = grid_f64(domain)
     lo, hi = np.array([v[0] for v in g]), np.array([v[-1] for v in g])
     dt, default_max = default_steps(domain, source, dt)
     max_steps = default_max if max_steps is None else int(max_steps)
@@ -229,8 +228,6 @@ def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sor
         if not isinstance(image, engine.DetectorImage) or image.kind != engine.IMG_COUNTS:
             raise ValueError("image must be an engine.DetectorImage of counts")
         own_image = False
-    if fields is not None and fields.domain is not domain:
-        raise ValueError("fields holds the fields of another domain")
 
     s0 = source.states()
     n = s0.shape[1]
@@ -241,22 +238,16 @@ def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sor
     steps = np.zeros(n, np.int32)
     idx = np.nonzero(meets)[0]
     stats = engine.PushStats(0.0, 0, 0, 0, 0)
-    if len(idx):
-        sub = s_in[:, idx]
-        if sort:
-            order = entry_cell_order(sub, g)
-            idx, sub = idx[order], sub[:, order]
-        own = fields is None
-        src = SourceFields(domain) if own else fields
-        if E is not None and B is not None and np.asarray(E).dtype != np.asarray(B).dtype:
-            E, B = np.asarray(E, np.float64), np.asarray(B, np.float64)  # the kernel reads both fields in one dtype
-        try:
-            out = engine.push_particles(None if E is None else src.get("E", E), None if B is None else src.get("B", B),
-                                        np.ascontiguousarray(sub), source.qm, dt, max_steps, a, det_pos, hit_scale, image=image)
-        finally:
-            if own:
-                src.close()
-        sf[:, idx], hits[:, idx], flags[idx], steps[idx], stats = out["sf"], out["hits"], out["flags"], out["steps"], out["stats"]
+    with staged(domain, fields) as src:  # fields of another domain are refused whether or not a particle meets the box
+        if len(idx):
+            sub = s_in[:, idx]
+            if sort:
+                order = entry_cell_order(sub, g)
+                idx, sub = idx[order], sub[:, order]
+            f = src.get_all({"E": None if E is None else np.asarray(E), "B": None if B is None else np.asarray(B)})
+            out = engine.push_particles(f["E"], f["B"], np.ascontiguousarray(sub), source.qm, dt, max_steps, a, det_pos, hit_scale,
+                                        image=image)
+            sf[:, idx], hits[:, idx], flags[idx], steps[idx], stats = out["sf"], out["hits"], out["flags"], out["steps"], out["stats"]
     counts = np.array(image.counts_f64())
     x_lo, x_hi, y_lo, y_hi = image.range
     rest = ~meets & (flags == 0)

@@ -18,6 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import engine
+from .fields import grid_f64, locate, staged
 
 E_CHARGE = engine.E_CHARGE    # C
 EPS0 = 8.8541878128e-12       # F/m (CODATA 2018)
@@ -155,15 +156,8 @@ def instrument_convolve(power, wavelengths, fwhm):
 
 def _at(domain, arrays, points):
     """The trilinear values of the 3-D `arrays` at `points` (M, 3) on the host (NaN outside the grid): the volume centres."""
-    g = [np.float64(np.float32(a)) for a in (domain.x, domain.y, domain.z)]
-    inside = np.ones(len(points), bool)
-    cells, ws = [], []
-    for k in range(3):
-        p = points[:, k]
-        inside &= (p >= g[k][0]) & (p <= g[k][-1])
-        i = np.clip(np.searchsorted(g[k], p, side="right") - 1, 0, len(g[k]) - 2)
-        cells.append(i)
-        ws.append((np.clip(p, g[k][0], g[k][-1]) - g[k][i]) / (g[k][i + 1] - g[k][i]))
+    cells, ws, ins = zip(*(locate(g, points[:, k]) for k, g in enumerate(grid_f64(domain))))
+    inside = ins[0] & ins[1] & ins[2]
     out = []
     for a in arrays:
         v = np.zeros(len(points))
@@ -182,18 +176,14 @@ def spectra(domain, probe, collection, wavelengths, ion_mass, instrument_fwhm=No
     `collection` at `wavelengths` [m], the ion's mass number ion_mass: a ThomsonSpectra with
         power = r_e^2 (1 - (ks . e)^2) P        (the polarisation factor is 1 when the probe has no polarisation)
     P engine.thomson's, in scattered energy per incident energy, per steradian and per metre of wavelength.  instrument_fwhm
-    [m]: a Gaussian instrument function applied on the host (instrument_convolve; a uniform grid).  fields: an
-    orientation.SourceFields of the domain whose uploads are reused across calls (a fit loop, a sweep)."""
-    from .orientation import SourceFields
-
+    [m]: a Gaussian instrument function applied on the host (instrument_convolve; a uniform grid).  fields: a
+    fields.SourceFields of the domain whose uploads are reused across calls (a fit loop, a sweep)."""
     if not isinstance(probe, Probe) or not isinstance(collection, Collection):
         raise ValueError("probe must be a thomson.Probe and collection a thomson.Collection")
     ne, Te, Z = getattr(domain, "ne", None), getattr(domain, "Te", None), getattr(domain, "Z", None)
     if ne is None or Te is None or Z is None:
         raise ValueError("the domain needs ne, Te (external_Te) and Z (external_Z)")
     Ti, V = getattr(domain, "Ti", None), getattr(domain, "V", None)
-    if fields is not None and fields.domain is not domain:
-        raise ValueError("fields holds the fields of another domain")
     lam = np.asarray(wavelengths, np.float64)
     if lam.ndim != 1 or not np.all(np.isfinite(lam)) or np.any(lam <= 0):
         raise ValueError("wavelengths must be one-dimensional, finite and positive")
@@ -209,28 +199,12 @@ def spectra(domain, probe, collection, wavelengths, ion_mass, instrument_fwhm=No
              "Z": np.asarray(Z) if np.ndim(Z) == 3 else None, "V": None if V is None else np.asarray(V)}
     if named["V"] is not None and named["V"].shape != tuple(shape) + (3,):
         raise ValueError(f"V has shape {named['V'].shape}, the domain needs {tuple(shape) + (3,)}")
-    # the kernel reads every field in one dtype: float32 when all are, else float64 (uploaded under a name of its own)
-    single = all(a.dtype == np.float32 for a in named.values() if a is not None)
     pts, wts = collection.quadrature(probe)
-    own = fields is None
-    src = SourceFields(domain) if own else fields
-
-    def field(name):
-        a = named[name]
-        if a is None:
-            return None
-        if single or a.dtype == np.float64:
-            return src.get(name, a)
-        return src.get(name + ":float64", np.asarray(a, np.float64))
-
-    try:
-        f_ne = field("ne")
-        P, weight = engine.thomson(f_ne, field("Te"), field("Ti"), field("Z") if named["Z"] is not None else float(Z), field("V"),
+    with staged(domain, fields) as src:
+        f = src.get_all(named)  # the kernel reads every field in one dtype
+        P, weight = engine.thomson(f["ne"], f["Te"], f["Ti"], f["Z"] if f["Z"] is not None else float(Z), f["V"],
                                    probe.wavelength, ion_mass, pts, wts, ki, ks, lam)
-        kernel_ms = f_ne.last_kernel_ms
-    finally:
-        if own:
-            src.close()
+        kernel_ms = f["ne"].last_kernel_ms
     pol = 1.0 if probe.polarisation is None else 1.0 - (ks @ probe.polarisation) ** 2
     power = (R_E * R_E * pol * np.ones(len(ks)))[:, None] * P
     if instrument_fwhm is not None:

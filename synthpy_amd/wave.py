@@ -21,6 +21,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
+from .fields import staged
 
 _LATERAL = {0: ("y", "z"), 1: ("x", "z"), 2: ("x", "y")}
 
@@ -161,10 +162,9 @@ def propagate(domain, source, toward="+", absorb=False, absorber=None, fields=No
     """March `source` (a Source) through `domain` (a ScalarDomain of either API generation) along its probing_direction: a
     WaveField on the last node plane of the march.  toward "+": from the first node plane to the last (the way the rays
     travel), "-": the reverse.  absorb: inverse-bremsstrahlung absorption from the domain's Te (external_Te) and Z (external_Z; an
-    array or a number).  absorber: None, a fraction (edge_absorber(mu, mv, frac)) or the windows (wu, wv) themselves.  fields: an
-    orientation.SourceFields of the domain whose uploads are reused across calls."""
+    array or a number).  absorber: None, a fraction (edge_absorber(mu, mv, frac)) or the windows (wu, wv) themselves.  fields: a
+    fields.SourceFields of the domain whose uploads are reused across calls."""
     from .emission import _toward
-    from .orientation import SourceFields
 
     if not isinstance(source, Source):
         raise ValueError("source must be a wave.Source")
@@ -173,8 +173,6 @@ def propagate(domain, source, toward="+", absorb=False, absorber=None, fields=No
     ne = getattr(domain, "ne", None)
     if ne is None:
         raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
-    if fields is not None and fields.domain is not domain:
-        raise ValueError("fields holds the fields of another domain")
     named = {"ne": np.asarray(ne)}
     Z_value = 0.0
     if absorb:
@@ -189,24 +187,9 @@ def propagate(domain, source, toward="+", absorb=False, absorber=None, fields=No
     mu, mv = source.U.shape
     if absorber is not None and np.ndim(absorber) == 0:
         absorber = edge_absorber(mu, mv, absorber)
-    single = all(a.dtype == np.float32 for a in named.values())
-    own = fields is None
-    src = SourceFields(domain) if own else fields
-
-    def field(name):
-        a = named.get(name)
-        if a is None:
-            return None
-        if single or a.dtype == np.float64:
-            return src.get(name, a)
-        return src.get(name + ":float64", np.asarray(a, np.float64))
-
-    try:
-        f_ne = field("ne")
-        res = engine.wave(f_ne, field("Te"), field("Z") if "Z" in named else Z_value, source.U, source.frame, source.wavelength, axis,
-                          sign, absorber, time_parts=time_parts)
-        kernel_ms = f_ne.last_kernel_ms
-    finally:
-        if own:
-            src.close()
+    with staged(domain, fields) as src:
+        f = src.get_all(named)  # the kernel reads every field in one dtype
+        res = engine.wave(f["ne"], f.get("Te"), f.get("Z", Z_value), source.U, source.frame, source.wavelength, axis, sign, absorber,
+                          time_parts=time_parts)
+        kernel_ms = f["ne"].last_kernel_ms
     return WaveField(res[0], source.frame, source.wavelength, _LATERAL[axis], res[1], kernel_ms, res[2] if time_parts else None)

@@ -281,7 +281,7 @@ def test_header_ctypes_and_python_signatures(built):
 
     names = lambda f: list(inspect.signature(f).parameters)
     assert names(engine.emission) == ["ne", "Te", "Z", "omegas", "axis", "toward", "backlight"]
-    assert names(emission.self_emission) == ["domain", "wavelengths", "toward", "backlight"]
+    assert names(emission.self_emission) == ["domain", "wavelengths", "toward", "backlight", "fields"]
     assert names(NewDomain.self_emission) == names(OldDomain.self_emission) == ["self", "wavelengths", "toward", "backlight"]
     # the host's band constants against their definitions in np.longdouble: a few roundings each
     Lw = np.longdouble

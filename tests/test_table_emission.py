@@ -389,7 +389,7 @@ def test_header_ctypes_and_python_signatures(built):
 
     names = lambda f: list(inspect.signature(f).parameters)
     assert names(engine.emission_table) == ["ne", "Te", "Z", "table", "axis", "toward", "backlight"]
-    assert names(emission.table_emission) == ["domain", "table", "toward", "backlight"]
+    assert names(emission.table_emission) == ["domain", "table", "toward", "backlight", "fields"]
     assert names(NewDomain.table_emission) == names(OldDomain.table_emission) == ["self", "table", "toward", "backlight"]
     assert names(eos_opacity.read_propaceos) == ["file_name", "need_zf_table", "need_en_table", "need_eion", "need_eele", "need_pion",
                                                  "need_pele", "need_ross_opacity", "need_emiss_opacity", "need_abs_opacity"]

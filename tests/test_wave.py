@@ -697,9 +697,9 @@ def test_field_checks_need_live_fields(eng):
     moved = eng.Field(p["Te"], AX32[0], AX32[1], AX32[2] + np.float32(1e-6))
     small = eng.Field(p["Z"][:-1], AX32[0][:-1], AX32[1], AX32[2])
     try:
-        for args, msg in (((vec, None, None), "ne is a vector field"), ((ne, vec, 1.0), "Te is a vector field"),
-                          ((ne, Te32, 1.0), "Te and ne differ in dtype"), ((ne, moved, 1.0), "grids of Te and ne differ on axis 2"),
-                          ((ne, Te, small), "grids of Z and ne differ on axis 0"), ((ne, Te, np.nan), "uniform Z")):
+        for args, msg in (((vec, None, None), "ne must have n_comp == 1"), ((ne, vec, 1.0), "Te must have n_comp == 1"),
+                          ((ne, Te32, 1.0), "ne and Te differ in dtype"), ((ne, moved, 1.0), "grids of ne and Te differ on axis 2"),
+                          ((ne, Te, small), "grids of ne and Z differ on axis 0"), ((ne, Te, np.nan), "uniform Z")):
             with pytest.raises(built.SynthrayError, match=msg):
                 eng.wave(*args, U, frame, LAM, 2)
         with pytest.raises(ValueError, match="absorber"):
