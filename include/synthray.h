@@ -54,6 +54,17 @@ int sr_synchronize(void);            /* waits for every stream of the library */
 /* HBM free / in all on the selected device (hipMemGetInfo): what ScalarDomain's auto_batching sizes its regions from
  * (the reference asks psutil / pynvml, src/simulator/domain.py:140-165) */
 int sr_device_memory(int64_t *free_bytes, int64_t *total_bytes);
+/* Every launch that covers its work with a grid-stride loop takes min(the blocks the work needs, n_cu * k) blocks (k = 4 .. 64
+ * per site, at least one block).  sr_grid_cus sets the n_cu those caps are sized for -- a measurement and test knob, like
+ * SYNTHRAY_RESAMPLE_BRICK: fewer compute units make the loops take their later trips at small sizes, and it is an occupancy
+ * knob for timing.  n_cu > 0: as on a device of n_cu compute units; 0: back to the device's own count (the default; results
+ * and grids are then exactly what they are without this call); -1: read only; anything else is SR_ERR_INVALID.  *in_force
+ * (may be NULL) receives the count now in force.  No kernel needs a minimum grid: results do not depend on the count, bit for
+ * bit, except where an entry point says that it adds with floating-point atomics. */
+int sr_grid_cus(int n_cu, int *in_force);
+/* out[0]: launches sized by such a cap since the last reset; out[1]: those of them that got fewer blocks than they wanted,
+ * i.e. whose loop takes a second trip.  reset != 0 zeroes both after reading; out may be NULL. */
+int sr_grid_stats(int64_t out[2], int reset);
 /* Every call queues its GPU work on the library's SELECTED stream (0 by default; 1 = a second one).  Work on different
  * streams may overlap: a job of many small ray bundles alternates them so that one bundle's tail runs beside the next
  * one's start-up (the reference's drivers trace 5e5-ray chunks one after the other, pvti_trace_mpi.py:144-163).  The

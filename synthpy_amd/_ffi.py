@@ -114,6 +114,8 @@ SYMBOLS = {
     "sr_device_count": (_i, []),
     "sr_synchronize": (_i, []),
     "sr_device_memory": (_i, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sr_grid_cus": (_i, [_i, C.POINTER(C.c_int)]),
+    "sr_grid_stats": (_i, [C.POINTER(C.c_int64), _i]),
     "sr_last_error": (C.c_char_p, []),
     "sr_version": (C.c_char_p, []),
     "sr_stream_select": (_i, [_i]),

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -54,6 +55,10 @@ struct Context {
   hipEvent_t side_ev[kStreams][2] = {};
   int current = 0;
   int n_cu = 256;
+  // sr_grid_cus / sr_grid_stats (capped_grid below): the compute-unit count the grid caps are sized for when > 0 (0: n_cu),
+  // the launches that went through capped_grid since the last reset, and those that got fewer blocks than they wanted
+  int grid_cus_override = 0;
+  int64_t grid_launches = 0, grid_short = 0;
 };
 Context &ctx();
 int ensure_init();  // sr_init(0) on first use
@@ -70,6 +75,24 @@ inline void dev_free(void *p) {
 }
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+// The grid of every launch that covers its work with a grid-stride loop: the blocks the work needs, at most per_cu blocks per
+// compute unit (and at least one).  Each call is ONE launch: it is counted in the context, and so is a launch that gets fewer
+// blocks than it wanted and therefore takes a second trip through its loop (sr_grid_stats).  grid_cus() is the device's
+// compute-unit count unless sr_grid_cus has set another one, a measurement and test knob: no kernel needs a minimum grid to
+// be correct, so every site takes the cap as it comes (at 1 compute unit: per_cu blocks).
+inline int grid_cus() {
+  const Context &c = ctx();
+  return c.grid_cus_override > 0 ? c.grid_cus_override : c.n_cu;
+}
+inline unsigned capped_grid(int64_t blocks_wanted, int per_cu) {
+  Context &c = ctx();
+  const int n_cu = grid_cus();
+  const int64_t cap = (int64_t)n_cu * per_cu;
+  ++c.grid_launches;
+  if (blocks_wanted > cap) ++c.grid_short;
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_wanted, cap));
+}
 
 // Device memory for the staging of ONE call (download in ray order, counts as float64, amplitude, sr_rays_optics): a block per
 // stream that grows and is kept, so that the entry points a caller loops over do not hipMalloc / hipFree (each waits for the

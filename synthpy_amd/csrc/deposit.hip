@@ -1070,7 +1070,7 @@ int sr_rays_deposit(const sr_rays *r, const sr_optic *chain, int n_ops, const sr
   if (exact) {
     SR_HIP(hipGetLastError());
     if ((rc = sr::retrace_f64(r, G.list, G.count))) return rc;
-    const unsigned lgrid = (unsigned)std::min<int64_t>(grid, (int64_t)c.n_cu * 8);
+    const unsigned lgrid = sr::capped_grid(grid, 8);
     hipLaunchKernelGGL(k_deposit_list, dim3(lgrid), dim3(256), 0, st, C, N, rf, ex, ey, (uint32_t *)img->d, r->counters,
                        (const uint32_t *)G.list, (const unsigned long long *)G.count);
   }

@@ -199,7 +199,7 @@ void launch(const EmArgs &A, const typename P::Args &X, size_t lds_bytes, int ax
               constexpr int kNb = decltype(nb)::value;
               if (axis == 2) {
                 // one wavefront per column, 4 to a workgroup; at most 8 workgroups per CU, the remaining columns by grid stride
-                const unsigned grid = (unsigned)std::min<int64_t>((A.ncol + 3) / 4, (int64_t)sr::ctx().n_cu * 8);
+                const unsigned grid = sr::capped_grid((A.ncol + 3) / 4, 8);
                 hipLaunchKernelGGL((k_emission_z<T, kTe, kZ, kNb, P>), dim3(grid), dim3(256), lds_bytes, st, A, X);
               } else {
                 hipLaunchKernelGGL((k_emission_xy<T, kTe, kZ, kNb, P>), dim3(sr::grid_for(A.ncol, P::kXYBlock)), dim3(P::kXYBlock),

@@ -214,8 +214,7 @@ int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[
     return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
   }
   const int block = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((nn + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
-  hipLaunchKernelGGL(k_to_complex, dim3(grid), dim3(block), 0, st, (const double *)d_r, nn, d_w);
+  hipLaunchKernelGGL(k_to_complex, dim3(sr::capped_grid((nn + block - 1) / block, 32)), dim3(block), 0, st, (const double *)d_r, nn, d_w);
   if ((rc = fft_plan(F, ndim, (int)n[0], (int)n[1], (int)n[2], &plan))) {
     cleanup();
     return rc;
@@ -228,7 +227,7 @@ int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[
   }
   const int lds = n_bins <= kMaxLdsBins;
   const size_t lds_bytes = lds ? (sizeof(double) + sizeof(unsigned long long)) * (size_t)n_bins : 0;
-  const unsigned bgrid = std::min<unsigned>(grid, (unsigned)sr::ctx().n_cu * 8);
+  const unsigned bgrid = sr::capped_grid((nn + block - 1) / block, 8);
   const double *k0 = d_k, *k1 = d_k + n[0], *k2 = d_k + n[0] + n[1];
   if (rule == SR_SPECTRUM_EDGES)
     hipLaunchKernelGGL(k_spectrum_bins<SR_SPECTRUM_EDGES>, dim3(bgrid), dim3(block), lds_bytes, st, (const double2 *)d_w, nn,
@@ -362,12 +361,12 @@ hipError_t run_modesum(const double *d_in, int pmask, int M, const int64_t n[3],
   double2 *X = d_tab, *Y = X + p0 * M, *S = Y + p1 * M, *D = S + n[2] * M;
   const int block = 256;
   const int64_t n_tab = (p0 + p1 + n[2]) * M;
-  const unsigned tgrid = (unsigned)std::min<int64_t>((n_tab + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+  const unsigned tgrid = sr::capped_grid((n_tab + block - 1) / block, 32);
   hipLaunchKernelGGL(k_modesum_tables, dim3(tgrid), dim3(block), 0, st, d_in, d_in + n_axes, d_in + n_axes + 3 * M,
                      d_in + n_axes + 4 * M, pmask, M, n[0], n[1], n[2], p0, p1, X, Y, S, D);
   const int64_t tiles_l = (n[2] + 63) / 64, n_tiles = tiles_l * (p1 / JT) * (p0 / T);
   const int64_t waves = kModesumBlock / 64;
-  const unsigned grid = (unsigned)std::min<int64_t>((n_tiles + waves - 1) / waves, (int64_t)sr::ctx().n_cu * 64);
+  const unsigned grid = sr::capped_grid((n_tiles + waves - 1) / waves, 64);
   hipLaunchKernelGGL((k_modesum<T, JT>), dim3(grid), dim3(kModesumBlock), 0, st, (const double2 *)X, (const double2 *)Y,
                      (const double2 *)S, (const double2 *)D, M, n[0], n[1], n[2], p0, p1, tiles_l, n_tiles, out);
   return hipGetLastError();
@@ -460,8 +459,8 @@ extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0,
   SR_TRY(hipMemcpyAsync(d_a, amp, sizeof(float) * n, hipMemcpyHostToDevice, st));
   SR_TRY(hipMemsetAsync(d_m, 0, sizeof(unsigned long long), st));
   const int block = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
-  hipLaunchKernelGGL(k_shape_noise, dim3(grid), dim3(block), 0, st, d_w, (const float *)d_a, n);
+  const int64_t blocks = (n + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
+  hipLaunchKernelGGL(k_shape_noise, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_w, (const float *)d_a, n);
   SR_TRY(hipGetLastError());
   if ((rc = fft_plan(F, 3, n0, n1, n2, &plan))) {  // C order: n2 fastest, as the NumPy array
     cleanup();
@@ -472,8 +471,8 @@ extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0,
   sr::dev_free(d_a);
   d_a = nullptr;
   SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_f), sizeof(double) * n));
-  hipLaunchKernelGGL(k_real_scaled, dim3(grid), dim3(block), 0, st, (const double2 *)d_w, n, 1.0 / (double)n, d_f, d_m);
-  if (normalise) hipLaunchKernelGGL(k_divide, dim3(grid), dim3(block), 0, st, d_f, n, (const unsigned long long *)d_m);
+  hipLaunchKernelGGL(k_real_scaled, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const double2 *)d_w, n, 1.0 / (double)n, d_f, d_m);
+  if (normalise) hipLaunchKernelGGL(k_divide, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_f, n, (const unsigned long long *)d_m);
   SR_TRY(hipGetLastError());
   SR_TRY(hipMemcpyAsync(out, d_f, sizeof(double) * n, hipMemcpyDeviceToHost, st));
   SR_TRY(hipStreamSynchronize(st));

@@ -524,7 +524,7 @@ struct Buffers {
   } while (0)
 
 unsigned grid_of(int64_t n, int block, int per_cu) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, (int64_t)sr::ctx().n_cu * per_cu));
+  return sr::capped_grid((n + block - 1) / block, per_cu);
 }
 
 // Andrew's monotone chain over the rays idx: the strict convex hull (collinear and repeated points dropped),

@@ -120,7 +120,7 @@ int sr_volume_project(const sr_volume *v, double *maps, uint32_t *have) {
   SR_HIP(hipMemcpyAsync(d_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, st));
   // memory-bound: at most 8 blocks of 256 threads per CU, the remaining column groups by grid stride
   const int block_threads = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((ncol * 8 + block_threads - 1) / block_threads, (int64_t)sr::ctx().n_cu * 8);
+  const unsigned grid = sr::capped_grid((ncol * 8 + block_threads - 1) / block_threads, 8);
   const bool ph = v->L != nullptr, ka = v->K != nullptr, fa = v->Q != nullptr;
 #define SR_PROJ_LAUNCH(PH, KA, FA) hipLaunchKernelGGL((k_project<PH, KA, FA>), dim3(grid), dim3(block_threads), 0, st, A)
   switch ((ph ? 1 : 0) | (ka ? 2 : 0) | (fa ? 4 : 0)) {

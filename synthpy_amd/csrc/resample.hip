@@ -226,7 +226,7 @@ int sr_field_resample(const sr_field *f, const sr_resample_params *p, int mx, in
 
   SR_HIP(hipMemcpyAsync(d_o, o.data(), sizeof(double) * o.size(), hipMemcpyHostToDevice, st));
   // a gather bound by memory latency: 8 workgroups of 256 threads per CU, the remaining bricks by grid stride (a multiple of 8)
-  const unsigned grid = (unsigned)std::min<int64_t>(A.nvb, (int64_t)c.n_cu * 8);
+  const unsigned grid = sr::capped_grid(A.nvb, 8);
   SR_HIP(hipEventRecord(c.ev[0], st));
   if (f->is_f64) {
     if (f->n_comp == 3)

@@ -414,6 +414,26 @@ int sr_device_memory(int64_t *free_bytes, int64_t *total_bytes) {
   return SR_OK;
 }
 
+// The compute-unit count sr::capped_grid sizes its caps for (common.hpp) and what it has counted.
+int sr_grid_cus(int n_cu, int *in_force) {
+  SR_CHECK(n_cu >= -1, "sr_grid_cus: n_cu must be > 0 (set), 0 (the device's own count) or -1 (read only), got %d", n_cu);
+  int rc = sr::ensure_init();
+  if (rc) return rc;
+  if (n_cu >= 0) sr::ctx().grid_cus_override = n_cu;
+  if (in_force) *in_force = sr::grid_cus();
+  return SR_OK;
+}
+
+int sr_grid_stats(int64_t out[2], int reset) {
+  sr::Context &c = sr::ctx();
+  if (out) {
+    out[0] = c.grid_launches;
+    out[1] = c.grid_short;
+  }
+  if (reset) c.grid_launches = c.grid_short = 0;
+  return SR_OK;
+}
+
 int sr_synchronize(void) {
   if (sr::ctx().device < 0) return SR_OK;
   for (int q = 0; q < sr::kStreams; ++q)

@@ -906,7 +906,7 @@ int tile_records(const sr_volume *v, const TraceKnobs &knobs, hipStream_t st, bo
       (void)hipGetLastError();
       return SR_OK;
     }
-    const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(count / 16 + 255) / 256, (int64_t)sr::ctx().n_cu * 64);
+    const unsigned grid = sr::capped_grid((int64_t)(count / 16 + 255) / 256, 64);
     sr::with_flags([&](auto ph) { hipLaunchKernelGGL(k_build_records<ph.value>, dim3(grid), dim3(256), 0, st, vol_dev(v), R); }, v->L != nullptr);
     hipError_t err = hipGetLastError();
     // The volume is shared by every stream that traces through it (the job driver alternates its bundles between the library's two
@@ -1297,7 +1297,7 @@ void launch_time(const sr_volume *v, TraceArgs &A, hipStream_t st) {
   A.in_count = A.out_count;
   A.out_list = nullptr;
   A.out_count = nullptr;
-  const unsigned fgrid = (unsigned)std::min<int64_t>(sr::grid_for(A.N, block), (int64_t)sr::ctx().n_cu * 4);
+  const unsigned fgrid = sr::capped_grid(sr::grid_for(A.N, block), 4);
   sr::with_flags(
       [&](auto ph, auto ax) { hipLaunchKernelGGL((k_trace_time<ph.value, ax.value>), dim3(fgrid), dim3(block), 0, st, A); },
       v->L != nullptr, v->K != nullptr || v->Q != nullptr);
@@ -1332,7 +1332,7 @@ int read_bbox(sr_rays *r, hipStream_t st) {
   unsigned long long *box = r->counters + 10, hb[6];
   SR_HIP(hipMemsetAsync(box, 0xff, 3 * sizeof(unsigned long long), st));
   SR_HIP(hipMemsetAsync(box + 3, 0, 3 * sizeof(unsigned long long), st));
-  const unsigned grid = (unsigned)std::min<int64_t>(sr::grid_for(r->n, 256), (int64_t)sr::ctx().n_cu * 8);
+  const unsigned grid = sr::capped_grid(sr::grid_for(r->n, 256), 8);
   hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(256), 0, st, (const double *)r->s0, r->n, box);
   SR_HIP(hipGetLastError());
   SR_HIP(hipMemcpyAsync(hb, box, sizeof hb, hipMemcpyDeviceToHost, st));

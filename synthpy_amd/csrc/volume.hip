@@ -385,22 +385,22 @@ int create_impl(sr_volume **out, const void *ne, int ne_is_f64, int nx, int ny, 
     A.co[k].uniform = hc[k].uniform;
   }
   const int block = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(src_total + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+  const int64_t blocks = (int64_t)(src_total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
   if (ne_is_f64)
-    hipLaunchKernelGGL(k_ne_nc_f64, dim3(grid), dim3(block), 0, st, (const double *)d_ne, (int64_t)src_total, ncrit, d_nenc);
+    hipLaunchKernelGGL(k_ne_nc_f64, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const double *)d_ne, (int64_t)src_total, ncrit, d_nenc);
   else
-    hipLaunchKernelGGL(k_ne_nc_f32, dim3(grid), dim3(block), 0, st, (const float *)d_ne, (int64_t)src_total, (float)ncrit, d_nenc);
+    hipLaunchKernelGGL(k_ne_nc_f32, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const float *)d_ne, (int64_t)src_total, (float)ncrit, d_nenc);
   const bool phase = (flags & SR_VOL_PHASE) != 0;
   if (ne_is_f64) {
     if (phase)
-      hipLaunchKernelGGL((k_pack_from_ne<double, true>), dim3(grid), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_ne<double, true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
     else
-      hipLaunchKernelGGL((k_pack_from_ne<double, false>), dim3(grid), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_ne<double, false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
   } else {
     if (phase)
-      hipLaunchKernelGGL((k_pack_from_ne<float, true>), dim3(grid), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_ne<float, true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
     else
-      hipLaunchKernelGGL((k_pack_from_ne<float, false>), dim3(grid), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_ne<float, false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
   }
   SR_TRY(hipGetLastError());
   SR_TRY(hipStreamSynchronize(st));
@@ -465,11 +465,11 @@ int sr_volume_create_from_fields(sr_volume **out, const float *dndx, const float
   if (e == hipSuccess) {
     PackArgs A = pack_args(v);
     const int block = 256;
-    const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(total + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+    const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
     if (nref)
-      hipLaunchKernelGGL((k_pack_from_fields<true>), dim3(grid), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_fields<true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
     else
-      hipLaunchKernelGGL((k_pack_from_fields<false>), dim3(grid), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
+      hipLaunchKernelGGL((k_pack_from_fields<false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
   }
@@ -488,14 +488,14 @@ int sr_volume_fields(const sr_volume *v, float *dndx, float *dndy, float *dndz, 
   const size_t total = (size_t)v->nx * v->ny * v->nz;
   PackArgs A = pack_args(v);
   const int block = 256;
-  const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(total + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
+  const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
   float *outs[3] = {dndx, dndy, dndz};
   for (int k = 0; k < 3; ++k) {
     if (!outs[k]) continue;
     float *tmp = nullptr;
     int rc = sr::dev_alloc(&tmp, total);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_unpack_f32, dim3(grid), dim3(block), 0, st, A, v->P, k, tmp);
+    hipLaunchKernelGGL(k_unpack_f32, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, v->P, k, tmp);
     hipError_t e = hipMemcpyAsync(outs[k], tmp, total * sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     sr::dev_free(tmp);
@@ -506,7 +506,7 @@ int sr_volume_fields(const sr_volume *v, float *dndx, float *dndy, float *dndz, 
     double *tmp = nullptr;
     int rc = sr::dev_alloc(&tmp, total);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_unpack_nm1, dim3(grid), dim3(block), 0, st, A, v->P, v->L, tmp);
+    hipLaunchKernelGGL(k_unpack_nm1, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, v->P, v->L, tmp);
     hipError_t e = hipMemcpyAsync(nref_minus_1, tmp, total * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     sr::dev_free(tmp);
@@ -557,8 +557,8 @@ int sr_volume_attach_aux(sr_volume *v, const double *kappa, const double *ne, co
   }
   if (e == hipSuccess) {
     const int block = 256;
-    const unsigned grid = (unsigned)std::min<int64_t>((int64_t)(total + block - 1) / block, (int64_t)sr::ctx().n_cu * 32);
-    hipLaunchKernelGGL(k_pack_aux, dim3(grid), dim3(block), 0, st, pack_args(v), (const double *)d_k, (const double *)d_ne,
+    const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
+    hipLaunchKernelGGL(k_pack_aux, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, pack_args(v), (const double *)d_k, (const double *)d_ne,
                        (const double *)d_B, v->K, v->Q);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -4,6 +4,7 @@ library; nothing here does the path's arithmetic in NumPy.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -73,6 +74,41 @@ def device_memory():
     f, t = C.c_int64(0), C.c_int64(0)
     check(lib.sr_device_memory(C.byref(f), C.byref(t)))
     return int(f.value), int(t.value)
+
+
+def compute_units() -> int:
+    """Compute units of the selected device (256 on an MI355X), whatever grid_cus() has in force."""
+    now, dev = C.c_int(0), C.c_int(0)
+    check(lib.sr_grid_cus(-1, C.byref(now)))
+    check(lib.sr_grid_cus(0, C.byref(dev)))
+    if now.value != dev.value:
+        check(lib.sr_grid_cus(now.value, None))
+    return int(dev.value)
+
+
+def grid_stats():
+    """(launches sized by a grid cap since the last reset, those of them that got fewer blocks than they wanted): sr_grid_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib.sr_grid_stats(out, 0))
+    return int(out[0]), int(out[1])
+
+
+@contextlib.contextmanager
+def grid_cus(n: int):
+    """Size every grid cap as on a device of n compute units inside the block (sr_grid_cus; 0: the device's own count): a
+    measurement and test knob.  The counters of grid_stats() start at zero on entry; the previous setting comes back on exit."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"grid_cus: a compute-unit count or 0, got {n}")
+    now = C.c_int(0)
+    check(lib.sr_grid_cus(-1, C.byref(now)))
+    before = 0 if now.value == compute_units() else now.value
+    check(lib.sr_grid_cus(n, None))
+    check(lib.sr_grid_stats(None, 1))
+    try:
+        yield
+    finally:
+        check(lib.sr_grid_cus(before, None))
 
 
 def volume_bytes_estimate(n_nodes, phaseshift=False, inv_brems=False, B_on=False, ne_itemsize=8):

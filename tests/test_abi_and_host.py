@@ -33,8 +33,13 @@ def test_library_exports_every_declared_symbol(built):
     declared = _declared_symbols()
     assert len(declared) >= 30
     assert {"sr_rays_launch_order", "sr_rays_set_count"} <= set(declared)  # what tests/test_ray_order.py reads the binning through
+    assert {"sr_grid_cus", "sr_grid_stats"} <= set(declared)  # the grid caps' knob and counters (tests/test_grid_caps.py)
+    assert built.SYMBOLS["sr_grid_cus"] == (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)])
+    assert built.SYMBOLS["sr_grid_stats"] == (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int])
+    header = open(os.path.join(ROOT, "include", "synthray.h")).read()
+    assert "int sr_grid_cus(int n_cu, int *in_force);" in header and "int sr_grid_stats(int64_t out[2], int reset);" in header
     lib = ctypes.CDLL(built.LIB_PATH)
-    missing = [s for s in declared if not hasattr(lib, s)]
+    missing =[s for s in declared if not hasattr(lib, s)]
     assert not missing, f"declared in synthray.h but not exported: {missing}"
     assert sorted(built.SYMBOLS) == declared, "ctypes table and header out of step"
     nm = subprocess.run(["nm", "-D", "--defined-only", built.LIB_PATH], capture_output=True, text=True).stdout
@@ -89,6 +94,15 @@ def test_argument_validation_before_device(built):
         engine.optics(np.zeros((4, 1)), [(0, 1.0)] * 40)
     with pytest.raises(built.SynthrayError, match="unknown optic"):
         engine.optics(np.zeros((4, 1)), [(17, 1.0)])
+    # sr_grid_cus: only > 0, 0 and -1 mean something; refused with text before the device is asked for
+    for bad in (-2, -256):
+        assert built.lib.sr_grid_cus(bad, None) == -1  # SR_ERR_INVALID
+        assert f"got {bad}" in built.lib.sr_last_error().decode() and "sr_grid_cus" in built.lib.sr_last_error().decode()
+    with pytest.raises(ValueError):
+        with engine.grid_cus(-1):
+            pass
+    out = (ctypes.c_int64 * 2)(7, 7)
+    assert built.lib.sr_grid_stats(out, 0) == 0 and list(out) == [0, 0]  # the counters need no device
 
 
 # ---------------------------------------------------------------- host inputs vs the reference

@@ -588,6 +588,39 @@ def test_smallest_case_and_many_slabs(eng, axis):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("dtype_name", ["float32", "float64"])
+@pytest.mark.parametrize("toward", [+1, -1])
+def test_z_march_over_several_workgroups_of_columns(eng, toward, dtype_name):
+    """k_slab takes 64 columns per workgroup, and every other z march of this module has at most 30: a 9 x 15 x 40 domain has
+    135 columns -- three workgroups, the last one with 7 -- and two slabs, the second one of 8 planes.  Te and Z fields, the edge
+    absorber, a 20 x 12 frame; the field within the module's bound, the power within twice that."""
+    dims, shape = (9, 15, 40), (20, 12)
+    assert dims[0] * dims[1] > 2 * 64 and (dims[0] * dims[1]) % 64 and 32 < dims[2] < 64
+    rng = np.random.default_rng(13)
+    axes = [Q * np.cumsum(rng.integers(1, 4, n)).astype(np.float64) for n in dims]
+    axes = [a - a[0] for a in axes]
+    f = {"ne": rng.uniform(0.0, 0.1 * N_CRIT, dims), "Te": rng.uniform(20.0, 400.0, dims), "Z": rng.uniform(1.0, 8.0, dims)}
+    f = {k: np.ascontiguousarray(v, dtype=np.dtype(dtype_name)) for k, v in f.items()}
+    frame = (float(axes[0][0]), float(Q * np.ceil((axes[0][-1] - axes[0][0]) / (shape[0] - 1) / Q)), float(axes[1][0]),
+             float(Q * np.ceil((axes[1][-1] - axes[1][0]) / (shape[1] - 1) / Q)))
+    U, win = field_in(shape, 6), _absorber(shape)
+    n_cells = dims[2] - 1
+    info = {}
+    ref, p_ref = restate(f, axes, U, frame, LAM, 2, toward, win, info=info)
+    assert info["inside"].sum() > 0.8 * info["inside"].size  # the frame looks through the columns of all three workgroups
+    F = {k: eng.Field(v, *[np.float32(a) for a in axes]) for k, v in f.items()}
+    try:
+        out, power = eng.wave(F["ne"], F["Te"], F["Z"], U, frame, LAM, 2, toward, win)
+    finally:
+        for fld in F.values():
+            fld.close()
+    assert out.shape == shape and power.shape == (n_cells,) and np.all(np.isfinite(out.view(float)))
+    err, lim = float(np.max(np.abs(out - ref))), bound(n_cells, shape, float(np.max(np.abs(ref))))
+    print(f"9 x 15 x 40 along z, toward {toward:+d}, {dtype_name}: {err / lim * K_GPU:.3f} of the allowed {K_GPU:g} units")
+    assert err <= lim and power_close(power, p_ref, info, n_cells, shape)
+
+
+@pytest.mark.gpu
 def test_power(eng):
     """power: (a) without absorption, windows or over-critical nodes the march is unitary: every power[c] equals the input's
     sum |U|^2 to K u n_cells, as the issue sets it: |power[c] / power_in - 1| <= K_GPU u n_cells.  (b) uniform ne, Te, Z, a plane
