@@ -639,6 +639,14 @@ int sr_rays_tile_records(const sr_rays *r);
  * The order of the rays inside one cell (one key) is not defined.  SR_ERR_STATE before any trace (a slab entry is one) has been
  * queued for the bundle; N = 0 copies nothing. */
 int sr_rays_launch_order(const sr_rays *r, uint32_t *order);
+/* The lateral cells the tile path's LAST binning found for the rays, read-only (for tests; never on a timed path): waits for the
+ * library's stream and copies N uint32, each ib | ic << 16 (cell indices along the volume's axes b = (axis + 1) % 3 and
+ * c = (axis + 2) % 3), 0xFFFFFFFF for a ray outside the lateral grid or dead.  The tile kernel places its tiles from these words
+ * instead of searching again.  Entry k belongs to
+ *   - the ray with index k (as uploaded), where it meets the entry plane, after a tile-path trace of ONE segment from s0;
+ *   - place k of the records the last segment was binned from, after a trace of several segments or a slab entry.
+ * SR_ERR_STATE while the bundle has not been traced on the tile path since it was made / resized. */
+int sr_rays_binned_cells(const sr_rays *r, uint32_t *cells);
 /* The bundle holds n rays from now on, 0 <= n <= the count it was created with (its capacity; SR_ERR_INVALID otherwise): what
  * sr_trace's pipeline does for a shorter last chunk.  Every device buffer keeps its size; the rows of s0 and of the results are at
  * pitch n afterwards, so whatever the bundle held (rays, results, hand-off records, bounding box, launch order) is forgotten:

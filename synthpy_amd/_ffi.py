@@ -172,6 +172,7 @@ SYMBOLS = {
     "sr_tile_min_density": (_d, []),
     "sr_rays_tile_records": (_i, [_vp]),
     "sr_rays_launch_order": (_i, [_vp, _vp]),
+    "sr_rays_binned_cells": (_i, [_vp, _vp]),
     "sr_rays_set_count": (_i, [_vp, _i64]),
     "sr_rays_set_bbox": (_i, [_vp, _vp]),
     "sr_rays_get_bbox": (_i, [_vp, _vp, C.POINTER(C.c_int)]),

@@ -282,6 +282,10 @@ struct sr_rays {
   double *rec = nullptr;                   // (10, N) hand-off records (A12), allocated at first use
   double *rec2 = nullptr;                  // the records' second buffer and the new order, for the tile path's re-binning (trace_tile.inc)
   uint32_t *order2 = nullptr;
+  // the tile path's binning: the packed lateral cell (ib | ic << 16; 0xFFFFFFFF: none) of every ray where the LAST binning found it,
+  // by the ray's index (binning from s0) or by its place in the records it was binned from; the tile kernel places its tile from it
+  uint32_t *cells = nullptr;
+  bool have_cells = false;
   // the tile path's stragglers (trace_tile.inc): (10, cap) records of the rays a tile lost, in the order they were lost -- the state
   // they entered their segment with, then (k_trace_f64 on the side stream) their state on the volume's / slab's last node plane --
   // and the entry counts after each segment (what one straggler launch takes)

@@ -35,6 +35,9 @@ struct VolDev {
   double verdet;
   int64_t OS;           // nodes per octet of node planes: nb*nc*8 (the packed node order, common.hpp)
   const double *R;      // ready-made coefficient records per (node plane, lateral cell), or nullptr (common.hpp: sr_volume::R)
+  // cells per metre of the two lateral axes, (n - 1) / (g[n-1] - g[0]): find_cell's first guess, formed once on the host (the same
+  // IEEE quotient as on the device) for the tile path's key kernels and start-up
+  double rb0, rc0;
 };
 
 // The packed node order (sr::node_index): column (ib, ic) starts at col8() inside every octet, node plane k of a column
@@ -765,6 +768,8 @@ VolDev vol_dev(const sr_volume *v) {
   V.verdet = v->verdet;
   V.OS = (int64_t)v->nb * v->nc * 8;
   V.R = v->R;
+  V.rb0 = v->hg[1].size() > 1 ? (v->nb - 1) / (v->hg[1].back() - v->hg[1].front()) : 0.0;
+  V.rc0 = v->hg[2].size() > 1 ? (v->nc - 1) / (v->hg[2].back() - v->hg[2].front()) : 0.0;
   return V;
 }
 
@@ -802,6 +807,12 @@ int bin_rays(sr_rays *r, int64_t N, int lo_bits, int n_coarse, uint32_t *out, hi
 // the band order (trace_tile.inc): keys from s0 (rec == nullptr) or from the hand-off records, then the sort
 int bin_by_band(sr_rays *r, const sr_volume *v, const TileGeom &g, const double *rec, uint32_t *out, hipStream_t st) {
   const int64_t N = r->n;
+  SR_CHECK(v->nb - 1 <= 0xFFFF && v->nc - 1 <= 0xFFFF, "lateral grid of %d x %d cells: a packed cell holds 16 bits per axis", v->nb - 1, v->nc - 1);
+  if (!r->cells) {  // by the bundle's capacity, as the other buffers of the tile path
+    int rc = sr::dev_alloc(&r->cells, (size_t)std::max<int64_t>(std::max(r->cap, N), 1));
+    if (rc) return rc;
+  }
+  r->have_cells = true;
   const int64_t n_bands = (v->nb - 1 + g.band - 1) / g.band;
   const int64_t n_keys = n_bands * (int64_t)(v->nc - 1) * g.band;  // band keys of the cells: 0 .. n_keys - 1
   // More keys than the two LDS levels of the sort hold (2^22, about 2048 x 2048 cells): drop low key bits, so that a few
@@ -817,10 +828,10 @@ int bin_by_band(sr_rays *r, const sr_volume *v, const TileGeom &g, const double 
   SR_CHECK(n_coarse <= kBinMaxDigits + 1, "band key of %lld does not fit the LDS counters of the ray binning", (long long)key_max);
   const unsigned nblk = sr::grid_for(N, 256);
   if (rec)
-    hipLaunchKernelGGL(k_keys_band_rec, dim3(nblk), dim3(256), 0, st, vol_dev(v), rec, N, g.band, (uint32_t)key_max, shift, r->keys);
+    hipLaunchKernelGGL(k_keys_band_rec, dim3(nblk), dim3(256), 0, st, vol_dev(v), rec, N, g.band, (uint32_t)key_max, shift, r->keys, r->cells);
   else
     hipLaunchKernelGGL(k_keys_band, dim3(nblk), dim3(256), 0, st, vol_dev(v), (const double *)r->s0, N, v->axis, g.band, (uint32_t)key_max,
-                       shift, r->keys);
+                       shift, r->keys, r->cells);
   return bin_rays(r, N, lo_bits, n_coarse, out, st);
 }
 
@@ -976,6 +987,7 @@ bool tile_plan(const sr_rays *r, const sr_volume *v, const sr_trace_params *p, i
     tp.rec = tp.rec && tp.g.tb == 8 && tp.g.tc <= 8;  // a tile column is one DMA's kilobyte: eight cells
   }
   if (v->nb - 1 < tp.g.tb || v->nc - 1 < tp.g.tc || v->na < 3) return false;
+  if (v->nb - 1 > 0xFFFF || v->nc - 1 > 0xFFFF) return false;  // the packed cells of the binning hold 16 bits per axis (bin_by_band)
   if (aux && (tp.g.tb * tp.g.tc > 64 || threads < 128)) return false;  // one wavefront of producers per kind
   {
     const int steps = v->na - 1, n_seg = (steps + tp.seg - 1) / tp.seg;
@@ -1143,6 +1155,10 @@ int trace_tiled(sr_rays *r, const sr_volume *v, const sr_trace_params *p, const 
       T.order = r->order2;
       T.A.rec = r->rec2;
     }
+    // the cells the binning before this launch found (bin_by_band: here, or sr_rays_trace's from s0 -- which also makes the buffer,
+    // so the pointer is read only now)
+    SR_CHECK(r->cells != nullptr, "tile path: the rays were not binned by band before the launch");
+    T.cells = r->cells;
     if (timed) SR_HIP(hipEventRecord(c.ev[4 + 2 * q], st));
     if ((rc = launch_tile(T, phase, aux, tp.rec, lds, st))) return rc;
     if (timed) SR_HIP(hipEventRecord(c.ev[5 + 2 * q], st));
@@ -1428,7 +1444,7 @@ void sr_rays_destroy(sr_rays *r) {
   if (!r) return;
   for (void *q : {(void *)r->s0, (void *)r->sf, (void *)r->rf, (void *)r->Jf, (void *)r->perm, (void *)r->keys, (void *)r->bins,
                   (void *)r->sort_tmp, (void *)r->fb_list, (void *)r->counters, (void *)r->rec, (void *)r->rec2, (void *)r->order2,
-                  (void *)r->strag_rec, (void *)r->strag_snap, (void *)r->guard, r->guard_set})
+                  (void *)r->strag_rec, (void *)r->strag_snap, (void *)r->guard, r->guard_set, (void *)r->cells})
     sr::dev_free(q);
   delete r;
 }
@@ -1663,11 +1679,21 @@ int sr_rays_launch_order(const sr_rays *r, uint32_t *order) {
   return SR_OK;
 }
 
+int sr_rays_binned_cells(const sr_rays *r, uint32_t *cells) {
+  SR_CHECK(r && cells, "sr_rays_binned_cells: NULL argument");
+  if (!r->have_cells) return sr::fail(SR_ERR_STATE, "sr_rays_binned_cells: the tile path has not binned these rays");
+  if (r->n == 0) return SR_OK;
+  hipStream_t st = sr::ctx().stream;
+  SR_HIP(hipMemcpyAsync(cells, r->cells, sizeof(uint32_t) * (size_t)r->n, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  return SR_OK;
+}
+
 int sr_rays_set_count(sr_rays *r, int64_t n) {
   SR_CHECK(r != nullptr, "sr_rays_set_count: NULL rays");
   SR_CHECK(n >= 0 && n <= r->cap, "sr_rays_set_count: %lld rays in a bundle made for %lld", (long long)n, (long long)r->cap);
   r->n = n;  // every buffer keeps its size (by cap); rows are at pitch n from now on, so what the bundle held is gone
-  r->have_s0 = r->traced = r->sorted = r->have_rec = r->have_order = false;
+  r->have_s0 = r->traced = r->sorted = r->have_rec = r->have_order = r->have_cells = false;
   r->have_bbox = r->bbox_given = false;
   r->guard_live = false;
   r->last_vol = nullptr;

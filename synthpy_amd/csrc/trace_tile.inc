@@ -84,6 +84,9 @@ struct TileArgs {
   const double *rec_in;
   const uint32_t *order;
   uint32_t *perm_out;
+  // the packed cell (k_keys_band / k_keys_band_rec) of every ray on node plane k0, where the binning before this launch found it: by
+  // the ray's index (first) or by its place in rec_in -- read through perm / order as the state is
+  const uint32_t *cells;
   // the rays this launch loses (they left their tile, or the volume): appended to the straggler records, (10, strag_cap),
   // *strag_count entries so far -- the state they entered this segment with; k_trace_f64 takes them from there (see the header)
   double *strag_rec;
@@ -113,7 +116,9 @@ __host__ __device__ constexpr int tile_rec(bool aux, bool rec = false) { return 
 constexpr int kTabLo = 4, kTabHi = 5;
 __host__ __device__ constexpr int tile_tab_entries(int t) { return kTabLo + t + kTabHi; }
 // REC: the tables lie where those of the largest tile (8 x 8) would, so that their LDS addresses are constants of the kernel
-__host__ __device__ constexpr int tile_tab_doubles(int tb, int tc) { return 2 * tile_tab_entries(tb) + 2 * tile_tab_entries(tc) + 4; }  // + 8 words for the placement
+// + the placement's scratch: the bounds of each wavefront's cells, four packed words per wavefront, 16 wavefronts at the most (see
+// `box` in the kernel)
+__host__ __device__ constexpr int tile_tab_doubles(int tb, int tc) { return 2 * tile_tab_entries(tb) + 2 * tile_tab_entries(tc) + 32; }
 static_assert(tile_tab_doubles(8, 8) * sizeof(double) <= 1024, "the records kernel's table head is one KiB");
 
 __host__ __device__ inline size_t tile_lds_bytes(const TileGeom &g, int seg_steps, bool aux = false, bool rec = false) {
@@ -125,6 +130,33 @@ __host__ __device__ inline size_t tile_lds_bytes(const TileGeom &g, int seg_step
   return sizeof(double) * (head + (size_t)5 * g.tb * g.tc * tile_rec(aux, rec));
 }
 
+// Two uint16 in a word, minimum / maximum of each half (v_pk_min_u16 / v_pk_max_u16), and their reduction over a wavefront in
+// registers: four DPP steps inside a row of 16 lanes (the quad's two exchanges, the half row's and the row's mirror), then row 0
+// into row 1 and row 2 into row 3 (row_bcast:15), rows 0-1 into rows 2-3 (row_bcast:31).  LANE 63 holds the wavefront's result.
+// Every lane of the wavefront must be active.
+typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(pk_u16, a), __builtin_bit_cast(pk_u16, b)));
+}
+__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(pk_u16, a), __builtin_bit_cast(pk_u16, b)));
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ unsigned dpp_from(unsigned v) {  // lanes of the rows not in ROWS keep their own value
+  return (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWS, 0xf, false);
+}
+template <bool MAX>
+__device__ __forceinline__ unsigned wave_pk_u16(unsigned v) {
+  auto op = [](unsigned a, unsigned b) { return MAX ? pk_max_u16(a, b) : pk_min_u16(a, b); };
+  v = op(v, dpp_from<0xB1, 0xf>(v));   // quad_perm:[1,0,3,2]
+  v = op(v, dpp_from<0x4E, 0xf>(v));   // quad_perm:[2,3,0,1]
+  v = op(v, dpp_from<0x141, 0xf>(v));  // row_half_mirror
+  v = op(v, dpp_from<0x140, 0xf>(v));  // row_mirror
+  v = op(v, dpp_from<0x142, 0xa>(v));  // row_bcast:15 into rows 1 and 3
+  v = op(v, dpp_from<0x143, 0xc>(v));  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
 // the key of the band order (see the header); cells outside the volume / dead rays: `oob`
 __device__ __forceinline__ uint32_t band_key(int ib, int ic, int ncc, int band) {
   const int bnd = ib / band, row = ib - bnd * band;
@@ -133,8 +165,11 @@ __device__ __forceinline__ uint32_t band_key(int ib, int ic, int ncc, int band) 
 }
 
 // shift: low key bits dropped (bin_by_band: band keys past what the LDS counters of the sort hold)
+// cells: the cell itself beside its key, packed (ib | ic << 16; kNoCell: outside the volume / dead) -- the tile kernel places its
+// tile from it instead of searching again (bin_by_band refuses lateral grids of more than 65535 cells a side)
+constexpr uint32_t kNoCell = 0xFFFFFFFFu;
 __global__ void k_keys_band(VolDev V, const double *__restrict__ s0, int64_t N, int axis, int band, uint32_t oob_key, int shift,
-                            uint32_t *__restrict__ keys) {
+                            uint32_t *__restrict__ keys, uint32_t *__restrict__ cells) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int b = (axis + 1) % 3, c = (axis + 2) % 3;
@@ -147,30 +182,34 @@ __global__ void k_keys_band(VolDev V, const double *__restrict__ s0, int64_t N, 
     pc = pc + vc * tau;
   }
   const double gb0 = V.g[1][0], gbL = V.g[1][V.nb - 1], gc0 = V.g[2][0], gcL = V.g[2][V.nc - 1];
-  uint32_t key = oob_key;
+  uint32_t key = oob_key, cell = kNoCell;
   if (pb >= gb0 && pb <= gbL && pc >= gc0 && pc <= gcL) {
-    const int ib = find_cell(V.g[1], V.nb, pb, gb0, (V.nb - 1) / (gbL - gb0));
-    const int ic = find_cell(V.g[2], V.nc, pc, gc0, (V.nc - 1) / (gcL - gc0));
+    const int ib = find_cell(V.g[1], V.nb, pb, gb0, V.rb0);
+    const int ic = find_cell(V.g[2], V.nc, pc, gc0, V.rc0);
     key = band_key(ib, ic, V.nc - 1, band) >> shift;
+    cell = (uint32_t)ib | ((uint32_t)ic << 16);
   }
   keys[i] = key;
+  cells[i] = cell;
 }
 
 // between two segments: the key of a ray's CURRENT cell, from its hand-off record (rows 0, 1 = p_b, p_c; row 2 = v_a; NaN: not a
 // plane-form ray, -inf: a straggler, gone from the tile path -- both sort behind every cell)
 __global__ void k_keys_band_rec(VolDev V, const double *__restrict__ rec, int64_t N, int band, uint32_t oob_key, int shift,
-                                uint32_t *__restrict__ keys) {
+                                uint32_t *__restrict__ keys, uint32_t *__restrict__ cells) {
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j >= N) return;
   const double pb = rec[j], pc = rec[N + j], va = rec[2 * N + j];
   const double gb0 = V.g[1][0], gbL = V.g[1][V.nb - 1], gc0 = V.g[2][0], gcL = V.g[2][V.nc - 1];
-  uint32_t key = oob_key;
+  uint32_t key = oob_key, cell = kNoCell;
   if (va > 0 && pb >= gb0 && pb <= gbL && pc >= gc0 && pc <= gcL) {
-    const int ib = find_cell(V.g[1], V.nb, pb, gb0, (V.nb - 1) / (gbL - gb0));
-    const int ic = find_cell(V.g[2], V.nc, pc, gc0, (V.nc - 1) / (gcL - gc0));
+    const int ib = find_cell(V.g[1], V.nb, pb, gb0, V.rb0);
+    const int ic = find_cell(V.g[2], V.nc, pc, gc0, V.rc0);
     key = band_key(ib, ic, V.nc - 1, band) >> shift;
+    cell = (uint32_t)ib | ((uint32_t)ic << 16);
   }
   keys[j] = key;
+  cells[j] = cell;
 }
 
 // after a segment's launch: how many straggler entries there are now (what the segment's k_trace_f64 launch on the side stream
@@ -259,7 +298,8 @@ __global__ __launch_bounds__(256) void k_build_records(VolDev V, double *__restr
 
 // Diagnostic builds (tools/build_variant.sh <name> -DSR_TILE_EXP_...; wrong results, timing only; DESIGN.md round 3 has the numbers):
 // SR_TILE_EXP_NOBARRIER (no barrier in the step loop), SR_TILE_EXP_NOPRODUCE (no plane is loaded or built in the loop),
-// SR_TILE_EXP_NORELOC (a ray never changes its cell).  SR_TILE_EXP_DMA_SADDR (right results): the records kernel's LDS-DMA by an
+// SR_TILE_EXP_NORELOC (a ray never changes its cell), SR_TILE_EXP_NOSTEPS (the step loop runs no step: what a launch costs before
+// its first step and after its last; profiles/r08_tile_startup.txt).  SR_TILE_EXP_DMA_SADDR (right results): the records kernel's LDS-DMA by an
 // inline statement in the scalar-base form (lds_dma16, trace.hip; profiles/r06_step_loop.txt).
 #ifndef SR_TILE_THREADS
 // 256 rays per workgroup with an 8 x 8 tile (46 KB of LDS): THREE workgroups share a CU -- 12 wavefronts, 3 per SIMD at 168
@@ -298,12 +338,13 @@ __global__ __launch_bounds__(256) void k_build_records(VolDev V, double *__restr
 template <bool PHASE, bool AUX = false, bool REC = false>
 __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES : SR_TILE_WAVES)) void k_trace_tile(TileArgs T) {
   static_assert(!(AUX && REC), "the ready-made records hold the gradient fields only");
+  static_assert(SR_TILE_THREADS % 64 == 0 && SR_TILE_THREADS / 64 <= 16, "the placement's scratch holds one slot per wavefront, 16 at the most");
   constexpr int kTileRec = tile_rec(AUX, REC);
   extern __shared__ double lds[];
   const TraceArgs &A = T.A;
   const VolDev &V = A.V;
   const int TB = T.G.tb, TC = T.G.tc, NC = TB * TC;
-  // LDS: [node table b: {g, r} x (TB + 9)][node table c: {g, r} x (TC + 9)][placement: 8 ints][records: 5 slots x NC x kTileRec]
+  // LDS: [node table b: {g, r} x (TB + 9)][node table c: {g, r} x (TC + 9)][placement: 16 x 4 words][records: 5 slots x NC x kTileRec]
   // (tile_tab_entries: sentinels on both sides; REC: laid out for 8 x 8, so that both tables' addresses are constants)
   const int tab_nb = tile_tab_entries(REC ? 8 : TB), tab_nc = tile_tab_entries(REC ? 8 : TC);
   int *org = reinterpret_cast<int *>(lds + 2 * (tab_nb + tab_nc));
@@ -356,8 +397,10 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     }
     return ok;
   };
+  uint32_t pk = kNoCell;  // the ray's packed cell on node plane k0, as the binning found it
   if (T.first) {
     i = have ? (int64_t)A.perm[j] : 0;
+    if (have) pk = T.cells[i];
     if (have) alive = from_s0(A, i, y0, y1, y2, y3, y4, y5, y6);
     if (AUX && have) {
       y7 = A.s0[6 * N + i];
@@ -367,6 +410,7 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   } else if (have) {
     const int64_t o = (int64_t)T.order[j];  // where the ray's record sits in the buffer the segment before wrote
     const double *R = T.rec_in;
+    pk = T.cells[o];
     if (AUX) {
       y7 = R[7 * N + o];
       y8 = R[8 * N + o];
@@ -394,36 +438,58 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   // ---- the tile: placed around the cells the workgroup's rays are in now AND the cells a straight line takes them to by the
   // segment's end (the rays that leave a tile are the fast ones, and neighbouring rays are deflected alike: the box of the
   // predicted paths follows them); the box is centred in the tile.  Where the predicted box does not fit, the entry cells alone.
+  // The entry cell is the one the binning before this launch found for the ray (T.cells: the same find_cell of the same
+  // position; a cell that were off is put right by stage 1's weight test or loses the ray to k_trace_f64: the bits stay), and the
+  // cell's own node and reciprocal width come straight from the volume's arrays -- the values the tile's node table will hold.
+  // The predicted exit cell is a heuristic: the entry cell moved on by floor(weight + lateral travel x the cell's reciprocal
+  // width), the travel with 1 / v_a from the float32 reciprocal -- no search, no division.
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int ln = (int)(threadIdx.x & 63);
   int cb = 0, cc = 0, xb = 0, xc = 0;
+  double lo_b = 0, r_b = 1, lo_c = 0, r_c = 1;
   if (alive) {
     const double gb0 = V.g[1][0], gbL = V.g[1][V.nb - 1], gc0 = V.g[2][0], gcL = V.g[2][V.nc - 1];
-    if (y0 >= gb0 && y0 < gbL && y1 >= gc0 && y1 < gcL) {  // strictly inside: the volume's last nodes are k_trace_f64's business
-      const double rb0 = (V.nb - 1) / (gbL - gb0), rc0 = (V.nc - 1) / (gcL - gc0);
-      cb = find_cell(V.g[1], V.nb, y0, gb0, rb0);
-      cc = find_cell(V.g[2], V.nc, y1, gc0, rc0);
-      const double dz = (V.g[0][T.k1] - V.g[0][T.k0]) / y2;
-      const double eb = fmin(fmax(fma(y3, dz, y0), gb0), gbL), ec = fmin(fmax(fma(y4, dz, y1), gc0), gcL);
-      xb = find_cell(V.g[1], V.nb, eb, gb0, rb0);
-      xc = find_cell(V.g[2], V.nc, ec, gc0, rc0);
+    // strictly inside: the volume's last nodes are k_trace_f64's business (the key kernels' test admits them)
+    if (y0 >= gb0 && y0 < gbL && y1 >= gc0 && y1 < gcL && pk != kNoCell) {
+      cb = min((int)(pk & 0xffffu), V.nb - 2);
+      cc = min((int)(pk >> 16), V.nc - 2);
+      lo_b = V.g[1][cb];
+      r_b = V.rg[1][cb];
+      lo_c = V.g[2][cc];
+      r_c = V.rg[2][cc];
+      const double dz = (V.g[0][T.k1] - V.g[0][T.k0]) * rcp_f64_from_f32(y2);
+      const double ub = fma(y3 * dz, r_b, (y0 - lo_b) * r_b), uc = fma(y4 * dz, r_c, (y1 - lo_c) * r_c);
+      xb = min(max(cb + (int)floor(fmin(fmax(ub, -65536.0), 65536.0)), 0), V.nb - 2);
+      xc = min(max(cc + (int)floor(fmin(fmax(uc, -65536.0), 65536.0)), 0), V.nc - 2);
     } else {
       alive = false;  // starts outside the volume: lost to this kernel
     }
   }
-  if (threadIdx.x < 8) org[threadIdx.x] = (threadIdx.x & 2) ? -1 : 0x7fffffff;  // {min b, min c, max b, max c} of the entry cells; of entry + predicted
-  __syncthreads();
-  if (alive) {
-    atomicMin(&org[0], cb);
-    atomicMin(&org[1], cc);
-    atomicMax(&org[2], cb);
-    atomicMax(&org[3], cc);
-    atomicMin(&org[4], min(cb, xb));
-    atomicMin(&org[5], min(cc, xc));
-    atomicMax(&org[6], max(cb, xb));
-    atomicMax(&org[7], max(cc, xc));
+  // box: {min b, min c} of the entry cells, of entry + predicted, {max b, max c} of the entry cells, of entry + predicted -- four words
+  // of two uint16, reduced over the wavefront in registers (wave_pk_u16) and over the workgroup's wavefronts through one LDS slot each
+  uint4 *box = reinterpret_cast<uint4 *>(org);
+  {
+    unsigned e = 0xFFFFFFFFu, x = 0xFFFFFFFFu, E = 0u, X = 0u;
+    if (alive) {
+      e = E = (unsigned)cb | ((unsigned)cc << 16);
+      x = (unsigned)min(cb, xb) | ((unsigned)min(cc, xc) << 16);
+      X = (unsigned)max(cb, xb) | ((unsigned)max(cc, xc) << 16);
+    }
+    e = wave_pk_u16<false>(e);
+    x = wave_pk_u16<false>(x);
+    E = wave_pk_u16<true>(E);
+    X = wave_pk_u16<true>(X);
+    if (ln == 63) box[wv] = make_uint4(e, x, E, X);
   }
   __syncthreads();
+  uint4 bx = box[0];
+#pragma unroll
+  for (int w = 1; w < SR_TILE_THREADS / 64; ++w) {
+    const uint4 o = box[w];
+    bx = make_uint4(pk_min_u16(bx.x, o.x), pk_min_u16(bx.y, o.y), pk_max_u16(bx.z, o.z), pk_max_u16(bx.w, o.w));
+  }
   auto place = [](int lo_e, int hi_e, int lo_x, int hi_x, int t, int cells) {
-    if (hi_e < 0) return 0;  // no live ray
+    if (hi_e < lo_e) return 0;  // no live ray
     int lo = lo_x, hi = hi_x;
     if (hi - lo + 1 > t) {
       lo = lo_e;
@@ -432,7 +498,8 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
     if (hi - lo + 1 > t) hi = lo + t - 1;  // the entry cells span more than a tile: the rays beyond it are lost below
     return min(max(lo - (t - (hi - lo + 1)) / 2, 0), cells - t);
   };
-  const int ob = place(org[0], org[2], org[4], org[6], TB, V.nb - 1), oc = place(org[1], org[3], org[5], org[7], TC, V.nc - 1);
+  const int ob = place((int)(bx.x & 0xffffu), (int)(bx.z & 0xffffu), (int)(bx.y & 0xffffu), (int)(bx.w & 0xffffu), TB, V.nb - 1);
+  const int oc = place((int)(bx.x >> 16), (int)(bx.z >> 16), (int)(bx.y >> 16), (int)(bx.w >> 16), TC, V.nc - 1);
   typedef double d2 __attribute__((ext_vector_type(2)));
   typedef __attribute__((address_space(3))) d2 *lds_d2_t;
   // the node tables: nodes 0 .. t of the tile between their sentinels (tile_tab_entries)
@@ -445,20 +512,10 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
       ((lds_d2_t)(uintptr_t)tab)[n] = e;
     }
   };
-  fill_table(tab_b, TB, V.g[1], V.rg[1], ob);
-  fill_table(tab_c, TC, V.g[2], V.rg[2], oc);
-  __syncthreads();
+  // (the tables are filled further down, while the first node planes are on their way; the lane's own entries {lo, r} it has already)
   int tb = cb - ob, tc = cc - oc;
   if (alive && !(tb >= 0 && tb < TB && tc >= 0 && tc < TC)) alive = false;  // the workgroup's rays span more than a tile
   if (!alive) tb = tc = 0;
-  double lo_b, r_b, lo_c, r_c;
-  {
-    const d2 eb = ((lds_d2_t)(uintptr_t)tab_b)[tb], ec = ((lds_d2_t)(uintptr_t)tab_c)[tc];
-    lo_b = eb.x;
-    r_b = eb.y;
-    lo_c = ec.x;
-    r_c = ec.y;
-  }
   int cell = cell_off(tb, tc);  // record offset inside a slot, in doubles: column-major (see the banks note below)
 
   // ---- producers: NC consecutive lanes, one cell each.  WHICH lanes rotates with the workgroup index: a CU holds three
@@ -580,8 +637,7 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   };
   // REC: wavefront w brings tile columns 2w and 2w + 1 of a node plane into a slot: lane l's 16 bytes are piece l % 8 of the
   // record of cell (ob + l / 8, oc + column), and land at the slot's column + l * 16 -- the DMA's own lane-linear order
-  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int ln = (int)(threadIdx.x & 63);
+  // (wv, ln: the wavefront and the lane in it, from the placement above)
   // Addresses: everything but the lane's place inside its kilobyte is wave-uniform -- the tile's first record, the node plane, the
   // column -- and is kept in scalar registers (ob, oc come out of LDS: readfirstlane tells the compiler); the lane adds ONE 32-bit
   // offset, the same for the whole launch (how the step loop keeps it that way: see lds_dma16 and the loop's DMA).  (Formed per lane in 64-bit integer arithmetic the two addresses were 15 vector
@@ -618,10 +674,16 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
       ((lds_d2_t)(uintptr_t)(unsigned)(mid + mid_lane))[q * (kRecColD / 2)] = a + b;
     }
   };
+  // Start-up order: the first two node planes are asked for as soon as the tile's place is known; the node tables are filled
+  // while they are on their way; ONE wait, the mid record, and the barrier that ends the start-up (tables, records, mid record).
   if (REC && wg_live) {
     const char *p0 = wcol_r + (int64_t)T.k0 * plane_bytes;
     dma_cols(p0, p0 + col_bytes, slot_h(T.k0 % 3));
     dma_cols(p0 + plane_bytes, p0 + plane_bytes + col_bytes, slot_h((T.k0 + 1) % 3));
+  }
+  fill_table(tab_b, TB, V.g[1], V.rg[1], ob);
+  fill_table(tab_c, TC, V.g[2], V.rg[2], oc);
+  if (REC && wg_live) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     mid_from(slot_h(T.k0 % 3), slot_h((T.k0 + 1) % 3), slot_h(3 + T.k0 % 2), 2 * wv < TC, 2 * wv + 1 < TC);
   }
@@ -741,7 +803,12 @@ __global__ __launch_bounds__(SR_TILE_THREADS, AUX ? 2 : (REC ? SR_TILE_REC_WAVES
   const cdbl_t tab0 = ctab + 8 * (int64_t)T.k0;
   cdbl_t tab = tab0;
   double nh = tab[0], nhh = tab[1], nh6 = tab[2], nh6w = tab[6];
-  for (int k = T.k0; k < T.k1; ++k) {
+#ifdef SR_TILE_EXP_NOSTEPS
+  const int k_stop = T.k0;  // no step at all: a launch is its start-up and its tail
+#else
+  const int k_stop = T.k1;
+#endif
+  for (int k = T.k0; k < k_stop; ++k) {
     const double Sh = nh, Shh = nhh, Sh6 = nh6, Sh6w = nh6w;
     {
       tab = k + 1 < T.k1 ? tab + 8 : tab0;

@@ -924,6 +924,15 @@ class RayBundle:
         check(lib.sr_rays_launch_order(self._h, ptr(out)))
         return out
 
+    def binned_cells(self):
+        """(2, N) int64: the lateral cell (ib, ic) the tile path's last binning found for each ray, -1 for none
+        (sr_rays_binned_cells: by ray index after a one-segment trace from s0).  Waits for the stream; for tests."""
+        out = np.empty(self.n, np.uint32)
+        check(lib.sr_rays_binned_cells(self._h, ptr(out)))
+        cells = np.stack([out & 0xFFFF, out >> 16]).astype(np.int64)
+        cells[:, out == 0xFFFFFFFF] = -1
+        return cells
+
     def resize(self, n_rays: int):
         """The bundle holds n_rays <= its capacity (the count it was created with) from now on, in the same device buffers; what
         it held is forgotten: upload again (sr_rays_set_count)."""
