@@ -37,6 +37,13 @@ int fail(int code, const char *fmt, ...);
     if (!(cond)) return sr::fail(SR_ERR_INVALID, __VA_ARGS__); \
   } while (0)
 
+// a callee that has set the error text and returns a status: a non-zero one is handed on
+#define SR_RC(call)         \
+  do {                      \
+    const int rc_ = (call); \
+    if (rc_) return rc_;    \
+  } while (0)
+
 // ---- context ---------------------------------------------------------------------
 constexpr int kStreams = 2;
 constexpr int kMaxTileSegs = 8;  // segments of a tile-path trace that are timed one by one (trace.hip: trace_tiled)
@@ -73,6 +80,57 @@ int dev_alloc(T **p, size_t count) {
 inline void dev_free(void *p) {
   if (p) (void)hipFree(p);
 }
+
+// The device buffers of ONE call of an entry point that takes host arrays: fresh hipMallocs (a volume's staging is gigabytes, and
+// the scratch block below is kept from call to call), freed together when the owner goes -- on every return, early or not -- or
+// one by one with release().  Helpers take the owner by reference and add their buffers to it.
+class CallBuffers {
+ public:
+  CallBuffers() = default;
+  CallBuffers(const CallBuffers &) = delete;
+  CallBuffers &operator=(const CallBuffers &) = delete;
+  ~CallBuffers() {
+    for (void *p : held_) dev_free(p);
+  }
+  template <typename T>
+  int alloc(T **p, size_t count) {
+    SR_RC(dev_alloc(p, count));
+    if (*p) held_.push_back(*p);
+    return SR_OK;
+  }
+  template <typename T>
+  int zeroed(T **p, size_t count, hipStream_t st) {  // a result that kernels add into
+    SR_RC(alloc(p, count));
+    if (*p) SR_HIP(hipMemsetAsync(*p, 0, count * sizeof(T), st));
+    return SR_OK;
+  }
+  // a host array into a fresh buffer, the copy queued on `st`; a NULL array is skipped and *p stays NULL (sr_optics without E)
+  template <typename T>
+  int upload(T **p, const T *host, size_t count, hipStream_t st) {
+    *p = nullptr;
+    if (!host) return SR_OK;
+    SR_RC(alloc(p, count));
+    if (*p) SR_HIP(hipMemcpyAsync(*p, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return SR_OK;
+  }
+  void release(void *p) {  // free one buffer before the call ends (to cap its peak)
+    const auto it = std::find(held_.begin(), held_.end(), p);
+    if (it == held_.end()) return;
+    dev_free(p);
+    held_.erase(it);
+  }
+
+ private:
+  std::vector<void *> held_;
+};
+// The tail of such a call, after its launches: their error, the results to the host (a NULL destination is skipped), and the
+// stream is waited for -- the call is done with its buffers.
+struct HostOut {
+  void *host;
+  const void *dev;
+  size_t bytes;
+};
+int stage_out(hipStream_t st, std::initializer_list<HostOut> out);
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 

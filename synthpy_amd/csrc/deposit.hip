@@ -11,7 +11,7 @@
 // Layout: the loaders and tests the kernels share (exit_ray, load_field / store_field, bin_hist2, guard_seed / guard_uncertain,
 // add_hits); ONE skeleton for the fused deposits, deposit_patch (one ray per work-item, the workgroup's patch of the detector
 // privatised in LDS), which a kernel gives a front end (bins ray i, says what it adds) and a patch type (tile shape and layout,
-// what a hit adds to a tile bin and an image bin, how a flush item goes to the image); host side: stage_in / stage_out,
+// what a hit adds to a tile bin and an image bin, how a flush item goes to the image); host side: sr::CallBuffers / sr::stage_out,
 // read_out, deposit_begin / deposit_finish, guard_queue_reset, kernels picked by sr::with_flags / sr::with_count.
 #include <algorithm>
 
@@ -700,56 +700,7 @@ int make_analysers(const double *ab, int n_ch, Analysers &A) {
   return SR_OK;
 }
 
-// ---- staging of the host-array entry points ----------------------------------------------------------------------------
-// a device buffer for the length of one call
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { sr::dev_free(p); }
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-    if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    return SR_OK;
-  }
-  int zeroed(size_t bytes, hipStream_t st) {  // a result that kernels add into
-    int rc = alloc(bytes);
-    if (rc) return rc;
-    SR_HIP(hipMemsetAsync(p, 0, bytes, st));
-    return SR_OK;
-  }
-  template <typename T>
-  T *as() const {
-    return static_cast<T *>(p);
-  }
-};
-struct HostIn {
-  DevBuf &buf;
-  const void *host;
-  size_t bytes;
-};
-struct HostOut {
-  void *host;
-  const void *dev;
-  size_t bytes;
-};
-// host arrays into fresh device buffers: all are allocated, then all copies are queued on `st`; a NULL array is skipped and
-// its buffer stays NULL (sr_optics without E)
-int stage_in(hipStream_t st, std::initializer_list<HostIn> in) {
-  for (const HostIn &a : in)
-    if (a.host)
-      if (int rc = a.buf.alloc(a.bytes)) return rc;
-  for (const HostIn &a : in)
-    if (a.host) SR_HIP(hipMemcpyAsync(a.buf.p, a.host, a.bytes, hipMemcpyHostToDevice, st));
-  return SR_OK;
-}
-// after the launches: their error, the results to the host (a NULL destination is skipped), and the stream is waited for -- the
-// call is done with its buffers
-int stage_out(hipStream_t st, std::initializer_list<HostOut> out) {
-  SR_HIP(hipGetLastError());
-  for (const HostOut &a : out)
-    if (a.host) SR_HIP(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipStreamSynchronize(st));
-  return SR_OK;
-}
+// ---- staging of the host-array entry points: sr::CallBuffers and sr::stage_out (common.hpp), and ---------------------------
 // n doubles for the host: fill(d, grid, st) launches the kernel that writes them into the call's scratch block (256 per workgroup)
 template <typename Fill>
 int read_out(double *host, int64_t n, Fill &&fill) {
@@ -757,7 +708,7 @@ int read_out(double *host, int64_t n, Fill &&fill) {
   double *d = static_cast<double *>(sr::scratch(sizeof(double) * n));
   if (!d) return SR_ERR_HIP;
   fill(d, dim3(sr::grid_for(n, 256)), st);
-  return stage_out(st, {{host, d, sizeof(double) * n}});
+  return sr::stage_out(st, {{host, d, sizeof(double) * n}});
 }
 
 // ---- what the bundle deposits share --------------------------------------------------------------------------------------
@@ -836,16 +787,18 @@ int sr_optics(const sr_optic *chain, int n_ops, double kwave, int64_t N, const d
   if (N == 0) return SR_OK;
   if ((rc = sr::ensure_init())) return rc;
   hipStream_t st = sr::ctx().stream;
-  DevBuf dr, dE;
+  sr::CallBuffers buf;
+  double *dr = nullptr, *dE = nullptr;
   const size_t rb = sizeof(double) * 4 * N;
-  if ((rc = stage_in(st, {{dr, r_in, rb}, {dE, E_in, rb}}))) return rc;
+  SR_RC(buf.upload(&dr, r_in, 4 * (size_t)N, st));
+  SR_RC(buf.upload(&dE, E_in, 4 * (size_t)N, st));
   sr::with_flags(
       [&](auto with_e) {
-        hipLaunchKernelGGL((k_optics<with_e.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N, dr.as<const double>(),
-                           dE.as<const double>(), dr.as<double>(), dE.as<double>());
+        hipLaunchKernelGGL((k_optics<with_e.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, C, N, (const double *)dr,
+                           (const double *)dE, dr, dE);
       },
       E_in != nullptr);
-  return stage_out(st, {{r_out, dr.p, rb}, {E_out, dE.p, rb}});
+  return sr::stage_out(st, {{r_out, dr, rb}, {E_out, dE, rb}});
 }
 
 int sr_hist2d(const double *x, const double *y, int64_t N, int nxb, int nyb, double x_lo, double x_hi, double y_lo,
@@ -856,15 +809,18 @@ int sr_hist2d(const double *x, const double *y, int64_t N, int nxb, int nyb, dou
   int rc = sr::ensure_init();
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
-  DevBuf dx, dy, dH;
-  const size_t hb = sizeof(uint32_t) * (size_t)nxb * nyb;
-  if ((rc = dH.zeroed(hb, st))) return rc;
+  sr::CallBuffers buf;
+  double *dx = nullptr, *dy = nullptr;
+  uint32_t *dH = nullptr;
+  const size_t bins = (size_t)nxb * nyb;
+  SR_RC(buf.zeroed(&dH, bins, st));
   if (N > 0) {
-    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}}))) return rc;
-    hipLaunchKernelGGL(k_hist2d, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(), N,
-                       make_edges(x_lo, x_hi, nxb), make_edges(y_lo, y_hi, nyb), dH.as<uint32_t>());
+    SR_RC(buf.upload(&dx, x, (size_t)N, st));
+    SR_RC(buf.upload(&dy, y, (size_t)N, st));
+    hipLaunchKernelGGL(k_hist2d, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx, (const double *)dy, N,
+                       make_edges(x_lo, x_hi, nxb), make_edges(y_lo, y_hi, nyb), dH);
   }
-  return stage_out(st, {{H, dH.p, hb}});
+  return sr::stage_out(st, {{H, dH, sizeof(uint32_t) * bins}});
 }
 
 int sr_interferogram(const double *x, const double *y, const double *E, int64_t N, int nxe, int nye, double x_lo,
@@ -875,20 +831,23 @@ int sr_interferogram(const double *x, const double *y, const double *E, int64_t 
   int rc = sr::ensure_init();
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
-  DevBuf dx, dy, dE, dA;
+  sr::CallBuffers buf;
+  double *dx = nullptr, *dy = nullptr, *dE = nullptr, *dA = nullptr;
   const int64_t plane = (int64_t)(nxe - 1) * (nye - 1);
   const size_t ab = sizeof(double) * 4 * (size_t)plane;
-  if ((rc = dA.zeroed(ab, st))) return rc;
+  SR_RC(buf.zeroed(&dA, 4 * (size_t)plane, st));
   if (N > 0) {
-    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
-    hipLaunchKernelGGL(k_interferogram, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(),
-                       dE.as<const double>(), N, make_edges(x_lo, x_hi, nxe - 1), make_edges(y_lo, y_hi, nye - 1), dA.as<double>());
+    SR_RC(buf.upload(&dx, x, (size_t)N, st));
+    SR_RC(buf.upload(&dy, y, (size_t)N, st));
+    SR_RC(buf.upload(&dE, E, 4 * (size_t)N, st));
+    hipLaunchKernelGGL(k_interferogram, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx, (const double *)dy,
+                       (const double *)dE, N, make_edges(x_lo, x_hi, nxe - 1), make_edges(y_lo, y_hi, nye - 1), dA);
   }
-  if (!H) return stage_out(st, {{amp, dA.p, ab}});
+  if (!H) return sr::stage_out(st, {{amp, dA, ab}});
   SR_HIP(hipGetLastError());
-  if (amp) SR_HIP(hipMemcpyAsync(amp, dA.p, ab, hipMemcpyDeviceToHost, st));
+  if (amp) SR_HIP(hipMemcpyAsync(amp, dA, ab, hipMemcpyDeviceToHost, st));
   return read_out(H, plane, [&](double *dH, dim3 grid, hipStream_t s) {
-    hipLaunchKernelGGL(k_amplitude, grid, dim3(256), 0, s, dA.as<const double>(), plane, dH);
+    hipLaunchKernelGGL(k_amplitude, grid, dim3(256), 0, s, (const double *)dA, plane, dH);
   });
 }
 
@@ -898,11 +857,14 @@ int sr_interfere_ref_beam(const double *x, const double *y, int64_t N, double n_
   int rc = sr::ensure_init();
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
-  DevBuf dx, dy, dE;
-  if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
-  hipLaunchKernelGGL(k_ref_beam, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(), dy.as<const double>(), N,
-                     make_ref(n_fringes, deg), dE.as<double>());
-  return stage_out(st, {{E, dE.p, sizeof(double) * 4 * N}});
+  sr::CallBuffers buf;
+  double *dx = nullptr, *dy = nullptr, *dE = nullptr;
+  SR_RC(buf.upload(&dx, x, (size_t)N, st));
+  SR_RC(buf.upload(&dy, y, (size_t)N, st));
+  SR_RC(buf.upload(&dE, E, 4 * (size_t)N, st));
+  hipLaunchKernelGGL(k_ref_beam, dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx, (const double *)dy, N,
+                     make_ref(n_fringes, deg), dE);
+  return sr::stage_out(st, {{E, dE, sizeof(double) * 4 * N}});
 }
 
 // ---- device-resident images -------------------------------------------------------------
@@ -987,7 +949,7 @@ int sr_rays_optics(const sr_rays *r, const sr_optic *chain, int n_ops, const sr_
                            with_e.value ? (const double *)r->Jf : nullptr, (const uint32_t *)r->perm, dr, dE);
       },
       E_out != nullptr);
-  rc = stage_out(st, {{rf_out, dr, sizeof(double) * 4 * N}, {E_out, dE, sizeof(double) * 4 * N}});
+  rc = sr::stage_out(st, {{rf_out, dr, sizeof(double) * 4 * N}, {E_out, dE, sizeof(double) * 4 * N}});
   if (rc) return rc;
   sr::scratch_trim();
   return SR_OK;
@@ -1088,20 +1050,23 @@ int sr_intensity2d(const double *x, const double *y, const double *E, int64_t N,
   if (rc) return rc;
   if ((rc = sr::ensure_init())) return rc;
   hipStream_t st = sr::ctx().stream;
-  DevBuf dx, dy, dE, dI;
-  const size_t ib = sizeof(double) * (size_t)n_ch * nxb * nyb;
-  if ((rc = dI.zeroed(ib, st))) return rc;
+  sr::CallBuffers buf;
+  double *dx = nullptr, *dy = nullptr, *dE = nullptr, *dI = nullptr;
+  const size_t cells = (size_t)n_ch * nxb * nyb;
+  SR_RC(buf.zeroed(&dI, cells, st));
   if (N > 0) {
-    if ((rc = stage_in(st, {{dx, x, sizeof(double) * N}, {dy, y, sizeof(double) * N}, {dE, E, sizeof(double) * 4 * N}}))) return rc;
+    SR_RC(buf.upload(&dx, x, (size_t)N, st));
+    SR_RC(buf.upload(&dy, y, (size_t)N, st));
+    SR_RC(buf.upload(&dE, E, 4 * (size_t)N, st));
     const Edges ex = make_edges(x_lo, x_hi, nxb), ey = make_edges(y_lo, y_hi, nyb);
     sr::with_count<SR_MAX_ANALYSERS>(
         [&](auto nch) {
-          hipLaunchKernelGGL((k_intensity2d<nch.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, dx.as<const double>(),
-                             dy.as<const double>(), dE.as<const double>(), N, ex, ey, A, dI.as<double>());
+          hipLaunchKernelGGL((k_intensity2d<nch.value>), dim3(sr::grid_for(N, 256)), dim3(256), 0, st, (const double *)dx,
+                             (const double *)dy, (const double *)dE, N, ex, ey, A, dI);
         },
         n_ch);
   }
-  return stage_out(st, {{I, dI.p, ib}});
+  return sr::stage_out(st, {{I, dI, sizeof(double) * cells}});
 }
 
 int sr_rays_deposit_intensity(const sr_rays *r, const sr_optic *chain, int n_ops, const double *analyser_ab, int n_ch,

@@ -3,6 +3,13 @@
 #pragma once
 #include <hipfft/hipfft.h>
 
+// the one check of a hipfftResult: the entry's name, the call's text and the result code
+#define SR_FFT(who, call)                                                                                        \
+  do {                                                                                                           \
+    const hipfftResult r_ = (call);                                                                              \
+    if (r_ != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: %s failed: hipfftResult %d", who, #call, (int)r_); \
+  } while (0)
+
 namespace sr {
 
 struct Fft {

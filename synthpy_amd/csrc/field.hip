@@ -48,10 +48,9 @@ int fft_plan(Fft *F, int rank, int n0, int n1, int n2, hipfftHandle *out) {
   auto it = cache.find(key);
   if (it == cache.end()) {
     hipfftHandle plan = nullptr;
-    const hipfftResult r = rank == 3   ? F->Plan3d(&plan, n0, n1, n2, HIPFFT_Z2Z)
-                           : rank == 2 ? F->Plan2d(&plan, n0, n1, HIPFFT_Z2Z)
-                                       : F->Plan1d(&plan, n0, HIPFFT_Z2Z, 1);
-    if (r != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "hipfftPlan%dd(%d, %d, %d) failed: hipfftResult %d", rank, n0, n1, n2, (int)r);
+    char who[64];
+    snprintf(who, sizeof who, "fft_plan(%d: %d, %d, %d)", rank, n0, n1, n2);
+    SR_FFT(who, rank == 3 ? F->Plan3d(&plan, n0, n1, n2, HIPFFT_Z2Z) : rank == 2 ? F->Plan2d(&plan, n0, n1, HIPFFT_Z2Z) : F->Plan1d(&plan, n0, HIPFFT_Z2Z, 1));
     it = cache.emplace(key, plan).first;
   }
   *out = it->second;
@@ -186,45 +185,28 @@ int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[
   const int64_t nn = n[0] * n[1] * n[2];
   const int64_t n_axes = n[0] + n[1] + n[2];
   const int n_edges = rule == SR_SPECTRUM_EDGES ? n_bins + 1 : 0;
+  sr::CallBuffers buf;
   double *d_r = nullptr, *d_k = nullptr, *d_sum = nullptr;
   double2 *d_w = nullptr;
   unsigned long long *d_cnt = nullptr;
   hipfftHandle plan = nullptr;
-  auto cleanup = [&]() {
-    sr::dev_free(d_r);
-    sr::dev_free(d_k);
-    sr::dev_free(d_sum);
-    sr::dev_free(d_w);
-    sr::dev_free(d_cnt);
-  };
   // d_k: the axes' coordinates, then the edges; d_cnt: n_bins counts, then the overflow count
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_r), sizeof(double) * nn);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_w), sizeof(double2) * nn);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_k), sizeof(double) * (size_t)(n_axes + n_edges));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_sum), sizeof(double) * n_bins);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_cnt), sizeof(unsigned long long) * (n_bins + 1));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_r, field, sizeof(double) * nn, hipMemcpyHostToDevice, st);
-  for (int d = 0; d < 3 && e == hipSuccess; ++d)
-    e = hipMemcpyAsync(d_k + (d > 0 ? n[0] : 0) + (d > 1 ? n[1] : 0), axis[d], sizeof(double) * n[d], hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_k + n_axes, edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_sum, 0, sizeof(double) * n_bins, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * (n_bins + 1), st);
-  if (e != hipSuccess) {
-    cleanup();
-    return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-  }
+  SR_RC(buf.alloc(&d_r, (size_t)nn));
+  SR_RC(buf.alloc(&d_w, (size_t)nn));
+  SR_RC(buf.alloc(&d_k, (size_t)(n_axes + n_edges)));
+  SR_RC(buf.alloc(&d_sum, (size_t)n_bins));
+  SR_RC(buf.alloc(&d_cnt, (size_t)n_bins + 1));
+  SR_HIP(hipMemcpyAsync(d_r, field, sizeof(double) * nn, hipMemcpyHostToDevice, st));
+  for (int d = 0; d < 3; ++d)
+    SR_HIP(hipMemcpyAsync(d_k + (d > 0 ? n[0] : 0) + (d > 1 ? n[1] : 0), axis[d], sizeof(double) * n[d], hipMemcpyHostToDevice, st));
+  if (n_edges) SR_HIP(hipMemcpyAsync(d_k + n_axes, edges, sizeof(double) * n_edges, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemsetAsync(d_sum, 0, sizeof(double) * n_bins, st));
+  SR_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * (n_bins + 1), st));
   const int block = 256;
   hipLaunchKernelGGL(k_to_complex, dim3(sr::capped_grid((nn + block - 1) / block, 32)), dim3(block), 0, st, (const double *)d_r, nn, d_w);
-  if ((rc = fft_plan(F, ndim, (int)n[0], (int)n[1], (int)n[2], &plan))) {
-    cleanup();
-    return rc;
-  }
-  hipfftResult fr = F->SetStream(plan, st);
-  if (fr == HIPFFT_SUCCESS) fr = F->ExecZ2Z(plan, d_w, d_w, HIPFFT_FORWARD);
-  if (fr != HIPFFT_SUCCESS) {
-    cleanup();
-    return sr::fail(SR_ERR_HIP, "%s: hipfftResult %d", who, (int)fr);
-  }
+  SR_RC(fft_plan(F, ndim, (int)n[0], (int)n[1], (int)n[2], &plan));
+  SR_FFT(who, F->SetStream(plan, st));
+  SR_FFT(who, F->ExecZ2Z(plan, d_w, d_w, HIPFFT_FORWARD));
   const int lds = n_bins <= kMaxLdsBins;
   const size_t lds_bytes = lds ? (sizeof(double) + sizeof(unsigned long long)) * (size_t)n_bins : 0;
   const unsigned bgrid = sr::capped_grid((nn + block - 1) / block, 8);
@@ -237,13 +219,7 @@ int spectrum_nd(const char *who, const double *field, int ndim, const int64_t n[
     hipLaunchKernelGGL(k_spectrum_bins<SR_SPECTRUM_SHELL>, dim3(bgrid), dim3(block), lds_bytes, st, (const double2 *)d_w, nn,
                        n[1], n[2], k0, k1, k2, (const double *)nullptr, n_bins, norm, lds, d_sum, d_cnt, d_cnt + n_bins);
   uint64_t n_over = 0;
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(sum, d_sum, sizeof(double) * n_bins, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(count, d_cnt, sizeof(uint64_t) * n_bins, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(&n_over, d_cnt + n_bins, sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  SR_RC(sr::stage_out(st, {{sum, d_sum, sizeof(double) * n_bins}, {count, d_cnt, sizeof(uint64_t) * n_bins}, {&n_over, d_cnt + n_bins, sizeof(uint64_t)}}));
   if (over) *over = n_over;
   return SR_OK;
 }
@@ -354,9 +330,9 @@ __global__ __launch_bounds__(kModesumBlock) void k_modesum(const double2 *__rest
   }
 }
 
-// The tables for a T x JT tile (padded rows p0, p1), then the sum.  Returns the HIP error of the launches.
+// The tables for a T x JT tile (padded rows p0, p1), then the sum.
 template <int T, int JT>
-hipError_t run_modesum(const double *d_in, int pmask, int M, const int64_t n[3], double2 *d_tab, double *out, hipStream_t st) {
+void run_modesum(const double *d_in, int pmask, int M, const int64_t n[3], double2 *d_tab, double *out, hipStream_t st) {
   const int64_t p0 = (n[0] + T - 1) / T * T, p1 = (n[1] + JT - 1) / JT * JT, n_axes = n[0] + n[1] + n[2];
   double2 *X = d_tab, *Y = X + p0 * M, *S = Y + p1 * M, *D = S + n[2] * M;
   const int block = 256;
@@ -369,13 +345,12 @@ hipError_t run_modesum(const double *d_in, int pmask, int M, const int64_t n[3],
   const unsigned grid = sr::capped_grid((n_tiles + waves - 1) / waves, 64);
   hipLaunchKernelGGL((k_modesum<T, JT>), dim3(grid), dim3(kModesumBlock), 0, st, (const double2 *)X, (const double2 *)Y,
                      (const double2 *)S, (const double2 *)D, M, n[0], n[1], n[2], p0, p1, tiles_l, n_tiles, out);
-  return hipGetLastError();
 }
 
-// table bytes of a T x JT tile
+// table entries of a T x JT tile
 template <int T, int JT>
-size_t modesum_table_bytes(int64_t M, const int64_t n[3]) {
-  return sizeof(double2) * (size_t)(((n[0] + T - 1) / T * T + (n[1] + JT - 1) / JT * JT + 2 * n[2]) * M);
+size_t modesum_table_len(int64_t M, const int64_t n[3]) {
+  return (size_t)(((n[0] + T - 1) / T * T + (n[1] + JT - 1) / JT * JT + 2 * n[2]) * M);
 }
 
 }  // namespace
@@ -425,61 +400,30 @@ extern "C" int sr_field_ifft_real(const double *noise, const float *amp, int n0,
   if ((rc = fft_lib(&F))) return rc;
   hipStream_t st = sr::ctx().stream;
   const int64_t n = (int64_t)n0 * n1 * n2;
+  sr::CallBuffers buf;
   double2 *d_w = nullptr;
   float *d_a = nullptr;
   double *d_f = nullptr;
   unsigned long long *d_m = nullptr;
   hipfftHandle plan = nullptr;
-  auto cleanup = [&]() {
-    sr::dev_free(d_w);
-    sr::dev_free(d_a);
-    sr::dev_free(d_f);
-    sr::dev_free(d_m);
-  };
-#define SR_TRY(call)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (call);                                                                                   \
-    if (e_ != hipSuccess) {                                                                                   \
-      cleanup();                                                                                              \
-      return sr::fail(SR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    }                                                                                                         \
-  } while (0)
-#define SR_TRY_FFT(call)                                                                \
-  do {                                                                                  \
-    hipfftResult r_ = (call);                                                           \
-    if (r_ != HIPFFT_SUCCESS) {                                                         \
-      cleanup();                                                                        \
-      return sr::fail(SR_ERR_HIP, "%s failed: hipfftResult %d", #call, (int)r_);        \
-    }                                                                                   \
-  } while (0)
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_w), sizeof(double2) * n));
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_a), sizeof(float) * n));
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_m), sizeof(unsigned long long)));
-  SR_TRY(hipMemcpyAsync(d_w, noise, sizeof(double2) * n, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_a, amp, sizeof(float) * n, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemsetAsync(d_m, 0, sizeof(unsigned long long), st));
+  SR_RC(buf.alloc(&d_w, (size_t)n));
+  SR_RC(buf.alloc(&d_a, (size_t)n));
+  SR_RC(buf.alloc(&d_m, 1));
+  SR_HIP(hipMemcpyAsync(d_w, noise, sizeof(double2) * n, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_a, amp, sizeof(float) * n, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemsetAsync(d_m, 0, sizeof(unsigned long long), st));
   const int block = 256;
   const int64_t blocks = (n + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
   hipLaunchKernelGGL(k_shape_noise, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_w, (const float *)d_a, n);
-  SR_TRY(hipGetLastError());
-  if ((rc = fft_plan(F, 3, n0, n1, n2, &plan))) {  // C order: n2 fastest, as the NumPy array
-    cleanup();
-    return rc;
-  }
-  SR_TRY_FFT(F->SetStream(plan, st));
-  SR_TRY_FFT(F->ExecZ2Z(plan, d_w, d_w, HIPFFT_BACKWARD));
-  sr::dev_free(d_a);
-  d_a = nullptr;
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_f), sizeof(double) * n));
+  SR_HIP(hipGetLastError());
+  SR_RC(fft_plan(F, 3, n0, n1, n2, &plan));  // C order: n2 fastest, as the NumPy array
+  SR_FFT("sr_field_ifft_real", F->SetStream(plan, st));
+  SR_FFT("sr_field_ifft_real", F->ExecZ2Z(plan, d_w, d_w, HIPFFT_BACKWARD));
+  buf.release(d_a);  // before d_f: the call's peak stays at the transform's buffer plus one field
+  SR_RC(buf.alloc(&d_f, (size_t)n));
   hipLaunchKernelGGL(k_real_scaled, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const double2 *)d_w, n, 1.0 / (double)n, d_f, d_m);
   if (normalise) hipLaunchKernelGGL(k_divide, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_f, n, (const unsigned long long *)d_m);
-  SR_TRY(hipGetLastError());
-  SR_TRY(hipMemcpyAsync(out, d_f, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipStreamSynchronize(st));
-#undef SR_TRY
-#undef SR_TRY_FFT
-  cleanup();
-  return SR_OK;
+  return sr::stage_out(st, {{out, d_f, sizeof(double) * n}});
 }
 
 extern "C" int sr_field_modesum(int ndim, const int64_t *shape, const double *coords, int nmodes, const double *k,
@@ -515,28 +459,17 @@ extern "C" int sr_field_modesum(int ndim, const int64_t *shape, const double *co
   int rc = sr::ensure_init();
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
+  sr::CallBuffers buf;
   double *d_in = nullptr, *d_out = nullptr;
   double2 *d_tab = nullptr;
-  auto cleanup = [&]() {
-    sr::dev_free(d_in);
-    sr::dev_free(d_out);
-    sr::dev_free(d_tab);
-  };
   const bool tile_j = n[1] > 1;  // 3-D: G is reused over T = 8 rows i and formed for 4 rows j; Y == 1: 16 rows i
-  const size_t tab_bytes = tile_j ? modesum_table_bytes<8, 4>(M, n) : modesum_table_bytes<16, 1>(M, n);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), sizeof(double) * h.size());
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tab), tab_bytes);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(double) * (size_t)n_cells);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_in, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) {
-    cleanup();
-    return sr::fail(SR_ERR_HIP, "sr_field_modesum: %s", hipGetErrorString(e));
-  }
-  e = tile_j ? run_modesum<8, 4>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st)
-             : run_modesum<16, 1>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_cells, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_field_modesum: %s", hipGetErrorString(e));
-  return SR_OK;
+  SR_RC(buf.alloc(&d_in, h.size()));
+  SR_RC(buf.alloc(&d_tab, tile_j ? modesum_table_len<8, 4>(M, n) : modesum_table_len<16, 1>(M, n)));
+  SR_RC(buf.alloc(&d_out, (size_t)n_cells));
+  SR_HIP(hipMemcpyAsync(d_in, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+  if (tile_j)
+    run_modesum<8, 4>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st);
+  else
+    run_modesum<16, 1>(d_in, kPmask[ndim - 1], nmodes, n, d_tab, d_out, st);
+  return sr::stage_out(st, {{out, d_out, sizeof(double) * (size_t)n_cells}});
 }

@@ -498,31 +498,6 @@ __global__ void k_crop(const double2 *__restrict__ F, int m1, int r0, int nr, in
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// device buffers of one call, freed together
-struct Buffers {
-  std::vector<void *> held;
-  ~Buffers() {
-    for (void *p : held) sr::dev_free(p);
-  }
-  template <typename T>
-  int alloc(T **p, size_t count) {
-    const int rc = sr::dev_alloc(p, count);
-    if (rc == SR_OK && *p) held.push_back(*p);
-    return rc;
-  }
-};
-
-#define SR_TRY(call)                                                                                                  \
-  do {                                                                                                                \
-    const hipError_t e_ = (call);                                                                                     \
-    if (e_ != hipSuccess) return sr::fail(SR_ERR_HIP, "%s: %s failed: %s", who, #call, hipGetErrorString(e_));        \
-  } while (0)
-#define SR_TRY_RC(call)      \
-  do {                       \
-    const int rc_ = (call);  \
-    if (rc_) return rc_;     \
-  } while (0)
-
 unsigned grid_of(int64_t n, int block, int per_cu) {
   return sr::capped_grid((n + block - 1) / block, per_cu);
 }
@@ -550,33 +525,33 @@ std::vector<uint32_t> monotone_chain(const double *x, const double *y, std::vect
 
 // Scatter to grid: d_amp, d_phase (ny x nx) and, with want_tri, d_tri (ny x nx x 3) on the device; stats as the header says.
 int scatter_to_grid(const char *who, int64_t n, const double *rx, const double *ry, const double *ra, const double *rp, int nx,
-                    const double *gx, int ny, const double *gy, bool want_tri, Buffers &buf, double **d_amp, double **d_phase,
+                    const double *gx, int ny, const double *gy, bool want_tri, sr::CallBuffers &buf, double **d_amp, double **d_phase,
                     int **d_tri, int64_t *stats) {
   hipStream_t st = sr::ctx().stream;
   const int64_t n_nodes = (int64_t)nx * ny;
   double *d_in = nullptr, *d_g = nullptr;
   unsigned long long *d_w = nullptr;  // [0..3] box, [4..67] extremes, [68..71] counters
-  SR_TRY_RC(buf.alloc(&d_in, (size_t)(4 * n)));
-  SR_TRY_RC(buf.alloc(&d_g, (size_t)(nx + ny)));
-  SR_TRY_RC(buf.alloc(&d_w, 4 + kDirs + 4));
-  SR_TRY_RC(buf.alloc(d_amp, (size_t)n_nodes));
-  SR_TRY_RC(buf.alloc(d_phase, (size_t)n_nodes));
-  if (want_tri) SR_TRY_RC(buf.alloc(d_tri, (size_t)(3 * n_nodes)));
+  SR_RC(buf.alloc(&d_in, (size_t)(4 * n)));
+  SR_RC(buf.alloc(&d_g, (size_t)(nx + ny)));
+  SR_RC(buf.alloc(&d_w, 4 + kDirs + 4));
+  SR_RC(buf.alloc(d_amp, (size_t)n_nodes));
+  SR_RC(buf.alloc(d_phase, (size_t)n_nodes));
+  if (want_tri) SR_RC(buf.alloc(d_tri, (size_t)(3 * n_nodes)));
   const double *x = d_in, *y = d_in + n, *a = d_in + 2 * n, *p = d_in + 3 * n;
-  SR_TRY_RC(sr::upload_sync(d_in, rx, sizeof(double) * n, st));
-  SR_TRY_RC(sr::upload_sync(d_in + n, ry, sizeof(double) * n, st));
-  SR_TRY_RC(sr::upload_sync(d_in + 2 * n, ra, sizeof(double) * n, st));
-  SR_TRY_RC(sr::upload_sync(d_in + 3 * n, rp, sizeof(double) * n, st));
-  SR_TRY(hipMemcpyAsync(d_g, gx, sizeof(double) * nx, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_g + nx, gy, sizeof(double) * ny, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemsetAsync(d_w, 0xff, 2 * sizeof(unsigned long long), st));
-  SR_TRY(hipMemsetAsync(d_w + 2, 0, (2 + kDirs + 4) * sizeof(unsigned long long), st));
+  SR_RC(sr::upload_sync(d_in, rx, sizeof(double) * n, st));
+  SR_RC(sr::upload_sync(d_in + n, ry, sizeof(double) * n, st));
+  SR_RC(sr::upload_sync(d_in + 2 * n, ra, sizeof(double) * n, st));
+  SR_RC(sr::upload_sync(d_in + 3 * n, rp, sizeof(double) * n, st));
+  SR_HIP(hipMemcpyAsync(d_g, gx, sizeof(double) * nx, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_g + nx, gy, sizeof(double) * ny, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemsetAsync(d_w, 0xff, 2 * sizeof(unsigned long long), st));
+  SR_HIP(hipMemsetAsync(d_w + 2, 0, (2 + kDirs + 4) * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(k_bbox, dim3(grid_of(n, 256, 8)), dim3(256), 0, st, x, y, n, d_w);
   hipLaunchKernelGGL(k_extremes, dim3(grid_of(n, 256, 8)), dim3(256), 0, st, x, y, n, rx[0], ry[0], d_w + 4);
-  SR_TRY(hipGetLastError());
+  SR_HIP(hipGetLastError());
   unsigned long long hw[4 + kDirs];
-  SR_TRY(hipMemcpyAsync(hw, d_w, sizeof hw, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipStreamSynchronize(st));
+  SR_HIP(hipMemcpyAsync(hw, d_w, sizeof hw, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
 
   // bins: ~kRaysPerBin rays each over the rays' box, square-ish
   const double bx0 = from_order_key(hw[0]), by0 = from_order_key(hw[1]);
@@ -593,14 +568,14 @@ int scatter_to_grid(const char *who, int64_t n, const double *rx, const double *
   uint32_t *d_start = nullptr, *d_cursor = nullptr, *d_sums = nullptr, *d_list = nullptr;
   double2 *d_xy = nullptr, *d_val = nullptr, *d_poly = nullptr;
   int *d_id = nullptr;
-  SR_TRY_RC(buf.alloc(&d_start, (size_t)(nb + 1)));
-  SR_TRY_RC(buf.alloc(&d_cursor, (size_t)(nb + 1)));
-  SR_TRY_RC(buf.alloc(&d_sums, (size_t)((nb + 1 + 2047) / 2048)));
-  SR_TRY_RC(buf.alloc(&d_xy, (size_t)n));
-  SR_TRY_RC(buf.alloc(&d_val, (size_t)n));
-  SR_TRY_RC(buf.alloc(&d_id, (size_t)n));
-  SR_TRY_RC(buf.alloc(&d_list, (size_t)std::max<int64_t>(n, n_nodes)));
-  SR_TRY_RC(buf.alloc(&d_poly, kDirs));
+  SR_RC(buf.alloc(&d_start, (size_t)(nb + 1)));
+  SR_RC(buf.alloc(&d_cursor, (size_t)(nb + 1)));
+  SR_RC(buf.alloc(&d_sums, (size_t)((nb + 1 + 2047) / 2048)));
+  SR_RC(buf.alloc(&d_xy, (size_t)n));
+  SR_RC(buf.alloc(&d_val, (size_t)n));
+  SR_RC(buf.alloc(&d_id, (size_t)n));
+  SR_RC(buf.alloc(&d_list, (size_t)std::max<int64_t>(n, n_nodes)));
+  SR_RC(buf.alloc(&d_poly, kDirs));
 
   // the pre-filter polygon: the hull of the 64 extreme rays
   std::vector<uint32_t> ext;
@@ -610,48 +585,48 @@ int scatter_to_grid(const char *who, int64_t n, const double *rx, const double *
   const int m = poly.size() >= 3 ? (int)poly.size() : 0;
   std::vector<double2> hpoly((size_t)m);
   for (int k = 0; k < m; ++k) hpoly[k] = make_double2(rx[poly[k]], ry[poly[k]]);
-  if (m) SR_TRY(hipMemcpyAsync(d_poly, hpoly.data(), sizeof(double2) * m, hipMemcpyHostToDevice, st));
+  if (m) SR_HIP(hipMemcpyAsync(d_poly, hpoly.data(), sizeof(double2) * m, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_hull_filter, dim3(sr::grid_for(n, 256)), dim3(256), 0, st, x, y, n, (const double2 *)d_poly, m, d_w + 68,
                      d_list);
   // the counting sort by bin
-  SR_TRY(hipMemsetAsync(d_start, 0, sizeof(uint32_t) * (nb + 1), st));
+  SR_HIP(hipMemsetAsync(d_start, 0, sizeof(uint32_t) * (nb + 1), st));
   hipLaunchKernelGGL(k_bin_count, dim3(grid_of(n, 256, 8)), dim3(256), 0, st, x, y, n, g, d_start);
   sr::exclusive_scan_u32(d_start, nb + 1, d_sums, st);
-  SR_TRY(hipMemcpyAsync(d_cursor, d_start, sizeof(uint32_t) * (nb + 1), hipMemcpyDeviceToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_cursor, d_start, sizeof(uint32_t) * (nb + 1), hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_bin_scatter, dim3(grid_of(n, 256, 8)), dim3(256), 0, st, x, y, a, p, n, g, d_cursor, d_xy, d_val, d_id);
-  SR_TRY(hipGetLastError());
+  SR_HIP(hipGetLastError());
   unsigned long long n_left = 0;
-  SR_TRY(hipMemcpyAsync(&n_left, d_w + 68, sizeof n_left, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipStreamSynchronize(st));
+  SR_HIP(hipMemcpyAsync(&n_left, d_w + 68, sizeof n_left, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
 
   // the exact hull of what the filter left
   std::vector<uint32_t> left((size_t)n_left);
-  if (n_left) SR_TRY(hipMemcpy(left.data(), d_list, sizeof(uint32_t) * n_left, hipMemcpyDeviceToHost));
+  if (n_left) SR_HIP(hipMemcpy(left.data(), d_list, sizeof(uint32_t) * n_left, hipMemcpyDeviceToHost));
   const std::vector<uint32_t> hull = monotone_chain(rx, ry, left);
   const int nh = hull.size() >= 3 ? (int)hull.size() : 0;
   double2 *d_hull = nullptr;
-  SR_TRY_RC(buf.alloc(&d_hull, (size_t)std::max(nh, 1)));
+  SR_RC(buf.alloc(&d_hull, (size_t)std::max(nh, 1)));
   std::vector<double2> hh((size_t)nh);
   for (int k = 0; k < nh; ++k) hh[k] = make_double2(rx[hull[k]], ry[hull[k]]);
-  if (nh) SR_TRY(hipMemcpyAsync(d_hull, hh.data(), sizeof(double2) * nh, hipMemcpyHostToDevice, st));
+  if (nh) SR_HIP(hipMemcpyAsync(d_hull, hh.data(), sizeof(double2) * nh, hipMemcpyHostToDevice, st));
 
-  SR_TRY(hipMemsetAsync(d_w + 68, 0, 4 * sizeof(unsigned long long), st));
+  SR_HIP(hipMemsetAsync(d_w + 68, 0, 4 * sizeof(unsigned long long), st));
   const Bins B{g, d_xy, d_val, d_id, d_start};
   const double *d_gx = d_g, *d_gy = d_g + nx;
   hipLaunchKernelGGL(k_locate, dim3(sr::grid_for(n_nodes, 256)), dim3(256), 0, st, B, (const double2 *)d_hull, nh, d_gx, nx, d_gy,
                      n_nodes, *d_amp, *d_phase, want_tri ? *d_tri : nullptr, d_w + 68, d_list);
-  SR_TRY(hipGetLastError());
+  SR_HIP(hipGetLastError());
   unsigned long long c[4];
-  SR_TRY(hipMemcpyAsync(c, d_w + 68, sizeof c, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipStreamSynchronize(st));
+  SR_HIP(hipMemcpyAsync(c, d_w + 68, sizeof c, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
   const unsigned long long n_second = c[0];
   if (n_second) {
     hipLaunchKernelGGL(k_locate_team, dim3(grid_of((int64_t)n_second * kTeam, kTeam, 4)), dim3(kTeam), 0, st, B,
                        (const uint32_t *)d_list, (int64_t)n_second, d_gx, nx, d_gy, *d_amp, *d_phase, want_tri ? *d_tri : nullptr,
                        d_w + 68);
-    SR_TRY(hipGetLastError());
-    SR_TRY(hipMemcpyAsync(c, d_w + 68, sizeof c, hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
+    SR_HIP(hipGetLastError());
+    SR_HIP(hipMemcpyAsync(c, d_w + 68, sizeof c, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipStreamSynchronize(st));
   }
   if (c[2]) return sr::fail(SR_ERR_HIP, "%s: %llu nodes were not located (a walk ran past %d steps)", who, c[2], kTeamSteps);
   if (stats) {
@@ -663,35 +638,33 @@ int scatter_to_grid(const char *who, int64_t n, const double *rx, const double *
 
 // fresnel_propagate on the device field d_u (m0 x m1, overwritten) -> out (nr x nc complex128, host)
 int propagate_field(const char *who, double2 *d_u, int m0, int m1, const double *fx, const double *fy, const sr_fresnel_params *p,
-                    double *out, Buffers &buf) {
+                    double *out, sr::CallBuffers &buf) {
   hipStream_t st = sr::ctx().stream;
   sr::Fft *F;
-  SR_TRY_RC(sr::fft_lib(&F));
+  SR_RC(sr::fft_lib(&F));
   hipfftHandle plan = nullptr;
-  SR_TRY_RC(sr::fft_plan(F, 2, m0, m1, 0, &plan));
+  SR_RC(sr::fft_plan(F, 2, m0, m1, 0, &plan));
   double *d_f = nullptr;
   double2 *d_out = nullptr;
-  SR_TRY_RC(buf.alloc(&d_f, (size_t)(m0 + m1)));
-  SR_TRY_RC(buf.alloc(&d_out, (size_t)p->nr * p->nc));
-  SR_TRY(hipMemcpyAsync(d_f, fx, sizeof(double) * m0, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_f + m0, fy, sizeof(double) * m1, hipMemcpyHostToDevice, st));
-  hipfftResult fr = F->SetStream(plan, st);
-  if (fr == HIPFFT_SUCCESS) fr = F->ExecZ2Z(plan, d_u, d_u, HIPFFT_FORWARD);
-  if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: forward FFT: hipfftResult %d", who, (int)fr);
+  SR_RC(buf.alloc(&d_f, (size_t)(m0 + m1)));
+  SR_RC(buf.alloc(&d_out, (size_t)p->nr * p->nc));
+  SR_HIP(hipMemcpyAsync(d_f, fx, sizeof(double) * m0, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_f + m0, fy, sizeof(double) * m1, hipMemcpyHostToDevice, st));
+  SR_FFT(who, F->SetStream(plan, st));
+  SR_FFT(who, F->ExecZ2Z(plan, d_u, d_u, HIPFFT_FORWARD));
   const int64_t n = (int64_t)m0 * m1;
   hipLaunchKernelGGL(k_transfer, dim3(grid_of(n, 256, 32)), dim3(256), 0, st, d_u, m0, m1, (const double *)d_f,
                      (const double *)(d_f + m0), p->pi_lz, p->psf);
-  SR_TRY(hipGetLastError());
-  fr = F->ExecZ2Z(plan, d_u, d_u, HIPFFT_BACKWARD);
-  if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: inverse FFT: hipfftResult %d", who, (int)fr);
+  SR_HIP(hipGetLastError());
+  SR_FFT(who, F->ExecZ2Z(plan, d_u, d_u, HIPFFT_BACKWARD));
   const int64_t nout = (int64_t)p->nr * p->nc;
   if (nout) {
     hipLaunchKernelGGL(k_crop, dim3(grid_of(nout, 256, 32)), dim3(256), 0, st, (const double2 *)d_u, m1, p->r0, p->nr, p->c0, p->nc,
                        p->post_re, p->post_im, d_out);
-    SR_TRY(hipGetLastError());
-    SR_TRY(hipMemcpyAsync(out, d_out, sizeof(double2) * nout, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipGetLastError());
+    SR_HIP(hipMemcpyAsync(out, d_out, sizeof(double2) * nout, hipMemcpyDeviceToHost, st));
   }
-  SR_TRY(hipStreamSynchronize(st));
+  SR_HIP(hipStreamSynchronize(st));
   return SR_OK;
 }
 
@@ -719,32 +692,30 @@ extern "C" int sr_fresnel_grid(int64_t n_rays, const double *rx, const double *r
                                const double *gx, int ny, const double *gy, double *amp_out, double *phase_out, int32_t *tri_out,
                                int64_t *stats) {
   const char *who = "sr_fresnel_grid";
-  SR_TRY_RC(check_rays(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy));
+  SR_RC(check_rays(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy));
   SR_CHECK(amp_out && phase_out, "%s: NULL argument", who);
-  SR_TRY_RC(sr::ensure_init());
+  SR_RC(sr::ensure_init());
   hipStream_t st = sr::ctx().stream;
-  Buffers buf;
+  sr::CallBuffers buf;
   double *d_amp = nullptr, *d_phase = nullptr;
   int *d_tri = nullptr;
-  SR_TRY_RC(scatter_to_grid(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy, tri_out != nullptr, buf, &d_amp, &d_phase, &d_tri, stats));
+  SR_RC(scatter_to_grid(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy, tri_out != nullptr, buf, &d_amp, &d_phase, &d_tri, stats));
   const int64_t n_nodes = (int64_t)nx * ny;
-  SR_TRY(hipMemcpyAsync(amp_out, d_amp, sizeof(double) * n_nodes, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipMemcpyAsync(phase_out, d_phase, sizeof(double) * n_nodes, hipMemcpyDeviceToHost, st));
-  if (tri_out) SR_TRY(hipMemcpyAsync(tri_out, d_tri, sizeof(int32_t) * 3 * n_nodes, hipMemcpyDeviceToHost, st));
-  SR_TRY(hipStreamSynchronize(st));
-  return SR_OK;
+  return sr::stage_out(st, {{amp_out, d_amp, sizeof(double) * n_nodes},
+                            {phase_out, d_phase, sizeof(double) * n_nodes},
+                            {tri_out, d_tri, sizeof(int32_t) * 3 * n_nodes}});
 }
 
 extern "C" int sr_fresnel_propagate(const double *u0, int m0, int m1, const double *fx, const double *fy, const sr_fresnel_params *p,
                                     double *out) {
   const char *who = "sr_fresnel_propagate";
   SR_CHECK(u0 && out, "%s: NULL argument", who);
-  SR_TRY_RC(check_params(who, m0, m1, fx, fy, p));
-  SR_TRY_RC(sr::ensure_init());
-  Buffers buf;
+  SR_RC(check_params(who, m0, m1, fx, fy, p));
+  SR_RC(sr::ensure_init());
+  sr::CallBuffers buf;
   double2 *d_u = nullptr;
-  SR_TRY_RC(buf.alloc(&d_u, (size_t)m0 * m1));
-  SR_TRY_RC(sr::upload_sync(d_u, u0, sizeof(double2) * (size_t)m0 * m1, sr::ctx().stream));
+  SR_RC(buf.alloc(&d_u, (size_t)m0 * m1));
+  SR_RC(sr::upload_sync(d_u, u0, sizeof(double2) * (size_t)m0 * m1, sr::ctx().stream));
   return propagate_field(who, d_u, m0, m1, fx, fy, p, out, buf);
 }
 
@@ -753,28 +724,28 @@ extern "C" int sr_fresnel_rays(int64_t n_rays, const double *rx, const double *r
                                const double *w1, int m0, int m1, const double *fx, const double *fy, const sr_fresnel_params *p,
                                double *out, int64_t *stats) {
   const char *who = "sr_fresnel_rays";
-  SR_TRY_RC(check_rays(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy));
+  SR_RC(check_rays(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy));
   SR_CHECK(src0 && src1 && w0 && w1 && out, "%s: NULL argument", who);
-  SR_TRY_RC(check_params(who, m0, m1, fx, fy, p));
+  SR_RC(check_params(who, m0, m1, fx, fy, p));
   for (int r = 0; r < m0; ++r) SR_CHECK(src0[r] >= 0 && src0[r] < ny, "%s: src0[%d] = %d outside 0..%d", who, r, src0[r], ny - 1);
   for (int c = 0; c < m1; ++c) SR_CHECK(src1[c] >= 0 && src1[c] < nx, "%s: src1[%d] = %d outside 0..%d", who, c, src1[c], nx - 1);
-  SR_TRY_RC(sr::ensure_init());
+  SR_RC(sr::ensure_init());
   hipStream_t st = sr::ctx().stream;
-  Buffers buf;
+  sr::CallBuffers buf;
   double *d_amp = nullptr, *d_phase = nullptr, *d_w = nullptr;
   int *d_tri = nullptr, *d_src = nullptr;
   double2 *d_u = nullptr;
-  SR_TRY_RC(scatter_to_grid(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy, false, buf, &d_amp, &d_phase, &d_tri, stats));
-  SR_TRY_RC(buf.alloc(&d_src, (size_t)(m0 + m1)));
-  SR_TRY_RC(buf.alloc(&d_w, (size_t)(m0 + m1)));
-  SR_TRY_RC(buf.alloc(&d_u, (size_t)m0 * m1));
-  SR_TRY(hipMemcpyAsync(d_src, src0, sizeof(int32_t) * m0, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_src + m0, src1, sizeof(int32_t) * m1, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_w, w0, sizeof(double) * m0, hipMemcpyHostToDevice, st));
-  SR_TRY(hipMemcpyAsync(d_w + m0, w1, sizeof(double) * m1, hipMemcpyHostToDevice, st));
+  SR_RC(scatter_to_grid(who, n_rays, rx, ry, amp, phase, nx, gx, ny, gy, false, buf, &d_amp, &d_phase, &d_tri, stats));
+  SR_RC(buf.alloc(&d_src, (size_t)(m0 + m1)));
+  SR_RC(buf.alloc(&d_w, (size_t)(m0 + m1)));
+  SR_RC(buf.alloc(&d_u, (size_t)m0 * m1));
+  SR_HIP(hipMemcpyAsync(d_src, src0, sizeof(int32_t) * m0, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_src + m0, src1, sizeof(int32_t) * m1, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_w, w0, sizeof(double) * m0, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(d_w + m0, w1, sizeof(double) * m1, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_pad_window, dim3(grid_of((int64_t)m0 * m1, 256, 32)), dim3(256), 0, st, (const double *)d_amp,
                      (const double *)d_phase, nx, (const int *)d_src, (const int *)(d_src + m0), (const double *)d_w,
                      (const double *)(d_w + m0), m0, m1, d_u);
-  SR_TRY(hipGetLastError());
+  SR_HIP(hipGetLastError());
   return propagate_field(who, d_u, m0, m1, fx, fy, p, out, buf);
 }

@@ -94,6 +94,14 @@ void scratch_release() {
   }
 }
 
+int stage_out(hipStream_t st, std::initializer_list<HostOut> out) {
+  SR_HIP(hipGetLastError());
+  for (const HostOut &a : out)
+    if (a.host) SR_HIP(hipMemcpyAsync(a.host, a.dev, a.bytes, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
+  return SR_OK;
+}
+
 bool Carve::alloc() {
   char *block = static_cast<char *>(scratch(bytes_));
   if (!block) return false;

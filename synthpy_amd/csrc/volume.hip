@@ -6,6 +6,8 @@
 // line-sized streams and each 128-byte line serves eight consecutive node planes of one column.
 // The file is compiled with -ffp-contract=off: the float32 gradient arithmetic must round
 // exactly as numpy's separate multiply and add ufuncs do.
+#include <memory>
+
 #include "common.hpp"
 
 namespace {
@@ -287,6 +289,9 @@ void sr_volume_destroy(sr_volume *v) {
 
 namespace {
 
+// a volume under construction: destroyed on every early return, release()d into *out on success
+using VolumePtr = std::unique_ptr<sr_volume, void (*)(sr_volume *)>;
+
 // nx, ny, nz, x, y, z: the whole domain; the volume built holds node planes k_lo..k_hi of the probing axis and `ne`
 // holds planes max(k_lo-1, 0)..min(k_hi+1, n-1) (the whole array when k_lo = 0 and k_hi = n-1)
 int create_impl(sr_volume **out, const void *ne, int ne_is_f64, int nx, int ny, int nz, const float *x, const float *y,
@@ -320,41 +325,23 @@ int create_impl(sr_volume **out, const void *ne, int ne_is_f64, int nx, int ny, 
   pdims[a_ax] = k_hi - k_lo + 1;
   const float *pco[3] = {x, y, z};
   pco[a_ax] += k_lo;
-  sr_volume *v = new sr_volume();
-  rc = volume_common(v, pdims[0], pdims[1], pdims[2], pco[0], pco[1], pco[2], probing_axis, flags & SR_VOL_PHASE, omega);
-  if (rc) {
-    sr_volume_destroy(v);
-    return rc;
-  }
+  VolumePtr v(new sr_volume(), sr_volume_destroy);
+  SR_RC(volume_common(v.get(), pdims[0], pdims[1], pdims[2], pco[0], pco[1], pco[2], probing_axis, flags & SR_VOL_PHASE, omega));
   v->is_slab = !whole;
   v->k_lo = k_lo;
   v->k_hi = k_hi;
   v->n_glob = n_a;
   const size_t src_total = (size_t)sdims[0] * sdims[1] * sdims[2];
-  void *d_ne = nullptr;
-  float *d_nenc = nullptr, *d_coef = nullptr;
   const size_t ne_bytes = src_total * (ne_is_f64 ? sizeof(double) : sizeof(float));
-  auto cleanup = [&]() {
-    sr::dev_free(d_ne);
-    sr::dev_free(d_nenc);
-    sr::dev_free(d_coef);
-  };
-#define SR_TRY(call)                                                                                     \
-  do {                                                                                                   \
-    hipError_t e_ = (call);                                                                              \
-    if (e_ != hipSuccess) {                                                                              \
-      cleanup();                                                                                         \
-      sr_volume_destroy(v);                                                                              \
-      return sr::fail(SR_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    }                                                                                                    \
-  } while (0)
-  SR_TRY(hipMalloc(&d_ne, ne_bytes));
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_nenc), src_total * sizeof(float)));
-  SR_TRY(hipMemcpyAsync(d_ne, ne, ne_bytes, hipMemcpyHostToDevice, st));
+  sr::CallBuffers buf;
+  char *d_ne = nullptr;  // float64 or float32, as the caller's
+  float *d_nenc = nullptr, *d_coef = nullptr;
+  SR_RC(buf.alloc(&d_ne, ne_bytes));
+  SR_RC(buf.alloc(&d_nenc, src_total));
+  SR_HIP(hipMemcpyAsync(d_ne, ne, ne_bytes, hipMemcpyHostToDevice, st));
 
   // gradient coefficients (float32, numpy's arithmetic) for x, y, z
   const int dims[3] = {nx, ny, nz};
-  const float *co[3] = {x, y, z};
   HostCoef hc[3] = {make_coef(x, nx), make_coef(y, ny), make_coef(z, nz)};
   std::vector<float> flat;
   size_t off[3][3];
@@ -366,10 +353,8 @@ int create_impl(sr_volume **out, const void *ne, int ne_is_f64, int nx, int ny, 
     off[k][2] = flat.size();
     flat.insert(flat.end(), hc[k].cc.begin(), hc[k].cc.end());
   }
-  (void)co;
-  SR_TRY(hipMalloc(reinterpret_cast<void **>(&d_coef), flat.size() * sizeof(float)));
-  SR_TRY(hipMemcpyAsync(d_coef, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice, st));
-  PackArgs A = pack_args(v);
+  SR_RC(buf.upload(&d_coef, flat.data(), flat.size(), st));
+  PackArgs A = pack_args(v.get());
   A.sny = sdims[1];
   A.snz = sdims[2];
   A.a_src_off = k_lo - h_lo;
@@ -386,28 +371,45 @@ int create_impl(sr_volume **out, const void *ne, int ne_is_f64, int nx, int ny, 
   }
   const int block = 256;
   const int64_t blocks = (int64_t)(src_total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
-  if (ne_is_f64)
-    hipLaunchKernelGGL(k_ne_nc_f64, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const double *)d_ne, (int64_t)src_total, ncrit, d_nenc);
-  else
-    hipLaunchKernelGGL(k_ne_nc_f32, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, (const float *)d_ne, (int64_t)src_total, (float)ncrit, d_nenc);
-  const bool phase = (flags & SR_VOL_PHASE) != 0;
-  if (ne_is_f64) {
-    if (phase)
-      hipLaunchKernelGGL((k_pack_from_ne<double, true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
-    else
-      hipLaunchKernelGGL((k_pack_from_ne<double, false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const double *)d_ne, v->P, v->L);
-  } else {
-    if (phase)
-      hipLaunchKernelGGL((k_pack_from_ne<float, true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
-    else
-      hipLaunchKernelGGL((k_pack_from_ne<float, false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, (const float *)d_ne, v->P, v->L);
-  }
-  SR_TRY(hipGetLastError());
-  SR_TRY(hipStreamSynchronize(st));
-#undef SR_TRY
-  cleanup();
-  *out = v;
+  sr::with_flags(
+      [&](auto f64, auto phase) {
+        using NE = std::conditional_t<f64.value, double, float>;
+        const NE *d_src = reinterpret_cast<const NE *>(d_ne);
+        if constexpr (f64.value)
+          hipLaunchKernelGGL(k_ne_nc_f64, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_src, (int64_t)src_total, ncrit, d_nenc);
+        else
+          hipLaunchKernelGGL(k_ne_nc_f32, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, d_src, (int64_t)src_total, (float)ncrit, d_nenc);
+        hipLaunchKernelGGL((k_pack_from_ne<NE, phase.value>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_nenc, d_src, v->P, v->L);
+      },
+      ne_is_f64 != 0, (flags & SR_VOL_PHASE) != 0);
+  SR_RC(sr::stage_out(st, {}));  // nothing to copy back: the launches' error and the wait
+  *out = v.release();
   return SR_OK;
+}
+
+// the new v->K (kappa given) and v->Q (ne and B given) of sr_volume_attach_aux, which frees them if this fails
+int pack_aux(sr_volume *v, const double *kappa, const double *ne, const double *B) {
+  hipStream_t st = sr::ctx().stream;
+  const size_t total = (size_t)v->nx * v->ny * v->nz;
+  const size_t packed = sr::packed_nodes(v->na, v->nb, v->nc);
+  sr::CallBuffers buf;
+  double *d_k = nullptr, *d_ne = nullptr, *d_B = nullptr;
+  if (kappa) {
+    SR_RC(buf.upload(&d_k, kappa, total, st));
+    SR_RC(sr::dev_alloc(&v->K, packed));
+    SR_HIP(hipMemsetAsync(v->K, 0, packed * sizeof(double), st));
+  }
+  if (ne) {
+    SR_RC(buf.upload(&d_ne, ne, total, st));
+    SR_RC(buf.upload(&d_B, B, 3 * total, st));
+    SR_RC(sr::dev_alloc(&v->Q, 4 * packed));
+    SR_HIP(hipMemsetAsync(v->Q, 0, 4 * packed * sizeof(double), st));
+  }
+  const int block = 256;
+  const int64_t blocks = (int64_t)(total + block - 1) / block;
+  hipLaunchKernelGGL(k_pack_aux, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, pack_args(v), (const double *)d_k, (const double *)d_ne,
+                     (const double *)d_B, v->K, v->Q);
+  return sr::stage_out(st, {});
 }
 
 }  // namespace
@@ -439,46 +441,25 @@ int sr_volume_create_from_fields(sr_volume **out, const float *dndx, const float
   rc = sr::ensure_init();
   if (rc) return rc;
   hipStream_t st = sr::ctx().stream;
-  sr_volume *v = new sr_volume();
-  rc = volume_common(v, nx, ny, nz, x, y, z, probing_axis, nref ? SR_VOL_PHASE : 0, omega);
-  if (rc) {
-    sr_volume_destroy(v);
-    return rc;
-  }
+  VolumePtr v(new sr_volume(), sr_volume_destroy);
+  SR_RC(volume_common(v.get(), nx, ny, nz, x, y, z, probing_axis, nref ? SR_VOL_PHASE : 0, omega));
   const size_t total = (size_t)nx * ny * nz;
+  sr::CallBuffers buf;
   float *d_f[3] = {nullptr, nullptr, nullptr};
   double *d_n = nullptr;
-  auto cleanup = [&]() {
-    for (auto p : d_f) sr::dev_free(p);
-    sr::dev_free(d_n);
-  };
   const float *src[3] = {dndx, dndy, dndz};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && e == hipSuccess; ++k) {
-    e = hipMalloc(reinterpret_cast<void **>(&d_f[k]), total * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_f[k], src[k], total * sizeof(float), hipMemcpyHostToDevice, st);
-  }
-  if (e == hipSuccess && nref) {
-    e = hipMalloc(reinterpret_cast<void **>(&d_n), total * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_n, nref, total * sizeof(double), hipMemcpyHostToDevice, st);
-  }
-  if (e == hipSuccess) {
-    PackArgs A = pack_args(v);
-    const int block = 256;
-    const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
-    if (nref)
-      hipLaunchKernelGGL((k_pack_from_fields<true>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
-    else
-      hipLaunchKernelGGL((k_pack_from_fields<false>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  cleanup();
-  if (e != hipSuccess) {
-    sr_volume_destroy(v);
-    return sr::fail(SR_ERR_HIP, "sr_volume_create_from_fields: %s", hipGetErrorString(e));
-  }
-  *out = v;
+  for (int k = 0; k < 3; ++k) SR_RC(buf.upload(&d_f[k], src[k], total, st));
+  SR_RC(buf.upload(&d_n, nref, total, st));
+  const PackArgs A = pack_args(v.get());
+  const int block = 256;
+  const int64_t blocks = (int64_t)(total + block - 1) / block;
+  sr::with_flags(
+      [&](auto phase) {
+        hipLaunchKernelGGL((k_pack_from_fields<phase.value>), dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, d_f[0], d_f[1], d_f[2], d_n, v->P, v->L);
+      },
+      nref != nullptr);
+  SR_RC(sr::stage_out(st, {}));
+  *out = v.release();
   return SR_OK;
 }
 
@@ -489,28 +470,22 @@ int sr_volume_fields(const sr_volume *v, float *dndx, float *dndy, float *dndz, 
   PackArgs A = pack_args(v);
   const int block = 256;
   const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
+  sr::CallBuffers buf;  // one output's buffer at a time
   float *outs[3] = {dndx, dndy, dndz};
   for (int k = 0; k < 3; ++k) {
     if (!outs[k]) continue;
     float *tmp = nullptr;
-    int rc = sr::dev_alloc(&tmp, total);
-    if (rc) return rc;
+    SR_RC(buf.alloc(&tmp, total));
     hipLaunchKernelGGL(k_unpack_f32, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, v->P, k, tmp);
-    hipError_t e = hipMemcpyAsync(outs[k], tmp, total * sizeof(float), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    sr::dev_free(tmp);
-    if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_volume_fields: %s", hipGetErrorString(e));
+    SR_RC(sr::stage_out(st, {{outs[k], tmp, total * sizeof(float)}}));
+    buf.release(tmp);
   }
   if (nref_minus_1) {
     SR_CHECK(v->L != nullptr, "sr_volume_fields: volume was created without SR_VOL_PHASE");
     double *tmp = nullptr;
-    int rc = sr::dev_alloc(&tmp, total);
-    if (rc) return rc;
+    SR_RC(buf.alloc(&tmp, total));
     hipLaunchKernelGGL(k_unpack_nm1, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, A, v->P, v->L, tmp);
-    hipError_t e = hipMemcpyAsync(nref_minus_1, tmp, total * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    sr::dev_free(tmp);
-    if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_volume_fields: %s", hipGetErrorString(e));
+    SR_RC(sr::stage_out(st, {{nref_minus_1, tmp, total * sizeof(double)}}));
   }
   return SR_OK;
 }
@@ -528,47 +503,15 @@ int sr_volume_attach_aux(sr_volume *v, const double *kappa, const double *ne, co
   SR_CHECK(v != nullptr, "sr_volume_attach_aux: NULL volume");
   SR_CHECK((ne == nullptr) == (B == nullptr), "sr_volume_attach_aux: ne and B go together (both or neither)");
   SR_CHECK(kappa || ne, "sr_volume_attach_aux: nothing to attach");
-  hipStream_t st = sr::ctx().stream;
-  const size_t total = (size_t)v->nx * v->ny * v->nz;
-  const size_t packed = sr::packed_nodes(v->na, v->nb, v->nc);
-  double *d_k = nullptr, *d_ne = nullptr, *d_B = nullptr;
-  auto cleanup = [&]() {
-    sr::dev_free(d_k);
-    sr::dev_free(d_ne);
-    sr::dev_free(d_B);
-  };
   sr::dev_free(v->K);
   sr::dev_free(v->Q);
   v->K = v->Q = nullptr;
-  hipError_t e = hipSuccess;
-  if (kappa) {
-    e = hipMalloc(reinterpret_cast<void **>(&d_k), total * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_k, kappa, total * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->K), packed * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(v->K, 0, packed * sizeof(double), st);
-  }
-  if (e == hipSuccess && ne) {
-    e = hipMalloc(reinterpret_cast<void **>(&d_ne), total * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ne, ne, total * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_B), 3 * total * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_B, B, 3 * total * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->Q), 4 * packed * sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(v->Q, 0, 4 * packed * sizeof(double), st);
-  }
-  if (e == hipSuccess) {
-    const int block = 256;
-    const int64_t blocks = (int64_t)(total + block - 1) / block;  // one capped_grid per launch: each is counted (sr_grid_stats)
-    hipLaunchKernelGGL(k_pack_aux, dim3(sr::capped_grid(blocks, 32)), dim3(block), 0, st, pack_args(v), (const double *)d_k, (const double *)d_ne,
-                       (const double *)d_B, v->K, v->Q);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  cleanup();
-  if (e != hipSuccess) {
+  const int rc = pack_aux(v, kappa, ne, B);
+  if (rc) {  // nothing half-attached
     sr::dev_free(v->K);
     sr::dev_free(v->Q);
     v->K = v->Q = nullptr;
-      return sr::fail(SR_ERR_HIP, "sr_volume_attach_aux: %s", hipGetErrorString(e));
+    return rc;
   }
   v->verdet = verdet;
   return SR_OK;

@@ -334,7 +334,7 @@ extern "C" int sr_field_wave(const sr_field *ne, const sr_field *Te, const sr_fi
   if (int rc = sr::upload_sync(d_U, U_in, sizeof(double2) * (size_t)npix, st)) return rc;
   SR_HIP(hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
   SR_HIP(hipMemcpyAsync(d_cell, cells.data(), sizeof(int) * cells.size(), hipMemcpyHostToDevice, st));
-  if (F->SetStream(plan, st) != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: hipfftSetStream failed", who);
+  SR_FFT(who, F->SetStream(plan, st));
 
   ScreenArgs A{};
   A.cu = d_cell;
@@ -384,13 +384,11 @@ extern "C" int sr_field_wave(const sr_field *ne, const sr_field *Te, const sr_fi
   const double scale = 1.0 / ((double)mu * (double)mv);
   const unsigned grid_pix = (unsigned)((npix + 255) / 256);
   auto diffract = [&](double d) -> int {
-    hipfftResult fr = F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_FORWARD);
-    if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: forward FFT: hipfftResult %d", who, (int)fr);
+    SR_FFT(who, F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_FORWARD));
     if (int rc = parts.mark(0, st)) return rc;
     hipLaunchKernelGGL(k_spectral, dim3(grid_pix), dim3(256), 0, st, d_U, mv, npix, d_fu, d_fv, p->pi_l * d, scale);
     if (int rc = parts.mark(1, st)) return rc;
-    fr = F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_BACKWARD);
-    if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: inverse FFT: hipfftResult %d", who, (int)fr);
+    SR_FFT(who, F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_BACKWARD));
     return parts.mark(0, st);
   };
 
@@ -467,7 +465,7 @@ extern "C" int sr_wave_image(const sr_wave_image_params *p, const double *fu, co
   if (int rc = sr::upload_sync(d_U, U_in, sizeof(double2) * (size_t)npix, st)) return rc;
   SR_HIP(hipMemcpyAsync(d_f, fu, sizeof(double) * mu, hipMemcpyHostToDevice, st));
   SR_HIP(hipMemcpyAsync(d_f + mu, fv, sizeof(double) * mv, hipMemcpyHostToDevice, st));
-  if (F->SetStream(plan, st) != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: hipfftSetStream failed", who);
+  SR_FFT(who, F->SetStream(plan, st));
   MaskArgs M{};
   M.pd = p->pi_l * p->defocus;
   M.scale = 1.0 / ((double)mu * (double)mv);
@@ -479,13 +477,11 @@ extern "C" int sr_wave_image(const sr_wave_image_params *p, const double *fu, co
   M.flags = p->flags;
   M.knife_axis = p->knife_axis;
   SR_HIP(hipEventRecord(c.ev[0], st));
-  hipfftResult fr = F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_FORWARD);
-  if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: forward FFT: hipfftResult %d", who, (int)fr);
+  SR_FFT(who, F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_FORWARD));
   hipLaunchKernelGGL(k_mask, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, d_U, mv, npix, (const double *)d_f,
                      (const double *)(d_f + mu), M);
   SR_HIP(hipGetLastError());
-  fr = F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_BACKWARD);
-  if (fr != HIPFFT_SUCCESS) return sr::fail(SR_ERR_HIP, "%s: inverse FFT: hipfftResult %d", who, (int)fr);
+  SR_FFT(who, F->ExecZ2Z(plan, reinterpret_cast<hipfftDoubleComplex *>(d_U), reinterpret_cast<hipfftDoubleComplex *>(d_U), HIPFFT_BACKWARD));
   SR_HIP(hipEventRecord(c.ev[1], st));
   SR_HIP(hipMemcpyAsync(U_out, d_U, sizeof(double2) * (size_t)npix, hipMemcpyDeviceToHost, st));
   return sr::finish_timed(c, kernel_ms);

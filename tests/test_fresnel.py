@@ -254,3 +254,12 @@ def test_grid_is_repeatable(dev):
     again = fi.grid_rays(x, y, jones, amp, phase, return_triangles=True)
     for u, w in zip(first[:3], again[:3]):
         assert np.array_equal(u, w)
+
+
+@pytest.mark.gpu
+def test_grid_without_triangles_equals_grid_with_them(dev):
+    """sr_fresnel_grid with tri_out NULL (no triangle buffer on the device): the same amplitude and phase, bit for bit"""
+    x, y, jones, amp, phase = mk.rays("sparse")
+    a, p = fi.grid_rays(x, y, jones, amp, phase)
+    a_t, p_t, tri, _ = fi.grid_rays(x, y, jones, amp, phase, return_triangles=True)
+    assert np.array_equal(a, a_t) and np.array_equal(p, p_t) and (tri[..., 0] >= 0).any()

@@ -50,6 +50,97 @@ def test_calc_dndr_float32_ne(eng, orc):
     assert np.array_equal(gx, ox) and np.array_equal(gy, oy) and np.array_equal(gz, oz)
 
 
+def _small_domain():
+    """A 16 x 12 x 10 domain on stretched axes: the optional arguments of the volume's host-array entry points, each at a size
+    that takes no time."""
+    rng = np.random.default_rng(41)
+    x, y, z = (np.float32(1e-4 * np.cumsum(1.0 + 0.3 * rng.random(m))) for m in (16, 12, 10))
+    X, Y, Z = np.meshgrid(x, y, z, indexing="ij", sparse=True)
+    ne = 1e25 * (1.0 + 0.3 * np.sin(4e3 * X) * np.cos(3e3 * Y) + 0.2 * np.sin(5e3 * Z))
+    return x, y, z, ne
+
+
+@pytest.mark.parametrize("phase", [False, True])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("pdir", ["x", "z"])
+def test_from_ne_dtypes_phase_and_field_subsets(eng, orc, pdir, dtype, phase):
+    """Volume.from_ne for float32 / float64 ne, with and without the phase field, against the oracle (gradients bit for bit,
+    n-1 to the 48 bits it is kept with); then sr_volume_fields asked for every subset of its outputs: what is asked for equals
+    the full read, what is not asked for is not written."""
+    from synthpy_amd import _ffi
+
+    x, y, z, ne = _small_domain()
+    ne = dtype(ne)
+    lwl = 1064e-9
+    vol = eng.Volume.from_ne(ne, x, y, z, lwl, pdir, phaseshift=phase)
+    om, *grads = orc.calc_dndr(ne, x, y, z, lwl)
+    full = vol.fields(phase=phase)
+    for a, b in zip(full[:3], grads):
+        assert np.array_equal(a, b)
+    if phase:
+        nm1 = orc.n_refrac(np.float64(ne), om) - 1.0
+        assert np.max(np.abs(full[3] - nm1)) <= 2e-15 * np.max(np.abs(nm1))
+    for mask in range(1, 16 if phase else 8):
+        outs = [np.full(vol.shape, -7.0, np.float32 if k < 3 else np.float64) for k in range(4)]
+        args = [_ffi.ptr(outs[k]) if mask >> k & 1 else None for k in range(4)]
+        assert _ffi.lib.sr_volume_fields(vol._h, *args) == 0, _ffi.last_error()
+        for k in range(4):
+            assert np.array_equal(outs[k], full[k]) if mask >> k & 1 else np.all(outs[k] == -7.0), (mask, k)
+    if not phase:  # n-1 of a volume without it: an argument error, after the outputs before it were written
+        out = np.empty(vol.shape)
+        assert _ffi.lib.sr_volume_fields(vol._h, None, None, None, _ffi.ptr(out)) == -1 and "SR_VOL_PHASE" in _ffi.last_error()
+    vol.close()
+
+
+@pytest.mark.parametrize("with_nref", [False, True])
+def test_from_fields_with_and_without_nref(eng, orc, with_nref):
+    """Volume.from_fields returns what it was given: the gradients bit for bit, n-1 to the 48 bits it is kept with."""
+    x, y, z, ne = _small_domain()
+    om, gx, gy, gz = orc.calc_dndr(ne, x, y, z, 1064e-9)
+    nref = orc.n_refrac(ne, om) if with_nref else None
+    for pdir in "xyz":
+        vol = eng.Volume.from_fields(gx, gy, gz, x, y, z, om, pdir, nref=nref)
+        assert vol.phase == with_nref
+        back = vol.fields(phase=with_nref)
+        assert np.array_equal(back[0], gx) and np.array_equal(back[1], gy) and np.array_equal(back[2], gz)
+        if with_nref:
+            assert np.max(np.abs(back[3] - (nref - 1.0))) <= 2e-15 * np.max(np.abs(nref - 1.0))
+        vol.close()
+
+
+def test_attach_aux_subsets_and_replacement(eng):
+    """attach_aux with kappa only, with ne and B only, with both, and a second time on the same volume (the fields of the first
+    call are replaced or dropped): which fields the volume holds (its size says so), and their values at the nodes that open a
+    cell on every axis -- the gathers' weights are 0 and 1 there, so the node values come back, to the bound of
+    test_aux_gathers_vs_reference."""
+    x, y, z, ne = _small_domain()
+    rng = np.random.default_rng(42)
+    kappa = [1e9 * (1.0 + rng.random(ne.shape)) for _ in range(2)]
+    nes = [ne * (1.0 + 0.5 * k) for k in range(2)]
+    B = [rng.standard_normal(ne.shape + (3,)) for _ in range(2)]
+    pts = np.stack(np.meshgrid(*(np.float64(a[:-1]) for a in (x, y, z)), indexing="ij"), axis=-1).reshape(-1, 3)
+    at_pts = lambda f: f[:-1, :-1, :-1].ravel()
+    for pdir in "xz":
+        vol = eng.Volume.from_ne(ne, x, y, z, 1064e-9, pdir)
+        na = vol.shape["xyz".index(pdir)]
+        packed = (na + 7) // 8 * 8 * (ne.size // na)
+        bare = vol.nbytes
+        # (kappa, ne + B) of each call, by index into the two sets above; None: not given.  Every call after the first replaces
+        calls = [(0, None), (None, 0), (1, 1), (None, 1), (0, None), (1, 0)]
+        for ik, iq in calls:
+            vol.attach_aux(None if ik is None else kappa[ik], None if iq is None else nes[iq], None if iq is None else B[iq], 2.5e-13)
+            assert vol.nbytes == bare + packed * 8 * ((ik is not None) + 4 * (iq is not None)), (pdir, ik, iq)
+            X = vol.sample_aux(pts)
+            ref = []
+            if ik is not None:
+                ref.append((X[0], at_pts(kappa[ik])))
+            if iq is not None:
+                ref += [(X[1], at_pts(nes[iq]))] + [(X[2 + c], at_pts(B[iq][..., c])) for c in range(3)]
+            for got, want in ref:
+                assert np.max(np.abs(got - want)) <= 1e-14 * np.max(np.abs(want)), (pdir, ik, iq)
+        vol.close()
+
+
 @pytest.mark.parametrize("name", FIELDS)
 @pytest.mark.parametrize("pdir", ["x", "y", "z"])
 def test_gather_vs_reference(eng, name, pdir):
