@@ -1,0 +1,116 @@
+"""What the two ScalarDomain mirrors (solvers_legacy/full_solver.py, simulator/domain.py) share: the NRL coefficients of the
+optional RHS terms, the argument tuple of engine.Volume.attach_aux, and the entry points that go beyond the reference
+(a new diagnostic of a domain is added here, once)."""
+from __future__ import annotations
+
+import numpy as np
+
+
+def omega_pe(ne):
+    """Electron plasma frequency [rad/s] of n_e [cm^-3] (NRL formulary p.28; full_solver.py:236-239, propagator.py:23-26)."""
+    return 5.64e4 * np.sqrt(ne)
+
+
+def kappa(ne, Te, Z, omega):
+    """Inverse-bremsstrahlung rate coefficient [1/s] of n_e [m^-3], T_e [eV], Z (NRL formulary; full_solver.py:243-268,
+    propagator.py:30-60): 3.1e-5 * Z * c * (n_e[cm^-3]/omega)^2 * ln(Lambda) * Te^-1.5, ln(Lambda) = max(2, ln(v_the /
+    (omega_max * L_max))).  Nothing is cast here: a float32 n_e is scaled in float32, as each caller always had it."""
+    from .engine import c  # (not at import: the simulator's domain module is host NumPy and loads without the library)
+
+    ne_cc = np.asarray(ne) * 1e-6
+    omega_max = np.maximum(omega_pe(ne_cc), omega)
+    L_max = np.maximum(Z * 1.602176634e-19 / Te,             # classical distance of closest approach
+                       2.760428269727312e-10 / np.sqrt(Te))  # de Broglie length
+    coulomb_log = np.maximum(2.0, np.log(4.19e5 * np.sqrt(Te) / (omega_max * L_max)))
+    return 3.1e-5 * Z * c * np.power(ne_cc / omega, 2) * coulomb_log * np.power(Te, -1.5)
+
+
+def full(a, shape):
+    """`a` broadcast to the grid, contiguous float64."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), shape))
+
+
+def aux_fields(inv_brems, B_on, ne, Te, Z, B, omega, verdet):
+    """What set_up_interps gives dsdt besides the gradients (full_solver.py:276-289; propagator.py:30-60, 137-165): the
+    arguments of engine.Volume.attach_aux, (kappa | None, ne | None, B | None, VerdetConst).  ne, Te, Z go into kappa() as
+    they are given."""
+    return (kappa(ne, Te, Z, omega) if inv_brems else None,
+            full(ne, np.shape(ne)) if B_on else None,
+            np.ascontiguousarray(B, np.float64) if B_on else None,
+            float(verdet) if B_on else 0.0)
+
+
+class DomainExtras:
+    """The entry points of a ScalarDomain that have no reference counterpart, for a class with x, y, z and the field
+    attributes ne, B, Te, Z."""
+
+    def external_E(self, E):
+        """(nx, ny, nz, 3) grid of the electric field in V/m: what proton_radiograph pushes its particles through beside B.
+        The tracer does not read it."""
+        E = np.asarray(E)
+        shape = (len(self.x), len(self.y), len(self.z), 3)
+        if E.shape != shape:
+            raise ValueError(f"E has shape {E.shape}, the domain needs {shape}")
+        self.E = E
+
+    def external_Ti(self, Ti, Ti_min=1.0):
+        """(nx, ny, nz) grid of T_i in eV, floored at Ti_min: what thomson_scattering reads beside Te.  Without it Ti = Te.
+        The tracer does not read it."""
+        self.Ti = np.maximum(Ti_min, Ti)
+
+    def external_V(self, V):
+        """(nx, ny, nz, 3) grid of the flow velocity in m/s: the Doppler shift of thomson_scattering.  The tracer does not
+        read it."""
+        self.V = V
+
+    def proton_radiograph(self, source, det_pos, **kw):
+        """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
+        particles have crossed this domain's B (external_B / test_B) and E (external_E): a radiography.Radiograph.
+        Keywords: radiography.radiograph's."""
+        from .radiography import radiograph
+
+        return radiograph(self, source, det_pos, **kw)
+
+    def thomson_scattering(self, probe, collection, wavelengths, ion_mass, **kw):
+        """The optical Thomson-scattering spectra of this domain's ne, Te (external_Te), Z (external_Z), Ti (external_Ti) and V
+        (external_V) for a thomson.Probe and a thomson.Collection at `wavelengths` [m], the ion's mass number ion_mass: a
+        thomson.ThomsonSpectra.  Keywords: thomson.spectra's."""
+        from .thomson import spectra
+
+        return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
+
+    def wave_propagate(self, source, **kw):
+        """The wave-optics march of a wave.Source through this domain's ne along its probing_direction: a wave.WaveField on
+        the exit plane.  Keywords: wave.propagate's."""
+        from .wave import propagate
+
+        return propagate(self, source, **kw)
+
+    def rotated(self, angle_deg=None, about="y", **kw):
+        """This domain seen from a frame turned by angle_deg about the lab axis `about` (or matrix=R): a new ScalarDomain of the
+        same generation (a legacy one wants its calc_dndr) whose probing axis is an oblique line of sight of this one
+        (orientation.rotated)."""
+        from .orientation import rotated
+
+        return rotated(self, angle_deg, about, **kw)
+
+    def self_emission(self, wavelengths, toward="+", backlight=None):
+        """The plasma's own light along the probing axis, emission with self-absorption: an emission.Emission with the
+        intensity and optical-depth maps per wavelength.  Needs external_Te() and external_Z()."""
+        from .emission import self_emission
+
+        return self_emission(self, wavelengths, toward=toward, backlight=backlight)
+
+    def table_emission(self, table, toward="+", backlight=None):
+        """self_emission with the opacities of an utils.eos_opacity.OpacityTable (PROPACEOS tables) in place of the NRL
+        coefficient: an emission.TableEmission, one band per band of the table.  Needs external_Te() and external_Z().  Not
+        modelled: Z from the table's zf_table, group-integrated Planck functions, refraction, detector optics."""
+        from .emission import table_emission
+
+        return table_emission(self, table, toward=toward, backlight=backlight)
+
+    def export_scalar_field(self, property: str = "ne", fname: str = None):
+        """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
+        from .utils.handle_filetypes import export_scalar_field
+
+        export_scalar_field(self, property, fname)

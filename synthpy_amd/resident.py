@@ -4,9 +4,10 @@ A synthPy caller writes (examples/jobs/run_scripts/pvti_trace_mpi.py:111-131, sr
 
     rf = field.solve(ss); sh = rtm.Shadowgraphy(rf); sh.two_lens_solve(); sh.histogram()
 
-The API hands `rf` over as a host array, but the rays themselves are still in HBM.  `register()` (called by the two
-solve() mirrors) remembers which bundle an `rf` / `Jf` pair came from; `attach()` (called by Rays.__init__ /
-Diagnostic.__init__) gives the bundle back when the arrays are THE arrays solve() returned and still hold what it wrote.
+The API hands `rf` over as a host array, but the rays themselves are still in HBM.  `register()` (called by
+`solve_in_bundle()`, the tail of every solve() mirror) remembers which bundle an `rf` / `Jf` pair came from; `attach()` (called
+by Rays.__init__ / Diagnostic.__init__ through _diagnostic.ResidentRays) gives the bundle back when the arrays are THE arrays
+solve() returned and still hold what it wrote.
 The diagnostic then records its optic chain in *_solve() and histogram() / interferogram() run the fused deposit
 (sr_rays_deposit: m_to_mm -> reference beams -> chain -> LDS-tiled detector atomics) on the resident rays; `.r0`, `.rf`,
 `.rE` / `.Jf` are formed on the device and copied to the host only when somebody reads them (sr_rays_optics).  intensity() /
@@ -275,6 +276,21 @@ def acquire(n, current=None):
         if b is not None and b.alive:
             release(b)
     return engine.RayBundle(n)
+
+
+def solve_in_bundle(domain, s0, trace, return_E):
+    """What every solve() mirror does with its rays: s0 (9, N) into the domain's bundle (acquire: its current one, domain._rays,
+    or a new one, which the domain holds from the upload on, so that the old one's HBM is free before the trace), trace(bundle)
+    -- one trace or a region loop's --, rf (and Jf with return_E) to the host, remembered for attach().  The traced bundle
+    stays in HBM: sf, and Jf without return_E, come back only when the domain is asked for them, and the diagnostics classes
+    find the bundle again through the arrays returned here and deposit from it instead of uploading rf again.
+    Returns (rf, Jf | None, what trace returned)."""
+    if s0.ndim != 2 or s0.shape[0] != 9:
+        raise ValueError(f"s0 must have shape (9, N), got {s0.shape}")
+    rays = domain._rays = acquire(s0.shape[1], getattr(domain, "_rays", None)).upload(s0)
+    out = trace(rays)
+    _, rf, Jf = rays.download(sf=False, Jf=return_E)
+    return (*register(rays, rf, Jf), out)  # the same memory, write-tracked (TrackedArray)
 
 
 def release(bundle):

@@ -13,12 +13,14 @@ Refractometry.coherent_solve is reproduced as written (the first aperture is app
 only contributes its field factor, diagnostics.py:505-511).  Not carried over, and saying so when called:
 Refractometry.fresnel_solve (needs the fresnel_integral module and attributes no caller sets) and Interferometry.bkg (as
 shipped it stops at its first line: `probing_direction` is not defined there, diagnostics.py:583-584).
+The resident-rays state machine, histogram(), intensity(), plot() and the chain-only *_solve() methods are the ones the
+legacy generation has too: synthpy_amd/_diagnostic.py.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .. import engine, resident
+from .. import _diagnostic, engine, resident
 from ..engine import OP_CIRC_AP, OP_CIRC_STOP, OP_DIST, OP_KNIFE, OP_LENS, OP_RECT_AP, OP_SCALE
 
 
@@ -86,13 +88,17 @@ def ray(x, θ, y, ϕ):
     return sym.Matrix([x, θ, y, ϕ])
 
 
-class Diagnostic:
+class Diagnostic(_diagnostic.ResidentRays):
     """Inheritable class for ray diagnostics (diagnostics.py:269-379).
 
     Built from the (rf, Jf) propagator.solve() has just returned, the object works on the bundle that call left in HBM
     (resident.attach): *_solve() and interfere_ref_beam() record what they would do, histogram() / interferogram() run the
     fused deposit (sr_rays_deposit), and .r0 / .rf / .Jf are copied to the host only when they are read.  Arrays from
-    anywhere else, or changed since solve() wrote them, take the host path."""
+    anywhere else, or changed since solve() wrote them, take the host path.  The state machine is
+    _diagnostic.ResidentRays; what this generation adds to it: Jf is an input of the next chain and its output, so once the
+    caller has assigned rf or Jf every later step runs on the host, on those arrays."""
+
+    _TRACKED = _CLEARED = ("_r0", "_rf", "_Jf")  # what the object hands out, and what the reference's methods read
 
     def __init__(self, wavelength, rf, Jf=None, *, focal_plane=0, L=400, R=25, Lx=18, Ly=13.5, x=None, y=None,
                  x_l=None, y_l=None, amp=None, phase=None):
@@ -104,36 +110,10 @@ class Diagnostic:
         self._r0 = self._rf = self._Jf = None
         self._has_Jf = Jf is not None
         self._assigned = False  # rf / Jf set by the caller or by a host-path step: work on THOSE, not on the resident rays
-        bundle = resident.attach(self, rf, Jf)
-        self._dev = None if bundle is None else resident.DeviceRays(bundle, Jf is not None)
-        if self._dev is None:
+        if not self._attach(rf, Jf):
             self._rf = np.array(rf, dtype=np.float64)
             self._Jf = None if Jf is None else np.array(Jf, dtype=np.complex128)
             self._r0 = m_to_mm(self._rf)
-
-    # ---- the rays, wherever they are ----------------------------------------------------------------
-    @property
-    def on_device(self) -> bool:
-        """True while histogram() / interferogram() deposit from the bundle solve() left in HBM."""
-        return self._dev is not None and self._dev.live
-
-    def _guard(self):
-        """The arrays this object hands out while its rays are resident (.r0, .rf, .Jf) are write-tracked
-        (resident.TrackedArray): once one of them has been written to, the object works on its host arrays, as they are
-        now, from here on -- what the reference's methods would read (diagnostics.py:323-379)."""
-        if self._dev is not None and any(resident.dirty(a) for a in (self._r0, self._rf, self._Jf)):
-            self._leave_device(keep=True)
-
-    @property
-    def r0(self):
-        if self._r0 is None and self.on_device:
-            self._r0 = resident.track(self._dev.host(ops=[], with_E=False)[0])
-        return self._r0
-
-    @r0.setter
-    def r0(self, value):
-        self._leave_device(keep=False)
-        self._r0 = value
 
     def _fetch(self):
         """rf and Jf as the reference would hold them now: the chain's output after a *_solve(), else the rays as given
@@ -178,43 +158,26 @@ class Diagnostic:
         self._Jf, self._assigned = value, True
         self._has_Jf = value is not None
 
-    def _to_host(self):
-        self._leave_device(keep=True)
+    def _field(self):
+        return self.Jf
 
-    def _leave_device(self, keep):
-        if self._dev is None:
-            return
-        if keep and self._dev.live:
-            _ = self.r0
-            self._fetch()
-        self._dev.drop(self)
-        self._dev = None
+    def _need_field(self, who):
+        if not self._has_Jf:
+            raise ValueError("This diagnostic requires a calculated Jf matrix.")
 
-    def __getstate__(self):
-        self._to_host()
-        return self.__dict__.copy()
+    def _records(self):
+        return self.on_device and not self._assigned
 
-    def _deposits_from_device(self):
-        return self.on_device and self._dev.ops is not None and not self._assigned
-
-    def _run(self, ops):
-        self._guard()
-        if self.on_device and not self._assigned:
-            self._dev.record(ops)
-            self._rf = None
-        else:
-            self.rf = _apply(self.r0, ops)[0]
+    def _output(self, rf, Jf, carries_field):
+        self._rf = rf  # None after a recording: the host copy of the last chain's output is out of date
+        if rf is not None:
+            self._assigned = True
+        if carries_field:
+            self._Jf = Jf
 
     def _run_field(self, ops):
         """A chain that carries the field: Jf *= exp(1j*k*|dr|) over its legs, k = 2*pi/wavelength (diagnostics.py:311-318)."""
-        k = 2 * np.pi / self.wavelength
-        self._guard()
-        if self.on_device and not self._assigned:
-            self._dev.record(ops, kwave=k)
-            self._rf = self._Jf = None
-        else:
-            r, E = _apply(self.r0, ops, E=self.Jf, kwave=k)
-            self._rf, self._Jf, self._assigned = r, E, True
+        self._run(ops, kwave=2 * np.pi / self.wavelength)
 
     def propagate_E(self, r1, r0):
         """Jf *= exp(1j * k * sqrt(dx^2 + dy^2)) for the leg r0 -> r1, k = 2*pi/wavelength (diagnostics.py:315-321).  The
@@ -225,25 +188,10 @@ class Diagnostic:
         self._to_host()
         self.Jf = self.Jf * np.exp(1.0j * k * np.sqrt(dx ** 2 + dy ** 2))
 
-    def histogram(self, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
-        """histogram2d of the detector-plane positions, H [y_bin, x_bin] (diagnostics.py:323-353)."""
-        nx, ny = pix_x // bin_scale, pix_y // bin_scale
-        rng = (-self.Lx / 2, self.Lx / 2, -self.Ly / 2, self.Ly / 2)
-        self._guard()
-        if self._deposits_from_device():
-            self.H = self._dev.counts(nx, ny, *rng)
-        else:
-            self.H = engine.hist2d(self.rf[0], self.rf[2], nx, ny, *rng).astype(np.float64)
-        self.xedges = np.linspace(-self.Lx / 2, self.Lx / 2, nx + 1)
-        self.yedges = np.linspace(-self.Ly / 2, self.Ly / 2, ny + 1)
-        if clear_mem:
-            clear_rays(self)
-
     def histogram_legacy(self, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
         """Per-pixel complex sums of Jf, H = sqrt(Re^2 + Re^2); edges linspace(-L // 2, L // 2, pix // bin_scale)
         with the floor divisions as written (diagnostics.py:358-379)."""
-        if not self._has_Jf:
-            raise ValueError("This diagnostic requires a calculated Jf matrix.")
+        self._need_field("histogram_legacy")
         rng = (-self.Lx // 2, self.Lx // 2, -self.Ly // 2, self.Ly // 2)
         self._guard()
         if self._deposits_from_device():
@@ -253,61 +201,21 @@ class Diagnostic:
         if clear_mem:
             clear_rays(self)
 
-    def intensity(self, analyser=None, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
-        """Analyser-weighted intensity images of the detector-plane rays: I (n_ch, pix_y // bin_scale, pix_x // bin_scale),
-        I[c] = np.histogram2d(..., weights=w_c) on histogram()'s detector, xedges / yedges as histogram() sets them; .H is
-        left alone.  No reference counterpart (the reference shows amplitude and polarisation in no image).
-
-        analyser: None, one angle [rad], or a sequence of up to 4 angles, None among them = no analyser.  An analyser at
-        angle beta, measured from the y axis in the sense `pol` is, passes the component of Jf along (-sin beta, cos beta):
-        w = |(-sin beta) E_x + (cos beta) E_y|^2 = amp^2 cos^2(pol - beta); without analyser w = |E_x|^2 + |E_y|^2 (the
-        attenuation image).  The sum over a pixel's rays is incoherent: no reference beam, no field propagation."""
-        if not self._has_Jf:
-            raise ValueError("This diagnostic requires a calculated Jf matrix.")
-        nx, ny = pix_x // bin_scale, pix_y // bin_scale
-        rng = (-self.Lx / 2, self.Lx / 2, -self.Ly / 2, self.Ly / 2)
-        self._guard()
-        # a reference beam added to the resident field is part of what .Jf holds: then the host arrays are what is binned
-        if self._deposits_from_device() and self._dev.has_E and not self._dev.refs:
-            self.I = self._dev.intensity(analyser, nx, ny, *rng)
-        else:
-            self.I = engine.intensity2d(self.rf[0], self.rf[2], self.Jf, analyser, nx, ny, *rng)
-        self.xedges = np.linspace(-self.Lx / 2, self.Lx / 2, nx + 1)
-        self.yedges = np.linspace(-self.Ly / 2, self.Ly / 2, ny + 1)
-        if clear_mem:
-            clear_rays(self)
-
-    def plot(self, ax, clim=None, cmap=None):
-        ax.imshow(self.H, interpolation="nearest", origin="lower", clim=clim, cmap=cmap,
-                  extent=[self.xedges[0], self.xedges[-1], self.yedges[0], self.yedges[-1]])
-
 
 def clear_rays(self):
-    self._leave_device(keep=False)
-    self._r0 = self._rf = self._Jf = None
-    self._assigned = False
+    """The reference's module-level spelling of Diagnostic.clear_rays (diagnostics.py:349-353)."""
+    self.clear_rays()
 
 
-class Shadowgraphy(Diagnostic):
-    def single_lens_solve(self):
-        self._run(engine.chain_shadow_single(self.L, self.R, self.focal_plane))
-
-    def two_lens_solve(self):
-        self._run(engine.chain_shadow_two(self.L, self.R, self.focal_plane))
+class Shadowgraphy(_diagnostic.ShadowgraphyChains, Diagnostic):
+    pass
 
 
-class Schlieren(Diagnostic):
-    def DF_solve(self, R=1):
-        self._run(engine.chain_schlieren(self.L, self.R, self.focal_plane, R, dark_field=True))
-
-    def LF_solve(self, R=1):
-        self._run(engine.chain_schlieren(self.L, self.R, self.focal_plane, R, dark_field=False))
+class Schlieren(_diagnostic.SchlierenChains, Diagnostic):
+    pass
 
 
-class Refractometry(Diagnostic):
-    def incoherent_solve(self):
-        self._run(engine.chain_refractometry(self.L, self.R, self.focal_plane))
-
+class Refractometry(_diagnostic.RefractometryChains, Diagnostic):
     def coherent_solve(self):
         if not self._has_Jf:
             raise ValueError("coherent_solve needs the field Jf (solve(..., return_E=True))")
@@ -332,7 +240,7 @@ class Interferometry(Diagnostic):
             return None
         self._guard()
         # resident rays that no *_solve() has moved yet: the beam is added by the deposit itself, before the chain
-        if self.on_device and not self._assigned and self._dev.ops is None and self._dev.add_ref(n_fringes, deg):
+        if self._records() and self._dev.ops is None and self._dev.add_ref(n_fringes, deg):
             self._Jf = None
             return None
         self._to_host()
@@ -352,29 +260,7 @@ class Interferometry(Diagnostic):
         self.histogram_legacy(bin_scale=bin_scale, pix_x=pix_x, pix_y=pix_y, clear_mem=clear_mem)
 
 
-class Polarimetry(Diagnostic):
-    """Faraday-rotation imaging through a pair of analysers at +beta and -beta: Shadowgraphy's imaging chains, and intensity
-    images weighted by what each analyser passes of the rays' Jones vector.  No reference counterpart: the reference
-    carries the rotation (state row 8) into Jf and has no diagnostic that shows it.
+class Polarimetry(_diagnostic.PolarimetryImages, Diagnostic):
+    """_diagnostic.PolarimetryImages on this generation's rays:
 
         po = Polarimetry(lwl, rf, Jf); po.two_lens_solve(); po.polarogram(); alpha = po.rotation()"""
-
-    def single_lens_solve(self):
-        self._run(engine.chain_shadow_single(self.L, self.R, self.focal_plane))
-
-    def two_lens_solve(self):
-        self._run(engine.chain_shadow_two(self.L, self.R, self.focal_plane))
-
-    def polarogram(self, beta=np.pi / 4, bin_scale=1, pix_x=3448, pix_y=2574, clear_mem=False):
-        """One pass over the rays, three images: H_plus and H_minus through analysers at +beta and -beta (0 < beta < pi/2),
-        H_total without analyser; .beta keeps the angle for rotation()."""
-        if not 0 < beta < np.pi / 2:
-            raise ValueError("beta must lie in (0, pi/2)")
-        self.intensity((beta, -beta, None), bin_scale=bin_scale, pix_x=pix_x, pix_y=pix_y, clear_mem=clear_mem)
-        self.H_plus, self.H_minus, self.H_total = self.I
-        self.beta = beta
-
-    def rotation(self):
-        """The polarisation rotation alpha [rad] per pixel from H_plus and H_minus (engine.rotation_map): NaN where no ray
-        landed; unambiguous for |alpha| < min(beta, pi/2 - beta)."""
-        return engine.rotation_map(self.H_plus, self.H_minus, self.beta)

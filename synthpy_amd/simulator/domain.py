@@ -14,8 +14,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from .. import _domain
 
-class ScalarDomain:
+
+class ScalarDomain(_domain.DomainExtras):
     def __init__(self, lengths, dims, *, ne_type=None, inv_brems=False, phaseshift=False, B_on=False,
                  probing_direction="z", auto_batching=True, iteration=1, region_count=1, leeway_factor=None,
                  coord_backup=None, future_dims=None, debug=False):
@@ -121,52 +123,11 @@ class ScalarDomain:
     def external_B(self, B):
         self.B = B
 
-    def external_E(self, E):
-        """Load an (x_n, y_n, z_n, 3) grid of the electric field in V/m (no reference counterpart): what proton_radiograph
-        pushes its particles through beside B.  The tracer does not read it."""
-        E = np.asarray(E)
-        if E.shape != tuple(self.dims) + (3,):
-            raise ValueError(f"E has shape {E.shape}, the domain needs {tuple(self.dims) + (3,)}")
-        self.E = E
-
-    def proton_radiograph(self, source, det_pos, **kw):
-        """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
-        particles have crossed this domain's B (external_B / test_B) and E (external_E) (no reference counterpart): a
-        radiography.Radiograph.  Keywords: radiography.radiograph's."""
-        from ..radiography import radiograph
-
-        return radiograph(self, source, det_pos, **kw)
-
     def external_Te(self, Te, Te_min=1.0):
         self.Te = np.maximum(Te_min, Te)
 
     def external_Z(self, Z):
         self.Z = Z
-
-    def external_Ti(self, Ti, Ti_min=1.0):
-        """Load the ion temperature in eV, floored at Ti_min (no reference counterpart): what thomson_scattering reads beside
-        Te.  Without it Ti = Te.  The tracer does not read it."""
-        self.Ti = np.maximum(Ti_min, Ti)
-
-    def external_V(self, V):
-        """Load an (x_n, y_n, z_n, 3) grid of the flow velocity in m/s (no reference counterpart): the Doppler shift of
-        thomson_scattering.  The tracer does not read it."""
-        self.V = V
-
-    def thomson_scattering(self, probe, collection, wavelengths, ion_mass, **kw):
-        """The optical Thomson-scattering spectra of this domain's ne, Te (external_Te), Z (external_Z), Ti (external_Ti) and V
-        (external_V) for a thomson.Probe and a thomson.Collection at `wavelengths` [m], the ion's mass number ion_mass (no
-        reference counterpart): a thomson.ThomsonSpectra.  Keywords: thomson.spectra's."""
-        from ..thomson import spectra
-
-        return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
-
-    def wave_propagate(self, source, **kw):
-        """The wave-optics march of a wave.Source through this domain's ne along its probing_direction (no reference
-        counterpart): a wave.WaveField on the exit plane.  Keywords: wave.propagate's."""
-        from ..wave import propagate
-
-        return propagate(self, source, **kw)
 
     def line_integrals(self, lwl=1064e-9, regions=None):
         """The line integrals of the domain along its probing axis (no reference counterpart): a projection.Projection
@@ -174,34 +135,6 @@ class ScalarDomain:
         from ..projection import line_integrals
 
         return line_integrals(self, lwl=lwl, regions=regions)
-
-    def rotated(self, angle_deg=None, about="y", **kw):
-        """This domain seen from a frame turned by angle_deg about the lab axis `about` (or matrix=R): a new ScalarDomain whose
-        probing axis is an oblique line of sight of this one (no reference counterpart; orientation.rotated)."""
-        from ..orientation import rotated
-
-        return rotated(self, angle_deg, about, **kw)
-
-    def self_emission(self, wavelengths, toward="+", backlight=None):
-        """The plasma's own light along the probing axis, emission with self-absorption (no reference counterpart): an
-        emission.Emission with the intensity and optical-depth maps per wavelength.  Needs external_Te() and external_Z()."""
-        from ..emission import self_emission
-
-        return self_emission(self, wavelengths, toward=toward, backlight=backlight)
-
-    def table_emission(self, table, toward="+", backlight=None):
-        """self_emission with the opacities of an utils.eos_opacity.OpacityTable (PROPACEOS tables) in place of the NRL
-        coefficient (no reference counterpart): an emission.TableEmission, one band per band of the table.  Needs external_Te()
-        and external_Z().  Not modelled: Z from the table's zf_table, group-integrated Planck functions, refraction, detector optics."""
-        from ..emission import table_emission
-
-        return table_emission(self, table, toward=toward, backlight=backlight)
-
-    def export_scalar_field(self, property: str = "ne", fname: str = None):
-        """Save n_e as <fname>.vti + <fname>.pvti (domain.py:505-579), written without pyvista."""
-        from ..utils.handle_filetypes import export_scalar_field
-
-        export_scalar_field(self, property, fname)
 
     def cleanup(self):
         self.XX = self.YY = self.ZZ = None

@@ -20,13 +20,9 @@ from time import time
 import numpy as np
 
 from .. import engine, resident
+from .._domain import aux_fields, full, kappa, omega_pe  # noqa: F401  (omega_pe, kappa: propagator.py:23-60)
 
 c = engine.c
-
-
-def omega_pe(ne):
-    """Electron plasma frequency, rad/s, ne in cm^-3 (NRL p.28; propagator.py:23-26)."""
-    return 5.64e4 * np.sqrt(ne)
 
 
 def n_refrac(ne, omega):
@@ -34,13 +30,11 @@ def n_refrac(ne, omega):
     return np.sqrt(1.0 - (omega_pe(ne * 1e-6) / omega) ** 2)
 
 
-def kappa(ne, Te, Z, omega):
-    """Inverse-bremsstrahlung rate coefficient [1/s] (NRL formulary; propagator.py:30-60)."""
-    ne_cc = np.asarray(ne) * 1e-6
-    omega_max = np.maximum(omega_pe(ne_cc), omega)
-    L_max = np.maximum(Z * 1.602176634e-19 / Te, 2.760428269727312e-10 / np.sqrt(Te))
-    coulomb_log = np.maximum(2.0, np.log(4.19e5 * np.sqrt(Te) / (omega_max * L_max)))
-    return 3.1e-5 * Z * c * np.power(ne_cc / omega, 2) * coulomb_log * np.power(Te, -1.5)
+def _float64_aux(inv_brems, B_on, ne, Te, Z, B, omega, verdet):
+    """_domain.aux_fields the way this generation always fed it: n_e in float64, T_e and Z broadcast to its grid."""
+    ne = np.asarray(ne, np.float64)
+    Te, Z = (full(a, ne.shape) for a in (Te, Z)) if inv_brems else (None, None)
+    return aux_fields(inv_brems, B_on, ne, Te, Z, B, omega, verdet)
 
 
 def _aux_fields(domain, lwl):
@@ -52,12 +46,8 @@ def _aux_fields(domain, lwl):
         raise ValueError("inv_brems=True needs external_Te() and external_Z()")
     if domain.B_on and domain.B is None:
         raise ValueError("B_on=True needs external_B()")
-    omega = 2 * np.pi * c / lwl
-    full = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), np.shape(domain.ne)))
-    return (kappa(np.asarray(domain.ne, np.float64), full(domain.Te), full(domain.Z), omega) if domain.inv_brems else None,
-            full(domain.ne) if domain.B_on else None,
-            np.ascontiguousarray(domain.B, np.float64) if domain.B_on else None,
-            2.62e-13 * lwl ** 2 if domain.B_on else 0.0)
+    return _float64_aux(domain.inv_brems, domain.B_on, domain.ne, domain.Te, domain.Z, domain.B, 2 * np.pi * c / lwl,
+                        2.62e-13 * lwl ** 2)
 
 
 def _volume_for(domain, lwl):
@@ -108,10 +98,7 @@ def dsdt(t, s, parallelise, inv_brems, phaseshift, B_on, ne, B, Te, Z, x, y, z, 
         if phaseshift:
             sprime[7] = omega * F[3]
         if inv_brems or B_on:
-            full = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), np.shape(ne)))
-            vol.attach_aux(kappa(np.asarray(ne, np.float64), full(Te), full(Z), omega) if inv_brems else None,
-                           full(ne) if B_on else None, np.ascontiguousarray(B, np.float64) if B_on else None,
-                           float(VerdetConst) if B_on else 0.0)
+            vol.attach_aux(*_float64_aux(inv_brems, B_on, ne, Te, Z, B, omega, VerdetConst))
             X = vol.sample_aux(pts)
             if inv_brems:
                 sprime[6] = X[0] * s[6]
@@ -202,15 +189,16 @@ def _solve_by_regions(s0, domain, probing_depth, return_E, lwl, substeps, precis
     cuts, slabs = _slab_volumes(domain, lwl, regions)
     start = time()
     t_end = np.sqrt(8.0) * probing_depth / c
-    rays = resident.acquire(s0.shape[1], getattr(domain, "_rays", None)).upload(s0)
-    domain._rays = rays
-    steps = 0
-    for q, vol in enumerate(slabs):
-        flags = (engine.HANDOFF_ENTER if q else 0) | (engine.HANDOFF_EXIT if q + 1 < len(cuts) else 0)
-        st = rays.trace(vol, t_end, probing_depth, row_order=engine.ROWS_JAX, substeps=substeps, precision=precision, handoff=flags)
-        steps += st.ray_steps
-    _, rf, Jf = rays.download(sf=False, Jf=return_E)
-    rf, Jf = resident.register(rays, rf, Jf)  # the same memory, write-tracked (resident.TrackedArray)
+
+    def trace(rays):
+        steps = 0
+        for q, vol in enumerate(slabs):
+            flags = (engine.HANDOFF_ENTER if q else 0) | (engine.HANDOFF_EXIT if q + 1 < len(cuts) else 0)
+            st = rays.trace(vol, t_end, probing_depth, row_order=engine.ROWS_JAX, substeps=substeps, precision=precision, handoff=flags)
+            steps += st.ray_steps
+        return steps
+
+    rf, Jf, steps = resident.solve_in_bundle(domain, s0, trace, return_E)
     duration = time() - start
     solve.last_stats = engine.TraceStats(steps, 0, 0.0, 0.0)
     return rf, Jf, duration
@@ -229,16 +217,7 @@ def solve(s0_import, ScalarDomain, probing_depth, *, return_E=False, parallelise
     vol = _volume_for(ScalarDomain, lwl)
     start = time()
     t_end = np.sqrt(8.0) * probing_depth / c
-    if s0.ndim != 2 or s0.shape[0] != 9:
-        raise ValueError(f"s0 must have shape (9, N), got {s0.shape}")
-    # the traced bundle stays in HBM and the Diagnostic classes find it again through the arrays returned here
-    # (resident.attach): their histogram() / interferogram() then deposit from it instead of uploading rf again
-    rays = resident.acquire(s0.shape[1], getattr(ScalarDomain, "_rays", None)).upload(s0)
-    ScalarDomain._rays = rays
-    stats = rays.trace(vol, t_end, probing_depth, row_order=engine.ROWS_JAX, substeps=substeps, precision=precision,
-                       resident=False)  # rf goes back to the caller, who may bin it: "auto" = float64
-    _, rf, Jf = rays.download(sf=False, Jf=return_E)
-    rf, Jf = resident.register(rays, rf, Jf)  # the same memory, write-tracked (resident.TrackedArray)
-    duration = time() - start
-    solve.last_stats = stats
-    return rf, Jf, duration
+    trace = lambda rays: rays.trace(vol, t_end, probing_depth, row_order=engine.ROWS_JAX, substeps=substeps, precision=precision,
+                                    resident=False)  # rf goes back to the caller, who may bin it: "auto" = float64
+    rf, Jf, solve.last_stats = resident.solve_in_bundle(ScalarDomain, s0, trace, return_E)
+    return rf, Jf, time() - start

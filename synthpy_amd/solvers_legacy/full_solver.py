@@ -25,12 +25,12 @@ from time import time
 
 import numpy as np
 
-from .. import _beam, engine, resident
+from .. import _beam, _domain, engine, resident
 
 c = engine.c
 
 
-class ScalarDomain:
+class ScalarDomain(_domain.DomainExtras):
     """Holds the scalar fields of the plasma volume and traces rays through them (full_solver.py:96-128)."""
 
     def __init__(self, x, y, z, extent, B_on=False, inv_brems=False, phaseshift=False, probing_direction="z"):
@@ -78,23 +78,6 @@ class ScalarDomain:
         self.B = B
         self._aux_ready = False
 
-    def external_E(self, E):
-        """(nx, ny, nz, 3) grid of the electric field in V/m (no reference counterpart): what proton_radiograph pushes its
-        particles through beside B.  The tracer does not read it."""
-        E = np.asarray(E)
-        shape = (len(self.x), len(self.y), len(self.z), 3)
-        if E.shape != shape:
-            raise ValueError(f"E has shape {E.shape}, the domain needs {shape}")
-        self.E = E
-
-    def proton_radiograph(self, source, det_pos, **kw):
-        """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
-        particles have crossed this domain's B (external_B / test_B) and E (external_E) (no reference counterpart): a
-        radiography.Radiograph.  Keywords: radiography.radiograph's."""
-        from ..radiography import radiograph
-
-        return radiograph(self, source, det_pos, **kw)
-
     def external_Te(self, Te, Te_min=1.0):
         """(nx, ny, nz) grid of T_e in eV, floored at Te_min."""
         self.Te = np.maximum(Te_min, Te)
@@ -105,45 +88,15 @@ class ScalarDomain:
         self.Z = Z
         self._aux_ready = False
 
-    def external_Ti(self, Ti, Ti_min=1.0):
-        """(nx, ny, nz) grid of T_i in eV, floored at Ti_min (no reference counterpart): what thomson_scattering reads beside Te.
-        Without it Ti = Te.  The tracer does not read it."""
-        self.Ti = np.maximum(Ti_min, Ti)
-
-    def external_V(self, V):
-        """(nx, ny, nz, 3) grid of the flow velocity in m/s (no reference counterpart): the Doppler shift of thomson_scattering.
-        The tracer does not read it."""
-        self.V = V
-
-    def thomson_scattering(self, probe, collection, wavelengths, ion_mass, **kw):
-        """The optical Thomson-scattering spectra of this domain's ne, Te (external_Te), Z (external_Z), Ti (external_Ti) and V
-        (external_V) for a thomson.Probe and a thomson.Collection at `wavelengths` [m], the ion's mass number ion_mass (no
-        reference counterpart): a thomson.ThomsonSpectra.  Keywords: thomson.spectra's."""
-        from ..thomson import spectra
-
-        return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
-
-    def wave_propagate(self, source, **kw):
-        """The wave-optics march of a wave.Source through this domain's ne along its probing_direction (no reference
-        counterpart): a wave.WaveField on the exit plane.  Keywords: wave.propagate's."""
-        from ..wave import propagate
-
-        return propagate(self, source, **kw)
-
     def test_B(self, Bmax=1.0):
         self.B = np.zeros((len(self.x), len(self.y), len(self.z), 3))
         self.B[:, :, :, 2] = self._full(Bmax * self.XX / self.extent)
         self._aux_ready = False
 
     def kappa(self):
-        """Inverse-bremsstrahlung rate coefficient [1/s] on the grid (NRL formulary; full_solver.py:243-268):
-        3.1e-5 * Z * c * (n_e[cm^-3]/omega)^2 * ln(Lambda) * Te^-1.5, ln(Lambda) = max(2, ln(v_the / (omega_max * L_max)))."""
-        ne_cc = np.asarray(self.ne) * 1e-6
-        omega_max = np.maximum(5.64e4 * np.sqrt(ne_cc), self.omega)          # max(omega_pe, omega)
-        L_max = np.maximum(self.Z * 1.602176634e-19 / self.Te,                # classical distance of closest approach
-                           2.760428269727312e-10 / np.sqrt(self.Te))          # de Broglie length
-        coulomb_log = np.maximum(2.0, np.log(4.19e5 * np.sqrt(self.Te) / (omega_max * L_max)))
-        return 3.1e-5 * self.Z * c * np.power(ne_cc / self.omega, 2) * coulomb_log * np.power(self.Te, -1.5)
+        """Inverse-bremsstrahlung rate coefficient [1/s] on the grid (full_solver.py:243-268): _domain.kappa of the fields as
+        they were loaded (a float32 n_e is scaled in float32)."""
+        return _domain.kappa(self.ne, self.Te, self.Z, self.omega)
 
     def n_refrac(self):
         """Plasma refractive index on the grid (full_solver.py:271-274), read back from the GPU volume."""
@@ -155,10 +108,9 @@ class ScalarDomain:
         if self._volume is None:
             raise RuntimeError("call calc_dndr(lwl) first")
         if self.inv_brems or self.B_on:
-            self._volume.attach_aux(self.kappa() if self.inv_brems else None,
-                                    self._full(np.asarray(self.ne, np.float64)) if self.B_on else None,
-                                    np.ascontiguousarray(self.B, np.float64) if self.B_on else None,
-                                    self.VerdetConst if self.B_on else 0.0)
+            Te, Z, B = (getattr(self, a, None) for a in ("Te", "Z", "B"))  # attributes of the terms that are switched on
+            self._volume.attach_aux(*_domain.aux_fields(self.inv_brems, self.B_on, self._full(self.ne), Te, Z, B, self.omega,
+                                                        getattr(self, "VerdetConst", 0.0)))
         self._aux_ready = True
 
     # ---- A1 / A5 ---------------------------------------------------------------------
@@ -181,29 +133,6 @@ class ScalarDomain:
         from ..projection import line_integrals
 
         return line_integrals(self)
-
-    def rotated(self, angle_deg=None, about="y", **kw):
-        """This domain seen from a frame turned by angle_deg about the lab axis `about` (or matrix=R): a new ScalarDomain (call
-        calc_dndr on it) whose probing axis is an oblique line of sight of this one (no reference counterpart;
-        orientation.rotated)."""
-        from ..orientation import rotated
-
-        return rotated(self, angle_deg, about, **kw)
-
-    def self_emission(self, wavelengths, toward="+", backlight=None):
-        """The plasma's own light along the probing axis, emission with self-absorption (no reference counterpart): an
-        emission.Emission with the intensity and optical-depth maps per wavelength.  Needs external_Te() and external_Z()."""
-        from ..emission import self_emission
-
-        return self_emission(self, wavelengths, toward=toward, backlight=backlight)
-
-    def table_emission(self, table, toward="+", backlight=None):
-        """self_emission with the opacities of an utils.eos_opacity.OpacityTable (PROPACEOS tables) in place of the NRL
-        coefficient (no reference counterpart): an emission.TableEmission, one band per band of the table.  Needs external_Te()
-        and external_Z().  Not modelled: Z from the table's zf_table, group-integrated Planck functions, refraction, detector optics."""
-        from ..emission import table_emission
-
-        return table_emission(self, table, toward=toward, backlight=backlight)
 
     def _field(self, k):
         if self._volume is None:
@@ -229,7 +158,7 @@ class ScalarDomain:
         """Electron plasma frequency [rad/s] of n_e [cm^-3] (NRL formulary; full_solver.py:236-239).  The reference defines
         it in the class body without `self` and calls it as a bare name, which is why its own phaseshift / inv_brems runs stop
         with NameError; here it is callable both ways."""
-        return 5.64e4 * np.sqrt(ne)
+        return _domain.omega_pe(ne)
 
     def plot_midline_gradients(self, ax, probing_direction):
         """The three gradient components along the line through the middle of the box (full_solver.py:291-315: along x for
@@ -287,18 +216,12 @@ class ScalarDomain:
         if s0.ndim == 1:
             s0 = s0.reshape(9, -1)
         start = time()
-        # the traced bundle stays in HBM: rf comes back now, Jf with return_E, and sf / Jf otherwise only when the
-        # attribute is read (0.72 GB of final states per 1e7 rays that most callers never look at).  The diagnostics
-        # classes find the bundle again through the arrays returned here (resident.attach) and deposit from it.
-        rays = resident.acquire(s0.shape[1], self._rays)
-        self._rays = rays.upload(s0)
-        self.trace_stats = rays.trace(self._volume, t_end, self.extent, row_order=engine.ROWS_LEGACY, precision=self.precision,
-                                      substeps=self.substeps, resident=False)  # rf goes back to the caller, who may bin it: "auto" = float64
-        self._sf = self._Jf = None
-        _, rf, Jf = rays.download(sf=False, Jf=return_E)
-        self.rf, Jf = resident.register(rays, rf, Jf)  # the same memory, write-tracked (resident.TrackedArray)
-        if return_E:
-            self._Jf = Jf
+        # rf comes back now, Jf with return_E, and sf / Jf otherwise only when the attribute is read (0.72 GB of final states
+        # per 1e7 rays that most callers never look at)
+        trace = lambda rays: rays.trace(self._volume, t_end, self.extent, row_order=engine.ROWS_LEGACY, precision=self.precision,
+                                        substeps=self.substeps, resident=False)  # rf goes back to the caller, who may bin it: "auto" = float64
+        self.rf, Jf, self.trace_stats = resident.solve_in_bundle(self, s0, trace, return_E)
+        self._sf, self._Jf = None, Jf  # (Jf is None without return_E)
         self.duration = time() - start
         return (self.rf, self._Jf) if return_E else self.rf
 
@@ -330,12 +253,6 @@ class ScalarDomain:
     def solve_at_depth(self, s0, z):
         """Trace for the time length z/c (full_solver.py:405-425)."""
         return self._solve(s0, z / c, False)
-
-    def export_scalar_field(self, property: str = "ne", fname: str = None):
-        """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512), written without pyvista."""
-        from ..utils.handle_filetypes import export_scalar_field
-
-        export_scalar_field(self, property, fname)
 
     def clear_memory(self):
         """Drop the volume and ray attributes (full_solver.py:427-440)."""

@@ -452,6 +452,137 @@ def test_simulator_flow_deposits_from_hbm(eng, orc, c1, c1_oracle):
     assert not dev.on_device and np.max(np.abs(dev.H - host.H)) <= 1e-9 * host.H.max()
 
 
+def _sim_solve(c1, dom=None, s0=None):
+    """propagator.solve of C1 with the field: (domain, rf, Jf), the arrays as solve() hands them out."""
+    from synthpy_amd.simulator import domain as d, propagator as p
+
+    x, ne, s0_c1, ext, lwl = c1
+    if dom is None:
+        dom = d.ScalarDomain(2 * ext, len(x), phaseshift=True)
+        dom.external_ne(ne)
+    rf, Jf, _ = p.solve(s0_c1 if s0 is None else s0, dom, ext, return_E=True, lwl=lwl)
+    return dom, rf, Jf
+
+
+def _sim_pair(cls, c1, rf, Jf):
+    """(device-backed, host-flow) objects of one simulator class: the second from copies of the same arrays."""
+    from synthpy_amd.simulator import diagnostics as diag
+
+    dev, host = getattr(diag, cls)(c1[4], rf, Jf), getattr(diag, cls)(c1[4], np.array(rf), np.array(Jf))
+    assert dev.on_device and not host.on_device
+    return dev, host
+
+
+def _forgotten(it):
+    return it.rf is None and it.r0 is None and it.Jf is None and not it.on_device
+
+
+def test_simulator_clear_mem_gives_the_image_and_forgets_the_rays(eng, c1):
+    """histogram(clear_mem=True) / intensity(clear_mem=True) on a device-backed simulator diagnostic: the host flow's image,
+    then no rays, no field, no bundle (diagnostics.py:349-353)."""
+    dom, rf, Jf = _sim_solve(c1)
+    dev, host = _sim_pair("Shadowgraphy", c1, rf, Jf)
+    for it in (dev, host):
+        it.two_lens_solve()
+        it.histogram(bin_scale=4, clear_mem=True)
+    assert host.H.sum() > 0 and np.array_equal(dev.H, host.H) and _forgotten(dev) and _forgotten(host)
+    dev, host = _sim_pair("Polarimetry", c1, rf, Jf)
+    for it in (dev, host):
+        it.two_lens_solve()
+        it.intensity((0.3, None), bin_scale=4, clear_mem=True)
+    assert dev.I.shape == host.I.shape and host.I.max() > 0
+    assert np.max(np.abs(dev.I - host.I)) <= 1e-9 * host.I.max() and _forgotten(dev) and _forgotten(host)
+
+
+def test_simulator_diagnostics_pickle_from_the_host(eng, c1):
+    """Pickling an attached simulator diagnostic takes its rays to the host: neither the original nor the clone deposits from
+    HBM afterwards, the clone holds the host flow's rf / Jf and goes on giving the host flow's images."""
+    dom, rf, Jf = _sim_solve(c1)
+    dev, host = _sim_pair("Shadowgraphy", c1, rf, Jf)
+    for it in (dev, host):
+        it.two_lens_solve()
+    clone = pickle.loads(pickle.dumps(dev))
+    assert not dev.on_device and not clone.on_device
+    assert np.array_equal(clone.rf, host.rf, equal_nan=True) and np.array_equal(clone.Jf, host.Jf, equal_nan=True)
+    for it in (clone, host):
+        it.histogram(bin_scale=5)
+    assert host.H.sum() > 0 and np.array_equal(clone.H, host.H)
+    dev, host = _sim_pair("Interferometry", c1, rf, Jf)
+    for it in (dev, host):
+        it.interfere_ref_beam(10, 10)
+        it.two_lens_solve()
+    assert dev.on_device
+    clone = pickle.loads(pickle.dumps(dev))
+    assert not dev.on_device and not clone.on_device
+    assert np.array_equal(clone.rf, host.rf, equal_nan=True) and np.array_equal(clone.Jf, host.Jf, equal_nan=True)
+    for it in (clone, host):
+        it.interferogram(bin_scale=10)
+    assert host.H.max() > 0 and np.max(np.abs(clone.H - host.H)) <= 1e-9 * host.H.max()
+
+
+def test_simulator_bundle_lifetime_between_solves(eng, c1):
+    """test_bundle_lifetime_between_solves through propagator.solve: a diagnostic keeps ITS bundle over the domain's next
+    solve(), a bundle nobody holds is reused, resident.release() brings an attached diagnostic to the host."""
+    from synthpy_amd import resident
+    from synthpy_amd.simulator import diagnostics as diag
+
+    x, ne, s0, ext, lwl = c1
+    dom, rf, Jf = _sim_solve(c1)
+    first = dom._rays
+    sh, host = _sim_pair("Shadowgraphy", c1, rf, Jf)
+    for it in (sh, host):
+        it.two_lens_solve()
+    s1 = s0.copy()
+    s1[0] += 2e-4
+    _, rf1, Jf1 = _sim_solve(c1, dom, s1)  # sh still holds the first bundle: the domain takes another one
+    assert dom._rays is not first and first.alive
+    for it in (sh, host):
+        it.histogram(bin_scale=10)
+    assert sh.on_device and host.H.sum() > 0 and np.array_equal(sh.H, host.H)
+    sh1 = diag.Shadowgraphy(lwl, rf1)
+    sh1.two_lens_solve()
+    sh1.histogram(bin_scale=10, clear_mem=True)
+    assert not np.array_equal(sh1.H, sh.H)
+    second = dom._rays
+    _sim_solve(c1, dom)  # nobody deposits from `second` any more: reused
+    assert dom._rays is second
+    resident.release(first)
+    assert not sh.on_device and not first.alive
+    for it in (sh, host):
+        it.histogram(bin_scale=5)
+    assert np.array_equal(sh.H, host.H) and np.array_equal(sh.rf, host.rf, equal_nan=True)
+
+
+def test_simulator_assigned_r0_and_Jf_are_what_the_next_step_reads(eng, c1):
+    """r0 assigned on an attached simulator diagnostic: other rays than the resident ones, so the object leaves the device
+    and the next *_solve() + histogram() bin the assigned rays.  Jf assigned after two_lens_solve(): interferogram() sums the
+    assigned field (the legacy E-setter case above; unlike that setter this one keeps the bundle -- Jf is an input of the next
+    chain, which then runs on the host -- so what is checked is that nothing deposits from HBM any more)."""
+    dom, rf, Jf = _sim_solve(c1)
+    dev, host = _sim_pair("Shadowgraphy", c1, rf, Jf)
+    r0 = np.array(dev.r0)
+    assert dev.on_device and np.array_equal(r0, host.r0, equal_nan=True)
+    r0[:, :2000] = np.nan
+    for it in (dev, host):
+        it.r0 = r0.copy()
+    assert not dev.on_device
+    for it in (dev, host):
+        it.two_lens_solve()
+        it.histogram(bin_scale=10)
+    assert np.array_equal(dev.H, host.H) and 0 < dev.H.sum() < 0.9 * r0.shape[1]
+    dev, host = _sim_pair("Interferometry", c1, rf, Jf)
+    for it in (dev, host):
+        it.two_lens_solve()
+        it.interferogram(bin_scale=10)
+    H_plain = host.H
+    for it in (dev, host):
+        it.Jf = np.array(it.Jf) * 0.5
+        it.interferogram(bin_scale=10)
+    assert not dev._deposits_from_device()
+    assert np.max(np.abs(dev.H - host.H)) <= 1e-9 * host.H.max()
+    assert np.max(np.abs(dev.H - 0.5 * H_plain)) <= 1e-9 * H_plain.max()
+
+
 def test_headline_shape_through_the_reference_api(eng, orc):
     """A dense bundle through the reference's API: 2e5 rays in a narrow beam (>= 16 rays per lateral cell) through
     bench.make_volume(256) -- solve() takes the tile kernel by itself, Interferometry deposits from HBM -- against the oracle
