@@ -277,6 +277,54 @@ typedef struct {
 int sr_field_emission_table(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *t,
                             const sr_emission_params *p, const double *backlight, double *I, double *tau, double *kernel_ms);
 
+/* ---- sightlines: emission and absorption along arbitrary chords ---------------------------------
+ * No reference counterpart.  The recurrence of sr_field_emission marched along n half-lines x(t) = o + d t, t >= 0, that need not
+ * be parallel to a grid axis: the converging lines of a pinhole camera, the diverging ones of a point backlighter, single chords
+ * of a diode or a spectrometer.  ne, Te, Z are sr_field_emission's fields (one grid, one dtype; a NULL Te or Z is the uniform value
+ * p->Te / p->Z and is not read); table NULL: the node is sr_field_emission's (the NRL node), otherwise sr_field_emission_table's with
+ * that table (p->omega is then ignored).  origin and dir are HOST arrays (3, n), float64, C order; dir need not be a unit vector.
+ * Everything is float64 and every operation below rounds on its own (sightlines.hip is compiled with -ffp-contract=off); lo_a and
+ * hi_a are the first and the last node coordinate of axis a, widened from float32.  Per line:
+ *   clip     t0 = 0, t1 = +inf; for a = x, y, z in that order: d_a == 0: the line misses unless lo_a <= o_a <= hi_a; otherwise
+ *              ta = (lo_a - o_a)/d_a;  tb = (hi_a - o_a)/d_a             (a division, not a reciprocal: 0*inf cannot arise)
+ *              t0 = max(t0, min(ta, tb));  t1 = min(t1, max(ta, tb))
+ *            and the line misses unless t1 > t0.  The origin may lie inside the box (t0 stays 0).
+ *   miss     I = backlight (0 when NULL), tau = 0, column = 0, chord = 0, steps = 0.
+ *   steps    len = sqrt((d0*d0 + d1*d1) + d2*d2);  chord = (t1 - t0)*len;  q = chord/step
+ *              n = q >= max_steps ? max_steps : max(1, (int)ceil(q));  dt = (t1 - t0)/n;  h = chord/n
+ *            (a q that is not below max_steps, NaN included, takes max_steps).
+ *   march    start from I = backlight (0 when NULL), tau = 0, column = 0; visit the samples k = 0 .. n-1 in that order for
+ *            toward = +1 (the light travels along +d, away from the origin: a backlighter) and k = n-1 .. 0 for toward = -1 (towards
+ *            the origin: a pinhole).  Per sample
+ *              t = t0 + (k + 0.5)*dt;  p_a = o_a + d_a*t
+ *            ne, Te, Z at p follow sr_field_resample's `cell`, `outside` and `blend` lines word for word (the same corner order,
+ *            u = 1 - w as the factors); the blended value of a float32 field stays float64.  A sample whose p lies outside the box
+ *            on any axis -- possible only within rounding of a face -- is dark: alpha = S = 0, and its ne counts as 0.  Otherwise
+ *            alpha and S per band are the node's, from the blended (ne, Te, Z), with the node's own dark conditions.  Then
+ *              dtau = alpha*h;  I <- I*exp(-dtau) + S*(-expm1(-dtau));  tau <- tau + dtau;  column <- column + ne*h
+ *            A NaN corner makes NaN the lines whose samples fall in its cell, zero weights included, and no other line.
+ * No atomics: a repeated call returns identical bits.  I, tau and backlight are HOST arrays (n_band, n); column [m^-2, the integral
+ * of ne dl], chord [m] and steps are HOST arrays (n) and may be NULL.  *kernel_ms (may be NULL) is the HIP-event time of the kernel.
+ * Not modelled: a finite pinhole or source, the cos^4 and solid-angle factors between radiance and film exposure, refraction, the
+ * detector's response, a table's own ionisation.
+ * Arguments are checked before the device is touched: a NULL p, origin, dir, I or tau; n < 0 (n == 0 succeeds and writes nothing);
+ * n_band, omega (table NULL), e_ph and c_omega as sr_field_emission checks them; toward not +-1; a step that is not finite and
+ * positive; max_steps < 1; everything sr_field_emission_table checks of a table; a non-finite entry of origin or dir; a dir column
+ * that is all zero; a NULL ne, a vector field, fields of different dtypes, grids that differ. */
+typedef struct {
+  int32_t toward;      /* +1: the light travels along +d (backlighter); -1: towards the origin (pinhole)    */
+  int32_t n_band;      /* 1..SR_MAX_BANDS                                                                    */
+  int32_t max_steps;   /* >= 1                                                                               */
+  int32_t reserved;
+  double step;         /* target sample spacing [m], finite, > 0                                            */
+  double omega[SR_MAX_BANDS], e_ph[SR_MAX_BANDS], c_omega[SR_MAX_BANDS]; /* as sr_emission_params          */
+  double Te, Z;        /* the uniform field values where the handle is NULL                                  */
+} sr_sightline_params;
+int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *table /* or NULL */,
+                        const sr_sightline_params *p, int64_t n, const double *origin, const double *dir,
+                        const double *backlight /* or NULL */, double *I, double *tau, double *column /* or NULL */,
+                        double *chord /* or NULL */, int32_t *steps /* or NULL */, double *kernel_ms);
+
 /* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
  * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
  * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be

@@ -109,6 +109,16 @@ class DomainExtras:
 
         return table_emission(self, table, toward=toward, backlight=backlight)
 
+    def sightline_emission(self, view, wavelengths=None, table=None, step=None, max_steps=None):
+        """What a sightlines.PinholeCamera, PointBacklighter or Chords sees of this domain: emission with self-absorption
+        along lines that converge on a pinhole, diverge from a point backlighter, or are single chords at any angle -- a
+        sightlines.SightlineEmission.  Exactly one of wavelengths (self_emission's node) and table (table_emission's).  Needs
+        external_Te() and external_Z().  Not modelled: a finite pinhole or source, the cos^4 and solid-angle factors of a film's
+        exposure, refraction, the detector's response, a table's own ionisation; one GPU."""
+        from .sightlines import sightline_emission
+
+        return sightline_emission(self, view, wavelengths=wavelengths, table=table, step=step, max_steps=max_steps)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
         from .utils.handle_filetypes import export_scalar_field

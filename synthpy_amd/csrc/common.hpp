@@ -225,6 +225,33 @@ __device__ __forceinline__ bool locate_in(const double *__restrict__ g, int n, d
 __device__ __forceinline__ bool locate(const double *__restrict__ g, int n, double inv_h, double p, int &cell, double &w) {
   return locate_in<false>(g, n, inv_h, 0.0, 0.0, p, cell, w);
 }
+// One scalar at the cell (ci, cj, ck) with the blend of sr_field_resample's rule (shared by thomson.hip and sightlines.hip); nc:
+// components per node, c: the one wanted; sx, sy: the node strides of x and y.  In two halves, so that a kernel can have the eight
+// corner reads of its next point in flight while it works on this one: corners_load only reads, corners_blend only computes.
+template <typename T>
+struct Corners {
+  T v[8];  // (di, dj, dk) at v[4*di + 2*dj + dk]
+};
+template <typename T>
+__device__ __forceinline__ Corners<T> corners_load(const T *__restrict__ src, int nc, int c, int64_t sx, int64_t sy, int ci, int cj,
+                                                   int ck) {
+  const T *lo = src + (((int64_t)ci * sx + (int64_t)cj * sy + (int64_t)ck) * nc + c);
+  const T *hi = lo + sx * nc;
+  const int64_t ry = sy * nc;
+  return Corners<T>{{lo[0], lo[nc], lo[ry], lo[ry + nc], hi[0], hi[nc], hi[ry], hi[ry + nc]}};
+}
+template <typename T>
+__device__ __forceinline__ double corners_blend(const Corners<T> &f, double ux, double wx, double w00, double w01, double w10,
+                                                double w11) {
+  const double s0 = (((double)f.v[0] * w00 + (double)f.v[1] * w01) + (double)f.v[2] * w10) + (double)f.v[3] * w11;
+  const double s1 = (((double)f.v[4] * w00 + (double)f.v[5] * w01) + (double)f.v[6] * w10) + (double)f.v[7] * w11;
+  return ux * s0 + wx * s1;
+}
+template <typename T>
+__device__ __forceinline__ double blend(const T *__restrict__ src, int nc, int c, int64_t sx, int64_t sy, int ci, int cj, int ck,
+                                        double ux, double wx, double w00, double w01, double w10, double w11) {
+  return corners_blend(corners_load(src, nc, c, sx, sy, ci, cj, ck), ux, wx, w00, w01, w10, w11);
+}
 #endif
 inline unsigned long long stripe_sum(const unsigned long long *host_words, int which) {
   unsigned long long t = 0;

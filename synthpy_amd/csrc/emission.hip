@@ -1,25 +1,9 @@
 // Self-emission images: emission with self-absorption along a grid axis (sr_field_emission; include/synthray.h states the rule
 // every node, cell and column follows, operation for operation).  The march -- k_emission_z, k_emission_xy, the cell, the host's
-// staging -- is emission_march.inc, shared with emission_table.hip; the NRL node is nrl_node.inc, shared with wave.hip; this unit
-// holds the node's policy and the entry.  No LDS.
+// staging, the NRL node's policy -- is emission_march.inc, shared with emission_table.hip and sightlines.hip; the NRL node is
+// nrl_node.inc, shared with wave.hip; this unit holds the entry.  No LDS.
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_emission.py).
 #include "emission_march.inc"
-
-namespace {
-
-struct NrlNode {
-  struct Args {};
-  static constexpr int kXYBlock = 64;
-  __device__ __forceinline__ explicit NrlNode(const Args &) {}
-  template <int NB>
-  __device__ __forceinline__ void eval(const EmArgs &A, double ne, double Te, double Z, double (&al)[NB], double (&S)[NB]) const {
-    const NodeTerms t = node_terms(ne, Te, Z);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) node_band(t, A.omega[b], A.e_ph[b], A.c_omega[b], al[b], S[b]);
-  }
-};
-
-}  // namespace
 
 extern "C" int sr_field_emission(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p,
                                  const double *backlight, double *I, double *tau, double *kernel_ms) {

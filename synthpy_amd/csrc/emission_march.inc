@@ -39,6 +39,19 @@ struct EmArgs {
 
 #include "nrl_node.inc"  // nmax and the NRL node (shared with wave.hip)
 
+// the NRL node as a policy (emission.hip, sightlines.hip); the tabulated one is table_node.inc
+struct NrlNode {
+  struct Args {};
+  static constexpr int kXYBlock = 64;
+  __device__ __forceinline__ explicit NrlNode(const Args &) {}
+  template <int NB>
+  __device__ __forceinline__ void eval(const EmArgs &A, double ne, double Te, double Z, double (&al)[NB], double (&S)[NB]) const {
+    const NodeTerms t = node_terms(ne, Te, Z);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) node_band(t, A.omega[b], A.e_ph[b], A.c_omega[b], al[b], S[b]);
+  }
+};
+
 template <typename T, bool HAS_TE, bool HAS_Z, int NB>
 __device__ __forceinline__ void load_node(const EmArgs &A, int64_t at, double &ne, double &Te, double &Z) {
   ne = (double)static_cast<const T *>(A.ne)[at];

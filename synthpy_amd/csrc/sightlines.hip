@@ -1,0 +1,269 @@
+// Sightlines: emission and absorption along arbitrary chords (sr_field_sightlines; include/synthray.h states the rule every line
+// and sample follows, operation for operation).  No reference counterpart.  The radiative-transfer recurrence of emission.hip
+// marched along lines that are not grid columns: a pinhole camera's converging lines, a point backlighter's diverging ones, a
+// diode's single chord.
+//
+// One line per lane, 256-lane workgroups; the line's geometry, its running (I, tau, column) and the sample in flight stay in
+// registers for the whole march: no scratch, no atomics, and LDS only where the tabulated node stages its table.  The node is the
+// policy emission_march.inc's kernels take (NrlNode there, TableNode in table_node.inc: one copy each), the cell search and the
+// blend are common.hpp's (sr::locate_in, sr::corners_load / corners_blend, shared with resample.hip, push.hip and thomson.hip).
+// The kernel is a gather: 8 corners times up to 3 fields per sample, at addresses that depend on the line.  A sample's cell search
+// and its corner reads are issued BEFORE the node arithmetic of the sample before it (two logs, an exp and an expm1 per band), so
+// the reads' latency runs under that arithmetic, as k_emission_xy keeps two planes in flight.  Lanes of a wavefront finish at
+// different step counts: a lane that is done is masked off, there are no cross-lane operations inside the loop.  Which lines share a
+// wavefront -- the locality of the gather -- is the caller's business (synthpy_amd/sightlines.py hands a pixel grid over in 8x8
+// tiles in Morton order).  k_sightlines is instantiated per (dtype, Te field?, Z field?, bands, node).
+// Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_sightlines.py).
+#include <vector>
+
+#include "emission_march.inc"
+
+namespace {
+#include "table_node.inc"
+
+struct LineArgs {
+  sr::FieldGrid f;      // lo, hi: the box
+  const double *o, *d;  // (3, n) origins and directions
+  double *column, *chord;
+  int32_t *steps;
+  int64_t n;
+  int max_steps;
+  double step;
+};
+
+// One sample of a line: where it lies in its cell, and the corners of the fields there (read, not yet blended)
+template <typename T, bool HAS_TE, bool HAS_Z>
+struct Sample {
+  bool in;
+  double ux, wx, w00, w01, w10, w11;
+  sr::Corners<T> ne, Te, Z;
+};
+
+template <typename T, bool HAS_TE, bool HAS_Z>
+__device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, double px, double py,
+                                      double pz, Sample<T, HAS_TE, HAS_Z> &s) {
+  int ci = 0, cj = 0, ck = 0;
+  double wx = 0, wy = 0, wz = 0;
+  const bool in_x = sr::locate_in<true>(f.g[0], f.n[0], f.inv_h[0], f.lo[0], f.hi[0], px, ci, wx);
+  const bool in_y = sr::locate_in<true>(f.g[1], f.n[1], f.inv_h[1], f.lo[1], f.hi[1], py, cj, wy);
+  const bool in_z = sr::locate_in<true>(f.g[2], f.n[2], f.inv_h[2], f.lo[2], f.hi[2], pz, ck, wz);
+  s.in = in_x && in_y && in_z;
+  if (s.in) {  // locate_in leaves every cell index in [0, n - 2]: the eight corners are nodes of the field
+    const double uy = 1.0 - wy, uz = 1.0 - wz;
+    s.ux = 1.0 - wx;
+    s.wx = wx;
+    s.w00 = uy * uz;
+    s.w01 = uy * wz;
+    s.w10 = wy * uz;
+    s.w11 = wy * wz;
+    s.ne = sr::corners_load(static_cast<const T *>(A.ne), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_TE) s.Te = sr::corners_load(static_cast<const T *>(A.Te), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_Z) s.Z = sr::corners_load(static_cast<const T *>(A.Z), 1, 0, sx, sy, ci, cj, ck);
+  }
+}
+
+template <typename T, bool HAS_TE, bool HAS_Z, int NB, typename P>
+__global__ void __launch_bounds__(256) k_sightlines(EmArgs A, LineArgs L, typename P::Args X) {
+  const P node(X);  // every thread of the workgroup, before any leaves
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= L.n) return;
+  const int64_t N = L.n;
+  const double o0 = L.o[i], o1 = L.o[N + i], o2 = L.o[2 * N + i];
+  const double d0 = L.d[i], d1 = L.d[N + i], d2 = L.d[2 * N + i];
+  double I[NB], tau[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    I[k] = A.back ? A.back[k * N + i] : 0.0;
+    tau[k] = 0.0;
+  }
+  // clip: the half-line t >= 0 against the box, axis by axis
+  double t0 = 0.0, t1 = HUGE_VAL;
+  bool hit = true;
+  auto clip = [&](double o, double d, double lo, double hi) {
+    if (d == 0.0) {
+      hit = hit && lo <= o && o <= hi;
+    } else {
+      const double ta = (lo - o) / d, tb = (hi - o) / d;
+      const double tn = ta < tb ? ta : tb, tf = ta < tb ? tb : ta;
+      t0 = t0 > tn ? t0 : tn;
+      t1 = t1 < tf ? t1 : tf;
+    }
+  };
+  clip(o0, d0, L.f.lo[0], L.f.hi[0]);
+  clip(o1, d1, L.f.lo[1], L.f.hi[1]);
+  clip(o2, d2, L.f.lo[2], L.f.hi[2]);
+  hit = hit && t1 > t0;
+  double column = 0.0, chord = 0.0;
+  int n = 0;
+  if (hit) {
+    const double len = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+    chord = (t1 - t0) * len;
+    const double q = chord / L.step;
+    if (!(q < (double)L.max_steps)) {  // q >= max_steps, or a NaN q (a direction whose squares underflow)
+      n = L.max_steps;
+    } else {
+      n = (int)ceil(q);
+      n = n < 1 ? 1 : n;
+    }
+    const double dt = (t1 - t0) / (double)n, h = chord / (double)n;
+    const int64_t sy = L.f.n[2], sx = (int64_t)L.f.n[1] * sy;
+    const int k0 = A.toward > 0 ? 0 : n - 1, dk = A.toward > 0 ? 1 : -1;
+    Sample<T, HAS_TE, HAS_Z> cur{}, nxt{};
+    {
+      const double t = t0 + ((double)k0 + 0.5) * dt;
+      fetch<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, o0 + d0 * t, o1 + d1 * t, o2 + d2 * t, cur);
+    }
+    for (int m = 0; m < n; ++m) {
+      // this sample's values (its reads were issued a sample ago) ...
+      double ne = 0.0, Te = A.uTe, Z = A.uZ;
+      if (cur.in) {
+        ne = sr::corners_blend(cur.ne, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
+        if (HAS_TE) Te = sr::corners_blend(cur.Te, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
+        if (HAS_Z) Z = sr::corners_blend(cur.Z, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
+      }
+      // ... the next sample's cell and corner reads, in flight during this sample's node arithmetic ...
+      nxt.in = false;
+      if (m + 1 < n) {
+        const double t = t0 + ((double)(k0 + (m + 1) * dk) + 0.5) * dt;
+        fetch<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, o0 + d0 * t, o1 + d1 * t, o2 + d2 * t, nxt);
+      }
+      // ... the node and the update; a sample outside the box (within rounding of a face) has ne = 0, which either node takes
+      // for dark: alpha = S = 0
+      double al[NB], S[NB];
+      node.template eval<NB>(A, ne, Te, Z, al, S);
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        const double dtau = al[k] * h;
+        I[k] = I[k] * exp(-dtau) + S[k] * (-expm1(-dtau));
+        tau[k] = tau[k] + dtau;
+      }
+      column = column + ne * h;
+      cur = nxt;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    A.I[k * N + i] = I[k];
+    A.tau[k * N + i] = tau[k];
+  }
+  L.column[i] = column;
+  L.chord[i] = chord;
+  L.steps[i] = n;
+}
+
+template <typename T, typename P>
+void launch_lines(const EmArgs &A, const LineArgs &L, const typename P::Args &X, size_t lds_bytes, bool has_te, bool has_z,
+                  int n_band, hipStream_t st) {
+  sr::with_flags(
+      [&](auto te, auto z) {
+        sr::with_count<SR_MAX_BANDS>(
+            [&](auto nb) {
+              constexpr bool kTe = decltype(te)::value, kZ = decltype(z)::value;
+              constexpr int kNb = decltype(nb)::value;
+              hipLaunchKernelGGL((k_sightlines<T, kTe, kZ, kNb, P>), dim3(sr::grid_for(L.n, 256)), dim3(256), lds_bytes, st, A, L, X);
+            },
+            n_band);
+      },
+      has_te, has_z);
+}
+
+}  // namespace
+
+extern "C" int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *table,
+                                   const sr_sightline_params *p, int64_t n, const double *origin, const double *dir,
+                                   const double *backlight, double *I, double *tau, double *column, double *chord, int32_t *steps,
+                                   double *kernel_ms) {
+  const char *who = "sr_field_sightlines";
+  SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
+  SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
+  SR_CHECK(p->n_band >= 1 && p->n_band <= SR_MAX_BANDS, "%s: n_band must be 1..%d, got %d", who, SR_MAX_BANDS, p->n_band);
+  for (int b = 0; b < p->n_band; ++b) {
+    SR_CHECK(table != nullptr || (std::isfinite(p->omega[b]) && p->omega[b] > 0.0), "%s: omega of band %d must be finite and positive",
+             who, b);
+    SR_CHECK(std::isfinite(p->e_ph[b]) && std::isfinite(p->c_omega[b]), "%s: non-finite e_ph or c_omega of band %d", who, b);
+  }
+  SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
+  SR_CHECK(sr::positive(p->step), "%s: step must be finite and positive", who);
+  SR_CHECK(p->max_steps >= 1, "%s: max_steps must be at least 1, got %d", who, p->max_steps);
+  if (table)
+    if (int rc = check_table(who, table, p->n_band)) return rc;
+  for (int64_t k = 0; k < 3 * n; ++k) {
+    SR_CHECK(std::isfinite(origin[k]), "%s: non-finite origin of line %lld", who, (long long)(k % n));
+    SR_CHECK(std::isfinite(dir[k]), "%s: non-finite direction of line %lld", who, (long long)(k % n));
+  }
+  for (int64_t k = 0; k < n; ++k)
+    SR_CHECK(dir[k] != 0.0 || dir[n + k] != 0.0 || dir[2 * n + k] != 0.0, "%s: the direction of line %lld is zero", who, (long long)k);
+  SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
+  if (int rc = sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}})) return rc;
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (n == 0) return SR_OK;
+  if (int rc = sr::ensure_init()) return rc;
+  sr::Context &c = sr::ctx();
+  hipStream_t st = c.stream;
+
+  std::vector<double> pack;
+  if (table) pack = pack_table(table, p->n_band);
+  const size_t tab_bytes = sizeof(double) * pack.size();
+  const int nb = p->n_band;
+  const size_t N = (size_t)n, map_bytes = sizeof(double) * nb * N;
+
+  // one scratch block: I | tau | backlight | origins | directions | column | chord | steps | table
+  EmArgs A{};
+  LineArgs L{};
+  char *tab = nullptr;
+  sr::Carve carve;
+  carve.take(&A.I, nb * N);
+  carve.take(&A.tau, nb * N);
+  if (backlight) carve.take(&A.back, nb * N);
+  carve.take(&L.o, 3 * N);
+  carve.take(&L.d, 3 * N);
+  carve.take(&L.column, N);
+  carve.take(&L.chord, N);
+  carve.take(&L.steps, N);
+  carve.take(&tab, tab_bytes);
+  if (!carve.alloc()) return SR_ERR_HIP;
+  A.ne = ne->data;
+  A.Te = Te ? Te->data : nullptr;
+  A.Z = Z ? Z->data : nullptr;
+  A.toward = p->toward;
+  A.ncol = n;
+  for (int b = 0; b < nb; ++b) {
+    A.omega[b] = p->omega[b];
+    A.e_ph[b] = p->e_ph[b];
+    A.c_omega[b] = p->c_omega[b];
+  }
+  A.uTe = p->Te;
+  A.uZ = p->Z;
+  L.f = sr::grid_of(ne);
+  L.n = n;
+  L.max_steps = p->max_steps;
+  L.step = p->step;
+
+  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.o), origin, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.d), dir, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  if (backlight) SR_HIP(hipMemcpyAsync(const_cast<double *>(A.back), backlight, map_bytes, hipMemcpyHostToDevice, st));
+  if (table) SR_HIP(hipMemcpyAsync(tab, pack.data(), tab_bytes, hipMemcpyHostToDevice, st));
+  SR_HIP(hipEventRecord(c.ev[0], st));
+  if (table) {
+    const TabArgs X = tab_args(table, nb, tab, pack.size());
+    sr::with_flags(
+        [&](auto in_lds, auto f64) {
+          using T = std::conditional_t<decltype(f64)::value, double, float>;
+          constexpr bool kLds = decltype(in_lds)::value;
+          launch_lines<T, TableNode<kLds>>(A, L, X, kLds ? tab_bytes : 0, Te != nullptr, Z != nullptr, nb, st);
+        },
+        tab_bytes <= kLdsBudget, (bool)ne->is_f64);
+  } else if (ne->is_f64) {
+    launch_lines<double, NrlNode>(A, L, NrlNode::Args{}, 0, Te != nullptr, Z != nullptr, nb, st);
+  } else {
+    launch_lines<float, NrlNode>(A, L, NrlNode::Args{}, 0, Te != nullptr, Z != nullptr, nb, st);
+  }
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], st));
+  SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
+  if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (chord) SR_HIP(hipMemcpyAsync(chord, L.chord, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (steps) SR_HIP(hipMemcpyAsync(steps, L.steps, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  return sr::finish_timed(c, kernel_ms);
+}

@@ -39,17 +39,7 @@ struct ThomsonArgs {
   double tpc, ce, ci, ee0, wi, kin;
 };
 
-// one scalar at the cell (ci, cj, ck) with the blend of sr_field_resample's rule; nc: components per node, c: the one wanted
-template <typename T>
-__device__ __forceinline__ double blend(const T *__restrict__ src, int nc, int c, int64_t sx, int64_t sy, int ci, int cj, int ck,
-                                        double ux, double wx, double w00, double w01, double w10, double w11) {
-  const T *lo = src + (((int64_t)ci * sx + (int64_t)cj * sy + (int64_t)ck) * nc + c);
-  const T *hi = lo + sx * nc;
-  const int64_t ry = sy * nc;
-  const double s0 = (((double)lo[0] * w00 + (double)lo[nc] * w01) + (double)lo[ry] * w10) + (double)lo[ry + nc] * w11;
-  const double s1 = (((double)hi[0] * w00 + (double)hi[nc] * w01) + (double)hi[ry] * w10) + (double)hi[ry + nc] * w11;
-  return ux * s0 + wx * s1;
-}
+using sr::blend;  // one scalar at a cell with the blend of sr_field_resample's rule (common.hpp, shared with sightlines.hip)
 
 // D(x) of the rule: Dawson's function F and E = exp(-x^2)
 __device__ __forceinline__ void dawson(double x, double &F, double &E) {

@@ -11,7 +11,9 @@ plane nearest the detector on the GPU (engine.emission -> sr_field_emission; inc
 propagator.kappa(ne, Te, Z, omega) / c -- the NRL low-frequency (inverse-bremsstrahlung) coefficient the tracer uses, trustworthy
 for hbar*omega <~ Te -- and S is the Planck function B_omega(Te), so the emissivity follows from Kirchhoff's law.  Refraction of the
 emitted light, line emission and detector optics are not modelled.  Where hbar*omega is above Te -- XUV and soft-X-ray bands, where
-bound-free and line opacity dominate -- the coefficient comes from an opacity table instead: table_emission below.
+bound-free and line opacity dominate -- the coefficient comes from an opacity table instead: table_emission below.  Both march
+columns parallel to a grid axis; a pinhole camera's converging lines, a point backlighter's diverging ones and single chords at any
+angle are sightlines.sightline_emission (domain.sightline_emission), with either node.
 
     table = OpacityTable.from_propaceos(read_propaceos(path, need_abs_opacity=True, need_emiss_opacity=True), A=12.011)
     em = table_emission(domain, table)                     # or domain.table_emission(table); a TableEmission
@@ -84,24 +86,30 @@ def _omegas(wavelengths):
     return lam, 2 * np.pi * c / lam
 
 
-def _march(domain, toward, fields, run):
-    """What self_emission and table_emission share: the domain's fields uploaded by self_emission's rules -- a Te or Z that is a
-    scalar (or broadcast from one) goes as a value, float32 only when every array is float32 (fields.SourceFields.get_all) --
-    then run(ne, Te, Z, axis, sign) -> (I, tau); returns (I, tau, axes, coords)."""
-    axis = engine.axis_index(domain.probing_direction)
-    sign = _toward(toward)
+def _upload(domain, fields, run):
+    """What every emission entry shares (self_emission, table_emission, sightlines.sightline_emission): the domain's fields
+    uploaded by self_emission's rules -- a Te or Z that is a scalar (or broadcast from one) goes as a value, float32 only when
+    every array is float32 (fields.SourceFields.get_all) -- then run(ne, Te, Z), whose result is returned."""
     ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
     if ne is None:
         raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
     if Te is None or Z is None:
         raise ValueError("self_emission needs external_Te() and external_Z()")
-    axes, coords = _lateral(domain, axis)
     shape = (len(domain.x), len(domain.y), len(domain.z))
     values = {"Te": uniform(Te), "Z": uniform(Z)}
     named = {name: np.broadcast_to(np.asarray(a), shape) for name, a in (("ne", ne), ("Te", Te), ("Z", Z)) if values.get(name) is None}
     with staged(domain, fields) as src:
         f = src.get_all(named)
-        I, tau = run(f["ne"], f.get("Te", values["Te"]), f.get("Z", values["Z"]), axis, sign)
+        return run(f["ne"], f.get("Te", values["Te"]), f.get("Z", values["Z"]))
+
+
+def _march(domain, toward, fields, run):
+    """What self_emission and table_emission share: _upload's fields, then run(ne, Te, Z, axis, sign) -> (I, tau) along the
+    probing axis; returns (I, tau, axes, coords)."""
+    axis = engine.axis_index(domain.probing_direction)
+    sign = _toward(toward)
+    I, tau = _upload(domain, fields, lambda ne, Te, Z: run(ne, Te, Z, axis, sign))
+    axes, coords = _lateral(domain, axis)
     return I, tau, axes, coords
 
 

@@ -543,6 +543,66 @@ def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
     return _emission(lib.sr_field_emission_table, ne, Te, Z, omegas, axis, toward, backlight, C.byref(t))
 
 
+_SIGHT_WANT = ("intensity", "optical_depth", "column", "chord", "steps")
+
+
+def sightline_params(omegas, toward, step, max_steps, Te=0.0, Z=0.0):
+    """sr_sightline_params: the bands of emission_params(omegas, ...), the march's direction, spacing and step cap."""
+    e = emission_params(omegas, 0, toward, Te, Z)
+    p = _ffi.SightlineParams()
+    p.toward, p.n_band, p.max_steps, p.reserved, p.step = int(toward), e.n_band, int(max_steps), 0, float(step)
+    p.omega[:], p.e_ph[:], p.c_omega[:] = list(e.omega), list(e.e_ph), list(e.c_omega)
+    p.Te, p.Z = e.Te, e.Z
+    return p
+
+
+def sightlines(ne, Te, Z, origins, directions, *, omegas=None, table=None, toward, step, max_steps, backlight=None,
+               want=_SIGHT_WANT):
+    """Emission and absorption along the n half-lines origins[:, i] + t * directions[:, i], t >= 0 (both (3, n) [m]; a direction
+    need not be a unit vector), through the fields ne [m^-3], Te [eV], Z (sr_field_sightlines; include/synthray.h states the
+    rule): each line is clipped to the grid's box and marched in samples about `step` apart (at most max_steps of them), the
+    fields interpolated trilinearly at every sample.  Exactly one of omegas (up to 4 angular frequencies: engine.emission's NRL
+    node) and table (an utils.eos_opacity.OpacityTable: engine.emission_table's node).  toward = +1: the light travels along
+    +direction, away from the origin (a backlighter at the origin); -1: towards the origin (a pinhole there).  Fields, uniform Te /
+    Z and handles are engine.emission's.  backlight: (n_band, n) behind the far end of every line, or None.  Returns a dict with
+    the arrays named in `want`: "intensity" and "optical_depth" (n_band, n), "column" (n; the integral of ne dl [m^-2]), "chord"
+    (n; the length inside the box [m], 0 for a line that misses it) and "steps" (n) int32.  ne.last_kernel_ms keeps the kernel's
+    time.  Not modelled: a finite pinhole or source, the cos^4 and solid-angle factors of a film's exposure, refraction, the
+    detector's response, a table's own ionisation; one GPU."""
+    h_ne = _handle("ne", ne)
+    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
+    if (omegas is None) == (table is None):
+        raise ValueError("exactly one of omegas (the NRL node) and table (an OpacityTable) must be given")
+    unknown = set(want) - set(_SIGHT_WANT)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT}")
+    o, d = f64(origins), f64(directions)
+    if o.ndim != 2 or o.shape[0] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and directions must both have shape (3, n), got {o.shape} and {d.shape}")
+    n = o.shape[1]
+    t, keep = None, None
+    if table is not None:
+        t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
+        omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
+        if len(omegas) != keep[2].shape[0]:
+            raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
+    p = sightline_params(omegas, toward, step, max_steps, *(0.0 if h else float(a) for h, a in zip(handles, (Te, Z))))
+    nb = p.n_band
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != (nb, n):
+            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lines give {(nb, n)}")
+    I, tau = np.empty((nb, n)), np.empty((nb, n))
+    opt = {"column": np.empty(n) if "column" in want else None, "chord": np.empty(n) if "chord" in want else None,
+           "steps": np.empty(n, np.int32) if "steps" in want else None}
+    ms = C.c_double(0.0)
+    check(lib.sr_field_sightlines(h_ne, *handles, None if t is None else C.byref(t), C.byref(p), n, ptr(o), ptr(d), ptr(backlight),
+                                  ptr(I), ptr(tau), ptr(opt["column"]), ptr(opt["chord"]), ptr(opt["steps"]), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    out = {"intensity": I, "optical_depth": tau, **opt}
+    return {k: out[k] for k in _SIGHT_WANT if k in want}
+
+
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
 _PUSH_WANT = ("sf", "hits", "steps", "flags")
 

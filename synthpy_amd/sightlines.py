@@ -1,0 +1,252 @@
+"""Sightlines: emission and absorption along lines that are not grid columns (no reference counterpart).
+
+    cam = sightlines.PinholeCamera(pinhole=(0, 0, 30e-3), look=(0, 0.2, -1), up=(0, 1, 0), det_distance=0.3, pixels=(256, 256), pitch=50e-6)
+    em = domain.sightline_emission(cam, wavelengths=[532e-9])           # or sightlines.sightline_emission(domain, cam, ...)
+    em.intensity, em.optical_depth, em.transmission                     # (n_band, nu, nv)
+    em.column, em.chord, em.steps                                       # (nu, nv): integral of ne dl [m^-2], length in the box [m]
+    bl = sightlines.PointBacklighter(source=(0, 0, -20e-3), look=(0, 0, 1), up=(0, 1, 0), det_distance=0.5, pixels=(512, 512),
+                                     pitch=100e-6, radiance=[3e-7])
+    domain.sightline_emission(bl, table=opacity_table)
+    sightlines.Chords(origins, directions, toward=-1)                   # any lines: diodes, bolometers, spectrometer chords
+
+emission.self_emission and table_emission march columns parallel to a grid axis.  Here the same radiative-transfer recurrence,
+dI/ds = alpha (S - I), runs along half-lines from a point: a pinhole camera looks along lines that CONVERGE on the pinhole
+(perspective, magnification, a view from any direction without resampling the volume with rotated()), a point-projection
+backlighter (an X-pinch, a laser-driven foil) sends DIVERGING lines from its source through the plasma onto film.  Each line is
+clipped to the domain's box and sampled about `step` apart, the fields interpolated trilinearly at every sample, on the GPU
+(engine.sightlines -> sr_field_sightlines; include/synthray.h states the rule).  The node is self_emission's (wavelengths=: the
+NRL inverse-bremsstrahlung coefficient and Planck's source function) or table_emission's (table=: an OpacityTable).
+
+Not modelled: a finite pinhole or source size (every line is a single ray through a point), the cos^4 and solid-angle factors
+that turn radiance into film exposure, refraction of the light, the detector's response, a table's own ionisation (Z is the
+domain's); one GPU.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import engine
+from .emission import _omegas, _upload
+
+c = engine.c
+
+
+def _vec(name, v):
+    v = np.asarray(v, np.float64)
+    if v.shape != (3,) or not np.all(np.isfinite(v)):
+        raise ValueError(f"{name} must be three finite numbers, got {v!r}")
+    return v
+
+
+def frame(look, up):
+    """The detector's right-handed frame (x, y, l) for a viewing direction `look` and any `up` not parallel to it: l = look / |look|,
+    y = the part of up perpendicular to l, normalised, x = y cross l (so that x cross y = l)."""
+    look, up = _vec("look", look), _vec("up", up)
+    n = np.linalg.norm(look)
+    if n == 0:
+        raise ValueError("look must not be zero")
+    l = look / n
+    y = up - np.dot(up, l) * l
+    ny = np.linalg.norm(y)
+    if ny <= 1e-12 * max(np.linalg.norm(up), 1e-300):
+        raise ValueError("up must not be parallel to look")
+    y = y / ny
+    return np.cross(y, l), y, l
+
+
+def _morton(i, j):
+    """Bit-interleaved (Z-order) key of the non-negative integer pairs (i, j), i in the odd bits."""
+    key = np.zeros(np.shape(i), np.int64)
+    i, j = np.asarray(i, np.int64), np.asarray(j, np.int64)
+    for b in range(24):
+        key |= ((i >> b) & 1) << (2 * b + 1) | ((j >> b) & 1) << (2 * b)
+    return key
+
+
+def tile_order(nu, nv, tile=8):
+    """The order in which a (nu, nv) pixel grid is handed to the kernel: perm (nu*nv) int64, line k is pixel perm[k] = i*nv + j.
+    Pixels go in tiles of tile x tile (row-major inside a tile: 64 pixels, one wavefront per full tile), the tiles in Morton order,
+    so that the lines of a wavefront, and of the wavefronts that run together, pass through neighbouring cells.  Tiles cut by
+    the grid's edge are shorter; nothing is padded, so perm is a permutation of range(nu*nv)."""
+    i, j = (a.ravel() for a in np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij"))
+    inside = (i % tile) * tile + j % tile
+    return np.lexsort((inside, _morton(i // tile, j // tile))).astype(np.int64)
+
+
+class Chords:
+    """Any lines: origins and directions (3, N) [m] (a direction need not be a unit vector), toward = +1 where the light
+    travels along +direction, away from the origin (a source there), -1 where it travels towards the origin (a detector there).
+    backlight: (n_band, N), (n_band,) or a number: the radiance behind the far end of every line, or None."""
+
+    def __init__(self, origins, directions, toward, backlight=None):
+        self.origins, self.directions = np.array(origins, np.float64, ndmin=2), np.array(directions, np.float64, ndmin=2)
+        if self.origins.shape[0] != 3 or self.origins.ndim != 2 or self.directions.shape != self.origins.shape:
+            raise ValueError(f"origins and directions must both have shape (3, N), got {self.origins.shape} and {self.directions.shape}")
+        if toward not in (1, -1):
+            raise ValueError(f"toward must be +1 or -1, got {toward!r}")
+        self.toward = int(toward)
+        self.shape = (self.origins.shape[1],)
+        self.radiance = backlight
+
+    def lines(self):
+        """(origins (3, N), directions (3, N)) in the view's own order (pixel i*nv + j for a pixel grid)."""
+        return self.origins, self.directions
+
+    def order(self):
+        """The order the lines are handed to the kernel in (a permutation of range(N)), or None: as they are."""
+        return None
+
+    def backlight(self, n_band):
+        if self.radiance is None:
+            return None
+        r = np.asarray(self.radiance, np.float64)
+        n = int(np.prod(self.shape))
+        if r.ndim <= 1:
+            r = np.broadcast_to(r.reshape(-1, 1), (n_band, n)) if r.size in (1, n_band) else None
+        elif r.shape != (n_band, n):
+            r = None
+        if r is None:
+            raise ValueError(f"the backlight must be a number, one per band ({n_band}) or (n_band, N), got shape {np.shape(self.radiance)}")
+        return np.ascontiguousarray(r)
+
+
+class _PixelView(Chords):
+    """A flat detector of pixels = (nu, nv) pixels of size `pitch` [m]: pixel (i, j) has its centre at
+    centre + u_i*x + v_j*y with u_i = (i - (nu-1)/2)*pitch, v_j = (j - (nv-1)/2)*pitch and (x, y, l) = frame(look, up)."""
+
+    def __init__(self, point, look, up, det_distance, pixels, pitch, side, toward, radiance=None):
+        self.point = _vec("the pinhole / source", point)
+        self.x, self.y, self.l = frame(look, up)
+        self.det_distance, self.pitch = float(det_distance), float(pitch)
+        if not (np.isfinite(self.det_distance) and self.det_distance > 0 and np.isfinite(self.pitch) and self.pitch > 0):
+            raise ValueError("det_distance and pitch must be finite and positive")
+        nu, nv = (int(m) for m in pixels)
+        if nu < 1 or nv < 1:
+            raise ValueError(f"pixels must be two positive counts, got {pixels!r}")
+        self.shape, self.toward, self.radiance = (nu, nv), toward, radiance
+        self.u = (np.arange(nu) - (nu - 1) / 2) * self.pitch
+        self.v = (np.arange(nv) - (nv - 1) / 2) * self.pitch
+        self._side = side
+
+    def pixel_centres(self):
+        """(3, nu, nv) [m]."""
+        centre = self.point + self._side * self.det_distance * self.l
+        return (centre[:, None, None] + self.x[:, None, None] * self.u[None, :, None] + self.y[:, None, None] * self.v[None, None, :])
+
+    def lines(self):
+        pix = self.pixel_centres().reshape(3, -1)
+        o = np.broadcast_to(self.point[:, None], pix.shape)
+        return np.ascontiguousarray(o), self._side * (pix - o)
+
+    def order(self):
+        return tile_order(*self.shape)
+
+    def magnification(self, object_distance):
+        """Image size / object size for an object plane object_distance [m] in front of the pinhole / source along look."""
+        return self.det_distance / float(object_distance)
+
+
+class PinholeCamera(_PixelView):
+    """An ideal pinhole at `pinhole` looking along `look`, its detector det_distance BEHIND it: pixel (i, j) has its centre at
+    pinhole - l*det_distance + u_i*x + v_j*y, its line starts at the pinhole with d = pinhole - pixel (out into the scene) and the
+    light travels towards the pinhole (toward = -1).  The image is inverted, as a pinhole's is: the object point pinhole + s*l + a*x
+    + b*y lands at (u, v) = -(a, b) * det_distance / s.  look and up are any two non-parallel vectors: oblique views need no
+    rotated().  magnification(object_distance) = det_distance / object_distance."""
+
+    def __init__(self, pinhole, look, up, det_distance, pixels, pitch):
+        super().__init__(pinhole, look, up, det_distance, pixels, pitch, side=-1, toward=-1)
+        self.pinhole = self.point
+
+
+class PointBacklighter(_PixelView):
+    """A point source at `source` shining along `look` onto a detector det_distance away: pixel (i, j) has its centre at
+    source + l*det_distance + u_i*x + v_j*y, its line starts at the source with d = pixel - source and the light travels away
+    from the source (toward = +1).  radiance: the source's spectral radiance per band (a number, or one per band) -- the
+    backlight of every line.  magnification(object_distance) = det_distance / object_distance (point projection)."""
+
+    def __init__(self, source, look, up, det_distance, pixels, pitch, radiance):
+        super().__init__(source, look, up, det_distance, pixels, pitch, side=+1, toward=+1, radiance=radiance)
+        self.source = self.point
+
+
+class SightlineEmission:
+    """What the lines of one view see.  intensity [W m^-2 sr^-1 (rad/s)^-1, spectral radiance per unit angular frequency] and
+    optical_depth are (n_band,) + view.shape -- (n_band, nu, nv) for a pixel grid, (n_band, N) for Chords; column (the integral
+    of ne dl [m^-2]), chord (the length inside the domain's box [m]; 0: the line misses it) and steps (samples marched) are
+    view.shape.  Bands: wavelengths [m] always; photon_energy [eV] and, where the table has them, edges ((n_band, 2), eV) and
+    band_radiance for a table (emission.TableEmission's)."""
+
+    def __init__(self, view, intensity, optical_depth, column, chord, steps, wavelengths, photon_energy=None, edges=None):
+        self.view = view
+        self.intensity, self.optical_depth = np.asarray(intensity, np.float64), np.asarray(optical_depth, np.float64)
+        self.column, self.chord, self.steps = np.asarray(column, np.float64), np.asarray(chord, np.float64), np.asarray(steps, np.int32)
+        self.wavelengths = np.atleast_1d(np.asarray(wavelengths, np.float64))
+        self.photon_energy = None if photon_energy is None else np.atleast_1d(np.asarray(photon_energy, np.float64))
+        self.edges = None if edges is None else np.asarray(edges, np.float64).reshape(len(self.wavelengths), 2)
+        want = (len(self.wavelengths),) + tuple(view.shape)
+        if self.intensity.shape != want or self.optical_depth.shape != want:
+            raise ValueError(f"the maps have shapes {self.intensity.shape} and {self.optical_depth.shape}, the bands and the view give {want}")
+
+    @property
+    def transmission(self):
+        """exp(-optical_depth): what a backlight keeps."""
+        return np.exp(-self.optical_depth)
+
+    @property
+    def band_radiance(self):
+        if self.edges is None:
+            raise ValueError("no band edges: band_radiance needs a table with the bands' widths")
+        d_omega = (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
+        return self.intensity * d_omega.reshape((-1,) + (1,) * (self.intensity.ndim - 1))
+
+
+def default_step(domain):
+    """Half the smallest cell edge of the domain's grid as the device holds it (float32 coordinates)."""
+    return 0.5 * min(float(np.min(np.diff(np.float64(np.float32(a))))) for a in (domain.x, domain.y, domain.z))
+
+
+def sightline_emission(domain, view, wavelengths=None, table=None, step=None, max_steps=None, fields=None):
+    """What `view` (a PinholeCamera, a PointBacklighter or Chords) sees of a domain of either API generation: a SightlineEmission.
+    Exactly one of wavelengths (up to 4 [m]: self_emission's NRL node) and table (an utils.eos_opacity.OpacityTable:
+    table_emission's node, one band per band of the table).  step [m]: the target sample spacing along a line, by default half the
+    smallest cell edge; max_steps: the most samples a line gets (a longer line is sampled more coarsely), by default
+    4 * (nx + ny + nz).  The domain needs external_Te() and external_Z(); its fields are uploaded by self_emission's rules, and
+    fields= (a fields.SourceFields of the domain) keeps them across calls.  A pixel grid's lines go to the kernel in 8x8 tiles in
+    Morton order (tile_order) and the maps come back in pixel order.  Not modelled: a finite pinhole or source, the cos^4 and
+    solid-angle factors of a film's exposure, refraction, the detector's response, a table's own ionisation; one GPU."""
+    if (wavelengths is None) == (table is None):
+        raise ValueError("exactly one of wavelengths (the NRL node) and table (an OpacityTable) must be given")
+    if not all(hasattr(view, name) for name in ("lines", "order", "backlight", "toward", "shape")):
+        raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
+    if table is None:
+        lam, omegas = _omegas(wavelengths)
+        kw, n_band = {"omegas": omegas}, len(lam)
+    else:
+        for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
+            if not hasattr(table, name):
+                raise ValueError(f"table must be an OpacityTable (utils.eos_opacity): it has no {name}")
+        kw, n_band = {"table": table}, len(np.atleast_1d(table.photon_energy))
+    step = default_step(domain) if step is None else float(step)
+    max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
+    o, d = view.lines()
+    back = view.backlight(n_band)
+    perm = view.order()
+    if perm is not None:
+        o, d = o[:, perm], d[:, perm]
+        back = None if back is None else back[:, perm]
+    res = _upload(domain, fields, lambda ne, Te, Z: engine.sightlines(ne, Te, Z, o, d, toward=view.toward, step=step, max_steps=max_steps,
+                                                                     backlight=back, **kw))
+
+    def place(a):  # kernel order -> the view's order and shape
+        if perm is not None:
+            out = np.empty_like(a)
+            out[..., perm] = a
+            a = out
+        return a.reshape(a.shape[:-1] + tuple(view.shape))
+
+    maps = {k: place(v) for k, v in res.items()}
+    if table is None:
+        return SightlineEmission(view, maps["intensity"], maps["optical_depth"], maps["column"], maps["chord"], maps["steps"], lam)
+    e_ph = np.atleast_1d(np.asarray(table.photon_energy, np.float64))
+    return SightlineEmission(view, maps["intensity"], maps["optical_depth"], maps["column"], maps["chord"], maps["steps"],
+                             2 * np.pi * engine.HBAR * c / (engine.E_CHARGE * e_ph), e_ph, getattr(table, "edges", None))

@@ -1,12 +1,14 @@
 """Registers, spills, LDS and scratch of every kernel of the library, from the compiler's own metadata:
     hipcc -S --cuda-device-only (the Makefile's flags) on each .hip file, then the amdhsa.kernels table of the assembly.
-    python tools/kernel_resources.py [> profiles/r04_kernel_resources.txt]"""
+    python tools/kernel_resources.py [> profiles/r04_kernel_resources.txt]
+    python tools/kernel_resources.py sightlines.hip emission_table.hip      # these files instead of the default list"""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "synthpy_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-munsafe-fp-atomics",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CS, "-S", "--cuda-device-only"] + sys.argv[1:]
+         "-I" + os.path.join(ROOT, "include"), "-I" + CS, "-S", "--cuda-device-only"] + [a for a in sys.argv[1:] if not a.endswith(".hip")]
+SOURCES = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["trace.hip", "deposit.hip", "volume.hip", "field.hip", "beam.hip", "comm.hip"]
 
 
 def demangle(names):
@@ -20,7 +22,7 @@ def demangle(names):
 print("# hipcc -S --cuda-device-only with the Makefile's flags; amdhsa.kernels metadata.  VGPR = .vgpr_count (the unified count, AGPRs included);")
 print("# 'spilled VGPR' with 0 bytes of scratch = parked in AGPRs (v_accvgpr_write / _read), not in memory")
 print(f"# {'kernel':<70s} VGPR  AGPR  SGPR  spilled VGPR / SGPR   LDS (static)  scratch B/lane   waves/SIMD by VGPRs")
-for src in ("trace.hip", "deposit.hip", "volume.hip", "field.hip", "beam.hip", "comm.hip"):
+for src in SOURCES:
     with tempfile.TemporaryDirectory() as d:
         s = os.path.join(d, "a.s")
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", s, os.path.join(CS, src)], check=True, capture_output=True)
