@@ -325,6 +325,34 @@ int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const sr_field *
                         const double *backlight /* or NULL */, double *I, double *tau, double *column /* or NULL */,
                         double *chord /* or NULL */, int32_t *steps /* or NULL */, double *kernel_ms);
 
+/* ---- sightline spectra: many frequencies along each chord ----------------------------------------
+ * sr_field_sightlines for a spectrum: n_freq frequencies (1..SR_MAX_FREQS) along every line in one call -- a spectrometer chord's
+ * continuum, the photon-energy groups of an opacity table, a filtered diode.  THE RULE IS sr_field_sightlines' (the section
+ * above: clip, miss, steps, march, sample, gather, node, update, NaN behaviour, what is not modelled), with "per band" read as
+ * "per frequency": for every line i and frequency f, I[i][f] and tau[i][f] are the same bits sr_field_sightlines returns for line
+ * i with frequency f as one of its bands, and column, chord and steps are the same bits too (sightline_spectra.hip is compiled with
+ * -ffp-contract=off from the same inline functions, and visits a line's samples in the same order per frequency).  The differences:
+ *   frequencies  omega, e_ph and c_omega are HOST arrays (n_freq), as sr_emission_params' per band; with a table omega is ignored and
+ *                may be NULL, and table->LA, table->LE are (n_freq, nT, nD): one band of the table per frequency.
+ *   layout       I, tau and backlight are HOST arrays (n, n_freq), float64, C order: a line's spectrum is contiguous.
+ *   params       sr_spectra_params carries toward, max_steps, step and the uniform Te, Z of sr_sightline_params.
+ * Arguments are checked before the device is touched: everything sr_field_sightlines checks; a NULL e_ph or c_omega; a NULL omega
+ * without a table; n_freq outside 1..SR_MAX_FREQS; an omega (table NULL) that is not finite and positive, a non-finite e_ph or
+ * c_omega; a table whose packed size, or an n times the frequency tiles of a line, that does not fit the launch's 32-bit counts (an
+ * error, not a cap).  n == 0 succeeds and writes nothing. */
+#define SR_MAX_FREQS 16384
+typedef struct {
+  int32_t toward;      /* +1 | -1, as sr_sightline_params                                                    */
+  int32_t max_steps;   /* >= 1                                                                               */
+  double step;         /* target sample spacing [m], finite, > 0                                            */
+  double Te, Z;        /* the uniform field values where the handle is NULL                                  */
+} sr_spectra_params;
+int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *table /* or NULL */,
+                               const sr_spectra_params *p, int64_t n, const double *origin, const double *dir, int32_t n_freq,
+                               const double *omega, const double *e_ph, const double *c_omega,
+                               const double *backlight /* (n, n_freq) or NULL */, double *I, double *tau /* (n, n_freq) */,
+                               double *column, double *chord, int32_t *steps /* (n), may be NULL */, double *kernel_ms);
+
 /* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
  * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
  * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be

@@ -119,6 +119,18 @@ class DomainExtras:
 
         return sightline_emission(self, view, wavelengths=wavelengths, table=table, step=step, max_steps=max_steps)
 
+    def sightline_spectra(self, view, wavelengths=None, photon_energies=None, table=None, step=None, max_steps=None):
+        """The spectrum every line of a sightlines.Chords, PinholeCamera or PointBacklighter sees of this domain: sightline_emission
+        at many frequencies (up to 16384) in one call, a GPU lane per frequency -- a sightlines.SightlineSpectra.  Exactly one of
+        wavelengths [m], photon_energies [eV] (the NRL node, which holds only for hbar*omega <~ Te) and table (an
+        utils.eos_opacity.SpectralOpacityTable: one frequency per group).  Needs external_Te() and external_Z().  Not modelled: a
+        finite pinhole or source, the cos^4 and solid-angle factors of a film's exposure, refraction, the detector's response
+        beyond SightlineSpectra.signal, a table's own ionisation, line shapes and Doppler shifts; one GPU."""
+        from .sightlines import sightline_spectra
+
+        return sightline_spectra(self, view, wavelengths=wavelengths, photon_energies=photon_energies, table=table, step=step,
+                                 max_steps=max_steps)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
         from .utils.handle_filetypes import export_scalar_field

@@ -76,6 +76,13 @@ class SightlineParams(C.Structure):
                 ("c_omega", C.c_double * MAX_BANDS), ("Te", C.c_double), ("Z", C.c_double)]
 
 
+MAX_FREQS = 16384  # SR_MAX_FREQS
+
+
+class SpectraParams(C.Structure):
+    _fields_ = [("toward", C.c_int32), ("max_steps", C.c_int32), ("step", C.c_double), ("Te", C.c_double), ("Z", C.c_double)]
+
+
 class PushParams(C.Structure):
     _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("max_steps", C.c_int32), ("axis", C.c_int32),
                 ("det_pos", C.c_double), ("hit_scale", C.c_double)]
@@ -158,6 +165,8 @@ SYMBOLS = {
                                      C.POINTER(C.c_double)]),
     "sr_field_sightlines": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(SightlineParams), _i64, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_sightline_spectra": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(SpectraParams), _i64, _vp, _vp, C.c_int32,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),

@@ -1,0 +1,113 @@
+// What the two sightline kernels must share so that they return the same bits (include/synthray.h's sightlines section: clip,
+// steps, sample, gather): sightlines.hip (k_sightlines: a line per lane, up to SR_MAX_BANDS bands) and sightline_spectra.hip
+// (k_sightline_spectra: a frequency per lane).  Included inside the including unit's anonymous namespace, after emission_march.inc
+// (EmArgs).
+
+struct LineArgs {
+  sr::FieldGrid f;      // lo, hi: the box
+  const double *o, *d;  // (3, n) origins and directions
+  double *column, *chord;
+  int32_t *steps;
+  int64_t n;
+  int max_steps;
+  double step;
+};
+
+// One sample of a line: where it lies in its cell, and the corners of the fields there (read, not yet blended)
+template <typename T, bool HAS_TE, bool HAS_Z>
+struct Sample {
+  bool in;
+  double ux, wx, w00, w01, w10, w11;
+  sr::Corners<T> ne, Te, Z;
+};
+
+template <typename T, bool HAS_TE, bool HAS_Z>
+__device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, double px, double py,
+                                      double pz, Sample<T, HAS_TE, HAS_Z> &s) {
+  int ci = 0, cj = 0, ck = 0;
+  double wx = 0, wy = 0, wz = 0;
+  const bool in_x = sr::locate_in<true>(f.g[0], f.n[0], f.inv_h[0], f.lo[0], f.hi[0], px, ci, wx);
+  const bool in_y = sr::locate_in<true>(f.g[1], f.n[1], f.inv_h[1], f.lo[1], f.hi[1], py, cj, wy);
+  const bool in_z = sr::locate_in<true>(f.g[2], f.n[2], f.inv_h[2], f.lo[2], f.hi[2], pz, ck, wz);
+  s.in = in_x && in_y && in_z;
+  if (s.in) {  // locate_in leaves every cell index in [0, n - 2]: the eight corners are nodes of the field
+    const double uy = 1.0 - wy, uz = 1.0 - wz;
+    s.ux = 1.0 - wx;
+    s.wx = wx;
+    s.w00 = uy * uz;
+    s.w01 = uy * wz;
+    s.w10 = wy * uz;
+    s.w11 = wy * wz;
+    s.ne = sr::corners_load(static_cast<const T *>(A.ne), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_TE) s.Te = sr::corners_load(static_cast<const T *>(A.Te), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_Z) s.Z = sr::corners_load(static_cast<const T *>(A.Z), 1, 0, sx, sy, ci, cj, ck);
+  }
+}
+
+// the blended (ne, Te, Z) of a fetched sample; outside the box (within rounding of a face): ne = 0, which either node takes for dark
+template <typename T, bool HAS_TE, bool HAS_Z>
+__device__ __forceinline__ void blend_sample(const EmArgs &A, const Sample<T, HAS_TE, HAS_Z> &s, double &ne, double &Te, double &Z) {
+  ne = 0.0, Te = A.uTe, Z = A.uZ;
+  if (s.in) {
+    ne = sr::corners_blend(s.ne, s.ux, s.wx, s.w00, s.w01, s.w10, s.w11);
+    if (HAS_TE) Te = sr::corners_blend(s.Te, s.ux, s.wx, s.w00, s.w01, s.w10, s.w11);
+    if (HAS_Z) Z = sr::corners_blend(s.Z, s.ux, s.wx, s.w00, s.w01, s.w10, s.w11);
+  }
+}
+
+// The clip and the steps of line i
+struct Line {
+  double o0, o1, o2, d0, d1, d2;
+  bool hit;
+  int n;                     // samples; 0: a miss
+  double t0, chord, dt, h;   // sample k lies at t0 + (k + 0.5)*dt
+};
+
+__device__ __forceinline__ Line line_of(const LineArgs &L, int64_t i) {
+  const int64_t N = L.n;
+  Line l;
+  l.o0 = L.o[i], l.o1 = L.o[N + i], l.o2 = L.o[2 * N + i];
+  l.d0 = L.d[i], l.d1 = L.d[N + i], l.d2 = L.d[2 * N + i];
+  // clip: the half-line t >= 0 against the box, axis by axis
+  double t0 = 0.0, t1 = HUGE_VAL;
+  bool hit = true;
+  auto clip = [&](double o, double d, double lo, double hi) {
+    if (d == 0.0) {
+      hit = hit && lo <= o && o <= hi;
+    } else {
+      const double ta = (lo - o) / d, tb = (hi - o) / d;
+      const double tn = ta < tb ? ta : tb, tf = ta < tb ? tb : ta;
+      t0 = t0 > tn ? t0 : tn;
+      t1 = t1 < tf ? t1 : tf;
+    }
+  };
+  clip(l.o0, l.d0, L.f.lo[0], L.f.hi[0]);
+  clip(l.o1, l.d1, L.f.lo[1], L.f.hi[1]);
+  clip(l.o2, l.d2, L.f.lo[2], L.f.hi[2]);
+  l.hit = hit && t1 > t0;
+  l.n = 0;
+  l.t0 = t0;
+  l.chord = l.dt = l.h = 0.0;
+  if (l.hit) {
+    const double len = sqrt((l.d0 * l.d0 + l.d1 * l.d1) + l.d2 * l.d2);
+    l.chord = (t1 - t0) * len;
+    const double q = l.chord / L.step;
+    if (!(q < (double)L.max_steps)) {  // q >= max_steps, or a NaN q (a direction whose squares underflow)
+      l.n = L.max_steps;
+    } else {
+      l.n = (int)ceil(q);
+      l.n = l.n < 1 ? 1 : l.n;
+    }
+    l.dt = (t1 - t0) / (double)l.n;
+    l.h = l.chord / (double)l.n;
+  }
+  return l;
+}
+
+// the cell search and the corner reads of sample k of a line
+template <typename T, bool HAS_TE, bool HAS_Z>
+__device__ __forceinline__ void fetch_sample(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, const Line &l, int k,
+                                             Sample<T, HAS_TE, HAS_Z> &s) {
+  const double t = l.t0 + ((double)k + 0.5) * l.dt;
+  fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, l.o0 + l.d0 * t, l.o1 + l.d1 * t, l.o2 + l.d2 * t, s);
+}

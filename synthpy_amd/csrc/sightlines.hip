@@ -21,46 +21,7 @@
 namespace {
 #include "table_node.inc"
 
-struct LineArgs {
-  sr::FieldGrid f;      // lo, hi: the box
-  const double *o, *d;  // (3, n) origins and directions
-  double *column, *chord;
-  int32_t *steps;
-  int64_t n;
-  int max_steps;
-  double step;
-};
-
-// One sample of a line: where it lies in its cell, and the corners of the fields there (read, not yet blended)
-template <typename T, bool HAS_TE, bool HAS_Z>
-struct Sample {
-  bool in;
-  double ux, wx, w00, w01, w10, w11;
-  sr::Corners<T> ne, Te, Z;
-};
-
-template <typename T, bool HAS_TE, bool HAS_Z>
-__device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, double px, double py,
-                                      double pz, Sample<T, HAS_TE, HAS_Z> &s) {
-  int ci = 0, cj = 0, ck = 0;
-  double wx = 0, wy = 0, wz = 0;
-  const bool in_x = sr::locate_in<true>(f.g[0], f.n[0], f.inv_h[0], f.lo[0], f.hi[0], px, ci, wx);
-  const bool in_y = sr::locate_in<true>(f.g[1], f.n[1], f.inv_h[1], f.lo[1], f.hi[1], py, cj, wy);
-  const bool in_z = sr::locate_in<true>(f.g[2], f.n[2], f.inv_h[2], f.lo[2], f.hi[2], pz, ck, wz);
-  s.in = in_x && in_y && in_z;
-  if (s.in) {  // locate_in leaves every cell index in [0, n - 2]: the eight corners are nodes of the field
-    const double uy = 1.0 - wy, uz = 1.0 - wz;
-    s.ux = 1.0 - wx;
-    s.wx = wx;
-    s.w00 = uy * uz;
-    s.w01 = uy * wz;
-    s.w10 = wy * uz;
-    s.w11 = wy * wz;
-    s.ne = sr::corners_load(static_cast<const T *>(A.ne), 1, 0, sx, sy, ci, cj, ck);
-    if (HAS_TE) s.Te = sr::corners_load(static_cast<const T *>(A.Te), 1, 0, sx, sy, ci, cj, ck);
-    if (HAS_Z) s.Z = sr::corners_load(static_cast<const T *>(A.Z), 1, 0, sx, sy, ci, cj, ck);
-  }
-}
+#include "sightline_march.inc"  // LineArgs, Sample, fetch, the clip and the step count (shared with sightline_spectra.hip)
 
 template <typename T, bool HAS_TE, bool HAS_Z, int NB, typename P>
 __global__ void __launch_bounds__(256) k_sightlines(EmArgs A, LineArgs L, typename P::Args X) {
@@ -68,65 +29,29 @@ __global__ void __launch_bounds__(256) k_sightlines(EmArgs A, LineArgs L, typena
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= L.n) return;
   const int64_t N = L.n;
-  const double o0 = L.o[i], o1 = L.o[N + i], o2 = L.o[2 * N + i];
-  const double d0 = L.d[i], d1 = L.d[N + i], d2 = L.d[2 * N + i];
   double I[NB], tau[NB];
 #pragma unroll
   for (int k = 0; k < NB; ++k) {
     I[k] = A.back ? A.back[k * N + i] : 0.0;
     tau[k] = 0.0;
   }
-  // clip: the half-line t >= 0 against the box, axis by axis
-  double t0 = 0.0, t1 = HUGE_VAL;
-  bool hit = true;
-  auto clip = [&](double o, double d, double lo, double hi) {
-    if (d == 0.0) {
-      hit = hit && lo <= o && o <= hi;
-    } else {
-      const double ta = (lo - o) / d, tb = (hi - o) / d;
-      const double tn = ta < tb ? ta : tb, tf = ta < tb ? tb : ta;
-      t0 = t0 > tn ? t0 : tn;
-      t1 = t1 < tf ? t1 : tf;
-    }
-  };
-  clip(o0, d0, L.f.lo[0], L.f.hi[0]);
-  clip(o1, d1, L.f.lo[1], L.f.hi[1]);
-  clip(o2, d2, L.f.lo[2], L.f.hi[2]);
-  hit = hit && t1 > t0;
-  double column = 0.0, chord = 0.0;
-  int n = 0;
-  if (hit) {
-    const double len = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
-    chord = (t1 - t0) * len;
-    const double q = chord / L.step;
-    if (!(q < (double)L.max_steps)) {  // q >= max_steps, or a NaN q (a direction whose squares underflow)
-      n = L.max_steps;
-    } else {
-      n = (int)ceil(q);
-      n = n < 1 ? 1 : n;
-    }
-    const double dt = (t1 - t0) / (double)n, h = chord / (double)n;
+  const Line l = line_of(L, i);
+  const double chord = l.chord;
+  const int n = l.n;
+  double column = 0.0;
+  if (l.hit) {
+    const double h = l.h;
     const int64_t sy = L.f.n[2], sx = (int64_t)L.f.n[1] * sy;
     const int k0 = A.toward > 0 ? 0 : n - 1, dk = A.toward > 0 ? 1 : -1;
     Sample<T, HAS_TE, HAS_Z> cur{}, nxt{};
-    {
-      const double t = t0 + ((double)k0 + 0.5) * dt;
-      fetch<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, o0 + d0 * t, o1 + d1 * t, o2 + d2 * t, cur);
-    }
+    fetch_sample<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, l, k0, cur);
     for (int m = 0; m < n; ++m) {
       // this sample's values (its reads were issued a sample ago) ...
-      double ne = 0.0, Te = A.uTe, Z = A.uZ;
-      if (cur.in) {
-        ne = sr::corners_blend(cur.ne, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
-        if (HAS_TE) Te = sr::corners_blend(cur.Te, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
-        if (HAS_Z) Z = sr::corners_blend(cur.Z, cur.ux, cur.wx, cur.w00, cur.w01, cur.w10, cur.w11);
-      }
+      double ne, Te, Z;
+      blend_sample<T, HAS_TE, HAS_Z>(A, cur, ne, Te, Z);
       // ... the next sample's cell and corner reads, in flight during this sample's node arithmetic ...
       nxt.in = false;
-      if (m + 1 < n) {
-        const double t = t0 + ((double)(k0 + (m + 1) * dk) + 0.5) * dt;
-        fetch<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, o0 + d0 * t, o1 + d1 * t, o2 + d2 * t, nxt);
-      }
+      if (m + 1 < n) fetch_sample<T, HAS_TE, HAS_Z>(A, L.f, sx, sy, l, k0 + (m + 1) * dk, nxt);
       // ... the node and the update; a sample outside the box (within rounding of a face) has ne = 0, which either node takes
       // for dark: alpha = S = 0
       double al[NB], S[NB];

@@ -44,11 +44,43 @@ __device__ __forceinline__ void locate(const double *L, int n, int s0, double x,
   f = nmin(nmax((x - l0) / (l1 - l0), 0.0), 1.0);
 }
 
-__device__ __forceinline__ double bilinear(const double *T, int o, int nD, double ft, double fd) {
-  const double t00 = T[o], t01 = T[o + 1], t10 = T[o + nD], t11 = T[o + nD + 1];
+// sd, st: the strides of the density and the temperature index (1 and nD band by band, int; F and nD*F where the F groups are
+// innermost, int64_t: nT*nD*F passes 2^31)
+template <typename Ix>
+__device__ __forceinline__ double bilinear(const double *T, Ix o, Ix sd, Ix st, double ft, double fd) {
+  const double t00 = T[o], t01 = T[o + sd], t10 = T[o + st], t11 = T[o + st + sd];
   const double p0 = t00 + fd * (t01 - t00);
   const double p1 = t10 + fd * (t11 - t10);
   return p0 + ft * (p1 - p0);
+}
+
+// A node in two parts, as nrl_node.inc's: what every band shares (the two searches, dark, rho), then one band from its
+// interpolated la = l(LA) and le = l(LE) (le is not used where has_le is false).
+struct TableTerms {
+  bool dark;  // Te <= 0, ne <= 0 or Z <= 0: alpha = S = 0
+  int o;      // i*nD + j: the cell's first corner in a (nT, nD) band
+  double Te, ft, fd, rho;
+};
+__device__ __forceinline__ TableTerms table_terms(const double *LT, int nT, int sT, const double *LD, int nD, int sD, double m_ion,
+                                                  double ne, double Te, double Z) {
+  TableTerms t;
+  t.dark = Te <= 0.0 || ne <= 0.0 || Z <= 0.0;
+  t.Te = Te;
+  const double ni = (ne * 1e-6) / Z;
+  int i, j;
+  locate(LT, nT, sT, log(Te), i, t.ft);
+  locate(LD, nD, sD, log(ni), j, t.fd);
+  t.o = i * nD + j;
+  t.rho = ni * m_ion;
+  return t;
+}
+__device__ __forceinline__ void table_band(const TableTerms &t, double la, double le, bool has_le, double e_ph, double c_omega,
+                                           double &al, double &S) {
+  const double planck = c_omega / expm1(e_ph / t.Te);
+  double s = planck;
+  if (has_le) s = exp(le - la) * planck;
+  al = t.dark ? 0.0 : (exp(la) * t.rho) * 100.0;
+  S = t.dark ? 0.0 : s;
 }
 
 template <bool LDS>
@@ -82,22 +114,13 @@ struct TableNode {
 
   template <int NB>
   __device__ __forceinline__ void eval(const EmArgs &A, double ne, double Te, double Z, double (&al)[NB], double (&S)[NB]) const {
-    const bool dark = Te <= 0.0 || ne <= 0.0 || Z <= 0.0;
-    const double ni = (ne * 1e-6) / Z;
-    int i, j;
-    double ft, fd;
-    locate(LT, nT, sT, log(Te), i, ft);
-    locate(LD, nD, sD, log(ni), j, fd);
-    const int o = i * nD + j, band = nT * nD;
-    const double rho = ni * m_ion;
+    const TableTerms t = table_terms(LT, nT, sT, LD, nD, sD, m_ion, ne, Te, Z);
+    const int band = nT * nD;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-      const double la = bilinear(LA + b * band, o, nD, ft, fd);
-      const double planck = A.c_omega[b] / expm1(A.e_ph[b] / Te);
-      double s = planck;
-      if (has_le) s = exp(bilinear(LE + b * band, o, nD, ft, fd) - la) * planck;
-      al[b] = dark ? 0.0 : (exp(la) * rho) * 100.0;
-      S[b] = dark ? 0.0 : s;
+      const double la = bilinear(LA + b * band, t.o, 1, nD, t.ft, t.fd);
+      const double le = has_le ? bilinear(LE + b * band, t.o, 1, nD, t.ft, t.fd) : 0.0;
+      table_band(t, la, le, has_le, A.e_ph[b], A.c_omega[b], al[b], S[b]);
     }
   }
 };

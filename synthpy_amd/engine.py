@@ -603,6 +603,65 @@ def sightlines(ne, Te, Z, origins, directions, *, omegas=None, table=None, towar
     return {k: out[k] for k in _SIGHT_WANT if k in want}
 
 
+def spectrum_constants(omegas):
+    """(omega, e_ph, c_omega), float64 (n_freq): emission_params' per-band constants for any number of frequencies, formed by the
+    same expressions on the same Python floats, so that a frequency has the bits it has as a band of engine.sightlines."""
+    om = np.atleast_1d(f64(omegas))
+    if om.ndim != 1:
+        raise ValueError(f"omegas must be a scalar or one-dimensional, got shape {om.shape}")
+    w = om.tolist()
+    return om, f64([HBAR * v / E_CHARGE for v in w]), f64([HBAR * v ** 3 / (4 * np.pi ** 3 * c ** 2) for v in w])
+
+
+def sightline_spectra(ne, Te, Z, origins, directions, *, omegas=None, table=None, toward, step, max_steps, backlight=None,
+                      want=_SIGHT_WANT):
+    """engine.sightlines for a spectrum: 1 to _ffi.MAX_FREQS (16384) frequencies along every line in one call, a GPU lane per
+    frequency (sr_field_sightline_spectra; include/synthray.h states the rule by reference to sr_field_sightlines').  Lines, fields,
+    uniform Te / Z, toward, step, max_steps and want are engine.sightlines'.  Exactly one of omegas (angular frequencies [rad/s]:
+    the NRL node, trustworthy for hbar*omega <~ Te) and table (an utils.eos_opacity.SpectralOpacityTable, or an OpacityTable: one
+    frequency per group, at its photon_energy).  backlight: (n, n_freq) behind the far end of every line, or None.  Returns
+    engine.sightlines' dict with "intensity" and "optical_depth" shaped (n, n_freq) -- a line's spectrum is contiguous -- whose
+    every element has the bits engine.sightlines returns for that line with that frequency as one of its (up to 4) bands; "column",
+    "chord", "steps" (n).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: what engine.sightlines does not model; line
+    shapes, Doppler shifts, group-integrated Planck functions; one GPU."""
+    h_ne = _handle("ne", ne)
+    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
+    if (omegas is None) == (table is None):
+        raise ValueError("exactly one of omegas (the NRL node) and table (a SpectralOpacityTable) must be given")
+    unknown = set(want) - set(_SIGHT_WANT)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT}")
+    o, d = f64(origins), f64(directions)
+    if o.ndim != 2 or o.shape[0] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and directions must both have shape (3, n), got {o.shape} and {d.shape}")
+    n = o.shape[1]
+    t, keep = None, None
+    if table is not None:
+        t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
+        omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
+        if len(omegas) != keep[2].shape[0]:
+            raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
+    om, e_ph, c_om = spectrum_constants(omegas)
+    nf = len(om)
+    p = _ffi.SpectraParams()
+    p.toward, p.max_steps, p.step = int(toward), int(max_steps), float(step)
+    p.Te, p.Z = (0.0 if h else float(a) for h, a in zip(handles, (Te, Z)))
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != (n, nf):
+            raise ValueError(f"backlight has shape {backlight.shape}, the lines and the frequencies give {(n, nf)}")
+    I, tau = np.empty((n, nf)), np.empty((n, nf))
+    opt = {"column": np.empty(n) if "column" in want else None, "chord": np.empty(n) if "chord" in want else None,
+           "steps": np.empty(n, np.int32) if "steps" in want else None}
+    ms = C.c_double(0.0)
+    check(lib.sr_field_sightline_spectra(h_ne, *handles, None if t is None else C.byref(t), C.byref(p), n, ptr(o), ptr(d), nf,
+                                         None if t is not None else ptr(om), ptr(e_ph), ptr(c_om), ptr(backlight), ptr(I), ptr(tau),
+                                         ptr(opt["column"]), ptr(opt["chord"]), ptr(opt["steps"]), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    out = {"intensity": I, "optical_depth": tau, **opt}
+    return {k: out[k] for k in _SIGHT_WANT if k in want}
+
+
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
 _PUSH_WANT = ("sf", "hits", "steps", "flags")
 

@@ -181,3 +181,56 @@ class OpacityTable:
             photon_energy = np.sqrt(groups[0] * groups[-1])
         return cls(data["temperatures"], data["densities"], data["abs_opacity"], photon_energy, A,
                    emission=data.get("emiss_opacity"), edges=edges)
+
+
+class SpectralOpacityTable(OpacityTable):
+    """An OpacityTable of many photon-energy groups (1 to _ffi.MAX_FREQS = 16384 bands): what sr_field_sightline_spectra
+    interpolates, one group per frequency of a spectrum (sightlines.sightline_spectra, engine.sightline_spectra).  The members,
+    their units and their conditions are OpacityTable's, checked by OpacityTable itself four bands at a time, so a ValueError names
+    the offending member in its words; edges, when given, must be (n_band, 2).  The entries that take at most 4 bands
+    (table_emission, sightline_emission) do not take this table: bands(indices) gives them an ordinary OpacityTable of up to 4
+    chosen groups.  read_propaceos yields group MEANS only, as the reference's reader does: multigroup tables come from arrays."""
+
+    def __init__(self, temperatures, densities, absorption, photon_energy, A, emission=None, edges=None):
+        from .._ffi import MAX_BANDS, MAX_FREQS
+
+        absorption = np.array(absorption, np.float64)
+        if absorption.ndim == 2:
+            absorption = absorption[None]
+        if absorption.ndim != 3:
+            raise ValueError(f"absorption has shape {absorption.shape}, a table is (n_band, nT, nD)")
+        n_band = len(absorption)
+        if not 1 <= n_band <= MAX_FREQS:
+            raise ValueError(f"absorption must hold 1 to {MAX_FREQS} bands, got {n_band}")
+        photon_energy = np.array(photon_energy, np.float64, ndmin=1)
+        if photon_energy.shape != (n_band,):
+            raise ValueError(f"photon_energy must be {n_band} finite positive value(s), got shape {photon_energy.shape}")
+        if emission is not None:
+            emission = np.array(emission, np.float64)
+            emission = emission[None] if emission.ndim == 2 else emission
+            if emission.shape != absorption.shape:
+                raise ValueError(f"emission has shape {emission.shape}, absorption {absorption.shape}")
+        if edges is not None:
+            edges = np.array(edges, np.float64)
+            if edges.shape != (n_band, 2):
+                raise ValueError(f"edges must be ({n_band}, 2), got shape {edges.shape}")
+        parts = [OpacityTable(temperatures, densities, absorption[k:k + MAX_BANDS], photon_energy[k:k + MAX_BANDS], A,
+                              emission=None if emission is None else emission[k:k + MAX_BANDS],
+                              edges=None if edges is None else edges[k:k + MAX_BANDS]) for k in range(0, n_band, MAX_BANDS)]
+        self.temperatures, self.densities, self.A = parts[0].temperatures, parts[0].densities, parts[0].A
+        self.absorption = np.ascontiguousarray(absorption)
+        self.emission = None if emission is None else np.ascontiguousarray(emission)
+        self.photon_energy, self.edges = photon_energy, edges
+
+    def bands(self, indices):
+        """An ordinary OpacityTable of the chosen groups (up to 4 indices, or a slice), for the entries that take at most 4 bands."""
+        idx = np.arange(self.n_band)[indices].ravel()
+        return OpacityTable(self.temperatures, self.densities, self.absorption[idx], self.photon_energy[idx], self.A,
+                            emission=None if self.emission is None else self.emission[idx],
+                            edges=None if self.edges is None else self.edges[idx])
+
+    def packed(self):
+        """(LT, LD, LA, LE) with the groups innermost -- LA and LE (nT, nD, n_band), C order, the transposes of logs()' -- as
+        sr_field_sightline_spectra lays the table out for its kernel; LE is None for LTE."""
+        LT, LD, LA, LE = self.logs()
+        return LT, LD, np.ascontiguousarray(LA.transpose(1, 2, 0)), None if LE is None else np.ascontiguousarray(LE.transpose(1, 2, 0))
