@@ -1,18 +1,14 @@
 // Self-emission images: emission with self-absorption along a grid axis (sr_field_emission; include/synthray.h states the rule
 // every node, cell and column follows, operation for operation).  The march -- k_emission_z, k_emission_xy, the cell, the host's
-// staging, the NRL node's policy -- is emission_march.inc, shared with emission_table.hip and sightlines.hip; the NRL node is
-// nrl_node.inc, shared with wave.hip; this unit holds the entry.  No LDS.
+// staging and band checks, the NRL node's policy -- is emission_march.inc, shared with emission_table.hip and the two sightline
+// units; the NRL node is nrl_node.inc, shared with wave.hip; this unit holds the entry.  No LDS.
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_emission.py).
 #include "emission_march.inc"
 
 extern "C" int sr_field_emission(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p,
                                  const double *backlight, double *I, double *tau, double *kernel_ms) {
   SR_CHECK(p != nullptr && I != nullptr && tau != nullptr, "sr_field_emission: NULL argument");
-  SR_CHECK(p->n_band >= 1 && p->n_band <= SR_MAX_BANDS, "sr_field_emission: n_band must be 1..%d, got %d", SR_MAX_BANDS, p->n_band);
-  for (int b = 0; b < p->n_band; ++b) {
-    SR_CHECK(std::isfinite(p->omega[b]) && p->omega[b] > 0.0, "sr_field_emission: omega of band %d must be finite and positive", b);
-    SR_CHECK(std::isfinite(p->e_ph[b]) && std::isfinite(p->c_omega[b]), "sr_field_emission: non-finite e_ph or c_omega of band %d", b);
-  }
+  SR_RC(check_bands("sr_field_emission", "band", p->n_band, SR_MAX_BANDS, p->omega, p->e_ph, p->c_omega));
   if (int rc = check_fields("sr_field_emission", ne, Te, Z, p)) return rc;
   EmArgs A;
   size_t map_bytes = 0;

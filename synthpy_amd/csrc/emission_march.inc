@@ -1,5 +1,6 @@
 // The march of the self-emission images, shared by emission.hip (sr_field_emission: the NRL node) and emission_table.hip
-// (sr_field_emission_table: the tabulated node); include/synthray.h states the rule every node, cell and column follows.
+// (sr_field_emission_table: the tabulated node); include/synthray.h states the rule every node, cell and column follows.  The two
+// sightline units take EmArgs, the NRL policy and, of the host section at the end, check_bands and fill_fields.
 //
 // An ORDERED recurrence per column, I <- I*a + b cell by cell, where k_project's line integral is an unordered sum.  The fields are
 // C order (nx, ny, nz), so the two kinds of axis want two kernels; in both, consecutive lanes read consecutive addresses, every
@@ -224,12 +225,42 @@ void launch(const EmArgs &A, const typename P::Args &X, size_t lds_bytes, int ax
       has_te, has_z);
 }
 
-// The checks the two entries share (`who` names the entry in the error text), before the device is touched.
+// ---- host: what the entries share; `who` names the entry in the error text, every check runs before the device is touched.
+
+// The per-band constants of all four entries: n of them, 1..max; `what` is "band" or "frequency" (n_band, n_freq: its first four
+// letters).  omega is NULL where a table gives alpha and omega is not read.
+inline int check_bands(const char *who, const char *what, int n, int max, const double *omega, const double *e_ph,
+                       const double *c_omega) {
+  SR_CHECK(n >= 1 && n <= max, "%s: n_%.4s must be 1..%d, got %d", who, what, max, n);
+  for (int b = 0; b < n; ++b) {
+    SR_CHECK(!omega || (std::isfinite(omega[b]) && omega[b] > 0.0), "%s: omega of %s %d must be finite and positive", who, what, b);
+    SR_CHECK(std::isfinite(e_ph[b]) && std::isfinite(c_omega[b]), "%s: non-finite e_ph or c_omega of %s %d", who, what, b);
+  }
+  return SR_OK;
+}
+
+// The checks the two grid marches share.
 inline int check_fields(const char *who, const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_params *p) {
   SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
   SR_CHECK(p->axis >= 0 && p->axis <= 2, "%s: axis must be 0, 1 or 2, got %d", who, p->axis);
   SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
   return sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}});
+}
+
+// The field half of EmArgs (the grid marches and both sightline entries); n_band = 0 where the frequencies' constants live elsewhere.
+inline void fill_fields(EmArgs &A, const sr_field *ne, const sr_field *Te, const sr_field *Z, int toward, double uTe, double uZ,
+                        int n_band, const double *omega, const double *e_ph, const double *c_omega) {
+  A.ne = ne->data;
+  A.Te = Te ? Te->data : nullptr;
+  A.Z = Z ? Z->data : nullptr;
+  A.toward = toward;
+  for (int b = 0; b < n_band; ++b) {
+    A.omega[b] = omega[b];
+    A.e_ph[b] = e_ph[b];
+    A.c_omega[b] = c_omega[b];
+  }
+  A.uTe = uTe;
+  A.uZ = uZ;
 }
 
 // Scratch for the maps (+ `extra` bytes behind them: *extra_at), the kernel's arguments, the backlight's upload.
@@ -248,23 +279,13 @@ inline int prepare(const sr_field *ne, const sr_field *Te, const sr_field *Z, co
   if (backlight) carve.take(&A.back, (size_t)nb * ncol);
   carve.take(extra_at ? extra_at : &behind, extra);
   if (!carve.alloc()) return SR_ERR_HIP;
-  A.ne = ne->data;
-  A.Te = Te ? Te->data : nullptr;
-  A.Z = Z ? Z->data : nullptr;
+  fill_fields(A, ne, Te, Z, p->toward, p->Te, p->Z, nb, p->omega, p->e_ph, p->c_omega);
   A.g = ne->g[axis];
   A.n = ne->n[axis];
-  A.toward = p->toward;
   A.ncol = ncol;
   A.nv = axis == 0 ? ncol : nz;       // x: the (y, z) plane is one contiguous run; y: rows of nz, one per ix
   A.row_stride = axis == 0 ? 0 : ny * nz;
   A.plane_stride = axis == 0 ? ny * nz : nz;
-  for (int b = 0; b < nb; ++b) {
-    A.omega[b] = p->omega[b];
-    A.e_ph[b] = p->e_ph[b];
-    A.c_omega[b] = p->c_omega[b];
-  }
-  A.uTe = p->Te;
-  A.uZ = p->Z;
   if (backlight) SR_HIP(hipMemcpyAsync(const_cast<double *>(A.back), backlight, map_bytes, hipMemcpyHostToDevice, c.stream));
   return SR_OK;
 }

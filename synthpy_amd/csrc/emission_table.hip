@@ -19,11 +19,7 @@ extern "C" int sr_field_emission_table(const sr_field *ne, const sr_field *Te, c
                                        const sr_emission_params *p, const double *backlight, double *I, double *tau,
                                        double *kernel_ms) {
   SR_CHECK(p != nullptr && I != nullptr && tau != nullptr, "sr_field_emission_table: NULL argument");
-  SR_CHECK(p->n_band >= 1 && p->n_band <= SR_MAX_BANDS, "sr_field_emission_table: n_band must be 1..%d, got %d", SR_MAX_BANDS,
-           p->n_band);
-  for (int b = 0; b < p->n_band; ++b)
-    SR_CHECK(std::isfinite(p->e_ph[b]) && std::isfinite(p->c_omega[b]), "sr_field_emission_table: non-finite e_ph or c_omega of band %d",
-             b);
+  SR_RC(check_bands("sr_field_emission_table", "band", p->n_band, SR_MAX_BANDS, nullptr, p->e_ph, p->c_omega));  // omega is not read
   if (int rc = check_table("sr_field_emission_table", t, p->n_band)) return rc;
   if (int rc = check_fields("sr_field_emission_table", ne, Te, Z, p)) return rc;
 

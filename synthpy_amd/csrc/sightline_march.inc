@@ -1,7 +1,7 @@
 // What the two sightline kernels must share so that they return the same bits (include/synthray.h's sightlines section: clip,
 // steps, sample, gather): sightlines.hip (k_sightlines: a line per lane, up to SR_MAX_BANDS bands) and sightline_spectra.hip
-// (k_sightline_spectra: a frequency per lane).  Included inside the including unit's anonymous namespace, after emission_march.inc
-// (EmArgs).
+// (k_sightline_spectra: a frequency per lane); after the device code, the host code the two entries run around their kernels.
+// Included inside the including unit's anonymous namespace, after emission_march.inc (EmArgs).
 
 struct LineArgs {
   sr::FieldGrid f;      // lo, hi: the box
@@ -110,4 +110,73 @@ __device__ __forceinline__ void fetch_sample(const EmArgs &A, const sr::FieldGri
                                              Sample<T, HAS_TE, HAS_Z> &s) {
   const double t = l.t0 + ((double)k + 0.5) * l.dt;
   fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, l.o0 + l.d0 * t, l.o1 + l.d1 * t, l.o2 + l.d2 * t, s);
+}
+
+// ---- host: what sr_field_sightlines and sr_field_sightline_spectra do around their kernels (`who` names the entry in the error
+// text).  An entry keeps its kernel and dispatch, its table's packing and the checks only it has.
+
+// the march: before the table's checks
+inline int check_march(const char *who, int toward, double step, int max_steps) {
+  SR_CHECK(toward == 1 || toward == -1, "%s: toward must be +1 or -1, got %d", who, toward);
+  SR_CHECK(sr::positive(step), "%s: step must be finite and positive", who);
+  SR_CHECK(max_steps >= 1, "%s: max_steps must be at least 1, got %d", who, max_steps);
+  return SR_OK;
+}
+
+// the lines and the fields: an entry's last checks (n == 0 does not skip them)
+inline int check_lines(const char *who, int64_t n, const double *origin, const double *dir, const sr_field *ne, const sr_field *Te,
+                       const sr_field *Z) {
+  for (int64_t k = 0; k < 3 * n; ++k) {
+    SR_CHECK(std::isfinite(origin[k]), "%s: non-finite origin of line %lld", who, (long long)(k % n));
+    SR_CHECK(std::isfinite(dir[k]), "%s: non-finite direction of line %lld", who, (long long)(k % n));
+  }
+  for (int64_t k = 0; k < n; ++k)
+    SR_CHECK(dir[k] != 0.0 || dir[n + k] != 0.0 || dir[2 * n + k] != 0.0, "%s: the direction of line %lld is zero", who, (long long)k);
+  SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
+  return sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}});
+}
+
+// LineArgs but for its pointers, and the head of the call's scratch block from the caller's Carve: I | tau | backlight | origins |
+// directions | column | chord | steps, I and tau with `per_line` values a line.  What one entry alone needs goes behind.
+inline void take_lines(sr::Carve &carve, EmArgs &A, LineArgs &L, const sr_field *ne, int64_t n, double step, int max_steps,
+                       size_t per_line, bool backlight) {
+  const size_t N = (size_t)n;
+  A.ncol = L.n = n;
+  L.f = sr::grid_of(ne);
+  L.max_steps = max_steps;
+  L.step = step;
+  carve.take(&A.I, per_line * N);
+  carve.take(&A.tau, per_line * N);
+  if (backlight) carve.take(&A.back, per_line * N);
+  carve.take(&L.o, 3 * N);
+  carve.take(&L.d, 3 * N);
+  carve.take(&L.column, N);
+  carve.take(&L.chord, N);
+  carve.take(&L.steps, N);
+}
+
+// origins, directions and the backlight (map_bytes of it) go up
+inline int upload_lines(const EmArgs &A, const LineArgs &L, const double *origin, const double *dir, const double *backlight,
+                        size_t map_bytes, hipStream_t st) {
+  const size_t bytes = sizeof(double) * 3 * (size_t)L.n;
+  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.o), origin, bytes, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.d), dir, bytes, hipMemcpyHostToDevice, st));
+  if (backlight) SR_HIP(hipMemcpyAsync(const_cast<double *>(A.back), backlight, map_bytes, hipMemcpyHostToDevice, st));
+  return SR_OK;
+}
+
+// After the launch: I, tau and the per-line outputs that were asked for come back, the kernel's time is read.
+inline int finish_lines(const EmArgs &A, const LineArgs &L, size_t map_bytes, double *I, double *tau, double *column, double *chord,
+                        int32_t *steps, double *kernel_ms) {
+  sr::Context &c = sr::ctx();
+  hipStream_t st = c.stream;
+  const size_t N = (size_t)L.n;
+  SR_HIP(hipGetLastError());
+  SR_HIP(hipEventRecord(c.ev[1], st));
+  SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
+  if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (chord) SR_HIP(hipMemcpyAsync(chord, L.chord, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  if (steps) SR_HIP(hipMemcpyAsync(steps, L.steps, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  return sr::finish_timed(c, kernel_ms);
 }

@@ -25,6 +25,8 @@
 // table are four contiguous runs.  The lattices (at most 2 x 512 float64) are staged in LDS for the searches, the opacities are
 // read where they lie, through L2.  Instantiated per (dtype, Te field?, Z field?, node, FL).
 // Compiled with -ffp-contract=off, as sightlines.hip: I[i][f] and tau[i][f] are the bits k_sightlines gives band f of line i.
+// This unit holds the kernel, its dispatch, lane_width, the workgroup-count check and the group-innermost packing; what the entry does
+// around them is sightline_march.inc's host section, shared with sightlines.hip, and emission_march.inc's (bands, EmArgs).
 #include <cstdlib>
 #include <vector>
 
@@ -189,37 +191,23 @@ extern "C" int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te
   SR_CHECK(e_ph != nullptr && c_omega != nullptr, "%s: NULL e_ph or c_omega", who);
   SR_CHECK(table != nullptr || omega != nullptr, "%s: NULL omega without a table", who);
   SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  SR_CHECK(n_freq >= 1 && n_freq <= SR_MAX_FREQS, "%s: n_freq must be 1..%d, got %d", who, SR_MAX_FREQS, n_freq);
-  for (int b = 0; b < n_freq; ++b) {
-    SR_CHECK(table != nullptr || (std::isfinite(omega[b]) && omega[b] > 0.0), "%s: omega of frequency %d must be finite and positive",
-             who, b);
-    SR_CHECK(std::isfinite(e_ph[b]) && std::isfinite(c_omega[b]), "%s: non-finite e_ph or c_omega of frequency %d", who, b);
-  }
-  SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
-  SR_CHECK(sr::positive(p->step), "%s: step must be finite and positive", who);
-  SR_CHECK(p->max_steps >= 1, "%s: max_steps must be at least 1, got %d", who, p->max_steps);
+  SR_RC(check_bands(who, "frequency", n_freq, SR_MAX_FREQS, table ? nullptr : omega, e_ph, c_omega));
+  SR_RC(check_march(who, p->toward, p->step, p->max_steps));
   size_t tab_words = 0;
   if (table) {
     if (table->nT >= 2 && table->nT <= kMaxLattice && table->nD >= 2 && table->nD <= kMaxLattice) {  // before any entry is read
       tab_words = (size_t)table->nT + table->nD + (size_t)table->nT * table->nD * n_freq * (table->LE ? 2 : 1);
       SR_CHECK(tab_words <= (size_t)2147483647, "%s: the packed table holds %zu values, more than 2^31 - 1", who, tab_words);
     }
-    if (int rc = check_table(who, table, n_freq)) return rc;
+    SR_RC(check_table(who, table, n_freq));
   }
   const int fl = lane_width(n_freq);
   const int64_t n_tiles = (n_freq + fl - 1) / fl;
   SR_CHECK(n <= (int64_t)2147483647 / n_tiles, "%s: n x frequency tiles exceeds 2^31 - 1 workgroups", who);
-  for (int64_t k = 0; k < 3 * n; ++k) {
-    SR_CHECK(std::isfinite(origin[k]), "%s: non-finite origin of line %lld", who, (long long)(k % n));
-    SR_CHECK(std::isfinite(dir[k]), "%s: non-finite direction of line %lld", who, (long long)(k % n));
-  }
-  for (int64_t k = 0; k < n; ++k)
-    SR_CHECK(dir[k] != 0.0 || dir[n + k] != 0.0 || dir[2 * n + k] != 0.0, "%s: the direction of line %lld is zero", who, (long long)k);
-  SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
-  if (int rc = sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}})) return rc;
+  SR_RC(check_lines(who, n, origin, dir, ne, Te, Z));
   if (kernel_ms) *kernel_ms = 0.0;
   if (n == 0) return SR_OK;
-  if (int rc = sr::ensure_init()) return rc;
+  SR_RC(sr::ensure_init());
   sr::Context &c = sr::ctx();
   hipStream_t st = c.stream;
 
@@ -238,38 +226,21 @@ extern "C" int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te
       q += cells * nf;
     }
   }
-  const size_t N = (size_t)n, nf = (size_t)n_freq, map_bytes = sizeof(double) * nf * N, freq_bytes = sizeof(double) * nf;
+  const size_t nf = (size_t)n_freq, map_bytes = sizeof(double) * nf * (size_t)n, freq_bytes = sizeof(double) * nf;
 
-  // one scratch block: I | tau | backlight | origins | directions | column | chord | steps | omega | e_ph | c_omega | table
+  // one scratch block: the lines' pieces (take_lines) | omega | e_ph | c_omega | table
   EmArgs A{};
   LineArgs L{};
   SpecArgs X{};
   double *tab = nullptr;
   sr::Carve carve;
-  carve.take(&A.I, nf * N);
-  carve.take(&A.tau, nf * N);
-  if (backlight) carve.take(&A.back, nf * N);
-  carve.take(&L.o, 3 * N);
-  carve.take(&L.d, 3 * N);
-  carve.take(&L.column, N);
-  carve.take(&L.chord, N);
-  carve.take(&L.steps, N);
+  take_lines(carve, A, L, ne, n, p->step, p->max_steps, nf, backlight != nullptr);
   if (!table) carve.take(&X.omega, nf);
   carve.take(&X.e_ph, nf);
   carve.take(&X.c_omega, nf);
   carve.take(&tab, tab_words);
   if (!carve.alloc()) return SR_ERR_HIP;
-  A.ne = ne->data;
-  A.Te = Te ? Te->data : nullptr;
-  A.Z = Z ? Z->data : nullptr;
-  A.toward = p->toward;
-  A.ncol = n;
-  A.uTe = p->Te;
-  A.uZ = p->Z;
-  L.f = sr::grid_of(ne);
-  L.n = n;
-  L.max_steps = p->max_steps;
-  L.step = p->step;
+  fill_fields(A, ne, Te, Z, p->toward, p->Te, p->Z, 0, nullptr, nullptr, nullptr);  // the frequencies' constants are X's
   X.n_freq = n_freq;
   X.n_tiles = (int)n_tiles;
   if (table) {
@@ -284,9 +255,7 @@ extern "C" int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te
     X.m_ion = table->m_ion;
   }
 
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.o), origin, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.d), dir, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  if (backlight) SR_HIP(hipMemcpyAsync(const_cast<double *>(A.back), backlight, map_bytes, hipMemcpyHostToDevice, st));
+  SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
   if (!table) SR_HIP(hipMemcpyAsync(const_cast<double *>(X.omega), omega, freq_bytes, hipMemcpyHostToDevice, st));
   SR_HIP(hipMemcpyAsync(const_cast<double *>(X.e_ph), e_ph, freq_bytes, hipMemcpyHostToDevice, st));
   SR_HIP(hipMemcpyAsync(const_cast<double *>(X.c_omega), c_omega, freq_bytes, hipMemcpyHostToDevice, st));
@@ -301,12 +270,5 @@ extern "C" int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te
                            dim3(kFl), 0, st, A, L, X);
       },
       (bool)ne->is_f64, Te != nullptr, Z != nullptr, table != nullptr, fl == 64);
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipEventRecord(c.ev[1], st));
-  SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
-  if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (chord) SR_HIP(hipMemcpyAsync(chord, L.chord, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (steps) SR_HIP(hipMemcpyAsync(steps, L.steps, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  return sr::finish_timed(c, kernel_ms);
+  return finish_lines(A, L, map_bytes, I, tau, column, chord, steps, kernel_ms);
 }

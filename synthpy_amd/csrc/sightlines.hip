@@ -12,7 +12,9 @@
 // the reads' latency runs under that arithmetic, as k_emission_xy keeps two planes in flight.  Lanes of a wavefront finish at
 // different step counts: a lane that is done is masked off, there are no cross-lane operations inside the loop.  Which lines share a
 // wavefront -- the locality of the gather -- is the caller's business (synthpy_amd/sightlines.py hands a pixel grid over in 8x8
-// tiles in Morton order).  k_sightlines is instantiated per (dtype, Te field?, Z field?, bands, node).
+// tiles in Morton order).  k_sightlines is instantiated per (dtype, Te field?, Z field?, bands, node).  This unit holds the kernel,
+// its dispatch and the entry; what the entry does around the launch is sightline_march.inc's host section, shared with
+// sightline_spectra.hip, emission_march.inc's (bands, EmArgs) and table_node.inc's (the table's checks and band-major packing).
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_sightlines.py).
 #include <vector>
 
@@ -21,7 +23,7 @@
 namespace {
 #include "table_node.inc"
 
-#include "sightline_march.inc"  // LineArgs, Sample, fetch, the clip and the step count (shared with sightline_spectra.hip)
+#include "sightline_march.inc"  // LineArgs, Sample, fetch, the clip and the step count; the host code around the kernel
 
 template <typename T, bool HAS_TE, bool HAS_Z, int NB, typename P>
 __global__ void __launch_bounds__(256) k_sightlines(EmArgs A, LineArgs L, typename P::Args X) {
@@ -101,28 +103,13 @@ extern "C" int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const
   const char *who = "sr_field_sightlines";
   SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
   SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  SR_CHECK(p->n_band >= 1 && p->n_band <= SR_MAX_BANDS, "%s: n_band must be 1..%d, got %d", who, SR_MAX_BANDS, p->n_band);
-  for (int b = 0; b < p->n_band; ++b) {
-    SR_CHECK(table != nullptr || (std::isfinite(p->omega[b]) && p->omega[b] > 0.0), "%s: omega of band %d must be finite and positive",
-             who, b);
-    SR_CHECK(std::isfinite(p->e_ph[b]) && std::isfinite(p->c_omega[b]), "%s: non-finite e_ph or c_omega of band %d", who, b);
-  }
-  SR_CHECK(p->toward == 1 || p->toward == -1, "%s: toward must be +1 or -1, got %d", who, p->toward);
-  SR_CHECK(sr::positive(p->step), "%s: step must be finite and positive", who);
-  SR_CHECK(p->max_steps >= 1, "%s: max_steps must be at least 1, got %d", who, p->max_steps);
-  if (table)
-    if (int rc = check_table(who, table, p->n_band)) return rc;
-  for (int64_t k = 0; k < 3 * n; ++k) {
-    SR_CHECK(std::isfinite(origin[k]), "%s: non-finite origin of line %lld", who, (long long)(k % n));
-    SR_CHECK(std::isfinite(dir[k]), "%s: non-finite direction of line %lld", who, (long long)(k % n));
-  }
-  for (int64_t k = 0; k < n; ++k)
-    SR_CHECK(dir[k] != 0.0 || dir[n + k] != 0.0 || dir[2 * n + k] != 0.0, "%s: the direction of line %lld is zero", who, (long long)k);
-  SR_CHECK(ne != nullptr, "%s: NULL ne field", who);
-  if (int rc = sr::check_fields(who, ne, "ne", {{"ne", ne, 1}, {"Te", Te, 1}, {"Z", Z, 1}})) return rc;
+  SR_RC(check_bands(who, "band", p->n_band, SR_MAX_BANDS, table ? nullptr : p->omega, p->e_ph, p->c_omega));
+  SR_RC(check_march(who, p->toward, p->step, p->max_steps));
+  if (table) SR_RC(check_table(who, table, p->n_band));
+  SR_RC(check_lines(who, n, origin, dir, ne, Te, Z));
   if (kernel_ms) *kernel_ms = 0.0;
   if (n == 0) return SR_OK;
-  if (int rc = sr::ensure_init()) return rc;
+  SR_RC(sr::ensure_init());
   sr::Context &c = sr::ctx();
   hipStream_t st = c.stream;
 
@@ -130,43 +117,19 @@ extern "C" int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const
   if (table) pack = pack_table(table, p->n_band);
   const size_t tab_bytes = sizeof(double) * pack.size();
   const int nb = p->n_band;
-  const size_t N = (size_t)n, map_bytes = sizeof(double) * nb * N;
+  const size_t map_bytes = sizeof(double) * nb * (size_t)n;
 
-  // one scratch block: I | tau | backlight | origins | directions | column | chord | steps | table
+  // one scratch block: the lines' pieces (take_lines) | table
   EmArgs A{};
   LineArgs L{};
   char *tab = nullptr;
   sr::Carve carve;
-  carve.take(&A.I, nb * N);
-  carve.take(&A.tau, nb * N);
-  if (backlight) carve.take(&A.back, nb * N);
-  carve.take(&L.o, 3 * N);
-  carve.take(&L.d, 3 * N);
-  carve.take(&L.column, N);
-  carve.take(&L.chord, N);
-  carve.take(&L.steps, N);
+  take_lines(carve, A, L, ne, n, p->step, p->max_steps, nb, backlight != nullptr);
   carve.take(&tab, tab_bytes);
   if (!carve.alloc()) return SR_ERR_HIP;
-  A.ne = ne->data;
-  A.Te = Te ? Te->data : nullptr;
-  A.Z = Z ? Z->data : nullptr;
-  A.toward = p->toward;
-  A.ncol = n;
-  for (int b = 0; b < nb; ++b) {
-    A.omega[b] = p->omega[b];
-    A.e_ph[b] = p->e_ph[b];
-    A.c_omega[b] = p->c_omega[b];
-  }
-  A.uTe = p->Te;
-  A.uZ = p->Z;
-  L.f = sr::grid_of(ne);
-  L.n = n;
-  L.max_steps = p->max_steps;
-  L.step = p->step;
+  fill_fields(A, ne, Te, Z, p->toward, p->Te, p->Z, nb, p->omega, p->e_ph, p->c_omega);
 
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.o), origin, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(L.d), dir, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  if (backlight) SR_HIP(hipMemcpyAsync(const_cast<double *>(A.back), backlight, map_bytes, hipMemcpyHostToDevice, st));
+  SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
   if (table) SR_HIP(hipMemcpyAsync(tab, pack.data(), tab_bytes, hipMemcpyHostToDevice, st));
   SR_HIP(hipEventRecord(c.ev[0], st));
   if (table) {
@@ -183,12 +146,5 @@ extern "C" int sr_field_sightlines(const sr_field *ne, const sr_field *Te, const
   } else {
     launch_lines<float, NrlNode>(A, L, NrlNode::Args{}, 0, Te != nullptr, Z != nullptr, nb, st);
   }
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipEventRecord(c.ev[1], st));
-  SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
-  if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (chord) SR_HIP(hipMemcpyAsync(chord, L.chord, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (steps) SR_HIP(hipMemcpyAsync(steps, L.steps, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  return sr::finish_timed(c, kernel_ms);
+  return finish_lines(A, L, map_bytes, I, tau, column, chord, steps, kernel_ms);
 }

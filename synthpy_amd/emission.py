@@ -30,7 +30,23 @@ c = engine.c
 _QUANTITIES = ("intensity", "optical_depth", "transmission")
 
 
-class Emission:
+class _Maps:
+    """What every result of the emission family has beside its optical_depth (Emission, TableEmission, sightlines.SightlineEmission,
+    sightlines.SightlineSpectra)."""
+
+    @property
+    def transmission(self):
+        """exp(-optical_depth): what a backlight keeps."""
+        return np.exp(-self.optical_depth)
+
+    def _d_omega(self, missing):
+        """The widths of the bands in angular frequency [rad/s] from `edges` [eV]; without edges ValueError(missing)."""
+        if self.edges is None:
+            raise ValueError(missing)
+        return (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
+
+
+class Emission(_Maps):
     """The self-emission maps of one line of sight.  `axes` names the two lateral axes in x < y < z order, `coords` holds their
     node coordinates (float64); intensity [W m^-2 sr^-1 (rad/s)^-1, spectral radiance per unit angular frequency] and
     optical_depth are (n_band, len(coords[0]), len(coords[1])), band b at wavelengths[b]."""
@@ -45,11 +61,6 @@ class Emission:
         for name in ("intensity", "optical_depth"):
             if getattr(self, name).shape != want:
                 raise ValueError(f"{name} has shape {getattr(self, name).shape}, the bands and the lateral grid give {want}")
-
-    @property
-    def transmission(self):
-        """exp(-optical_depth): what a backlight keeps."""
-        return np.exp(-self.optical_depth)
 
     def sample(self, p, q, what="intensity"):
         """Bilinear interpolation of a quantity at the lateral positions (p along axes[0], q along axes[1]) -> (n_band, N);
@@ -86,8 +97,15 @@ def _omegas(wavelengths):
     return lam, 2 * np.pi * c / lam
 
 
+def _check_table(table, kind):
+    """ValueError unless `table` has an OpacityTable's members; kind: the class the entry takes, with its article."""
+    for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
+        if not hasattr(table, name):
+            raise ValueError(f"table must be {kind} (utils.eos_opacity): it has no {name}")
+
+
 def _upload(domain, fields, run):
-    """What every emission entry shares (self_emission, table_emission, sightlines.sightline_emission): the domain's fields
+    """What every emission entry shares (self_emission, table_emission, sightlines.sightline_emission and sightline_spectra): the domain's fields
     uploaded by self_emission's rules -- a Te or Z that is a scalar (or broadcast from one) goes as a value, float32 only when
     every array is float32 (fields.SourceFields.get_all) -- then run(ne, Te, Z), whose result is returned."""
     ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
@@ -139,10 +157,7 @@ class TableEmission(Emission):
 
     @property
     def band_radiance(self):
-        if self.edges is None:
-            raise ValueError("the table has no band edges: band_radiance needs the bands' widths")
-        d_omega = (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
-        return self.intensity * d_omega[:, None, None]
+        return self.intensity * self._d_omega("the table has no band edges: band_radiance needs the bands' widths")[:, None, None]
 
 
 def table_emission(domain, table, toward="+", backlight=None, fields=None):
@@ -156,8 +171,6 @@ def table_emission(domain, table, toward="+", backlight=None, fields=None):
     functions, refraction of the emitted light, detector optics."""
     engine.axis_index(domain.probing_direction)
     _toward(toward)
-    for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
-        if not hasattr(table, name):
-            raise ValueError(f"table must be an OpacityTable (utils.eos_opacity): it has no {name}")
+    _check_table(table, "an OpacityTable")
     I, tau, axes, coords = _march(domain, toward, fields, lambda ne, Te, Z, axis, sign: engine.emission_table(ne, Te, Z, table, axis, sign, backlight))
     return TableEmission(I, tau, axes, coords, table.photon_energy, getattr(table, "edges", None))

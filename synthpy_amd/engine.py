@@ -452,18 +452,26 @@ HBAR = 6.62607015e-34 / (2 * np.pi)  # J s, from the exact h of the SI
 E_CHARGE = 1.602176634e-19           # C
 
 
-def emission_params(omegas, axis, toward=+1, Te=0.0, Z=0.0):
-    """sr_emission_params for the bands `omegas` [rad/s]: per band E_ph = hbar*omega/e [eV] and C_omega = hbar*omega^3/(4 pi^3 c^2),
-    the Planck function's prefactor, B_omega(Te) = C_omega / expm1(E_ph / Te); Te, Z: the uniform values of absent fields."""
+def spectrum_constants(omegas):
+    """(omega, e_ph, c_omega), float64 (n_freq): the per-band constants of every entry of the emission family for any number of
+    angular frequencies [rad/s], E_ph = hbar*omega/e [eV] and C_omega = hbar*omega^3/(4 pi^3 c^2), the Planck function's prefactor,
+    B_omega(Te) = C_omega / expm1(E_ph / Te).  Formed on Python floats, here and nowhere else, so that a frequency has the bits it
+    has as a band of engine.sightlines."""
     om = np.atleast_1d(f64(omegas))
     if om.ndim != 1:
         raise ValueError(f"omegas must be a scalar or one-dimensional, got shape {om.shape}")
+    w = om.tolist()
+    return om, f64([HBAR * v / E_CHARGE for v in w]), f64([HBAR * v ** 3 / (4 * np.pi ** 3 * c ** 2) for v in w])
+
+
+def emission_params(omegas, axis, toward=+1, Te=0.0, Z=0.0):
+    """sr_emission_params for the bands `omegas` [rad/s] with spectrum_constants' E_ph and C_omega per band; Te, Z: the uniform
+    values of absent fields."""
+    om, e_ph, c_omega = (a.tolist() for a in spectrum_constants(omegas))
     p = _ffi.EmissionParams()
     p.axis, p.toward, p.n_band, p.reserved = int(axis), int(toward), len(om), 0
-    for b, w in enumerate(om[:_ffi.MAX_BANDS].tolist()):
-        p.omega[b] = w
-        p.e_ph[b] = HBAR * w / E_CHARGE
-        p.c_omega[b] = HBAR * w ** 3 / (4 * np.pi ** 3 * c ** 2)
+    for b in range(min(len(om), _ffi.MAX_BANDS)):
+        p.omega[b], p.e_ph[b], p.c_omega[b] = om[b], e_ph[b], c_omega[b]
     p.Te, p.Z = float(Te), float(Z)
     return p
 
@@ -527,6 +535,16 @@ def emission_table_params(table):
     return t, (LT, LD, LA, LE)
 
 
+def _table_omegas(table):
+    """(t, keep, omegas): emission_table_params' struct and the arrays it points into (the caller holds them until the library
+    call returns), and the table's angular frequencies, one per band, at its photon_energy."""
+    t, keep = emission_table_params(table)
+    omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
+    if len(omegas) != keep[2].shape[0]:
+        raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
+    return t, keep, omegas
+
+
 def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
     """engine.emission with the absorption and emission opacities of `table` (utils.eos_opacity.OpacityTable: a temperature x
     ion-density lattice, up to 4 bands) in place of the NRL coefficient (sr_field_emission_table; include/synthray.h states the
@@ -536,10 +554,7 @@ def emission_table(ne, Te, Z, table, axis, toward=+1, backlight=None):
     frequency at photon_energy.  Fields, uniform Te / Z, axis, toward and backlight are engine.emission's.  Not modelled: Z from
     the table's own zf_table (the solve ne = ni * zf(T, ni)), group-integrated Planck functions, refraction, detector optics."""
     _handle("ne", ne)
-    t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
-    omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
-    if len(omegas) != keep[2].shape[0]:
-        raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
+    t, keep, omegas = _table_omegas(table)
     return _emission(lib.sr_field_emission_table, ne, Te, Z, omegas, axis, toward, backlight, C.byref(t))
 
 
@@ -556,6 +571,41 @@ def sightline_params(omegas, toward, step, max_steps, Te=0.0, Z=0.0):
     return p
 
 
+def _sightlines(params, table_kind, ne, Te, Z, origins, directions, omegas, table, backlight, want):
+    """What sightlines and sightline_spectra share: the handles, the uniform Te / Z, the lines, the table, the backlight's shape,
+    the outputs and ne's kernel time.  params(omegas, n, uniform, t) -> (the library call, its params struct, the shape of I and
+    tau, what that shape is made of (for the error text), the call's arguments between the directions and the backlight);
+    table_kind names the table's class in the error text."""
+    h_ne = _handle("ne", ne)
+    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
+    if (omegas is None) == (table is None):
+        raise ValueError(f"exactly one of omegas (the NRL node) and table ({table_kind}) must be given")
+    unknown = set(want) - set(_SIGHT_WANT)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT}")
+    o, d = f64(origins), f64(directions)
+    if o.ndim != 2 or o.shape[0] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and directions must both have shape (3, n), got {o.shape} and {d.shape}")
+    n = o.shape[1]
+    t, keep = None, None
+    if table is not None:
+        t, keep, omegas = _table_omegas(table)
+    entry, p, shape, made_of, between = params(omegas, n, (0.0 if h else float(a) for h, a in zip(handles, (Te, Z))), t)
+    if backlight is not None:
+        backlight = f64(backlight)
+        if backlight.shape != shape:
+            raise ValueError(f"backlight has shape {backlight.shape}, {made_of} give {shape}")
+    I, tau = np.empty(shape), np.empty(shape)
+    opt = {"column": np.empty(n) if "column" in want else None, "chord": np.empty(n) if "chord" in want else None,
+           "steps": np.empty(n, np.int32) if "steps" in want else None}
+    ms = C.c_double(0.0)
+    check(entry(h_ne, *handles, None if t is None else C.byref(t), C.byref(p), n, ptr(o), ptr(d), *between, ptr(backlight), ptr(I),
+                ptr(tau), ptr(opt["column"]), ptr(opt["chord"]), ptr(opt["steps"]), C.byref(ms)))
+    ne.last_kernel_ms = float(ms.value)
+    out = {"intensity": I, "optical_depth": tau, **opt}
+    return {k: out[k] for k in _SIGHT_WANT if k in want}
+
+
 def sightlines(ne, Te, Z, origins, directions, *, omegas=None, table=None, toward, step, max_steps, backlight=None,
                want=_SIGHT_WANT):
     """Emission and absorption along the n half-lines origins[:, i] + t * directions[:, i], t >= 0 (both (3, n) [m]; a direction
@@ -569,48 +619,11 @@ def sightlines(ne, Te, Z, origins, directions, *, omegas=None, table=None, towar
     (n; the length inside the box [m], 0 for a line that misses it) and "steps" (n) int32.  ne.last_kernel_ms keeps the kernel's
     time.  Not modelled: a finite pinhole or source, the cos^4 and solid-angle factors of a film's exposure, refraction, the
     detector's response, a table's own ionisation; one GPU."""
-    h_ne = _handle("ne", ne)
-    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
-    if (omegas is None) == (table is None):
-        raise ValueError("exactly one of omegas (the NRL node) and table (an OpacityTable) must be given")
-    unknown = set(want) - set(_SIGHT_WANT)
-    if unknown:
-        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT}")
-    o, d = f64(origins), f64(directions)
-    if o.ndim != 2 or o.shape[0] != 3 or d.shape != o.shape:
-        raise ValueError(f"origins and directions must both have shape (3, n), got {o.shape} and {d.shape}")
-    n = o.shape[1]
-    t, keep = None, None
-    if table is not None:
-        t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
-        omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
-        if len(omegas) != keep[2].shape[0]:
-            raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
-    p = sightline_params(omegas, toward, step, max_steps, *(0.0 if h else float(a) for h, a in zip(handles, (Te, Z))))
-    nb = p.n_band
-    if backlight is not None:
-        backlight = f64(backlight)
-        if backlight.shape != (nb, n):
-            raise ValueError(f"backlight has shape {backlight.shape}, the bands and the lines give {(nb, n)}")
-    I, tau = np.empty((nb, n)), np.empty((nb, n))
-    opt = {"column": np.empty(n) if "column" in want else None, "chord": np.empty(n) if "chord" in want else None,
-           "steps": np.empty(n, np.int32) if "steps" in want else None}
-    ms = C.c_double(0.0)
-    check(lib.sr_field_sightlines(h_ne, *handles, None if t is None else C.byref(t), C.byref(p), n, ptr(o), ptr(d), ptr(backlight),
-                                  ptr(I), ptr(tau), ptr(opt["column"]), ptr(opt["chord"]), ptr(opt["steps"]), C.byref(ms)))
-    ne.last_kernel_ms = float(ms.value)
-    out = {"intensity": I, "optical_depth": tau, **opt}
-    return {k: out[k] for k in _SIGHT_WANT if k in want}
+    def params(omegas, n, uniform, t):
+        p = sightline_params(omegas, toward, step, max_steps, *uniform)
+        return lib.sr_field_sightlines, p, (p.n_band, n), "the bands and the lines", ()
 
-
-def spectrum_constants(omegas):
-    """(omega, e_ph, c_omega), float64 (n_freq): emission_params' per-band constants for any number of frequencies, formed by the
-    same expressions on the same Python floats, so that a frequency has the bits it has as a band of engine.sightlines."""
-    om = np.atleast_1d(f64(omegas))
-    if om.ndim != 1:
-        raise ValueError(f"omegas must be a scalar or one-dimensional, got shape {om.shape}")
-    w = om.tolist()
-    return om, f64([HBAR * v / E_CHARGE for v in w]), f64([HBAR * v ** 3 / (4 * np.pi ** 3 * c ** 2) for v in w])
+    return _sightlines(params, "an OpacityTable", ne, Te, Z, origins, directions, omegas, table, backlight, want)
 
 
 def sightline_spectra(ne, Te, Z, origins, directions, *, omegas=None, table=None, toward, step, max_steps, backlight=None,
@@ -624,42 +637,16 @@ def sightline_spectra(ne, Te, Z, origins, directions, *, omegas=None, table=None
     every element has the bits engine.sightlines returns for that line with that frequency as one of its (up to 4) bands; "column",
     "chord", "steps" (n).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: what engine.sightlines does not model; line
     shapes, Doppler shifts, group-integrated Planck functions; one GPU."""
-    h_ne = _handle("ne", ne)
-    handles = [_handle(name, a, number=True) for name, a in (("Te", Te), ("Z", Z))]
-    if (omegas is None) == (table is None):
-        raise ValueError("exactly one of omegas (the NRL node) and table (a SpectralOpacityTable) must be given")
-    unknown = set(want) - set(_SIGHT_WANT)
-    if unknown:
-        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT}")
-    o, d = f64(origins), f64(directions)
-    if o.ndim != 2 or o.shape[0] != 3 or d.shape != o.shape:
-        raise ValueError(f"origins and directions must both have shape (3, n), got {o.shape} and {d.shape}")
-    n = o.shape[1]
-    t, keep = None, None
-    if table is not None:
-        t, keep = emission_table_params(table)  # keep: the arrays t points into, alive until the call returns
-        omegas = np.atleast_1d(f64(table.photon_energy)) * E_CHARGE / HBAR
-        if len(omegas) != keep[2].shape[0]:
-            raise ValueError(f"the table has {keep[2].shape[0]} band(s) and {len(omegas)} photon energies")
-    om, e_ph, c_om = spectrum_constants(omegas)
-    nf = len(om)
-    p = _ffi.SpectraParams()
-    p.toward, p.max_steps, p.step = int(toward), int(max_steps), float(step)
-    p.Te, p.Z = (0.0 if h else float(a) for h, a in zip(handles, (Te, Z)))
-    if backlight is not None:
-        backlight = f64(backlight)
-        if backlight.shape != (n, nf):
-            raise ValueError(f"backlight has shape {backlight.shape}, the lines and the frequencies give {(n, nf)}")
-    I, tau = np.empty((n, nf)), np.empty((n, nf))
-    opt = {"column": np.empty(n) if "column" in want else None, "chord": np.empty(n) if "chord" in want else None,
-           "steps": np.empty(n, np.int32) if "steps" in want else None}
-    ms = C.c_double(0.0)
-    check(lib.sr_field_sightline_spectra(h_ne, *handles, None if t is None else C.byref(t), C.byref(p), n, ptr(o), ptr(d), nf,
-                                         None if t is not None else ptr(om), ptr(e_ph), ptr(c_om), ptr(backlight), ptr(I), ptr(tau),
-                                         ptr(opt["column"]), ptr(opt["chord"]), ptr(opt["steps"]), C.byref(ms)))
-    ne.last_kernel_ms = float(ms.value)
-    out = {"intensity": I, "optical_depth": tau, **opt}
-    return {k: out[k] for k in _SIGHT_WANT if k in want}
+    def params(omegas, n, uniform, t):
+        om, e_ph, c_om = spectrum_constants(omegas)
+        p = _ffi.SpectraParams()
+        p.toward, p.max_steps, p.step = int(toward), int(max_steps), float(step)
+        p.Te, p.Z = uniform
+        # om, e_ph and c_om live as long as the pointers: ndarray.ctypes.data_as keeps a reference to its array
+        return (lib.sr_field_sightline_spectra, p, (n, len(om)), "the lines and the frequencies",
+                (len(om), None if t is not None else ptr(om), ptr(e_ph), ptr(c_om)))
+
+    return _sightlines(params, "a SpectralOpacityTable", ne, Te, Z, origins, directions, omegas, table, backlight, want)
 
 
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED

@@ -28,7 +28,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import engine
-from .emission import _omegas, _upload
+from .emission import _check_table, _Maps, _omegas, _upload
 
 c = engine.c
 
@@ -171,7 +171,20 @@ class PointBacklighter(_PixelView):
         self.source = self.point
 
 
-class SightlineEmission:
+class _LineMaps(_Maps):
+    """What the two results along lines share: the view, the two maps and the per-line column, chord and steps (view.shape)."""
+
+    def __init__(self, view, intensity, optical_depth, column, chord, steps):
+        self.view = view
+        self.intensity, self.optical_depth = np.asarray(intensity, np.float64), np.asarray(optical_depth, np.float64)
+        self.column, self.chord, self.steps = np.asarray(column, np.float64), np.asarray(chord, np.float64), np.asarray(steps, np.int32)
+
+    def _expect(self, want, what, made_of):
+        if self.intensity.shape != want or self.optical_depth.shape != want:
+            raise ValueError(f"the {what} have shapes {self.intensity.shape} and {self.optical_depth.shape}, {made_of} give {want}")
+
+
+class SightlineEmission(_LineMaps):
     """What the lines of one view see.  intensity [W m^-2 sr^-1 (rad/s)^-1, spectral radiance per unit angular frequency] and
     optical_depth are (n_band,) + view.shape -- (n_band, nu, nv) for a pixel grid, (n_band, N) for Chords; column (the integral
     of ne dl [m^-2]), chord (the length inside the domain's box [m]; 0: the line misses it) and steps (samples marched) are
@@ -179,32 +192,53 @@ class SightlineEmission:
     band_radiance for a table (emission.TableEmission's)."""
 
     def __init__(self, view, intensity, optical_depth, column, chord, steps, wavelengths, photon_energy=None, edges=None):
-        self.view = view
-        self.intensity, self.optical_depth = np.asarray(intensity, np.float64), np.asarray(optical_depth, np.float64)
-        self.column, self.chord, self.steps = np.asarray(column, np.float64), np.asarray(chord, np.float64), np.asarray(steps, np.int32)
+        super().__init__(view, intensity, optical_depth, column, chord, steps)
         self.wavelengths = np.atleast_1d(np.asarray(wavelengths, np.float64))
         self.photon_energy = None if photon_energy is None else np.atleast_1d(np.asarray(photon_energy, np.float64))
         self.edges = None if edges is None else np.asarray(edges, np.float64).reshape(len(self.wavelengths), 2)
-        want = (len(self.wavelengths),) + tuple(view.shape)
-        if self.intensity.shape != want or self.optical_depth.shape != want:
-            raise ValueError(f"the maps have shapes {self.intensity.shape} and {self.optical_depth.shape}, the bands and the view give {want}")
-
-    @property
-    def transmission(self):
-        """exp(-optical_depth): what a backlight keeps."""
-        return np.exp(-self.optical_depth)
+        self._expect((len(self.wavelengths),) + tuple(view.shape), "maps", "the bands and the view")
 
     @property
     def band_radiance(self):
-        if self.edges is None:
-            raise ValueError("no band edges: band_radiance needs a table with the bands' widths")
-        d_omega = (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
+        d_omega = self._d_omega("no band edges: band_radiance needs a table with the bands' widths")
         return self.intensity * d_omega.reshape((-1,) + (1,) * (self.intensity.ndim - 1))
 
 
 def default_step(domain):
     """Half the smallest cell edge of the domain's grid as the device holds it (float32 coordinates)."""
     return 0.5 * min(float(np.min(np.diff(np.float64(np.float32(a))))) for a in (domain.x, domain.y, domain.z))
+
+
+def _check_view(view):
+    if not all(hasattr(view, name) for name in ("lines", "order", "backlight", "toward", "shape")):
+        raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
+
+
+def _along(domain, view, fields, entry, n_band, axis, step, max_steps, **node):
+    """What the two entries share once the node is known: the defaults of step and max_steps, the view's lines and backlight in the
+    order they go to the kernel in, entry(ne, Te, Z, ...) on the domain's fields, and its five arrays -- their lines along `axis`:
+    -1 (bands first, the backlight (n_band, N)) or 0 (lines first, (N, n_band)) -- back in the view's order and shape."""
+    step = default_step(domain) if step is None else float(step)
+    max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
+    o, d = view.lines()
+    back = view.backlight(n_band)
+    perm = view.order()
+    if perm is not None:
+        o, d = o[:, perm], d[:, perm]
+        back = None if back is None else back[:, perm]
+    if back is not None and axis == 0:
+        back = np.ascontiguousarray(back.T)
+    res = _upload(domain, fields, lambda ne, Te, Z: entry(ne, Te, Z, o, d, toward=view.toward, step=step, max_steps=max_steps,
+                                                         backlight=back, **node))
+
+    def place(a):  # kernel order -> the view's order and shape
+        if perm is not None:
+            out = np.empty_like(a)
+            out[(perm,) if axis == 0 else (..., perm)] = a
+            a = out
+        return a.reshape(tuple(view.shape) + a.shape[1:] if axis == 0 else a.shape[:-1] + tuple(view.shape))
+
+    return [place(res[k]) for k in ("intensity", "optical_depth", "column", "chord", "steps")]
 
 
 def sightline_emission(domain, view, wavelengths=None, table=None, step=None, max_steps=None, fields=None):
@@ -218,74 +252,41 @@ def sightline_emission(domain, view, wavelengths=None, table=None, step=None, ma
     solid-angle factors of a film's exposure, refraction, the detector's response, a table's own ionisation; one GPU."""
     if (wavelengths is None) == (table is None):
         raise ValueError("exactly one of wavelengths (the NRL node) and table (an OpacityTable) must be given")
-    if not all(hasattr(view, name) for name in ("lines", "order", "backlight", "toward", "shape")):
-        raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
+    _check_view(view)
     if table is None:
         lam, omegas = _omegas(wavelengths)
         kw, n_band = {"omegas": omegas}, len(lam)
     else:
-        for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
-            if not hasattr(table, name):
-                raise ValueError(f"table must be an OpacityTable (utils.eos_opacity): it has no {name}")
+        _check_table(table, "an OpacityTable")
         kw, n_band = {"table": table}, len(np.atleast_1d(table.photon_energy))
-    step = default_step(domain) if step is None else float(step)
-    max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
-    o, d = view.lines()
-    back = view.backlight(n_band)
-    perm = view.order()
-    if perm is not None:
-        o, d = o[:, perm], d[:, perm]
-        back = None if back is None else back[:, perm]
-    res = _upload(domain, fields, lambda ne, Te, Z: engine.sightlines(ne, Te, Z, o, d, toward=view.toward, step=step, max_steps=max_steps,
-                                                                     backlight=back, **kw))
-
-    def place(a):  # kernel order -> the view's order and shape
-        if perm is not None:
-            out = np.empty_like(a)
-            out[..., perm] = a
-            a = out
-        return a.reshape(a.shape[:-1] + tuple(view.shape))
-
-    maps = {k: place(v) for k, v in res.items()}
+    maps = _along(domain, view, fields, engine.sightlines, n_band, -1, step, max_steps, **kw)
     if table is None:
-        return SightlineEmission(view, maps["intensity"], maps["optical_depth"], maps["column"], maps["chord"], maps["steps"], lam)
+        return SightlineEmission(view, *maps, lam)
     e_ph = np.atleast_1d(np.asarray(table.photon_energy, np.float64))
-    return SightlineEmission(view, maps["intensity"], maps["optical_depth"], maps["column"], maps["chord"], maps["steps"],
-                             2 * np.pi * engine.HBAR * c / (engine.E_CHARGE * e_ph), e_ph, getattr(table, "edges", None))
+    return SightlineEmission(view, *maps, 2 * np.pi * engine.HBAR * c / (engine.E_CHARGE * e_ph), e_ph, getattr(table, "edges", None))
 
 
-class SightlineSpectra:
+class SightlineSpectra(_LineMaps):
     """The spectrum every line of one view sees.  intensity [W m^-2 sr^-1 (rad/s)^-1, spectral radiance per unit angular frequency]
     and optical_depth are view.shape + (n_freq,) -- (nu, nv, n_freq) for a pixel grid, (N, n_freq) for Chords: a line's spectrum
     is contiguous; column, chord and steps are view.shape, as SightlineEmission's.  omega [rad/s], photon_energy [eV] and
     wavelengths [m] are (n_freq,); edges ((n_freq, 2), eV) where a table has them, and with them band_radiance."""
 
     def __init__(self, view, intensity, optical_depth, column, chord, steps, omega, edges=None):
-        self.view = view
-        self.intensity, self.optical_depth = np.asarray(intensity, np.float64), np.asarray(optical_depth, np.float64)
-        self.column, self.chord, self.steps = np.asarray(column, np.float64), np.asarray(chord, np.float64), np.asarray(steps, np.int32)
+        super().__init__(view, intensity, optical_depth, column, chord, steps)
         self.omega = np.atleast_1d(np.asarray(omega, np.float64))
         self.photon_energy = engine.HBAR * self.omega / engine.E_CHARGE
         self.wavelengths = 2 * np.pi * c / self.omega
         self.edges = None if edges is None else np.asarray(edges, np.float64).reshape(len(self.omega), 2)
-        want = tuple(view.shape) + (len(self.omega),)
-        if self.intensity.shape != want or self.optical_depth.shape != want:
-            raise ValueError(f"the spectra have shapes {self.intensity.shape} and {self.optical_depth.shape}, the view and the frequencies give {want}")
+        self._expect(tuple(view.shape) + (len(self.omega),), "spectra", "the view and the frequencies")
 
-    @property
-    def transmission(self):
-        """exp(-optical_depth): what a backlight keeps."""
-        return np.exp(-self.optical_depth)
-
-    def _d_omega(self):
-        if self.edges is None:
-            raise ValueError("no band edges: band_radiance needs a table with the groups' widths")
-        return (self.edges[:, 1] - self.edges[:, 0]) * engine.E_CHARGE / engine.HBAR
+    def _widths(self):
+        return self._d_omega("no band edges: band_radiance needs a table with the groups' widths")
 
     @property
     def band_radiance(self):
         """intensity times the group's width in angular frequency [W m^-2 sr^-1], as SightlineEmission's."""
-        return self.intensity * self._d_omega()
+        return self.intensity * self._widths()
 
     def signal(self, response=None):
         """The response-weighted integral of intensity over angular frequency per line [W m^-2 sr^-1], view.shape, on the host.
@@ -301,7 +302,7 @@ class SightlineSpectra:
         if R.shape != self.omega.shape:
             raise ValueError(f"response must give {len(self.omega)} value(s), one per frequency, got shape {R.shape}")
         if self.edges is not None:
-            return np.sum(self.intensity * (self._d_omega() * R), axis=-1)
+            return np.sum(self.intensity * (self._widths() * R), axis=-1)
         k = np.argsort(self.omega, kind="stable")
         y, w = (self.intensity * R)[..., k], self.omega[k]
         return np.sum(0.5 * (y[..., 1:] + y[..., :-1]) * np.diff(w), axis=-1)
@@ -334,35 +335,13 @@ def sightline_spectra(domain, view, wavelengths=None, photon_energies=None, tabl
     group-integrated Planck functions; one GPU."""
     if sum(a is not None for a in (wavelengths, photon_energies, table)) != 1:
         raise ValueError("exactly one of wavelengths, photon_energies (the NRL node) and table (a SpectralOpacityTable) must be given")
-    if not all(hasattr(view, name) for name in ("lines", "order", "backlight", "toward", "shape")):
-        raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
+    _check_view(view)
     if table is None:
         omega = _spectrum_omegas(wavelengths, photon_energies)
         kw, edges = {"omegas": omega}, None
     else:
-        for name in ("temperatures", "densities", "absorption", "photon_energy", "A"):
-            if not hasattr(table, name):
-                raise ValueError(f"table must be a SpectralOpacityTable (utils.eos_opacity): it has no {name}")
+        _check_table(table, "a SpectralOpacityTable")
         omega = np.atleast_1d(np.asarray(table.photon_energy, np.float64)) * engine.E_CHARGE / engine.HBAR
         kw, edges = {"table": table}, getattr(table, "edges", None)
-    step = default_step(domain) if step is None else float(step)
-    max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
-    o, d = view.lines()
-    back = view.backlight(len(omega))
-    perm = view.order()
-    if perm is not None:
-        o, d = o[:, perm], d[:, perm]
-        back = None if back is None else back[:, perm]
-    back = None if back is None else np.ascontiguousarray(back.T)  # (N, n_freq)
-    res = _upload(domain, fields, lambda ne, Te, Z: engine.sightline_spectra(ne, Te, Z, o, d, toward=view.toward, step=step,
-                                                                            max_steps=max_steps, backlight=back, **kw))
-
-    def place(a):  # kernel order -> the view's order and shape; the lines are axis 0
-        if perm is not None:
-            out = np.empty_like(a)
-            out[perm] = a
-            a = out
-        return a.reshape(tuple(view.shape) + a.shape[1:])
-
-    maps = {k: place(v) for k, v in res.items()}
-    return SightlineSpectra(view, maps["intensity"], maps["optical_depth"], maps["column"], maps["chord"], maps["steps"], omega, edges)
+    maps = _along(domain, view, fields, engine.sightline_spectra, len(omega), 0, step, max_steps, **kw)
+    return SightlineSpectra(view, *maps, omega, edges)

@@ -678,3 +678,26 @@ def test_end_to_end_on_both_generations(eng):
         assert np.array_equal(np.moveaxis(img.optical_depth[..., pick], -1, 0), em.optical_depth)
         assert np.array_equal(img.column, em.column) and np.array_equal(img.chord, em.chord) and np.array_equal(img.steps, em.steps)
         assert em.intensity.max() > 0 and 0 < (em.steps == 0).sum() < em.steps.size
+
+
+@pytest.mark.gpu
+def test_each_optional_output_asked_for_alone(eng, monkeypatch):
+    """13: want = ("column",), ("chord",), ("steps",) on grid A, five planted lines, 5 frequencies: the dict holds that key alone and
+    the array has the bits of the call that asks for everything (the three read-backs are separate branches of the host code),
+    which is held to the restatement."""
+    R = _config((5, 5, True, True, "A"), "nrl", -1, np.float64)
+    assert R["ref"]["miss"].tolist() == [False, False, False, False, True] and np.all(R["ref"]["column"][:4] > 0)
+    fields = _upload(eng, R)
+    try:
+        full = _spectra(eng, R, -1, fields=fields)
+        _assert_exact(full, R["ref"], "five planted lines")
+        _assert_close(full, R["ref"], "five planted lines")
+        for name in ("column", "chord", "steps"):
+            with monkeypatch.context() as m:  # an array the library does not write holds 0xA5 bytes, not a recycled buffer's
+                m.setattr(np, "empty", ts._poisoned(np.empty))
+                one = eng.sightline_spectra(*fields, R["o"], R["d"], toward=-1, step=R["step"], max_steps=R["max_steps"],
+                                            backlight=R["back"], want=(name,), **_node_kw(R))
+            assert list(one) == [name], f"want=({name!r},) returned {list(one)}"
+            assert one[name].dtype == full[name].dtype and np.array_equal(one[name], full[name]), f"{name} asked for alone differs"
+    finally:
+        _close(fields)

@@ -892,3 +892,69 @@ def test_end_to_end_views_of_both_generations(eng):
     ch = sightlines.Chords([[0.0], [-8e-3], [1e-3]], [[0.1], [1.0], [-0.05]], -1)
     em = new.sightline_emission(ch, wavelengths=[100e-9])
     assert em.intensity.shape == (1, 1) and em.column.shape == (1,) and em.chord[0] > 0 and em.steps[0] > 0
+
+
+def _five(nb=2):
+    """Grid A, five planted lines (inside, column, long, graze and beside: a miss), nb NRL bands, float64 fields."""
+    K = _grid("A")
+    P = _planted(K["g"])
+    names = ("inside", "column", "long", "graze", "beside")
+    o = np.ascontiguousarray(np.array([P[k][0] for k in names]).T)
+    d = np.ascontiguousarray(np.array([P[k][1] for k in names]).T)
+    back = np.random.default_rng(K["seed"] + 5).uniform(0.0, 2e-7, (nb, len(names)))
+    return dict(K=K, o=o, d=d, ne=K["ne"]["nrl"], Te=K["Te"], Z=K["Z"], back=back, nb=nb, table=None)
+
+
+def _poisoned(empty):
+    """np.empty with every byte 0xA5: an output the library does not write cannot hold the right values by chance, as the recycled
+    buffer of an equal array can."""
+    def poisoned(shape, dtype=np.float64, *args, **kw):
+        a = empty(shape, dtype, *args, **kw)
+        a.reshape(-1).view(np.uint8)[:] = 0xA5
+        return a
+
+    return poisoned
+
+
+@pytest.mark.gpu
+def test_each_optional_output_asked_for_alone(eng, monkeypatch):
+    """12: want = ("column",), ("chord",), ("steps",): the dict holds that key alone and the array has the bits of the call that
+    asks for everything (the three read-backs are separate branches of the host code), which is held to the restatement."""
+    R = _five()
+    K = R["K"]
+    full = _run(eng, R, "nrl", -1)
+    ref = restate(R["ne"], R["Te"], R["Z"], K["co"], R["o"], R["d"], _node_of(R, "nrl"), -1, K["step"], backlight=R["back"])
+    assert ref["miss"].tolist() == [False, False, False, False, True] and np.all(ref["column"][:4] > 0)
+    _assert_exact(full, ref, "five planted lines")
+    _assert_close(full, ref, "five planted lines")
+    fields = [eng.Field(a, *K["co"]) for a in (R["ne"], R["Te"], R["Z"])]
+    try:
+        for name in ("column", "chord", "steps"):
+            with monkeypatch.context() as m:
+                m.setattr(np, "empty", _poisoned(np.empty))
+                one = eng.sightlines(*fields, R["o"], R["d"], omegas=np.float64(K["bands"][0][:2]), toward=-1, step=K["step"],
+                                     max_steps=MAX_STEPS, backlight=R["back"], want=(name,))
+            assert list(one) == [name], f"want=({name!r},) returned {list(one)}"
+            assert one[name].dtype == full[name].dtype and np.array_equal(one[name], full[name]), f"{name} asked for alone differs"
+    finally:
+        for f in fields:
+            f.close()
+
+
+@pytest.mark.gpu
+def test_no_lines(eng):
+    """13: n = 0 is accepted: empty arrays of the right shapes and types, no kernel time."""
+    R = _five()
+    K = R["K"]
+    fields = [eng.Field(a, *K["co"]) for a in (R["ne"], R["Te"], R["Z"])]
+    try:
+        for back in (np.zeros((2, 0)), None):
+            out = eng.sightlines(*fields, np.zeros((3, 0)), np.zeros((3, 0)), omegas=np.float64(K["bands"][0][:2]), toward=+1,
+                                 step=K["step"], max_steps=MAX_STEPS, backlight=back)
+            assert list(out) == ["intensity", "optical_depth", "column", "chord", "steps"]
+            assert out["intensity"].shape == out["optical_depth"].shape == (2, 0)
+            assert out["column"].shape == out["chord"].shape == out["steps"].shape == (0,) and out["steps"].dtype == np.int32
+            assert fields[0].last_kernel_ms == 0.0
+    finally:
+        for f in fields:
+            f.close()

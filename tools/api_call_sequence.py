@@ -1,12 +1,15 @@
 """Every call into libsynthray.so that the two API generations make for one fixed flow, in order, with a hash of what each
 step handed back.  Run on two versions of the Python layer (TREE = a checkout with its library built; default: this one), the
 two logs must be equal line for line: the check that a change to the mirror classes reaches the device with the same calls
-and hands back the same bits (profiles/api_mirrors_rate.txt).
-    python tools/api_call_sequence.py OUTFILE [TREE]"""
+and hands back the same bits (profiles/api_mirrors_rate.txt).  --emission: the flow through the emission family instead
+(self_emission, table_emission, sightline_emission, sightline_spectra on a domain of each generation: emission_family below;
+profiles/emission_family_rate.txt).
+    python tools/api_call_sequence.py OUTFILE [TREE] [--emission]"""
 import hashlib, os, pickle, sys
 import numpy as np
 
-sys.path.insert(0, os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+sys.path.insert(0, os.path.abspath(ARGS[1]) if len(ARGS) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from synthpy_amd import _ffi
 
 log = []
@@ -43,7 +46,65 @@ def mark(label, *arrays):
     log.append(f"# {label} {h.hexdigest()[:16]}")
 
 
+def finish():
+    with open(ARGS[0], "w") as f:
+        f.write("\n".join(log) + "\n")
+    print(len(log), "lines ->", ARGS[0])
+
+
+def emission_family():
+    """Every entry of the emission family on a 24 x 20 x 16 domain of each generation, both nodes, a pixel grid (handed over in
+    tile order) and chords with a backlight."""
+    from synthpy_amd import sightlines
+    from synthpy_amd.utils.eos_opacity import OpacityTable, SpectralOpacityTable
+
+    dims, cell = (24, 20, 16), 2.5e-4
+    lengths = tuple(cell * (m - 1) for m in dims)
+    rng = np.random.default_rng(22)
+    ne = (1e25 * rng.uniform(0.5, 1.5, dims)).astype(np.float32)
+    Te = (80.0 * rng.uniform(0.5, 1.5, dims)).astype(np.float32)
+    T, D = np.geomspace(1.0, 500.0, 10), np.geomspace(1e17, 1e21, 12)
+    opac = lambda nb: 10.0 ** rng.uniform(1.0, 3.0, (nb, len(T), len(D)))
+    table = OpacityTable(T, D, opac(3), [90.0, 200.0, 450.0], 12.011, emission=opac(3), edges=[[60, 130], [130, 300], [300, 700]])
+    e30 = np.geomspace(30.0, 900.0, 30)
+    spectral = SpectralOpacityTable(T, D, opac(30), e30, 12.011, emission=opac(30), edges=np.stack([e30 / 1.06, e30 * 1.06], axis=1))
+    cam = sightlines.PinholeCamera((0, 0, 20e-3), (0.1, 0, -1), (0, 1, 0), 60e-3, (12, 10), cell * 3)
+    nch = 7
+    origins = np.stack([np.linspace(-2e-3, 2e-3, nch), np.full(nch, -8e-3), np.linspace(-1e-3, 1e-3, nch)])
+    dirs = np.stack([np.linspace(0.1, -0.1, nch), np.ones(nch), np.linspace(-0.05, 0.3, nch)])
+    chords = lambda toward, backlight: sightlines.Chords(origins, dirs, toward, backlight=backlight)
+    lam, e70 = [532e-9, 100e-9], np.geomspace(1.0, 60.0, 70)
+    sight = ("intensity", "optical_depth", "column", "chord", "steps")
+    for gen, dom in (("simulator", d.ScalarDomain(lengths, dims)),
+                     ("legacy", fs.ScalarDomain(*[np.linspace(-L / 2, L / 2, m) for L, m in zip(lengths, dims)], lengths[2] / 2))):
+        dom.external_ne(ne)
+        dom.external_Te(Te)
+        dom.external_Z(3.0)
+        back = rng.uniform(0.0, 2e-7, (2, dims[0], dims[1]))
+        for toward in ("+", "-"):
+            em = dom.self_emission(lam, toward=toward, backlight=back)
+            mark(f"{gen} self_emission {toward}", em.intensity, em.optical_depth, em.transmission)
+        em = dom.table_emission(table)
+        mark(f"{gen} table_emission", em.intensity, em.optical_depth, em.transmission, em.band_radiance)
+        for name, view, kw in (("pinhole", cam, {"wavelengths": lam}), ("pinhole", cam, {"table": table}),
+                               ("chords", chords(-1, rng.uniform(0.0, 2e-7, (2, nch))), {"wavelengths": lam}),
+                               ("chords", chords(-1, rng.uniform(0.0, 2e-7, (3, nch))), {"table": table})):
+            em = dom.sightline_emission(view, **kw)
+            mark(f"{gen} sightline_emission {name} {list(kw)[0]}", *(getattr(em, k) for k in sight), em.transmission)
+        mark(f"{gen} sightline_emission band_radiance", em.band_radiance)
+        for name, view, kw in (("chords", chords(-1, 1e-8), {"photon_energies": e70}),
+                               ("chords", chords(+1, rng.uniform(0.0, 2e-7, (30, nch))), {"table": spectral}),
+                               ("pinhole", cam, {"table": spectral})):
+            sp = dom.sightline_spectra(view, **kw)
+            mark(f"{gen} sightline_spectra {name} {list(kw)[0]}", *(getattr(sp, k) for k in sight), sp.transmission, sp.signal())
+        mark(f"{gen} sightline_spectra band_radiance", sp.band_radiance)
+
+
 engine.init(0)
+if "--emission" in sys.argv:
+    emission_family()
+    finish()
+    sys.exit(0)
 n, ext, lwl, N = 48, 5e-3, 1064e-9, 20000
 x = np.linspace(-ext, ext, n)
 X, Y, Z = np.meshgrid(x, x, x, indexing="ij", sparse=True)
@@ -142,6 +203,4 @@ for regions in (1, 3):
 s = s0[:, :64].flatten()
 ds = p.dsdt(0.0, s, True, True, True, True, ne, B, np.float32(Te), 3.0, sd.x, sd.y, sd.z, 2 * np.pi * engine.c / lwl, 2.62e-13 * lwl ** 2)
 mark("simulator dsdt", ds)
-with open(sys.argv[1], "w") as f:
-    f.write("\n".join(log) + "\n")
-print(len(log), "lines ->", sys.argv[1])
+finish()

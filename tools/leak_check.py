@@ -1,6 +1,6 @@
 """Repeated create / trace / deposit / destroy cycles, and one call of every host-array entry point that owns its device buffers
 for the length of the call (volume from fields and back, power spectrum, FFT field, mode sum, Fresnel gridding and
-propagation, host-array histogram and intensity image): device memory in use must not grow."""
+propagation, host-array histogram and intensity image, sightlines and sightline spectra): device memory in use must not grow."""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,6 +29,8 @@ jones = np.zeros((4, 20000))
 jones[0], jones[2] = rng.uniform(-2.2e-3, 2.2e-3, (2, jones.shape[1]))
 amp, phase = 1.0 + rng.random(jones.shape[1]), rng.standard_normal(jones.shape[1])
 E = rng.standard_normal((2, jones.shape[1])) + 1j * rng.standard_normal((2, jones.shape[1]))
+lines_o = np.stack([rng.uniform(-4e-3, 4e-3, 300), np.full(300, -9e-3), rng.uniform(-4e-3, 4e-3, 300)])
+lines_d = np.stack([rng.uniform(-0.2, 0.2, 300), np.ones(300), rng.uniform(-0.2, 0.2, 300)])
 marks = []
 for it in range(60):
     vol = eng.Volume.from_ne(ne, x, x, x, 1064e-9, "z", phaseshift=True)
@@ -50,6 +52,12 @@ for it in range(60):
     eng.hist2d(jones[0], jones[2], 64, 48, -2e-3, 2e-3, -2e-3, 2e-3)
     eng.intensity2d(jones[0], jones[2], E, [np.pi / 4, -np.pi / 4, None], 64, 48, -2e-3, 2e-3, -2e-3, 2e-3)
     eng.trace(eng.Volume.from_ne(ne, x, x, x, 1064e-9, "z"), s0[:, :1000], eng.default_t_end(5e-3), 5e-3)
+    f_ne = eng.Field(ne, x, x, x)
+    eng.sightlines(f_ne, 60.0, 3.0, lines_o, lines_d, omegas=[3.5e15, 1.9e16], toward=-1, step=1e-4, max_steps=300,
+                   backlight=np.full((2, 300), 1e-8) if it % 2 else None)
+    eng.sightline_spectra(f_ne, 60.0, 3.0, lines_o[:, :16], lines_d[:, :16], omegas=np.geomspace(2e15, 2e16, 70 + 200 * (it % 2)),
+                          toward=+1, step=1e-4, max_steps=300, want=("intensity", "optical_depth", "column"))
+    f_ne.close()
     if it in (9, 59):
         eng.synchronize(); marks.append(used())
 print("device MiB in use after 10 and 60 cycles:", [round(m, 1) for m in marks])
