@@ -353,6 +353,81 @@ int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te, const sr_
                                const double *backlight /* (n, n_freq) or NULL */, double *I, double *tau /* (n, n_freq) */,
                                double *column, double *chord, int32_t *steps /* (n), may be NULL */, double *kernel_ms);
 
+/* ---- line spectra along sightlines: Doppler-shifted, thermally broadened spectral lines ----------
+ * No reference counterpart.  What a spectrometer chord reads: for every line of sight (below a CHORD; a LINE is a spectral line) and
+ * every one of n_freq frequencies (1..SR_MAX_FREQS), the spectral radiance and the optical depth of n_line (1..SR_MAX_LINES)
+ * Gaussian lines whose centre follows the flow along the chord and whose width follows the ion temperature, sample by sample,
+ * optionally on top of the NRL continuum sr_field_sightline_spectra computes.  ne, Te, Z are sr_field_sightlines' fields (a NULL Te
+ * or Z is the uniform p->Te / p->Z); Ti [eV] is a scalar field, NULL: Ti = Te; V [m/s] is a 3-vector field, NULL: no shift, nothing
+ * of V is read and beta = 0.  All fields lie on ONE grid and have one dtype, checked as sr_field_thomson checks them.  Everything is
+ * float64 and every operation below rounds on its own (sightline_lines.hip is compiled with -ffp-contract=off); sqrt and / are the
+ * correctly rounded ones, exp, expm1 and log the device library's.
+ *   table    sr_line_table: nT, nD, LT, LD are exactly sr_emission_table's lattice, ln Te [eV] and ln ni [cm^-3] with
+ *            ni = (ne*1e-6)/Z, searched by the table section's rule (i, ft, j, fd; the edge value holds outside the table); w0[l] is
+ *            the rest angular frequency [rad/s] and A[l] the mass number of the emitting ion of line l; LJ[l][i][j] = ln of the
+ *            frequency-integrated emission coefficient [W m^-3 sr^-1]; LK[l][i][j] = ln of the frequency-integrated absorption
+ *            coefficient [m^-1 rad s^-1], or LK NULL: optically thin lines, LK is never read and aK = 0.  l(T) is the table
+ *            section's bilinear interpolant.
+ *   chord    clip, miss, steps, the sample positions, the gather (Ti and the components of V by the same cell and weights) and the
+ *            march order are sr_field_sightlines', word for word: column, chord and steps are the bits that entry returns.
+ *   sample   with c = 299792458.0, e = 1.602176634e-19, m_p = 1.67262192369e-27, ISP = 0.5641895835477563 and, per line,
+ *            ci_l = (2.0*e)/(A_l*m_p) (formed on the host):
+ *              su = toward/len;  vpar = ((V0*d0 + V1*d1) + V2*d2)*su;  beta = vpar/c
+ *            -- vpar is the flow's component along the direction the light travels; toward and len are sr_field_sightlines'.
+ *            The sample is DARK FOR LINES when Te <= 0, ne <= 0 or Z <= 0 (the table section's dark node), when Ti <= 0, or when
+ *            it lies outside the box.  Otherwise, per line l,
+ *              wc = w0_l*(1.0 + beta);  wd = w0_l*(sqrt(ci_l*Ti)/c);  iw = 1.0/wd;  g = ISP*iw
+ *              aJ = exp(l(LJ_l))*g;  aK = exp(l(LK_l))*g                                      (LK NULL: aK = 0)
+ *   term     per sample and frequency f: j = 0, aL = 0, counted = false; for l ascending
+ *              x = (omega_f - wc)*iw;  x2 = x*x;  the term is dropped when x2 > 40.0 (a NaN is not dropped); otherwise
+ *              phi = exp(-x2);  j = j + aJ*phi;  aL = aL + aK*phi;  counted = true
+ *            A dark sample counts nothing.  (ac, Sc) = the NRL node's alpha and S at omega_f (the self-emission section, with its own
+ *            dark condition) when p->continuum != 0, otherwise 0, 0.
+ *   update   not counted:  dtau = ac*h;  I <- I*exp(-dtau) + Sc*(-expm1(-dtau));  tau <- tau + dtau      (sr_field_sightlines')
+ *            counted:      a = ac + aL;  dtau = a*h
+ *              dtau == 0:  I <- I + j*h
+ *              otherwise:  I <- I*exp(-dtau) + ((ac*Sc + j)/a)*(-expm1(-dtau));  tau <- tau + dtau   (dtau > 0, or a NaN)
+ *            then column <- column + ne*h.  With the continuum off the first case is I <- I*1 + 0*0, tau <- tau + 0: the kernel
+ *            writes I + 0.0 and tau + 0.0, the same bits.  Dropping is exact, so the kernel may skip a line for a whole wavefront
+ *            whose frequencies all lie outside it: x and x2 are monotone in omega_f as rounded.
+ * At a frequency where every term of a chord is dropped, I and tau are the bits of sr_field_sightline_spectra there (continuum on) or
+ * the backlight and 0 (off).  The result for a frequency does not depend on the others or on their order.  A NaN Ti or V makes wc or
+ * iw NaN, x2 NaN and the term counted: the chords through that cell are NaN at every frequency; a NaN ne poisons column, the
+ * continuum, and the frequencies at which a term of that sample is counted.  No atomics: a repeated call returns identical bits.
+ * I, tau and backlight are HOST arrays (n, n_freq) as sr_field_sightline_spectra's; omega, e_ph, c_omega (n_freq) as there, all three
+ * always given.  I is the spectral radiance per unit angular frequency [W m^-2 sr^-1 (rad/s)^-1].  sr_lines_chunk() is the number of
+ * samples the kernel stages at a time (for tests that place sample counts on its boundaries).
+ * Not modelled: Lorentzian, Stark and Voigt wings; Zeeman splitting; line blending through the cutoff at exp(-40); partial
+ * redistribution; refraction; the instrument function (the host applies it, as thomson.py does); one GPU only.
+ * Arguments are checked before the device is touched: everything sr_field_sightline_spectra checks (omega always); a NULL line table
+ * or a NULL LT, LD, w0, A or LJ; n_line outside 1..SR_MAX_LINES; nT or nD outside 2..512; a w0 or an A that is not finite and
+ * positive; a lattice that is not finite or not strictly increasing; a non-finite LJ or LK entry; a Ti with n_comp != 1 or a V with
+ * n_comp != 3, or of another dtype or grid.  n == 0 or n_freq == 0 succeeds and writes nothing. */
+#define SR_MAX_LINES 32
+typedef struct {
+  int32_t nT, nD;        /* lattice nodes, as sr_emission_table                                           */
+  int32_t n_line;        /* 1..SR_MAX_LINES                                                               */
+  int32_t reserved;
+  const double *LT, *LD; /* log of the lattice [eV], [cm^-3]: nT, nD values                               */
+  const double *w0, *A;  /* rest angular frequency [rad/s], mass number of the emitter: n_line values     */
+  const double *LJ, *LK; /* (n_line, nT, nD): log emission [W m^-3 sr^-1], log absorption or NULL (thin)  */
+} sr_line_table;
+typedef struct {
+  int32_t toward;      /* +1 | -1, as sr_sightline_params                                                    */
+  int32_t max_steps;   /* >= 1                                                                               */
+  int32_t continuum;   /* != 0: the lines sit on the NRL continuum                                           */
+  int32_t reserved;
+  double step;         /* target sample spacing [m], finite, > 0                                            */
+  double Te, Z;        /* the uniform field values where the handle is NULL                                  */
+} sr_lines_params;
+int sr_lines_chunk(void);
+int sr_field_sightline_lines(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *Z,
+                             const sr_field *V /* or NULL */, const sr_line_table *lines, const sr_lines_params *p, int64_t n,
+                             const double *origin, const double *dir, int32_t n_freq, const double *omega, const double *e_ph,
+                             const double *c_omega, const double *backlight /* (n, n_freq) or NULL */, double *I,
+                             double *tau /* (n, n_freq) */, double *column, double *chord, int32_t *steps /* (n), may be NULL */,
+                             double *kernel_ms);
+
 /* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
  * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
  * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be

@@ -125,11 +125,24 @@ class DomainExtras:
         wavelengths [m], photon_energies [eV] (the NRL node, which holds only for hbar*omega <~ Te) and table (an
         utils.eos_opacity.SpectralOpacityTable: one frequency per group).  Needs external_Te() and external_Z().  Not modelled: a
         finite pinhole or source, the cos^4 and solid-angle factors of a film's exposure, refraction, the detector's response
-        beyond SightlineSpectra.signal, a table's own ionisation, line shapes and Doppler shifts; one GPU."""
+        beyond SightlineSpectra.signal, a table's own ionisation; one GPU.  Spectral lines are sightline_lines."""
         from .sightlines import sightline_spectra
 
         return sightline_spectra(self, view, wavelengths=wavelengths, photon_energies=photon_energies, table=table, step=step,
                                  max_steps=max_steps)
+
+    def sightline_lines(self, view, lines, wavelengths=None, photon_energies=None, continuum=False, step=None, max_steps=None):
+        """The line spectrum every chord of a sightlines.Chords, PinholeCamera or PointBacklighter sees of this domain: the lines
+        of an utils.eos_opacity.LineTable, Doppler-shifted by the flow (external_V; without it no shift) and broadened by the ion
+        temperature (external_Ti; without it Ti = Te) sample by sample, optionally on sightline_spectra's NRL continuum -- a
+        sightlines.LineSpectra, whose moments() give the flow velocity and Ti a spectrometer would infer.  Exactly one of
+        wavelengths [m] and photon_energies [eV].  Needs external_Te() and external_Z().  Not modelled: Lorentzian, Stark and
+        Voigt wings, Zeeman splitting, line blending through the cutoff at exp(-40), partial redistribution, refraction, the
+        instrument function; one GPU."""
+        from .sightlines import sightline_lines
+
+        return sightline_lines(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
+                               step=step, max_steps=max_steps)
 
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""

@@ -83,6 +83,19 @@ class SpectraParams(C.Structure):
     _fields_ = [("toward", C.c_int32), ("max_steps", C.c_int32), ("step", C.c_double), ("Te", C.c_double), ("Z", C.c_double)]
 
 
+MAX_LINES = 32  # SR_MAX_LINES
+
+
+class LineTable(C.Structure):
+    _fields_ = [("nT", C.c_int32), ("nD", C.c_int32), ("n_line", C.c_int32), ("reserved", C.c_int32), ("LT", C.c_void_p),
+                ("LD", C.c_void_p), ("w0", C.c_void_p), ("A", C.c_void_p), ("LJ", C.c_void_p), ("LK", C.c_void_p)]
+
+
+class LinesParams(C.Structure):
+    _fields_ = [("toward", C.c_int32), ("max_steps", C.c_int32), ("continuum", C.c_int32), ("reserved", C.c_int32),
+                ("step", C.c_double), ("Te", C.c_double), ("Z", C.c_double)]
+
+
 class PushParams(C.Structure):
     _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("max_steps", C.c_int32), ("axis", C.c_int32),
                 ("det_pos", C.c_double), ("hit_scale", C.c_double)]
@@ -167,6 +180,9 @@ SYMBOLS = {
                                  _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_sightline_spectra": (_i, [_vp, _vp, _vp, C.POINTER(EmissionTable), C.POINTER(SpectraParams), _i64, _vp, _vp, C.c_int32,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_lines_chunk": (_i, []),
+    "sr_field_sightline_lines": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(LineTable), C.POINTER(LinesParams), _i64, _vp, _vp, C.c_int32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),

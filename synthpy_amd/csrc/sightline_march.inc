@@ -1,7 +1,8 @@
-// What the two sightline kernels must share so that they return the same bits (include/synthray.h's sightlines section: clip,
-// steps, sample, gather): sightlines.hip (k_sightlines: a line per lane, up to SR_MAX_BANDS bands) and sightline_spectra.hip
-// (k_sightline_spectra: a frequency per lane); after the device code, the host code the two entries run around their kernels.
-// Included inside the including unit's anonymous namespace, after emission_march.inc (EmArgs).
+// What the sightline kernels must share so that they return the same bits (include/synthray.h's sightlines section: clip,
+// steps, sample, gather): sightlines.hip (k_sightlines: a line per lane, up to SR_MAX_BANDS bands), sightline_spectra.hip
+// (k_sightline_spectra: a frequency per lane) and sightline_lines.hip (k_sightline_lines: a frequency per lane, spectral lines on
+// the continuum; its samples also carry Ti and V: FlowSample); after the device code, the host code the entries run around their
+// kernels.  Included inside the including unit's anonymous namespace, after emission_march.inc (EmArgs) and <cstdlib>.
 
 struct LineArgs {
   sr::FieldGrid f;      // lo, hi: the box
@@ -21,9 +22,10 @@ struct Sample {
   sr::Corners<T> ne, Te, Z;
 };
 
-template <typename T, bool HAS_TE, bool HAS_Z>
+// more(ci, cj, ck): the corner reads of the fields a kernel gathers beside ne, Te, Z, at the cell of a sample inside the box
+template <typename T, bool HAS_TE, bool HAS_Z, typename More>
 __device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, double px, double py,
-                                      double pz, Sample<T, HAS_TE, HAS_Z> &s) {
+                                      double pz, Sample<T, HAS_TE, HAS_Z> &s, More &&more) {
   int ci = 0, cj = 0, ck = 0;
   double wx = 0, wy = 0, wz = 0;
   const bool in_x = sr::locate_in<true>(f.g[0], f.n[0], f.inv_h[0], f.lo[0], f.hi[0], px, ci, wx);
@@ -41,7 +43,13 @@ __device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, i
     s.ne = sr::corners_load(static_cast<const T *>(A.ne), 1, 0, sx, sy, ci, cj, ck);
     if (HAS_TE) s.Te = sr::corners_load(static_cast<const T *>(A.Te), 1, 0, sx, sy, ci, cj, ck);
     if (HAS_Z) s.Z = sr::corners_load(static_cast<const T *>(A.Z), 1, 0, sx, sy, ci, cj, ck);
+    more(ci, cj, ck);
   }
+}
+template <typename T, bool HAS_TE, bool HAS_Z>
+__device__ __forceinline__ void fetch(const EmArgs &A, const sr::FieldGrid &f, int64_t sx, int64_t sy, double px, double py,
+                                      double pz, Sample<T, HAS_TE, HAS_Z> &s) {
+  fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, px, py, pz, s, [](int, int, int) {});
 }
 
 // the blended (ne, Te, Z) of a fetched sample; outside the box (within rounding of a face): ne = 0, which either node takes for dark
@@ -112,6 +120,50 @@ __device__ __forceinline__ void fetch_sample(const EmArgs &A, const sr::FieldGri
   fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, l.o0 + l.d0 * t, l.o1 + l.d1 * t, l.o2 + l.d2 * t, s);
 }
 
+// A sample that also carries the ion temperature and the flow (sightline_lines.hip): Sample's cell and weights, and the corners of
+// Ti and of the three components of V (a (nx, ny, nz, 3) field) at the same cell.
+struct FlowArgs {
+  const void *Ti, *V;  // unused where the kernel is instantiated without them
+};
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>
+struct FlowSample {
+  Sample<T, HAS_TE, HAS_Z> s;
+  sr::Corners<T> Ti, V0, V1, V2;
+};
+
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>
+__device__ __forceinline__ void fetch_sample(const EmArgs &A, const FlowArgs &W, const sr::FieldGrid &f, int64_t sx, int64_t sy,
+                                             const Line &l, int k, FlowSample<T, HAS_TE, HAS_Z, HAS_TI, HAS_V> &s) {
+  const double t = l.t0 + ((double)k + 0.5) * l.dt;
+  fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, l.o0 + l.d0 * t, l.o1 + l.d1 * t, l.o2 + l.d2 * t, s.s, [&](int ci, int cj, int ck) {
+    if (HAS_TI) s.Ti = sr::corners_load(static_cast<const T *>(W.Ti), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_V) {
+      s.V0 = sr::corners_load(static_cast<const T *>(W.V), 3, 0, sx, sy, ci, cj, ck);
+      s.V1 = sr::corners_load(static_cast<const T *>(W.V), 3, 1, sx, sy, ci, cj, ck);
+      s.V2 = sr::corners_load(static_cast<const T *>(W.V), 3, 2, sx, sy, ci, cj, ck);
+    }
+  });
+}
+
+// blend_sample's (ne, Te, Z), and Ti (Te where there is no Ti field) and V (0 where there is no V field); outside the box Ti = Te
+// and V = 0 beside blend_sample's ne = 0
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>
+__device__ __forceinline__ void blend_sample(const EmArgs &A, const FlowSample<T, HAS_TE, HAS_Z, HAS_TI, HAS_V> &s, double &ne,
+                                             double &Te, double &Z, double &Ti, double (&V)[3]) {
+  blend_sample<T, HAS_TE, HAS_Z>(A, s.s, ne, Te, Z);
+  Ti = Te;
+  V[0] = V[1] = V[2] = 0.0;
+  if (s.s.in) {
+    const Sample<T, HAS_TE, HAS_Z> &c = s.s;
+    if (HAS_TI) Ti = sr::corners_blend(s.Ti, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    if (HAS_V) {
+      V[0] = sr::corners_blend(s.V0, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+      V[1] = sr::corners_blend(s.V1, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+      V[2] = sr::corners_blend(s.V2, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    }
+  }
+}
+
 // ---- host: what sr_field_sightlines and sr_field_sightline_spectra do around their kernels (`who` names the entry in the error
 // text).  An entry keeps its kernel and dispatch, its table's packing and the checks only it has.
 
@@ -121,6 +173,17 @@ inline int check_march(const char *who, int toward, double step, int max_steps) 
   SR_CHECK(sr::positive(step), "%s: step must be finite and positive", who);
   SR_CHECK(max_steps >= 1, "%s: max_steps must be at least 1, got %d", who, max_steps);
   return SR_OK;
+}
+
+// The kernels with a frequency per lane (sightline_spectra.hip, sightline_lines.hip): lanes per workgroup = frequencies per tile,
+// 256 or 64, whichever leaves fewer lanes of a line's last tile idle, 256 where they tie.  SYNTHRAY_SPECTRA_FL = 64 | 256 overrides
+// the choice (tools/sightline_spectra_rate.py measures the two against each other).
+inline int lane_width(int n_freq) {
+  if (const char *e = getenv("SYNTHRAY_SPECTRA_FL")) {
+    const int v = atoi(e);
+    if (v == 64 || v == 256) return v;
+  }
+  return (n_freq + 255) / 256 * 256 == (n_freq + 63) / 64 * 64 ? 256 : 64;  // 193..256 of every 256
 }
 
 // the lines and the fields: an entry's last checks (n == 0 does not skip them)

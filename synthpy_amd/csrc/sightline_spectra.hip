@@ -169,16 +169,6 @@ __global__ void __launch_bounds__(FL) k_sightline_spectra(EmArgs A, LineArgs L, 
   }
 }
 
-// lanes per workgroup = frequencies per tile.  SYNTHRAY_SPECTRA_FL = 64 | 256 overrides the choice (tools/sightline_spectra_rate.py
-// measures the two against each other).
-int lane_width(int n_freq) {
-  if (const char *e = getenv("SYNTHRAY_SPECTRA_FL")) {
-    const int v = atoi(e);
-    if (v == 64 || v == 256) return v;
-  }
-  return (n_freq + 255) / 256 * 256 == (n_freq + 63) / 64 * 64 ? 256 : 64;  // 193..256 of every 256
-}
-
 }  // namespace
 
 extern "C" int sr_field_sightline_spectra(const sr_field *ne, const sr_field *Te, const sr_field *Z, const sr_emission_table *table,

@@ -16,6 +16,7 @@
 // its dispatch and the entry; what the entry does around the launch is sightline_march.inc's host section, shared with
 // sightline_spectra.hip, emission_march.inc's (bands, EmArgs) and table_node.inc's (the table's checks and band-major packing).
 // Compiled with -ffp-contract=off: products and sums round separately, as the NumPy restatement's do (tests/test_sightlines.py).
+#include <cstdlib>
 #include <vector>
 
 #include "emission_march.inc"

@@ -104,10 +104,12 @@ def _check_table(table, kind):
             raise ValueError(f"table must be {kind} (utils.eos_opacity): it has no {name}")
 
 
-def _upload(domain, fields, run):
-    """What every emission entry shares (self_emission, table_emission, sightlines.sightline_emission and sightline_spectra): the domain's fields
+def _upload(domain, fields, run, more=None):
+    """What every emission entry shares (self_emission, table_emission, sightlines.sightline_emission, sightline_spectra and
+    sightline_lines): the domain's fields
     uploaded by self_emission's rules -- a Te or Z that is a scalar (or broadcast from one) goes as a value, float32 only when
-    every array is float32 (fields.SourceFields.get_all) -- then run(ne, Te, Z), whose result is returned."""
+    every array is float32 (fields.SourceFields.get_all) -- then run(ne, Te, Z), whose result is returned.  more: {name: array |
+    None} of further fields that go up with them, in the same dtype (sightline_lines' Ti and V); run then gets them by keyword."""
     ne, Te, Z = (getattr(domain, name, None) for name in ("ne", "Te", "Z"))
     if ne is None:
         raise ValueError("the domain holds no electron density: pass ne_type= or call external_ne()")
@@ -116,9 +118,10 @@ def _upload(domain, fields, run):
     shape = (len(domain.x), len(domain.y), len(domain.z))
     values = {"Te": uniform(Te), "Z": uniform(Z)}
     named = {name: np.broadcast_to(np.asarray(a), shape) for name, a in (("ne", ne), ("Te", Te), ("Z", Z)) if values.get(name) is None}
+    named.update(more or {})
     with staged(domain, fields) as src:
         f = src.get_all(named)
-        return run(f["ne"], f.get("Te", values["Te"]), f.get("Z", values["Z"]))
+        return run(f["ne"], f.get("Te", values["Te"]), f.get("Z", values["Z"]), **{name: f[name] for name in more or {}})
 
 
 def _march(domain, toward, fields, run):

@@ -635,8 +635,8 @@ def sightline_spectra(ne, Te, Z, origins, directions, *, omegas=None, table=None
     frequency per group, at its photon_energy).  backlight: (n, n_freq) behind the far end of every line, or None.  Returns
     engine.sightlines' dict with "intensity" and "optical_depth" shaped (n, n_freq) -- a line's spectrum is contiguous -- whose
     every element has the bits engine.sightlines returns for that line with that frequency as one of its (up to 4) bands; "column",
-    "chord", "steps" (n).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: what engine.sightlines does not model; line
-    shapes, Doppler shifts, group-integrated Planck functions; one GPU."""
+    "chord", "steps" (n).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: what engine.sightlines does not model;
+    group-integrated Planck functions; one GPU.  Spectral lines are engine.sightline_lines."""
     def params(omegas, n, uniform, t):
         om, e_ph, c_om = spectrum_constants(omegas)
         p = _ffi.SpectraParams()
@@ -647,6 +647,55 @@ def sightline_spectra(ne, Te, Z, origins, directions, *, omegas=None, table=None
                 (len(om), None if t is not None else ptr(om), ptr(e_ph), ptr(c_om)))
 
     return _sightlines(params, "a SpectralOpacityTable", ne, Te, Z, origins, directions, omegas, table, backlight, want)
+
+
+LINES_CHUNK = int(lib.sr_lines_chunk())  # samples of a chord sr_field_sightline_lines' kernel stages at a time
+
+
+def line_table_params(lines):
+    """sr_line_table for an utils.eos_opacity.LineTable (or anything with its members), and the arrays it points into (keep them
+    alive for the call): the logarithms of the lattice, of the emissivity and of the absorption, float64."""
+    LT, LD = np.log(f64(lines.temperatures)), np.log(f64(lines.ion_densities))
+    w0, A = np.atleast_1d(f64(lines.omega0)), np.atleast_1d(f64(lines.mass_number))
+    LJ = np.ascontiguousarray(np.log(f64(lines.emissivity)))
+    LK = None if lines.absorption is None else np.ascontiguousarray(np.log(f64(lines.absorption)))
+    if LJ.ndim != 3 or LJ.shape[1:] != (len(LT), len(LD)) or (LK is not None and LK.shape != LJ.shape):
+        raise ValueError(f"the line table's emissivity has shape {LJ.shape}, its lattice gives (n_line, {len(LT)}, {len(LD)})")
+    if w0.shape != (len(LJ),) or A.shape != (len(LJ),):
+        raise ValueError(f"the line table has {len(LJ)} line(s), {w0.size} rest frequencies and {A.size} mass numbers")
+    t = _ffi.LineTable()
+    t.nT, t.nD, t.n_line, t.reserved = len(LT), len(LD), len(LJ), 0
+    t.LT, t.LD, t.w0, t.A, t.LJ, t.LK = ptr(LT), ptr(LD), ptr(w0), ptr(A), ptr(LJ), ptr(LK)
+    return t, (LT, LD, w0, A, LJ, LK)
+
+
+def sightline_lines(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, continuum=False, toward, step, max_steps,
+                    backlight=None, want=_SIGHT_WANT):
+    """Spectral lines along every chord: the spectral radiance and the optical depth of the 1 to _ffi.MAX_LINES (32) lines of
+    `lines` (an utils.eos_opacity.LineTable) at 1 to _ffi.MAX_FREQS angular frequencies `omegas` [rad/s], a GPU lane per frequency
+    (sr_field_sightline_lines; include/synthray.h states the rule).  Each line is a Gaussian whose centre is shifted by the flow
+    V [m/s] (a vector Field, or None: no shift) along the direction the light travels and whose width is the thermal one of Ti
+    [eV] (a Field, or None: Ti = Te), sample by sample; emission and absorption strength come from the table at the sample's
+    (Te, ne / Z).  continuum=True puts the lines on engine.sightline_spectra's NRL continuum.  Chords, ne, Te, Z (Fields or
+    uniform numbers), toward, step, max_steps, backlight ((n, n_freq)) and want are engine.sightline_spectra's, and so is the dict
+    returned; where no line reaches a frequency its values have engine.sightline_spectra's bits (continuum) or are the backlight
+    and 0.  ne.last_kernel_ms keeps the kernel's time.  Not modelled: Lorentzian, Stark and Voigt wings, Zeeman splitting, line
+    blending through the cutoff at exp(-40), partial redistribution, refraction, the instrument function; one GPU."""
+    h_Ti, h_V = _handle("Ti", Ti, none=True), _handle("V", V, none=True)
+    t, keep = line_table_params(lines)
+
+    def params(omegas, n, uniform, _):
+        om, e_ph, c_om = spectrum_constants(omegas)
+        p = _ffi.LinesParams()
+        p.toward, p.max_steps, p.continuum, p.reserved, p.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
+        p.Te, p.Z = uniform
+
+        def entry(h_ne, h_Te, h_Z, _, *rest):  # the family's argument order -> sr_field_sightline_lines'
+            return lib.sr_field_sightline_lines(h_ne, h_Te, h_Ti, h_Z, h_V, C.byref(t), *rest)
+
+        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
+
+    return _sightlines(params, "a LineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
 
 
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED

@@ -10,6 +10,8 @@
     sightlines.Chords(origins, directions, toward=-1)                   # any lines: diodes, bolometers, spectrometer chords
     sp = domain.sightline_spectra(chords, photon_energies=np.geomspace(1, 50, 2048))   # a spectrum per line, a GPU lane per frequency
     sp.intensity, sp.signal(response)                                   # (N, n_freq); the response-weighted integral per line
+    ls = domain.sightline_lines(chords, line_table, wavelengths=lam)    # Doppler-shifted, thermally broadened lines (LineSpectra)
+    ls.moments(window)                                                  # per chord and line: radiance, flow velocity, Ti
 
 emission.self_emission and table_emission march columns parallel to a grid axis.  Here the same radiative-transfer recurrence,
 dI/ds = alpha (S - I), runs along half-lines from a point: a pinhole camera looks along lines that CONVERGE on the pinhole
@@ -214,10 +216,11 @@ def _check_view(view):
         raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
 
 
-def _along(domain, view, fields, entry, n_band, axis, step, max_steps, **node):
-    """What the two entries share once the node is known: the defaults of step and max_steps, the view's lines and backlight in the
+def _along(domain, view, fields, entry, n_band, axis, step, max_steps, more=None, **node):
+    """What the entries share once the node is known: the defaults of step and max_steps, the view's lines and backlight in the
     order they go to the kernel in, entry(ne, Te, Z, ...) on the domain's fields, and its five arrays -- their lines along `axis`:
-    -1 (bands first, the backlight (n_band, N)) or 0 (lines first, (N, n_band)) -- back in the view's order and shape."""
+    -1 (bands first, the backlight (n_band, N)) or 0 (lines first, (N, n_band)) -- back in the view's order and shape.  more:
+    emission._upload's further fields, which entry gets by keyword."""
     step = default_step(domain) if step is None else float(step)
     max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
     o, d = view.lines()
@@ -228,8 +231,8 @@ def _along(domain, view, fields, entry, n_band, axis, step, max_steps, **node):
         back = None if back is None else back[:, perm]
     if back is not None and axis == 0:
         back = np.ascontiguousarray(back.T)
-    res = _upload(domain, fields, lambda ne, Te, Z: entry(ne, Te, Z, o, d, toward=view.toward, step=step, max_steps=max_steps,
-                                                         backlight=back, **node))
+    res = _upload(domain, fields, lambda ne, Te, Z, **f: entry(ne, Te, Z, o, d, toward=view.toward, step=step, max_steps=max_steps,
+                                                              backlight=back, **f, **node), more)
 
     def place(a):  # kernel order -> the view's order and shape
         if perm is not None:
@@ -331,8 +334,8 @@ def sightline_spectra(domain, view, wavelengths=None, photon_energies=None, tabl
     4-band sightline_emission calls that gives the same numbers (profiles/sightline_spectra_rate.txt, 256^3): 16 chords x 2048
     frequencies 0.42 ms of kernel against 1.4 s, a 256 x 256 view x 64 frequencies 2.5 (NRL) to 3.9 (table) times faster.
     Not modelled: a finite pinhole or source size, the cos^4 and solid-angle factors that turn radiance into film exposure,
-    refraction of the light, the detector's response beyond signal(), a table's own ionisation, line shapes and Doppler shifts,
-    group-integrated Planck functions; one GPU."""
+    refraction of the light, the detector's response beyond signal(), a table's own ionisation, group-integrated Planck
+    functions; one GPU.  Spectral lines with their Doppler shifts and widths are sightline_lines."""
     if sum(a is not None for a in (wavelengths, photon_energies, table)) != 1:
         raise ValueError("exactly one of wavelengths, photon_energies (the NRL node) and table (a SpectralOpacityTable) must be given")
     _check_view(view)
@@ -345,3 +348,85 @@ def sightline_spectra(domain, view, wavelengths=None, photon_energies=None, tabl
         kw, edges = {"table": table}, getattr(table, "edges", None)
     maps = _along(domain, view, fields, engine.sightline_spectra, len(omega), 0, step, max_steps, **kw)
     return SightlineSpectra(view, *maps, omega, edges)
+
+
+M_P = 1.67262192369e-27  # kg
+
+
+class LineSpectra(SightlineSpectra):
+    """A SightlineSpectra of spectral lines: `lines` is the utils.eos_opacity.LineTable they came from; signal() works unchanged."""
+
+    def __init__(self, view, intensity, optical_depth, column, chord, steps, omega, lines):
+        super().__init__(view, intensity, optical_depth, column, chord, steps, omega)
+        self.lines = lines
+
+    def moments(self, window):
+        """What a spectrometer infers from each line, on the host, per chord and per line: a dict of "radiance", "velocity" and
+        "Ti", each view.shape + (n_line,).  window: the half-width [rad/s] (a number, or one per line) of the frequency window
+        |omega - omega0| <= window the moments are taken over, by the trapezoid over the frequencies in ascending order:
+            radiance = int I d omega  [W m^-2 sr^-1]
+            velocity = c * (int I (omega - omega0) d omega / radiance) / omega0  [m/s]: the line-of-sight velocity of the centroid,
+                       positive (a blue shift) where the plasma moves towards the observer
+            Ti       = A m_p c^2 var / (e omega0^2)  [eV], var the second central moment: the ion temperature of a Gaussian of
+                       that variance (its 1/e half-width is omega0 sqrt(2 e Ti / (A m_p)) / c)
+        Nothing is subtracted: a continuum or a neighbouring line inside the window counts.  A window with fewer than two
+        frequencies or no radiance gives NaN."""
+        w0 = self.lines.omega0
+        win = np.broadcast_to(np.asarray(window, np.float64), w0.shape)
+        if not np.all(np.isfinite(win) & (win > 0)):
+            raise ValueError(f"window must be finite and positive (a number or one per line), got {window!r}")
+        k = np.argsort(self.omega, kind="stable")
+        w, y = self.omega[k], self.intensity[..., k]
+        out = {name: np.full(tuple(self.view.shape) + w0.shape, np.nan) for name in ("radiance", "velocity", "Ti")}
+
+        def integral(f, x):
+            return np.sum(0.5 * (f[..., 1:] + f[..., :-1]) * np.diff(x), axis=-1)
+
+        for l in range(len(w0)):
+            sel = np.abs(w - w0[l]) <= win[l]
+            if np.count_nonzero(sel) < 2:
+                continue
+            x, f = w[sel] - w0[l], y[..., sel]
+            with np.errstate(all="ignore"):
+                m0 = integral(f, x)
+                m1 = integral(f * x, x) / m0
+                var = integral(f * (x - m1[..., None]) ** 2, x) / m0
+                ok = m0 > 0
+                out["radiance"][..., l] = np.where(ok, m0, np.nan)
+                out["velocity"][..., l] = np.where(ok, c * m1 / w0[l], np.nan)
+                out["Ti"][..., l] = np.where(ok, self.lines.mass_number[l] * M_P * c ** 2 * var / (engine.E_CHARGE * w0[l] ** 2), np.nan)
+        return out
+
+
+def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, step=None, max_steps=None,
+                    fields=None):
+    """The line spectrum `view` (Chords, a PinholeCamera or a PointBacklighter) sees of a domain of either API generation along
+    each of its chords: a LineSpectra (engine.sightline_lines -> sr_field_sightline_lines; include/synthray.h states the rule).
+    lines: an utils.eos_opacity.LineTable of 1 to 32 lines; each is a Gaussian whose centre moves with the flow's component along
+    the direction the light travels (the domain's V, external_V; without it no shift) and whose width is the thermal one of the
+    ion temperature (Ti, external_Ti; without it Ti = Te), sample by sample, with the table's emission and absorption at the
+    sample's (Te, ne / Z).  Exactly one of wavelengths [m] and photon_energies [eV]: up to 16384 frequencies, in any order (a
+    sorted list lets the kernel skip a line for whole wavefronts).  continuum=True puts the lines on sightline_spectra's NRL
+    continuum, with its caveat (hbar*omega <~ Te).  view.backlight, step, max_steps, the tile order of a pixel grid and fields=
+    are sightline_spectra's; Ti and V go up under the names thomson.spectra uses, so one fields.SourceFields serves both.
+    Not modelled: Lorentzian, Stark and Voigt wings, Zeeman splitting, line blending through the cutoff at exp(-40), partial
+    redistribution, refraction, the instrument function (convolve on the host, as thomson.instrument_convolve does); one GPU."""
+    if (wavelengths is None) == (photon_energies is None):
+        raise ValueError("exactly one of wavelengths [m] and photon_energies [eV] must be given")
+    _check_view(view)
+    for name in ("temperatures", "ion_densities", "emissivity", "omega0", "mass_number", "absorption"):
+        if not hasattr(lines, name):
+            raise ValueError(f"lines must be a LineTable (utils.eos_opacity): it has no {name}")
+    omega = _spectrum_omegas(wavelengths, photon_energies)
+    shape = (len(domain.x), len(domain.y), len(domain.z))
+    Ti, V = getattr(domain, "Ti", None), getattr(domain, "V", None)
+    more = {"Ti": None if Ti is None else (np.asarray(Ti) if np.ndim(Ti) == 3 else np.full(shape, float(Ti))),
+            "V": None if V is None else np.asarray(V)}
+    if more["V"] is not None and more["V"].shape != shape + (3,):
+        raise ValueError(f"V has shape {more['V'].shape}, the domain needs {shape + (3,)}")
+
+    def entry(ne, Te, Z, o, d, Ti=None, V=None, **kw):
+        return engine.sightline_lines(ne, Te, Ti, Z, V, o, d, lines=lines, omegas=omega, continuum=continuum, **kw)
+
+    maps = _along(domain, view, fields, entry, len(omega), 0, step, max_steps, more)
+    return LineSpectra(view, *maps, omega, lines)

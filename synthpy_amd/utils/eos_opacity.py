@@ -5,6 +5,9 @@ engine.emission_table -> sr_field_emission_table; no reference counterpart).
     d = read_propaceos("carbon.prp", need_emiss_opacity=True, need_abs_opacity=True)
     table = OpacityTable.from_propaceos(d, A=12.011)
     em = domain.table_emission(table)
+
+LineTable holds spectral lines on the same kind of lattice, from arrays: what sightlines.sightline_lines consumes
+(engine.sightline_lines -> sr_field_sightline_lines; no reference counterpart).
 """
 from __future__ import annotations
 
@@ -234,3 +237,78 @@ class SpectralOpacityTable(OpacityTable):
         sr_field_sightline_spectra lays the table out for its kernel; LE is None for LTE."""
         LT, LD, LA, LE = self.logs()
         return LT, LD, np.ascontiguousarray(LA.transpose(1, 2, 0)), None if LE is None else np.ascontiguousarray(LE.transpose(1, 2, 0))
+
+
+MAX_LINES = 32  # sr_field_sightline_lines: 1..32 spectral lines
+_HBAR, _E_CHARGE, _C = 6.62607015e-34 / (2 * np.pi), 1.602176634e-19, 299792458.0
+
+
+class LineTable:
+    """Spectral lines on a temperature x ion-density lattice: what sr_field_sightline_lines interpolates
+    (sightlines.sightline_lines, engine.sightline_lines), from arrays.
+
+    temperatures [eV] and ion_densities [cm^-3]: strictly increasing, finite, positive, 2 to 512 entries each (OpacityTable's
+    lattice).  emissivity: (n_line, nT, nD) (a 2-D array is one line), the frequency-integrated emission coefficient of each line
+    [W m^-3 sr^-1], finite and positive, 1 to 32 lines.  Exactly one of wavelengths [m] and photon_energy [eV], one per line: the
+    line's rest position (omega0 [rad/s] keeps it).  mass_number: the emitting ion's mass number, a number or one per line (the
+    thermal width is sqrt(2 e Ti / (A m_p)) omega0 / c).  absorption: (n_line, nT, nD), the frequency-integrated absorption
+    coefficient [m^-1 rad s^-1], or None: optically thin lines.  ValueError names the offending member."""
+
+    def __init__(self, temperatures, ion_densities, emissivity, wavelengths=None, photon_energy=None, mass_number=None,
+                 absorption=None):
+        lattice = OpacityTable(temperatures, ion_densities, np.ones((1, np.size(temperatures), np.size(ion_densities))), 1.0, 1.0)
+        self.temperatures, self.ion_densities = lattice.temperatures, lattice.densities
+        shape = (len(self.temperatures), len(self.ion_densities))
+        self.emissivity = OpacityTable._opacity("emissivity", emissivity, shape)
+        n_line = len(self.emissivity)
+        if not 1 <= n_line <= MAX_LINES:
+            raise ValueError(f"emissivity must hold 1 to {MAX_LINES} lines, got {n_line}")
+        self.absorption = None if absorption is None else OpacityTable._opacity("absorption", absorption, shape)
+        if self.absorption is not None and self.absorption.shape != self.emissivity.shape:
+            raise ValueError(f"absorption has shape {self.absorption.shape}, emissivity {self.emissivity.shape}")
+        if (wavelengths is None) == (photon_energy is None):
+            raise ValueError("exactly one of wavelengths [m] and photon_energy [eV] must be given")
+        name = "wavelengths" if photon_energy is None else "photon_energy"
+        pos = np.array(wavelengths if photon_energy is None else photon_energy, np.float64, ndmin=1)
+        if pos.shape != (n_line,) or not np.all(np.isfinite(pos) & (pos > 0)):
+            raise ValueError(f"{name} must be {n_line} finite positive value(s), got {pos.tolist()}")
+        self.omega0 = 2 * np.pi * _C / pos if photon_energy is None else pos * _E_CHARGE / _HBAR
+        if mass_number is None:
+            raise ValueError("mass_number must be given: the emitting ion's mass number, a number or one per line")
+        A = np.array(mass_number, np.float64, ndmin=1)
+        if A.shape not in ((1,), (n_line,)) or not np.all(np.isfinite(A) & (A > 0)):
+            raise ValueError(f"mass_number must be a finite positive number or {n_line} of them, got {A.tolist()}")
+        self.mass_number = np.array(np.broadcast_to(A, (n_line,)))
+
+    @property
+    def n_line(self):
+        return len(self.emissivity)
+
+    @property
+    def wavelengths(self):
+        """The lines' rest wavelengths [m]."""
+        return 2 * np.pi * _C / self.omega0
+
+    @property
+    def photon_energy(self):
+        """The lines' rest photon energies [eV]."""
+        return _HBAR * self.omega0 / _E_CHARGE
+
+    def thermal_width(self, Ti):
+        """The 1/e half-width in angular frequency of every line at the ion temperature Ti [eV]: omega0 sqrt(2 e Ti / (A m_p)) / c."""
+        return self.omega0 * np.sqrt(2 * _E_CHARGE * float(Ti) / (self.mass_number * 1.67262192369e-27)) / _C
+
+    def planck(self):
+        """B_omega(omega0, T) on the lattice's temperatures, (n_line, nT) [W m^-2 sr^-1 (rad/s)^-1]."""
+        w = self.omega0[:, None]
+        return _HBAR * w ** 3 / (4 * np.pi ** 3 * _C ** 2) / np.expm1(_HBAR * w / _E_CHARGE / self.temperatures[None, :])
+
+    def with_lte_absorption(self):
+        """This table with absorption = emissivity / B_omega(omega0, T) (Kirchhoff: ln K = ln J - ln B on the lattice), so that
+        every line's source function is Planck's and a thick line saturates at it."""
+        out = LineTable.__new__(LineTable)
+        out.__dict__.update(self.__dict__)
+        out.absorption = np.ascontiguousarray(self.emissivity / self.planck()[:, :, None])
+        if not np.all(np.isfinite(out.absorption) & (out.absorption > 0)):
+            raise ValueError("the Planck function under- or overflows on this lattice: no LTE absorption")
+        return out
