@@ -428,6 +428,88 @@ int sr_field_sightline_lines(const sr_field *ne, const sr_field *Te, const sr_fi
                              double *tau /* (n, n_freq) */, double *column, double *chord, int32_t *steps /* (n), may be NULL */,
                              double *kernel_ms);
 
+/* ---- Voigt lines along sightlines: Stark and Lorentz wings on the Doppler-shifted lines ----------
+ * No reference counterpart.  sr_field_sightline_lines with a Lorentzian half-width per line from the table, so that every line is a
+ * Voigt profile -- what a Stark-broadened line of a dense plasma looks like, and what an electron density is read from.  Wherever
+ * nothing is said here the rule is sr_field_sightline_lines', word for word: the chord, the clip, the samples, the gather, the dark
+ * conditions, beta, wc, wd, iw, g, aJ, aK, the continuum, the update, column, chord and steps.  Everything is float64 and every
+ * operation rounds on its own (sightline_voigt.hip is compiled with -ffp-contract=off); exp, sin, cos and rint are the device
+ * library's.
+ *   table    sr_voigt_table: `lines` is that entry's table; LG[l][i][j] = ln of the Lorentzian half width at half maximum of line l
+ *            [rad/s] on the same lattice, finite.
+ *   sample   per line l of a sample that is not dark:  gam = exp(l(LG_l));  a = gam*iw, with l(.) the table section's bilinear
+ *            interpolant at the same (i, ft, j, fd).
+ *   term     cut = wing*wing, formed once on the host (wing = p->wing > 0 in Doppler 1/e widths, +inf allowed).  Per sample and
+ *            frequency f, for l ascending:
+ *              x = (omega_f - wc)*iw;  x2 = x*x;  the term is dropped when x2 > cut (a NaN is not dropped); otherwise
+ *              phi = V(a, x);  j = j + aJ*phi;  aL = aL + aK*phi;  counted = true
+ *   V(a, x)  the Voigt function H(a, x) = Re w(x + i a), w the Faddeeva function, normalised so that H(0, x) = exp(-x^2): with
+ *            aJ = exp(l(LJ))*ISP*iw the line integrates to exp(l(LJ)) over omega, exactly as the Gaussian does.  With
+ *            z2 = x*x + a*a the regions are tested in this order:
+ *              not z2 < 1e17 (a NaN or an infinity too):   V = (ISP*a)/z2
+ *              z2 >= 100.0:                                V = CF(10)
+ *              a >= 2.0:                                   V = CF(40)
+ *              a <= 0.5:                                   V = R(0.25, 2.0, 0.5, CA, 13)
+ *              otherwise (0.5 < a < 2):                    V = R(0.1875, 2.6666666666666665, 0.375, CB, 18)
+ *            CF(K), Laplace's continued fraction of w(z) truncated at K levels, as one rational function:
+ *              Nr = x;  Ni = a;  Dr = 1;  Di = 0;  for k = K, K-1, ..., 1 in this order, with c = 0.5*k:
+ *                  tr = (Nr*x - Ni*a) - c*Dr;   ti = (Nr*a + Ni*x) - c*Di;   Dr = Nr;  Di = Ni;  Nr = tr;  Ni = ti
+ *              V = (ISP*(Dr*Ni - Di*Nr))/(Nr*Nr + Ni*Ni)
+ *            -- t_K = z, t_(k-1) = z - (k/2)/t_k as t = N/D, w = (i/sqrt(pi))/t_0 = (i/sqrt(pi)) D/N.
+ *            R(h, ih2, h2, C, NP), Rybicki's sampling form of Dawson's function (the Thomson section's D) at z = x + i a:
+ *              n0 = 2.0*rint(ih2*x);  xp = x - h*n0;  a2 = a*a;  g = exp(a2 - xp*xp);  th = (2.0*a)*xp
+ *              Gr = g*cos(th);  Gi = -(g*sin(th));  pe = exp(h2*xp);  me = 1.0/pe;  ca = cos(h2*a);  sa = sin(h2*a)
+ *              pr = pe*ca;  pi = pe*sa;  mr = me*ca;  mi = -(me*sa)
+ *              p2r = pr*pr - pi*pi;  p2i = (2.0*pr)*pi;  m2r = mr*mr - mi*mi;  m2i = (2.0*mr)*mi
+ *              d0 = n0*n0;  Sr = 0;  Si = 0;  for k = 0, 1, ..., NP-1 in this order, with n = 2k + 1:
+ *                  q = C[k]/(d0 - n*n)
+ *                  Sr = Sr + q*(pr*(n0 - n) + mr*(n0 + n));   Si = Si + q*(pi*(n0 - n) + mi*(n0 + n))
+ *                  (pr, pi) = (pr*p2r - pi*p2i, pr*p2i + pi*p2r);   (mr, mi) = (mr*m2r - mi*m2i, mr*m2i + mi*m2r)
+ *              imF = (Gr*Si + Gi*Sr)*ISP;   V = exp(a2 - x*x)*cos((2.0*a)*x) - (2.0*ISP)*imF
+ *            -- H = Re e^(-z^2) - (2/sqrt(pi)) Im F(z), F(z) = (1/sqrt(pi)) e^(-z'^2) sum_(n odd) C_n e^(2 h n z')/(n0 + n) with
+ *            z' = z - h n0; the terms n and -n over one denominator, the powers of e^(2 h z') by complex multiplication.
+ *            CA[k] = exp(-((2k+1)/4)^2) is the Thomson section's C[n]; CB[k] = exp(-(3(2k+1)/16)^2): 0.9654545521978378,
+ *            0.7287633299194912, 0.4152368286818413, 0.17859113461243561, 0.0579800525002544, 0.014208622931196246,
+ *            0.002628330960567707, 0.0003669972327972938, 3.8681223753184774e-05, 3.0774591584232196e-06, 1.8481578772048032e-07,
+ *            8.378003053124454e-09, 2.866794996873118e-10, 7.404699497933558e-12, 1.4436865682659833e-13, 2.1246777523216493e-15,
+ *            2.3603037795421644e-17, 1.9792352186549065e-19.  The step 3/16 keeps the sampling form's aliasing term,
+ *            exp(-(pi/(2h))^2 + pi*a/h), under 1.2e-16 up to a = 2 (with h = 1/4 it is 4e-15 at a = 0.5 and 6e-7 at a = 2).
+ *            Accuracy, measured against the real part of scipy.special.wofz on a in {1e-10, ..., 1e7} x x in [0, 1e7] with points
+ *            a hair on either side of every boundary above (tests/test_sightline_voigt.py states the grid): the worst error
+ *            RELATIVE TO H ITSELF is 1.6e-13, at a just under 2 where exp(a2) = 55 is cancelled; elsewhere 7e-14 or less.  The only
+ *            absolute floor is the continued fractions': they drop the Gaussian core Re e^(-z^2), at most exp(a2 - x*x) <=
+ *            exp(-(z2 - 2 a2)).  In CF(10)'s region that is exp(-100) = 3.7e-44 for a -> 0 against H >= ISP*a/z2 = 5.6e-13 at
+ *            a = 1e-10, z2 = 100 (6.6e-32 of H, and less for every larger a of the grid up to a = 5, beyond which CF(40)'s bound
+ *            holds); in CF(40)'s region a >= 2 and the core is exp(a2 - x*x)|cos| against H ~ ISP/a: it is part of what the 40
+ *            levels converge to, not dropped.  ISP*a/z2 errs by 1/(2 z2) <= 5e-18.
+ *   wing     dropping is exact for the reason it is in the line section: x and x2 are monotone in omega_f as rounded, so a
+ *            wavefront may skip a line whose window [-wing, wing] holds none of its frequencies (that section's test of the two
+ *            ends, against cut).  With wing = +inf nothing is ever dropped or skipped.  Where every term of a chord is dropped, I and
+ *            tau are the bits of sr_field_sightline_spectra (continuum on) or the backlight and 0 (off).
+ *   LG NULL  Gaussian lines: the entry computes sr_field_sightline_lines' rule with its cut at 40 and returns that entry's bits in
+ *            I, tau, column, chord and steps; wing is not read.
+ * NaN, poisoning and repeatability are the line section's: a NaN a or x gives a NaN term that is counted; no atomics; a repeated
+ * call returns identical bits.  sr_voigt_chunk() is the number of samples this kernel stages at a time.
+ * Not modelled: Zeeman splitting; asymmetric and shifted Stark profiles (a line's Stark shift can go into w0 only as a constant);
+ * ion-dynamics corrections; blending through wing; partial redistribution; refraction; the instrument function; one GPU only.
+ * Arguments are checked before the device is touched: everything sr_field_sightline_lines checks; a non-finite LG entry; a wing
+ * that is NaN or <= 0 (where LG is given). */
+typedef struct {
+  sr_line_table lines;
+  const double *LG; /* (n_line, nT, nD): ln of the Lorentzian HWHM [rad/s], finite; or NULL: Gaussian lines */
+} sr_voigt_table;
+typedef struct {
+  sr_lines_params march;
+  double wing;      /* > 0, may be +inf; in Doppler 1/e widths: a term with |x| > wing is dropped */
+} sr_voigt_params;
+int sr_voigt_chunk(void);
+int sr_field_sightline_voigt(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *Z,
+                             const sr_field *V /* or NULL */, const sr_voigt_table *lines, const sr_voigt_params *p, int64_t n,
+                             const double *origin, const double *dir, int32_t n_freq, const double *omega, const double *e_ph,
+                             const double *c_omega, const double *backlight /* (n, n_freq) or NULL */, double *I,
+                             double *tau /* (n, n_freq) */, double *column, double *chord, int32_t *steps /* (n), may be NULL */,
+                             double *kernel_ms);
+
 /* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
  * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
  * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be

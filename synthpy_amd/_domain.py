@@ -144,6 +144,18 @@ class DomainExtras:
         return sightline_lines(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
                                step=step, max_steps=max_steps)
 
+    def sightline_voigt(self, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None):
+        """sightline_lines with Voigt profiles: the lines of an utils.eos_opacity.VoigtLineTable, each with the Lorentzian (Stark,
+        natural) half-width its table gives at the sample's temperature and ion density beside the thermal width of Ti -- a
+        sightlines.LineSpectra, whose fwhm() gives the width an electron density is read from.  wing: terms further than that
+        many thermal 1/e widths from a line's centre are dropped (None: never).  Everything else is sightline_lines'.  Not
+        modelled: Zeeman splitting, asymmetric and shifted Stark profiles, ion dynamics, blending through wing, partial
+        redistribution, refraction, the instrument function; one GPU."""
+        from .sightlines import sightline_voigt
+
+        return sightline_voigt(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
+                               wing=wing, step=step, max_steps=max_steps)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
         from .utils.handle_filetypes import export_scalar_field

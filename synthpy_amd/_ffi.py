@@ -96,6 +96,14 @@ class LinesParams(C.Structure):
                 ("step", C.c_double), ("Te", C.c_double), ("Z", C.c_double)]
 
 
+class VoigtTable(C.Structure):
+    _fields_ = [("lines", LineTable), ("LG", C.c_void_p)]
+
+
+class VoigtParams(C.Structure):
+    _fields_ = [("march", LinesParams), ("wing", C.c_double)]
+
+
 class PushParams(C.Structure):
     _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("max_steps", C.c_int32), ("axis", C.c_int32),
                 ("det_pos", C.c_double), ("hit_scale", C.c_double)]
@@ -183,6 +191,9 @@ SYMBOLS = {
     "sr_lines_chunk": (_i, []),
     "sr_field_sightline_lines": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(LineTable), C.POINTER(LinesParams), _i64, _vp, _vp, C.c_int32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_voigt_chunk": (_i, []),
+    "sr_field_sightline_voigt": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(VoigtTable), C.POINTER(VoigtParams), _i64, _vp, _vp, C.c_int32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
@@ -251,6 +262,8 @@ for _name, (_res, _args) in SYMBOLS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header and library out of step
     _fn.restype = _res
     _fn.argtypes = _args
+
+VOIGT_CHUNK = int(lib.sr_voigt_chunk())  # samples of a chord sr_field_sightline_voigt's kernel stages at a time
 
 
 def last_error() -> str:

@@ -698,6 +698,52 @@ def sightline_lines(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, con
     return _sightlines(params, "a LineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
 
 
+VOIGT_CHUNK = _ffi.VOIGT_CHUNK  # samples of a chord sr_field_sightline_voigt's kernel stages at a time
+
+
+def voigt_table_params(lines):
+    """sr_voigt_table for an utils.eos_opacity.VoigtLineTable (or anything with its members; a table without lorentz_width, or with
+    None there, gives LG NULL: Gaussian lines), and the arrays it points into (keep them alive for the call)."""
+    t, keep = line_table_params(lines)
+    width = getattr(lines, "lorentz_width", None)
+    LG = None if width is None else np.ascontiguousarray(np.log(f64(width)))
+    if LG is not None and LG.shape != keep[4].shape:
+        raise ValueError(f"the line table's lorentz_width has shape {LG.shape}, its emissivity {keep[4].shape}")
+    v = _ffi.VoigtTable()
+    v.lines, v.LG = t, ptr(LG)
+    return v, keep + (LG,)
+
+
+def sightline_voigt(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, continuum=False, wing=np.inf, toward, step, max_steps,
+                    backlight=None, want=_SIGHT_WANT):
+    """engine.sightline_lines with Voigt profiles: every line of `lines` (an utils.eos_opacity.VoigtLineTable) has, beside its
+    thermal width, the Lorentzian half-width [rad/s] the table gives at the sample's (Te, ne / Z) -- Stark and natural broadening --
+    and its shape is the Voigt function of the two, accurate relative to itself far into the wings (sr_field_sightline_voigt;
+    include/synthray.h states the rule and the algorithm).  wing: a term further than `wing` thermal 1/e widths from its line's
+    centre is dropped (+inf, the default: never; a finite wing lets the kernel skip a line for whole wavefronts of a sorted
+    frequency list).  Everything else -- the chords, the fields, continuum, toward, step, max_steps, backlight, want and the dict
+    returned -- is engine.sightline_lines'; a table without lorentz_width gives that entry's bits.  ne.last_kernel_ms keeps the
+    kernel's time.  Not modelled: Zeeman splitting, asymmetric and shifted Stark profiles, ion dynamics, blending through wing,
+    partial redistribution, refraction, the instrument function; one GPU."""
+    h_Ti, h_V = _handle("Ti", Ti, none=True), _handle("V", V, none=True)
+    t, keep = voigt_table_params(lines)
+
+    def params(omegas, n, uniform, _):
+        om, e_ph, c_om = spectrum_constants(omegas)
+        p = _ffi.VoigtParams()
+        m = p.march
+        m.toward, m.max_steps, m.continuum, m.reserved, m.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
+        m.Te, m.Z = uniform
+        p.wing = float(wing)
+
+        def entry(h_ne, h_Te, h_Z, _, *rest):  # the family's argument order -> sr_field_sightline_voigt's
+            return lib.sr_field_sightline_voigt(h_ne, h_Te, h_Ti, h_Z, h_V, C.byref(t), *rest)
+
+        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
+
+    return _sightlines(params, "a VoigtLineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
+
+
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
 _PUSH_WANT = ("sf", "hits", "steps", "flags")
 

@@ -370,7 +370,8 @@ class LineSpectra(SightlineSpectra):
             Ti       = A m_p c^2 var / (e omega0^2)  [eV], var the second central moment: the ion temperature of a Gaussian of
                        that variance (its 1/e half-width is omega0 sqrt(2 e Ti / (A m_p)) / c)
         Nothing is subtracted: a continuum or a neighbouring line inside the window counts.  A window with fewer than two
-        frequencies or no radiance gives NaN."""
+        frequencies or no radiance gives NaN.  Ti assumes a Gaussian line: a Voigt line (sightline_voigt) has no variance, and
+        its "Ti" grows with the window without bound; use fwhm() there."""
         w0 = self.lines.omega0
         win = np.broadcast_to(np.asarray(window, np.float64), w0.shape)
         if not np.all(np.isfinite(win) & (win > 0)):
@@ -397,6 +398,38 @@ class LineSpectra(SightlineSpectra):
                 out["Ti"][..., l] = np.where(ok, self.lines.mass_number[l] * M_P * c ** 2 * var / (engine.E_CHARGE * w0[l] ** 2), np.nan)
         return out
 
+    def fwhm(self, window):
+        """The full width at half maximum [rad/s] of each line, on the host, per chord and per line: view.shape + (n_line,).
+        window: as moments()'.  Inside |omega - omega0| <= window, over the frequencies in ascending order, the greatest
+        intensity is the maximum; on either side of it the nearest pair of neighbouring frequencies between which the intensity
+        falls through half of it gives a crossing by linear interpolation, and the width is the distance of the two crossings.
+        NaN where either side has no crossing (the window ends above half maximum, or holds fewer than three frequencies).
+        Nothing is subtracted: a continuum or a neighbour inside the window counts, and a thick line's width is its saturated one."""
+        w0 = self.lines.omega0
+        win = np.broadcast_to(np.asarray(window, np.float64), w0.shape)
+        if not np.all(np.isfinite(win) & (win > 0)):
+            raise ValueError(f"window must be finite and positive (a number or one per line), got {window!r}")
+        k = np.argsort(self.omega, kind="stable")
+        w, y = self.omega[k], self.intensity[..., k]
+        out = np.full((int(np.prod(self.view.shape, dtype=np.int64)), len(w0)), np.nan)
+        for l in range(len(w0)):
+            sel = np.abs(w - w0[l]) <= win[l]
+            if np.count_nonzero(sel) < 3:
+                continue
+            x, f = w[sel], y[..., sel].reshape(len(out), -1)
+            for r, g in enumerate(f):
+                if not np.all(np.isfinite(g)) or not g.max() > 0:
+                    continue
+                top, half = int(np.argmax(g)), 0.5 * g.max()
+                lo, hi = np.nonzero(g[:top] <= half)[0], np.nonzero(g[top + 1:] <= half)[0]
+                if len(lo) == 0 or len(hi) == 0:
+                    continue
+                a, b = lo[-1], top + 1 + hi[0]
+                left = x[a] + (x[a + 1] - x[a]) * (half - g[a]) / (g[a + 1] - g[a])
+                right = x[b - 1] + (x[b] - x[b - 1]) * (g[b - 1] - half) / (g[b - 1] - g[b])
+                out[r, l] = right - left
+        return out.reshape(tuple(self.view.shape) + w0.shape)
+
 
 def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, step=None, max_steps=None,
                     fields=None):
@@ -411,6 +444,15 @@ def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None,
     are sightline_spectra's; Ti and V go up under the names thomson.spectra uses, so one fields.SourceFields serves both.
     Not modelled: Lorentzian, Stark and Voigt wings, Zeeman splitting, line blending through the cutoff at exp(-40), partial
     redistribution, refraction, the instrument function (convolve on the host, as thomson.instrument_convolve does); one GPU."""
+    if getattr(lines, "lorentz_width", None) is not None:
+        raise ValueError("lines is a VoigtLineTable: its Lorentzian widths need sightline_voigt (sightline_lines draws Gaussian lines)")
+    return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_lines,
+                         continuum=continuum)
+
+
+def _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, call, **opts):
+    """What sightline_lines and sightline_voigt share: the checks, the frequencies, the domain's Ti and V, and `call` (the engine's
+    entry, with `opts`) along the view."""
     if (wavelengths is None) == (photon_energies is None):
         raise ValueError("exactly one of wavelengths [m] and photon_energies [eV] must be given")
     _check_view(view)
@@ -426,7 +468,25 @@ def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None,
         raise ValueError(f"V has shape {more['V'].shape}, the domain needs {shape + (3,)}")
 
     def entry(ne, Te, Z, o, d, Ti=None, V=None, **kw):
-        return engine.sightline_lines(ne, Te, Ti, Z, V, o, d, lines=lines, omegas=omega, continuum=continuum, **kw)
+        return call(ne, Te, Ti, Z, V, o, d, lines=lines, omegas=omega, **opts, **kw)
 
     maps = _along(domain, view, fields, entry, len(omega), 0, step, max_steps, more)
     return LineSpectra(view, *maps, omega, lines)
+
+
+def sightline_voigt(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
+                    fields=None):
+    """sightline_lines with Voigt profiles: a LineSpectra (engine.sightline_voigt -> sr_field_sightline_voigt; include/synthray.h
+    states the rule and the algorithm of the Voigt function).  lines: an utils.eos_opacity.VoigtLineTable, whose lorentz_width is
+    each line's Lorentzian half-width at half maximum [rad/s] on the lattice -- Stark and natural broadening; a line's shape at a
+    sample is the Voigt function of that and the thermal width of Ti, accurate relative to itself at any distance from the centre,
+    so the far wings of a thick line are right.  wing: a term further than `wing` thermal 1/e widths from its line's centre is
+    dropped; None: never (a finite wing lets the kernel skip a line for whole wavefronts of a sorted frequency list, at the price
+    of a step of the dropped wing's height in the spectrum).  LineSpectra.fwhm() reads each line's width, from which
+    VoigtLineTable.power_law's density follows; moments()' Ti does not apply to such lines.  Everything else is sightline_lines'.
+    Not modelled: Zeeman splitting, asymmetric and shifted Stark profiles (a constant Stark shift can go into the line's rest
+    position), ion dynamics, blending through wing, partial redistribution, refraction, the instrument function; one GPU."""
+    if getattr(lines, "lorentz_width", None) is None:
+        raise ValueError("lines must be a VoigtLineTable (utils.eos_opacity): it has no lorentz_width")
+    return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_voigt,
+                         continuum=continuum, wing=np.inf if wing is None else wing)
