@@ -626,6 +626,56 @@ int sr_field_thomson(const sr_field *ne, const sr_field *Te, const sr_field *Ti 
                      const double *pts, const double *wts, const double *ki, const double *ks, int32_t n_lambda,
                      const double *lambda, double *P, double *weight, double *kernel_ms);
 
+/* ---- optical Thomson scattering with several ion species and drifting electrons --------------------------------
+ * No reference counterpart.  sr_field_thomson's model with n_species = 1 .. SR_MAX_SPECIES Maxwellian ion species in place of one
+ * and, optionally, electrons that drift against the ions.  Species j = 0 .. n_species-1 has the mass number p->A[j] (uniform), the
+ * charge Z_j and the relative abundance f_j -- each either the scalar sr_field Zs[j] / fracs[j] or, where that entry (or the whole
+ * array) is NULL, the uniform p->Z[j] / p->frac[j].  The f_j are relative ion NUMBER fractions and need not sum to 1.  Ti and the
+ * flow V are shared by all species.  Vd [m/s] is a 3-vector sr_field: the drift of the electrons relative to the ions,
+ * Vd = -J/(e ne); NULL: no drift, nothing of Vd is read and the electron line reads ae = a.  All fields lie on ONE grid and have
+ * one dtype.  Everything sr_field_thomson states holds unchanged -- the constants, the `volume` and `wavelength` lines, the gather
+ * rule, D(x), the `output` line, float64 throughout, thomson_multi.hip compiled with -ffp-contract=off -- with
+ * ci_j = (2.0*e)/(A_j*m_p) formed on the host and
+ *   point q       ne, Te, Ti and V as sr_field_thomson gathers them; every Z_j and f_j that is a field and the three components of
+ *                 Vd with the same cell and weights.  The point is DROPPED under sr_field_thomson's conditions, when any gathered
+ *                 Z_j, f_j or component of Vd is NaN, or when any Z_j < 0 or f_j < 0.  Otherwise wn, ivte, pe, vs, vi as there and
+ *                   zb = 0.0;  for j ascending: zb = zb + f_j*Z_j
+ *                   c_j = zb > 0.0 ? (f_j*Z_j)/zb : 0.0;  g_j = Z_j*c_j;  zt_j = (g_j*Te)/Ti;  ivti_j = 1.0/sqrt(ci_j*Ti)
+ *                   ds = (D0*ks0 + D1*ks1) + D2*ks2;  di = (D0*ki0 + D1*ki1) + D2*ki2         (D = Vd; only when Vd is given)
+ *                 -- c_j is the share of the electrons that species j supplies, g_j = Z_j^2 n_j/ne.
+ *   sample (l, q) wp = w - (ksc*vs - kin*vi)  (V given, else wp = w);  a = wp*rk
+ *                 ae = (wp - (ksc*ds - kin*di))*rk  (Vd given, else ae = a)
+ *                 xe = ae*ivte;  al = pe*rk2;  (Fe, Ee) = D(xe);  cer = al*(1.0 - (2.0*xe)*Fe);  cei = al*((SP*xe)*Ee)
+ *                 er = 1.0 + cer;  ei = cei;  sr = 1.0;  si = 0.0
+ *                 for j ascending:  xi = a*ivti_j;  az = al*zt_j;  (Fi, Ei_j) = D(xi)
+ *                                   cir = az*(1.0 - (2.0*xi)*Fi);  cii = az*((SP*xi)*Ei_j)
+ *                                   er = er + cir;  ei = ei + cii;  sr = sr + cir;  si = si + cii
+ *                 ie2 = 1.0/(er*er + ei*ei);  n1 = sr*sr + si*si;  n2 = cer*cer + cei*cei;  t = n2*ie2
+ *                 ion = 0.0;  for j ascending: ion = ion + ((g_j*t)*Ei_j)*ivti_j
+ *                 S = (TSP*rk) * (((n1*ie2)*Ee)*ivte + ion)
+ *               -- S = (2 pi/k) [ |1 + sum_j chi_j|^2/|eps|^2 f_e + sum_j (Z_j^2 n_j/ne) |chi_e|^2/|eps|^2 f_j ] with
+ *               chi_j = alpha^2 (Z_j^2 n_j/ne)(Te/Ti) W(xi_j), the electrons' argument moved by k.Vd.  A species whose g_j is 0
+ *               at a point adds exact zeros (the kernel skips it).  One species with f = 1 and Z >= 0 gives sr_field_thomson's
+ *               bits: c = 1 exactly, and every added 0.0 + and 1.0 + is exact.
+ * Arguments are checked before the device is touched: everything sr_field_thomson checks; n_species outside 1 .. SR_MAX_SPECIES;
+ * an A[j] not finite and positive; a uniform Z[j] or frac[j] that is read (its field is NULL) and is not finite or is negative;
+ * Vd with n_comp != 3; a Zs or fracs entry with n_comp != 1 (named Z0.., f0.. in the text); differing dtypes or grids.
+ * n_vol == 0 or n_lambda == 0 succeeds and writes nothing. */
+#define SR_MAX_SPECIES 4
+typedef struct {
+  double lambda_i;      /* probe wavelength [m] */
+  int32_t n_species;    /* 1 .. SR_MAX_SPECIES */
+  int32_t reserved;
+  double A[SR_MAX_SPECIES];     /* mass numbers (m_j = A_j*m_p) */
+  double Z[SR_MAX_SPECIES];     /* the uniform charge of species j where Zs[j] is NULL */
+  double frac[SR_MAX_SPECIES];  /* the uniform relative abundance of species j where fracs[j] is NULL */
+} sr_thomson_multi_params;      /* 112 bytes */
+int sr_field_thomson_multi(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *V /* or NULL */,
+                           const sr_field *Vd /* or NULL */, const sr_field *const *Zs /* NULL, or n_species entries each field or NULL */,
+                           const sr_field *const *fracs /* likewise */, const sr_thomson_multi_params *p, int64_t n_vol,
+                           int32_t n_quad, const double *pts, const double *wts, const double *ki, const double *ks,
+                           int32_t n_lambda, const double *lambda, double *P, double *weight, double *kernel_ms);
+
 /* ---- wave optics: a paraxial split-step march of a complex field through a domain ----------
  * No counterpart in the reference's sources (its authors compare the tracer with a CPU beam-propagation library,
  * evaluation/c.f._diffraction).  A complex scalar field U on a uniform lateral FRAME of mu x mv pixels is carried through the

@@ -63,6 +63,11 @@ class DomainExtras:
         read it."""
         self.V = V
 
+    def external_Vd(self, Vd):
+        """(nx, ny, nz, 3) grid of the electrons' drift relative to the ions in m/s, -J/(e ne) (thomson.drift_velocity): the
+        asymmetry of the ion-acoustic peaks in thomson_scattering_multi.  The tracer does not read it."""
+        self.Vd = Vd
+
     def proton_radiograph(self, source, det_pos, **kw):
         """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
         particles have crossed this domain's B (external_B / test_B) and E (external_E): a radiography.Radiograph.
@@ -78,6 +83,14 @@ class DomainExtras:
         from .thomson import spectra
 
         return spectra(self, probe, collection, wavelengths, ion_mass, **kw)
+
+    def thomson_scattering_multi(self, probe, collection, wavelengths, species, **kw):
+        """thomson_scattering for a plasma of several ion species -- `species`, 1 to 4 thomson.Species (mass number, charge,
+        relative number fraction; this domain's Z is not read) sharing Ti and V -- whose electrons may drift against the ions
+        (external_Vd): a thomson.ThomsonSpectra.  Keywords: thomson.spectra_multi's."""
+        from .thomson import spectra_multi
+
+        return spectra_multi(self, probe, collection, wavelengths, species, **kw)
 
     def wave_propagate(self, source, **kw):
         """The wave-optics march of a wave.Source through this domain's ne along its probing_direction: a wave.WaveField on

@@ -121,6 +121,14 @@ class ThomsonParams(C.Structure):
     _fields_ = [("lambda_i", C.c_double), ("A", C.c_double), ("Z", C.c_double)]
 
 
+MAX_SPECIES = 4  # SR_MAX_SPECIES
+
+
+class ThomsonMultiParams(C.Structure):
+    _fields_ = [("lambda_i", C.c_double), ("n_species", C.c_int32), ("reserved", C.c_int32), ("A", C.c_double * MAX_SPECIES),
+                ("Z", C.c_double * MAX_SPECIES), ("frac", C.c_double * MAX_SPECIES)]
+
+
 class WaveParams(C.Structure):
     _fields_ = [("axis", C.c_int32), ("toward", C.c_int32), ("mu", C.c_int32), ("mv", C.c_int32), ("u0", C.c_double),
                 ("du", C.c_double), ("v0", C.c_double), ("dv", C.c_double), ("lambda_", C.c_double), ("omega", C.c_double),
@@ -197,6 +205,8 @@ SYMBOLS = {
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_thomson_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _pp, _pp, C.POINTER(ThomsonMultiParams), _i64, C.c_int32, _vp, _vp, _vp,
+                                    _vp, C.c_int32, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_wave": (_i, [_vp, _vp, _vp, C.POINTER(WaveParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_wave_image": (_i, [C.POINTER(WaveImageParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),

@@ -799,6 +799,9 @@ def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, im
     return out
 
 
+MAX_SPECIES = _ffi.MAX_SPECIES  # the ion species thomson_multi takes at most
+
+
 def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavelengths):
     """The Thomson-scattering spectral density summed over the quadrature of each scattering volume (sr_field_thomson;
     include/synthray.h states the rule): (P (M, n_lambda), weight (M)) float64, P = (1/2pi) sum_q w_q ne_q S_q (1 + 2w/wi)
@@ -809,6 +812,14 @@ def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavel
     wavelengths (n_lambda) [m].  ne.last_kernel_ms keeps the kernel's time."""
     handles = [_handle("ne", ne), _handle("Te", Te), _handle("Ti", Ti, none=True), _handle("Z", Z, number=True),
                _handle("V", V, none=True)]
+    p = _ffi.ThomsonParams()
+    p.lambda_i, p.A, p.Z = float(lambda_i), float(ion_mass), 0.0 if isinstance(Z, Field) else float(Z)
+    return _thomson(lib.sr_field_thomson, ne, handles, p, points, weights, ki, ks, wavelengths)
+
+
+def _thomson(entry, ne, head, p, points, weights, ki, ks, wavelengths):
+    """What thomson and thomson_multi share: the volumes' arrays, the outputs and ne's kernel time; entry: the library call, head: its
+    arguments before the params p."""
     points, weights = f64(points), f64(weights)
     if points.ndim != 3 or points.shape[2] != 3 or weights.shape != points.shape[:2]:
         raise ValueError(f"points must be (M, Nq, 3) and weights (M, Nq), got {points.shape} and {weights.shape}")
@@ -822,14 +833,33 @@ def thomson(ne, Te, Ti, Z, V, lambda_i, ion_mass, points, weights, ki, ks, wavel
     lam = f64(wavelengths)
     if lam.ndim != 1:
         raise ValueError(f"wavelengths must be one-dimensional, got shape {lam.shape}")
-    p = _ffi.ThomsonParams()
-    p.lambda_i, p.A, p.Z = float(lambda_i), float(ion_mass), 0.0 if isinstance(Z, Field) else float(Z)
     P, weight = np.zeros((M, len(lam))), np.zeros(M)
     ms = C.c_double(0.0)
-    check(lib.sr_field_thomson(*handles, C.byref(p), M, nq, ptr(points), ptr(weights), ptr(dirs[0]), ptr(dirs[1]), len(lam), ptr(lam),
-                               ptr(P), ptr(weight), C.byref(ms)))
+    check(entry(*head, C.byref(p), M, nq, ptr(points), ptr(weights), ptr(dirs[0]), ptr(dirs[1]), len(lam), ptr(lam), ptr(P), ptr(weight),
+                C.byref(ms)))
     ne.last_kernel_ms = float(ms.value)
     return P, weight
+
+
+def thomson_multi(ne, Te, Ti, V, Vd, species, lambda_i, points, weights, ki, ks, wavelengths):
+    """thomson for a plasma of 1 to _ffi.MAX_SPECIES ion species whose electrons may drift against the ions
+    (sr_field_thomson_multi; include/synthray.h states the rule): (P (M, n_lambda), weight (M)) float64.  ne, Te, Ti, V and the
+    volumes' arguments are thomson's.  Vd [m/s]: a vector Field, the electrons' drift relative to the ions -J/(e ne), or None (no
+    drift).  species: a sequence of (A, Z, fraction) -- the mass number, and the charge and the relative number fraction (they need
+    not sum to 1), each a scalar Field or a float (uniform, not negative).  All fields on one grid and of one dtype.
+    ne.last_kernel_ms keeps the kernel's time."""
+    head = [_handle("ne", ne), _handle("Te", Te), _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("Vd", Vd, none=True)]
+    species = [tuple(s) for s in species]
+    n = len(species)
+    if not 1 <= n <= _ffi.MAX_SPECIES or any(len(s) != 3 for s in species):
+        raise ValueError(f"species must be 1 to {_ffi.MAX_SPECIES} entries (A, Z, fraction), got {n}")
+    p = _ffi.ThomsonMultiParams()
+    p.lambda_i, p.n_species, p.reserved = float(lambda_i), n, 0
+    Zs, fracs = (C.c_void_p * n)(), (C.c_void_p * n)()
+    for j, (A, Z, frac) in enumerate(species):
+        Zs[j], fracs[j] = _handle(f"Z{j}", Z, number=True), _handle(f"f{j}", frac, number=True)
+        p.A[j], p.Z[j], p.frac[j] = float(A), 0.0 if isinstance(Z, Field) else float(Z), 0.0 if isinstance(frac, Field) else float(frac)
+    return _thomson(lib.sr_field_thomson_multi, ne, head + [Zs, fracs], p, points, weights, ki, ks, wavelengths)
 
 
 def wave_params(frame, shape, lambda_, axis, toward=+1, Z=0.0, time_parts=False):

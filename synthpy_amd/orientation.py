@@ -27,7 +27,7 @@ _QUARTER = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}  
 # vacuum for ne and B; Te at external_Te's floor Te_min = 1.0; Z = 1.0 (kappa() divides by neither's zero)
 DEFAULT_FILL = {"ne": 0.0, "Te": 1.0, "Z": 1.0, "B": 0.0}
 _E_FILL = 0.0  # a domain's E (external_E; proton radiography) is vacuum outside the source box, or fill["E"]
-_EXTRA_FILL = {"E": _E_FILL, "Ti": DEFAULT_FILL["Te"], "V": 0.0}  # the fields only some domains hold: Ti as Te, V at rest
+_EXTRA_FILL = {"E": _E_FILL, "Ti": DEFAULT_FILL["Te"], "V": 0.0, "Vd": 0.0}  # the fields only some domains hold: Ti as Te, V and Vd at rest
 
 
 def rotation_matrix(angle_deg, about="y"):
@@ -94,10 +94,10 @@ def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=N
     """A new ScalarDomain of the same generation and flags holding the source's fields seen from the frame turned by R =
     rotation_matrix(angle_deg, about), or `matrix` (orthonormal to 1e-12, else ValueError): ne'(q) = ne(R q), Te and Z the
     same when they are arrays (scalars pass through), B'(q) = R^T B(R q), and E as B when the domain holds one; Ti goes as Te and
-    the flow V as B when the domain holds them.  The view grid
+    the flow V and the electron drift Vd (external_Vd) as B when the domain holds them.  The view grid
     is the source's lengths and dims unless `dims` / `lengths` say otherwise.  Outside the source box the fields take `fill`:
     None for the defaults
-    (DEFAULT_FILL: vacuum, Te_min, Z = 1), a number for ne, or a dict over "ne", "Te", "Z", "B", "E", "Ti", "V" (Ti: Te_min, V: at rest).  `source`: a SourceFields
+    (DEFAULT_FILL: vacuum, Te_min, Z = 1), a number for ne, or a dict over "ne", "Te", "Z", "B", "E", "Ti", "V", "Vd" (Ti: Te_min, V and Vd: at rest).  `source`: a SourceFields
     of the same domain whose uploads are reused (views())."""
     if (angle_deg is None) == (matrix is None):
         raise ValueError("give either angle_deg (with about) or matrix")
@@ -129,9 +129,10 @@ def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=N
         E = getattr(domain, "E", None)
         if E is not None:
             new.E = src.get("E", E).resample(R, zero, grid, V=R.T, fill=fills.get("E", _E_FILL))
-        V = getattr(domain, "V", None)
-        if V is not None:
-            new.V = src.get("V", V).resample(R, zero, grid, V=R.T, fill=fills.get("V", _EXTRA_FILL["V"]))
+        for name in ("V", "Vd"):
+            v = getattr(domain, name, None)
+            if v is not None:
+                setattr(new, name, src.get(name, v).resample(R, zero, grid, V=R.T, fill=fills.get(name, _EXTRA_FILL[name])))
     return new
 
 

@@ -27,7 +27,7 @@ class ScalarDomain(_domain.DomainExtras):
             dims (int | 3 ints): number of nodes per axis
             ne_type (str): 'test_null' | 'test_slab' | 'test_linear_cos' | 'test_exponential_cos' | None
         """
-        self.ne = self.B = self.Te = self.Z = self.E = self.Ti = self.V = None
+        self.ne = self.B = self.Te = self.Z = self.E = self.Ti = self.V = self.Vd = None
         self.inv_brems, self.phaseshift, self.B_on = inv_brems, phaseshift, B_on
         if probing_direction not in ("x", "y", "z"):
             raise ValueError(f"probing_direction must be 'x', 'y' or 'z', got {probing_direction!r}")

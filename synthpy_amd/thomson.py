@@ -10,6 +10,15 @@ ne, Te, Ti, Z and the flow V at every quadrature point and sums the spectral den
 them, per wavelength (engine.thomson -> sr_field_thomson; include/synthray.h states the rule).  Validity: non-relativistic,
 unmagnetised, Maxwellian electrons and one Maxwellian ion species sharing the flow, vacuum wavenumbers (ne << n_crit), no probe
 absorption or refraction, no collection optics beyond one direction per volume.
+
+Several ion species and a current (spectra_multi; engine.thomson_multi -> sr_field_thomson_multi):
+
+    ch = [thomson.Species(12, 6, 0.5), thomson.Species(1, 1, 0.5)]             # mass number, charge, relative number fraction
+    domain.external_Vd(thomson.drift_velocity(J, domain.ne))                    # the electrons' drift against the ions, -J/(e ne)
+    sp = domain.thomson_scattering_multi(probe, coll, wavelengths, ch)
+
+1 to 4 Maxwellian ion species that share Ti and the flow; their relative Landau damping shapes the ion-acoustic feature, and the
+drift shows as the asymmetry of its two peaks.  A species' charge and fraction may vary over the grid.
 """
 from __future__ import annotations
 
@@ -183,28 +192,55 @@ def spectra(domain, probe, collection, wavelengths, ion_mass, instrument_fwhm=No
     ne, Te, Z = getattr(domain, "ne", None), getattr(domain, "Te", None), getattr(domain, "Z", None)
     if ne is None or Te is None or Z is None:
         raise ValueError("the domain needs ne, Te (external_Te) and Z (external_Z)")
-    Ti, V = getattr(domain, "Ti", None), getattr(domain, "V", None)
-    lam = np.asarray(wavelengths, np.float64)
-    if lam.ndim != 1 or not np.all(np.isfinite(lam)) or np.any(lam <= 0):
-        raise ValueError("wavelengths must be one-dimensional, finite and positive")
+    lam = _wavelengths(wavelengths)
     ion_mass = float(ion_mass)
     if not (np.isfinite(ion_mass) and ion_mass > 0):
         raise ValueError(f"ion_mass must be finite and positive, got {ion_mass!r}")
-    ks, ki = collection.direction, probe.direction
-    if np.any(np.all(ks == ki[None, :], axis=1)):
-        raise ValueError("a collection direction equals the probe's direction: no scattering wavevector")
-    shape = np.shape(ne)
-    named = {"ne": np.asarray(ne), "Te": np.asarray(Te) if np.ndim(Te) == 3 else np.full(shape, float(Te)),
-             "Ti": None if Ti is None else (np.asarray(Ti) if np.ndim(Ti) == 3 else np.full(shape, float(Ti))),
-             "Z": np.asarray(Z) if np.ndim(Z) == 3 else None, "V": None if V is None else np.asarray(V)}
-    if named["V"] is not None and named["V"].shape != tuple(shape) + (3,):
-        raise ValueError(f"V has shape {named['V'].shape}, the domain needs {tuple(shape) + (3,)}")
+    named = _plasma_arrays(domain, probe, collection)
+    named["Z"] = np.asarray(Z) if np.ndim(Z) == 3 else None
+    named["V"] = named.pop("V")  # the order the fields go up in: ne, Te, Ti, Z, V
     pts, wts = collection.quadrature(probe)
     with staged(domain, fields) as src:
         f = src.get_all(named)  # the kernel reads every field in one dtype
         P, weight = engine.thomson(f["ne"], f["Te"], f["Ti"], f["Z"] if f["Z"] is not None else float(Z), f["V"],
-                                   probe.wavelength, ion_mass, pts, wts, ki, ks, lam)
+                                   probe.wavelength, ion_mass, pts, wts, probe.direction, collection.direction, lam)
         kernel_ms = f["ne"].last_kernel_ms
+    return _spectra_of(domain, probe, collection, lam, named, P, weight, kernel_ms, instrument_fwhm)
+
+
+def _wavelengths(wavelengths):
+    lam = np.asarray(wavelengths, np.float64)
+    if lam.ndim != 1 or not np.all(np.isfinite(lam)) or np.any(lam <= 0):
+        raise ValueError("wavelengths must be one-dimensional, finite and positive")
+    return lam
+
+
+def _vector(domain, name, shape):
+    """The domain's vector field `name` as an array of the grid's shape + (3,), or None."""
+    v = getattr(domain, name, None)
+    if v is None:
+        return None
+    v = np.asarray(v)
+    if v.shape != tuple(shape) + (3,):
+        raise ValueError(f"{name} has shape {v.shape}, the domain needs {tuple(shape) + (3,)}")
+    return v
+
+
+def _plasma_arrays(domain, probe, collection):
+    """What spectra and spectra_multi read alike: {ne, Te, Ti | None, V | None} as arrays on the grid, after the check that every
+    volume has a scattering wavevector."""
+    if np.any(np.all(collection.direction == probe.direction[None, :], axis=1)):
+        raise ValueError("a collection direction equals the probe's direction: no scattering wavevector")
+    ne, Te, Ti = domain.ne, domain.Te, getattr(domain, "Ti", None)
+    shape = np.shape(ne)
+    return {"ne": np.asarray(ne), "Te": np.asarray(Te) if np.ndim(Te) == 3 else np.full(shape, float(Te)),
+            "Ti": None if Ti is None else (np.asarray(Ti) if np.ndim(Ti) == 3 else np.full(shape, float(Ti))),
+            "V": _vector(domain, "V", shape)}
+
+
+def _spectra_of(domain, probe, collection, lam, named, P, weight, kernel_ms, instrument_fwhm):
+    """The ThomsonSpectra of the engine's P and weight: r_e^2 and the polarisation factor, the instrument function, theta, alpha."""
+    ks, ki = collection.direction, probe.direction
     pol = 1.0 if probe.polarisation is None else 1.0 - (ks @ probe.polarisation) ** 2
     power = (R_E * R_E * pol * np.ones(len(ks)))[:, None] * P
     if instrument_fwhm is not None:
@@ -216,3 +252,70 @@ def spectra(domain, probe, collection, wavelengths, ion_mass, instrument_fwhm=No
     with np.errstate(divide="ignore", invalid="ignore"):
         alpha = np.where((ne_c > 0) & (Te_c > 0), np.sqrt(ne_c * E_CHARGE / (EPS0 * Te_c)) / k, np.nan)
     return ThomsonSpectra(lam, power, weight, theta, alpha, kernel_ms)
+
+
+class Species:
+    """One ion species of spectra_multi: the mass number `mass`, the charge `charge` and the relative number fraction `fraction`
+    among the ions (the fractions need not sum to 1) -- charge and fraction each a number or an (nx, ny, nz) array on the domain's
+    grid, finite numbers not negative (a NaN or negative node of an array drops the points that read it)."""
+
+    def __init__(self, mass, charge, fraction=1.0):
+        self.mass = float(mass)
+        if not (np.isfinite(self.mass) and self.mass > 0):
+            raise ValueError(f"a species' mass must be finite and positive, got {mass!r}")
+        self.charge, self.fraction = (self._value(name, v) for name, v in (("charge", charge), ("fraction", fraction)))
+
+    @staticmethod
+    def _value(name, v):
+        if np.ndim(v) == 0:
+            v = float(v)
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"a species' {name} must be finite and not negative, got {v!r}")
+            return v
+        v = np.asarray(v)
+        if v.ndim != 3:
+            raise ValueError(f"a species' {name} must be a number or an (nx, ny, nz) array, got shape {v.shape}")
+        return v
+
+
+def drift_velocity(J, ne):
+    """The electrons' drift relative to the ions [m/s] of the current density J (nx, ny, nz, 3) [A/m^2] and ne (nx, ny, nz)
+    [m^-3]: -J/(e ne), and 0 where ne <= 0 -- what external_Vd takes."""
+    J, ne = np.asarray(J, np.float64), np.asarray(ne, np.float64)
+    if J.shape != ne.shape + (3,):
+        raise ValueError(f"J has shape {J.shape}, ne's {ne.shape} needs {ne.shape + (3,)}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((ne > 0)[..., None], -J / (E_CHARGE * ne[..., None]), 0.0)
+
+
+def spectra_multi(domain, probe, collection, wavelengths, species, instrument_fwhm=None, fields=None):
+    """spectra for a plasma of several ion species whose electrons may drift against the ions: `species` is a sequence of 1 to 4
+    Species (mass number, charge, relative number fraction; domain.Z is not read), the drift is domain.Vd (external_Vd; see
+    drift_velocity; without it none); ne, Te, Ti and V are read as spectra reads them, and all species share Ti and V.  A
+    ThomsonSpectra, power = r_e^2 (1 - (ks . e)^2) P with P engine.thomson_multi's.  The species' arrays go up under the names
+    Z0.., f0.. and the drift as Vd, so a fields.SourceFields serves a fit loop over other arguments."""
+    if not isinstance(probe, Probe) or not isinstance(collection, Collection):
+        raise ValueError("probe must be a thomson.Probe and collection a thomson.Collection")
+    if getattr(domain, "ne", None) is None or getattr(domain, "Te", None) is None:
+        raise ValueError("the domain needs ne and Te (external_Te)")
+    lam = _wavelengths(wavelengths)
+    species = list(species)
+    if not 1 <= len(species) <= engine.MAX_SPECIES or not all(isinstance(s, Species) for s in species):
+        raise ValueError(f"species must be 1 to {engine.MAX_SPECIES} thomson.Species, got {len(species)} entries")
+    named = _plasma_arrays(domain, probe, collection)
+    shape = named["ne"].shape
+    named["Vd"] = _vector(domain, "Vd", shape)
+    for j, s in enumerate(species):
+        for name, v in ((f"Z{j}", s.charge), (f"f{j}", s.fraction)):
+            if np.ndim(v) == 3:
+                if v.shape != shape:
+                    raise ValueError(f"the array {name} of species {j} has shape {v.shape}, the domain needs {shape}")
+                named[name] = v
+    pts, wts = collection.quadrature(probe)
+    with staged(domain, fields) as src:
+        f = src.get_all(named)  # the kernel reads every field in one dtype
+        triples = [(s.mass, f.get(f"Z{j}", s.charge), f.get(f"f{j}", s.fraction)) for j, s in enumerate(species)]
+        P, weight = engine.thomson_multi(f["ne"], f["Te"], f["Ti"], f["V"], f["Vd"], triples, probe.wavelength, pts, wts,
+                                         probe.direction, collection.direction, lam)
+        kernel_ms = f["ne"].last_kernel_ms
+    return _spectra_of(domain, probe, collection, lam, named, P, weight, kernel_ms, instrument_fwhm)
