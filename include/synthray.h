@@ -510,6 +510,88 @@ int sr_field_sightline_voigt(const sr_field *ne, const sr_field *Te, const sr_fi
                              double *tau /* (n, n_freq) */, double *column, double *chord, int32_t *steps /* (n), may be NULL */,
                              double *kernel_ms);
 
+/* ---- Zeeman-split lines along sightlines: Stokes I, Q, U, V of lines in a magnetic field ----------
+ * No reference counterpart.  sr_field_sightline_voigt with every line split by the magnetic field B [T] of the sample into its
+ * Zeeman components (the weak-field, LS-coupling pattern the table gives), and four Stokes parameters marched along the chord
+ * instead of one intensity -- what a polarisation-resolved spectrometer reads of a magnetised plasma.  Wherever nothing is said
+ * here the rule is sr_field_sightline_voigt's, word for word: the chord, the clip, the samples, the gather, the dark conditions,
+ * beta, wc, wd, iw, g, aJ, aK, gam, a, V(a, x), cut = wing*wing, the continuum, column, chord and steps.  Everything is float64
+ * and every operation rounds on its own (sightline_zeeman.hip is compiled with -ffp-contract=off); exp, expm1, sqrt are the
+ * device library's.  There is no trigonometry anywhere in what this section adds.
+ *   table    sr_zeeman_table: `voigt` is that entry's table; n_comp[l] in 1..SR_MAX_ZEEMAN (24: every pattern up to
+ *            J = 7/2 <-> 7/2, whose three groups hold 7 + 8 + 7 = 22) is the number of components of line l, and comp holds, line
+ *            after line, (q, g, s) per component: q in {-1, 0, +1} is m_upper - m_lower, g the component's shift in units of the
+ *            Larmor frequency (finite), s > 0 its strength relative to its q group.  The strengths of every q group that is
+ *            present sum to 1 within 1e-9 (the sum taken in the table's order), checked on the host.  voigt.LG NULL here means
+ *            a = 0 for every line -- Gaussian components through the same V(a, x) -- and does NOT delegate.
+ *   frame    per chord, on the host, in float64, once (ref is (3, n), one reference direction per chord, any length):
+ *              su = toward/sqrt((d0*d0 + d1*d1) + d2*d2);   nk = dk*su  (k = 0, 1, 2): n^ is the direction the light travels
+ *              p = (r0*n0 + r1*n1) + r2*n2;   tk = rk - p*nk;   t = sqrt((t0*t0 + t1*t1) + t2*t2);   e1k = tk/t
+ *              e2 = n^ x e1 = (n1*e12 - n2*e11, n2*e10 - n0*e12, n0*e11 - n1*e10)
+ *            A ref with a non-finite component, or with not t > 1e-6*sqrt((r0*r0 + r1*r1) + r2*r2) (parallel to the chord within
+ *            1e-6 rad, or zero), is an argument error.
+ *   sample   B is gathered with the same cell and weights as the other fields (each component as V's: a (nx, ny, nz, 3) field);
+ *            outside the box (within rounding of a face) B = 0 beside ne = 0.  With kL = e/(2.0*m_e), formed on the host from
+ *            e = 1.602176634e-19 and m_e = 9.1093837015e-31:
+ *              Bn = (B0*n0 + B1*n1) + B2*n2;   Bu = (B0*e10 + B1*e11) + B2*e12;   Bv = (B0*e20 + B1*e21) + B2*e22
+ *              T = Bu*Bu + Bv*Bv;   B2 = T + Bn*Bn
+ *              B2 == 0:   wL = 0;  sP = 1;  cS = 0.5;  cQ = cU = cV = 0
+ *              otherwise (B2 > 0 or a NaN):   r = sqrt(B2);  wL = kL*r;  sP = T/B2;  cS = 0.5*(1.0 + (Bn*Bn)/B2)
+ *                                             cQ = (Bu*Bu - Bv*Bv)/B2;  cU = ((2.0*Bu)*Bv)/B2;  cV = Bn/r
+ *            sP is sin^2 of the angle between B and the light, cS = (1 + cos^2)/2, (cQ, cU) = sin^2 (cos 2chi, sin 2chi) with chi
+ *            the azimuth of B's transverse part from e1, cV = cos.  The dark conditions are the line section's: B plays no part
+ *            in them, and a NaN B is not dark: it poisons every frequency of the sample.
+ *   term     per sample that is not dark and frequency f, for lines l ascending and, within a line, components k ascending:
+ *              sh = g_k*wL;   x = ((omega_f - wc) - sh)*iw;   the term is dropped when x*x > cut (a NaN is not dropped); otherwise
+ *              P_q = P_q + s_k*V(a, x)  (q = q_k; P0, Pp, Pm start at 0 for every line);   the line has a term
+ *            and after the components of a line that has a term (a line all of whose components were dropped adds nothing):
+ *              Ps = Pp + Pm;   eI = 0.5*(sP*P0) + (0.5*cS)*Ps;   eP = 0.5*(P0 - 0.5*Ps);   eV = 0.5*(Pp - Pm)
+ *              jI = jI + aJ*eI;   jQ = jQ + aJ*(eP*cQ);   jU = jU + aJ*(eP*cU);   jV = jV + aJ*(eV*cV);   aL = aL + aK*eI
+ *              counted = true
+ *            Over omega every q group integrates to 1/ISP/iw, so the line's jI integrates to exp(l(LJ))*0.5*(sP + 2 cS) =
+ *            exp(l(LJ)) at any angle, and jQ, jU, jV to 0.
+ *   signs    A component with q = +1 (m_upper - m_lower = +1) emitted along +B has positive helicity, and Vs > 0 there: with B
+ *            along the light (cV = +1) the q = +1 components give Vs = +I.  Q > 0 is linear polarisation along e1, U > 0 along
+ *            the bisector of e1 and e2: seen across B (B along e1) the pi components are polarised along B, Q = +I, the sigma
+ *            components across it, Q = -I.
+ *   update   the line section's, on four parameters with ONE scalar attenuation.  Counted:  a = ac + aL;  dtau = a*h;
+ *              dtau == 0:   I = I + jI*h;  Q = Q + jQ*h;  U = U + jU*h;  Vs = Vs + jV*h
+ *              otherwise:   E = exp(-dtau);  F = -expm1(-dtau);  I = I*E + ((ac*Sc + jI)/a)*F;  Q = Q*E + (jQ/a)*F;
+ *                           U = U*E + (jU/a)*F;  Vs = Vs*E + (jV/a)*F;  tau = tau + dtau
+ *            Not counted, continuum on:  dtau = ac*h;  E = exp(-dtau);  I = I*E + Sc*(-expm1(-dtau));  Q = Q*E;  U = U*E;
+ *            Vs = Vs*E;  tau = tau + dtau.  Not counted, continuum off:  each of the five + 0.0.  The backlight is unpolarised: I
+ *            starts at it (or 0), Q = U = Vs = tau = 0.  The cone I*I >= Q*Q + U*U + Vs*Vs is closed under this update: the
+ *            emitted (jI, jQ, jU, jV) lies in it line by line, the continuum adds to I alone, and all four decay alike.
+ *   wing     dropping is exact and x stays monotone in omega_f as rounded (two subtractions and a product by iw >= 0), so a
+ *            wavefront may skip a component whose window holds none of its frequencies: that section's test of the two ends with
+ *            x as above.
+ *   B NULL   the entry is sr_field_sightline_voigt: it returns that entry's bits in I, tau, column, chord and steps and exact
+ *            zeros in those of Q, U, Vs that are not NULL; n_comp, comp and ref are not read.
+ * A chord that misses the box: I = the backlight (or 0), Q = U = Vs = tau = 0.  NaN, poisoning and repeatability are the line
+ * section's; no atomics; a repeated call returns identical bits.  sr_zeeman_chunk() is the number of samples this kernel stages at
+ * a time.
+ * Not modelled: dichroism and magneto-optical (anomalous-dispersion) rotation in the absorption matrix -- absorption acts equally
+ * on all four parameters; Faraday rotation of the continuum; the Paschen-Back regime and hyperfine structure; and what
+ * sr_field_sightline_voigt does not model.
+ * Arguments are checked before the device is touched: everything sr_field_sightline_voigt checks (wing also where LG is NULL); with
+ * B given a NULL table, n_comp, comp, ref, Q, U or Vs; an n_comp outside 1..SR_MAX_ZEEMAN; a q that is not -1, 0 or +1; a
+ * non-finite g; an s that is not finite and positive; a q group whose strengths do not sum to 1; a ref as above; a B that is not a
+ * 3-vector field on ne's grid and of its dtype.  n == 0 or n_freq == 0 succeeds after the checks and writes nothing. */
+#define SR_MAX_ZEEMAN 24
+typedef struct {
+  sr_voigt_table voigt;
+  const int32_t *n_comp; /* (n_line): components of each line, 1..SR_MAX_ZEEMAN */
+  const double *comp;    /* (sum of n_comp, 3): q, g, s of every component, line after line */
+} sr_zeeman_table;
+int sr_zeeman_chunk(void);
+int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *Z,
+                              const sr_field *V /* or NULL */, const sr_field *B /* or NULL: sr_field_sightline_voigt */,
+                              const sr_zeeman_table *lines, const sr_voigt_params *p, int64_t n, const double *origin,
+                              const double *dir, const double *ref /* (3, n) */, int32_t n_freq, const double *omega,
+                              const double *e_ph, const double *c_omega, const double *backlight /* (n, n_freq) or NULL */,
+                              double *I, double *Q, double *U, double *Vs, double *tau /* (n, n_freq) */, double *column,
+                              double *chord, int32_t *steps /* (n), may be NULL */, double *kernel_ms);
+
 /* ---- proton radiography: charged particles pushed through prescribed E and B ----------------
  * No reference counterpart.  n independent particles of charge/mass qm are pushed through the fields E [V/m] and B [T], 3-vector
  * sr_fields (n_comp == 3) on ONE grid (when both are given the node coordinates are compared bit for bit, and the dtypes must be

@@ -169,6 +169,21 @@ class DomainExtras:
         return sightline_voigt(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
                                wing=wing, step=step, max_steps=max_steps)
 
+    def sightline_zeeman(self, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
+                         reference=None):
+        """sightline_voigt in this domain's magnetic field (external_B): the lines of an utils.eos_opacity.ZeemanLineTable, each
+        split by B at every sample into the pi and sigma components of its Zeeman pattern, and the Stokes parameters I, Q, U, V
+        along every chord -- a sightlines.StokesSpectra, whose analysed() gives what a linear or circular analyser passes and
+        b_parallel() the field along the chord a polarisation-resolved spectrometer would infer.  reference: the direction Q is
+        measured from, (3,) or one per chord; None: a pixel view's up, for Chords the lab axis least aligned with each chord.
+        Everything else is sightline_voigt's.  Not modelled: dichroism and magneto-optical (anomalous-dispersion) rotation in the
+        absorption matrix (absorption acts equally on all four parameters), Faraday rotation of the continuum, the Paschen-Back
+        regime, hyperfine structure, and what sightline_voigt does not model; one GPU."""
+        from .sightlines import sightline_zeeman
+
+        return sightline_zeeman(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
+                                wing=wing, step=step, max_steps=max_steps, reference=reference)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
         from .utils.handle_filetypes import export_scalar_field

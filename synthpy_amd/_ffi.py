@@ -104,6 +104,13 @@ class VoigtParams(C.Structure):
     _fields_ = [("march", LinesParams), ("wing", C.c_double)]
 
 
+MAX_ZEEMAN = 24  # SR_MAX_ZEEMAN
+
+
+class ZeemanTable(C.Structure):
+    _fields_ = [("voigt", VoigtTable), ("n_comp", C.c_void_p), ("comp", C.c_void_p)]
+
+
 class PushParams(C.Structure):
     _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("max_steps", C.c_int32), ("axis", C.c_int32),
                 ("det_pos", C.c_double), ("hit_scale", C.c_double)]
@@ -202,6 +209,9 @@ SYMBOLS = {
     "sr_voigt_chunk": (_i, []),
     "sr_field_sightline_voigt": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(VoigtTable), C.POINTER(VoigtParams), _i64, _vp, _vp, C.c_int32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_zeeman_chunk": (_i, []),
+    "sr_field_sightline_zeeman": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ZeemanTable), C.POINTER(VoigtParams), _i64, _vp, _vp, _vp,
+                                       C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
@@ -274,6 +284,7 @@ for _name, (_res, _args) in SYMBOLS.items():
     _fn.argtypes = _args
 
 VOIGT_CHUNK = int(lib.sr_voigt_chunk())  # samples of a chord sr_field_sightline_voigt's kernel stages at a time
+ZEEMAN_CHUNK = int(lib.sr_zeeman_chunk())  # and sr_field_sightline_zeeman's
 
 
 def last_error() -> str:

@@ -164,6 +164,46 @@ __device__ __forceinline__ void blend_sample(const EmArgs &A, const FlowSample<T
   }
 }
 
+// Sample k's cell and weights alone (fetch's search, the same bits) and the corners of the three components of `vec` (a
+// (nx, ny, nz, 3) field) there, in the slots a FlowSample keeps for V: how a lane that stages no sample of its own carries a
+// second vector field (sightline_zeeman.hip: B) across a march without any lane's live state growing.
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI>
+__device__ __forceinline__ void fetch_vector(const void *vec, const sr::FieldGrid &f, int64_t sx, int64_t sy, const Line &l, int k,
+                                             FlowSample<T, HAS_TE, HAS_Z, HAS_TI, true> &s) {
+  const double t = l.t0 + ((double)k + 0.5) * l.dt;
+  const double px = l.o0 + l.d0 * t, py = l.o1 + l.d1 * t, pz = l.o2 + l.d2 * t;
+  int ci = 0, cj = 0, ck = 0;
+  double wx = 0, wy = 0, wz = 0;
+  const bool in_x = sr::locate_in<true>(f.g[0], f.n[0], f.inv_h[0], f.lo[0], f.hi[0], px, ci, wx);
+  const bool in_y = sr::locate_in<true>(f.g[1], f.n[1], f.inv_h[1], f.lo[1], f.hi[1], py, cj, wy);
+  const bool in_z = sr::locate_in<true>(f.g[2], f.n[2], f.inv_h[2], f.lo[2], f.hi[2], pz, ck, wz);
+  s.s.in = in_x && in_y && in_z;
+  if (s.s.in) {
+    const double uy = 1.0 - wy, uz = 1.0 - wz;
+    s.s.ux = 1.0 - wx;
+    s.s.wx = wx;
+    s.s.w00 = uy * uz;
+    s.s.w01 = uy * wz;
+    s.s.w10 = wy * uz;
+    s.s.w11 = wy * wz;
+    s.V0 = sr::corners_load(static_cast<const T *>(vec), 3, 0, sx, sy, ci, cj, ck);
+    s.V1 = sr::corners_load(static_cast<const T *>(vec), 3, 1, sx, sy, ci, cj, ck);
+    s.V2 = sr::corners_load(static_cast<const T *>(vec), 3, 2, sx, sy, ci, cj, ck);
+  }
+}
+
+// the vector fetch_vector read, blended; outside the box 0
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI>
+__device__ __forceinline__ void blend_vector(const FlowSample<T, HAS_TE, HAS_Z, HAS_TI, true> &s, double (&B)[3]) {
+  B[0] = B[1] = B[2] = 0.0;
+  if (s.s.in) {
+    const Sample<T, HAS_TE, HAS_Z> &c = s.s;
+    B[0] = sr::corners_blend(s.V0, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    B[1] = sr::corners_blend(s.V1, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    B[2] = sr::corners_blend(s.V2, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+  }
+}
+
 // ---- host: what sr_field_sightlines and sr_field_sightline_spectra do around their kernels (`who` names the entry in the error
 // text).  An entry keeps its kernel and dispatch, its table's packing and the checks only it has.
 

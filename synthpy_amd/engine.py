@@ -744,6 +744,84 @@ def sightline_voigt(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, con
     return _sightlines(params, "a VoigtLineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
 
 
+ZEEMAN_CHUNK = _ffi.ZEEMAN_CHUNK  # samples of a chord sr_field_sightline_zeeman's kernel stages at a time
+M_ELECTRON = 9.1093837015e-31   # kg
+LARMOR = E_CHARGE / (2.0 * M_ELECTRON)  # kL [rad/s/T], formed as sr_field_sightline_zeeman forms it
+
+
+def zeeman_table_params(lines):
+    """sr_zeeman_table for an utils.eos_opacity.ZeemanLineTable (or anything with its members: a VoigtLineTable's, where
+    lorentz_width may be None -- Gaussian components -- and `patterns`, one (n, 3) array of (q, g, s) rows per line), and the arrays
+    it points into (keep them alive for the call).  A table without patterns gives NULL component members: only a call without B
+    accepts it."""
+    v, keep = voigt_table_params(lines)
+    patterns = getattr(lines, "patterns", None)
+    n_comp = comp = None
+    if patterns is not None:
+        n_comp = np.array([len(p) for p in patterns], np.int32)
+        comp = np.ascontiguousarray(np.concatenate([f64(p).reshape(-1, 3) for p in patterns], axis=0))
+        if len(n_comp) != v.lines.n_line:
+            raise ValueError(f"the line table has {v.lines.n_line} line(s) and {len(n_comp)} Zeeman pattern(s)")
+    z = _ffi.ZeemanTable()
+    z.voigt, z.n_comp, z.comp = v, ptr(n_comp), ptr(comp)
+    return z, keep + (n_comp, comp)
+
+
+def sightline_zeeman(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lines, omegas, continuum=False, wing=np.inf, toward,
+                     step, max_steps, backlight=None, want=_SIGHT_WANT + ("Q", "U", "V")):
+    """engine.sightline_voigt in a magnetic field: every line of `lines` (an utils.eos_opacity.ZeemanLineTable) is split by the
+    field B [T] (a vector Field on ne's grid, gathered at every sample like V) into the pi and sigma components of its pattern,
+    each a Voigt profile shifted by g e |B| / (2 m_e), and the four Stokes parameters are marched along every chord with one scalar
+    attenuation (sr_field_sightline_zeeman; include/synthray.h states the rule and the sign conventions).  reference: (3, n), or
+    (3,) for all chords: with n^ the direction the light travels, e1 is `reference` minus its part along n^, normalised, and
+    e2 = n^ x e1; Q > 0 is linear polarisation along e1, U > 0 along the bisector of e1 and e2, V > 0 the helicity of a q = +1
+    component emitted along +B.  A reference parallel to its chord is an error.  Everything else -- the chords, the other fields,
+    continuum, wing, toward, step, max_steps, backlight (unpolarised) and want -- is engine.sightline_voigt's, and the dict
+    returned is its dict plus "Q", "U", "V", shaped as "intensity".  B = None: engine.sightline_voigt's bits and exact zeros in
+    Q, U, V; the patterns and the reference are not read.  A table without lorentz_width has Gaussian components (it does NOT fall
+    back to engine.sightline_lines).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: dichroism and magneto-optical
+    rotation in the absorption matrix (absorption acts equally on all four parameters), Faraday rotation of the continuum, the
+    Paschen-Back regime, hyperfine structure, and what engine.sightline_voigt does not model; one GPU."""
+    h_Ti, h_V, h_B = _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("B", B, none=True)
+    t, keep = zeeman_table_params(lines)
+    stokes_names = ("Q", "U", "V")
+    unknown = set(want) - set(_SIGHT_WANT) - set(stokes_names)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT + stokes_names}")
+    stokes = {}
+
+    def params(omegas, n, uniform, _):
+        om, e_ph, c_om = spectrum_constants(omegas)
+        p = _ffi.VoigtParams()
+        m = p.march
+        m.toward, m.max_steps, m.continuum, m.reserved, m.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
+        m.Te, m.Z = uniform
+        p.wing = float(wing)
+        ref = None
+        if h_B is not None:
+            if reference is None:
+                raise ValueError("reference must be given with B: the direction Q is measured from, (3,) or (3, n)")
+            ref = f64(reference)
+            if ref.shape == (3,):
+                ref = np.repeat(ref[:, None], n, axis=1)
+            if ref.shape != (3, n):
+                raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
+            ref = np.ascontiguousarray(ref)
+        for k in stokes_names:
+            stokes[k] = np.empty((n, len(om)))
+
+        def entry(h_ne, h_Te, h_Z, _, p_, n_, o, d, nf, w, e, c, back, I, tau, *rest):  # the family's order -> this entry's
+            return lib.sr_field_sightline_zeeman(h_ne, h_Te, h_Ti, h_Z, h_V, h_B, C.byref(t), p_, n_, o, d, ptr(ref), nf, w, e, c, back, I,
+                                                 ptr(stokes["Q"]), ptr(stokes["U"]), ptr(stokes["V"]), tau, *rest)
+
+        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
+
+    out = _sightlines(params, "a ZeemanLineTable", ne, Te, Z, origins, directions, omegas, None, backlight,
+                      tuple(k for k in want if k in _SIGHT_WANT))
+    out.update({k: stokes[k] for k in stokes_names if k in want})
+    return out
+
+
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
 _PUSH_WANT = ("sf", "hits", "steps", "flags")
 

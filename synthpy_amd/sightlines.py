@@ -216,11 +216,11 @@ def _check_view(view):
         raise ValueError("view must be a sightlines.PinholeCamera, PointBacklighter or Chords")
 
 
-def _along(domain, view, fields, entry, n_band, axis, step, max_steps, more=None, **node):
+def _along(domain, view, fields, entry, n_band, axis, step, max_steps, more=None, extra=(), **node):
     """What the entries share once the node is known: the defaults of step and max_steps, the view's lines and backlight in the
     order they go to the kernel in, entry(ne, Te, Z, ...) on the domain's fields, and its five arrays -- their lines along `axis`:
     -1 (bands first, the backlight (n_band, N)) or 0 (lines first, (N, n_band)) -- back in the view's order and shape.  more:
-    emission._upload's further fields, which entry gets by keyword."""
+    emission._upload's further fields, which entry gets by keyword.  extra: further maps of entry's dict, placed after the five."""
     step = default_step(domain) if step is None else float(step)
     max_steps = 4 * (len(domain.x) + len(domain.y) + len(domain.z)) if max_steps is None else int(max_steps)
     o, d = view.lines()
@@ -241,7 +241,7 @@ def _along(domain, view, fields, entry, n_band, axis, step, max_steps, more=None
             a = out
         return a.reshape(tuple(view.shape) + a.shape[1:] if axis == 0 else a.shape[:-1] + tuple(view.shape))
 
-    return [place(res[k]) for k in ("intensity", "optical_depth", "column", "chord", "steps")]
+    return [place(res[k]) for k in ("intensity", "optical_depth", "column", "chord", "steps") + tuple(extra)]
 
 
 def sightline_emission(domain, view, wavelengths=None, table=None, step=None, max_steps=None, fields=None):
@@ -450,9 +450,10 @@ def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None,
                          continuum=continuum)
 
 
-def _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, call, **opts):
-    """What sightline_lines and sightline_voigt share: the checks, the frequencies, the domain's Ti and V, and `call` (the engine's
-    entry, with `opts`) along the view."""
+def _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, call, reference=None, **opts):
+    """What sightline_lines, sightline_voigt and sightline_zeeman share: the checks, the frequencies, the domain's Ti and V, and
+    `call` (the engine's entry, with `opts`) along the view.  reference (sightline_zeeman alone: (3, N) in the view's order, already
+    resolved): the domain's B goes up as well, the call is engine.sightline_zeeman's, and a StokesSpectra comes back."""
     if (wavelengths is None) == (photon_energies is None):
         raise ValueError("exactly one of wavelengths [m] and photon_energies [eV] must be given")
     _check_view(view)
@@ -466,6 +467,22 @@ def _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_s
             "V": None if V is None else np.asarray(V)}
     if more["V"] is not None and more["V"].shape != shape + (3,):
         raise ValueError(f"V has shape {more['V'].shape}, the domain needs {shape + (3,)}")
+
+    if reference is not None:
+        B = getattr(domain, "B", None)
+        if B is None:
+            raise ValueError("the domain holds no magnetic field: call external_B() (without B the lines are sightline_voigt's)")
+        more["B"] = np.asarray(B)
+        if more["B"].shape != shape + (3,):
+            raise ValueError(f"B has shape {more['B'].shape}, the domain needs {shape + (3,)}")
+        perm = view.order()
+        ref = reference if perm is None else reference[:, perm]
+
+        def stokes_entry(ne, Te, Z, o, d, Ti=None, V=None, B=None, **kw):
+            return call(ne, Te, Ti, Z, V, B, o, d, ref, lines=lines, omegas=omega, **opts, **kw)
+
+        maps = _along(domain, view, fields, stokes_entry, len(omega), 0, step, max_steps, more, extra=("Q", "U", "V"))
+        return StokesSpectra(view, *maps[:5], omega, lines, *maps[5:], reference)
 
     def entry(ne, Te, Z, o, d, Ti=None, V=None, **kw):
         return call(ne, Te, Ti, Z, V, o, d, lines=lines, omegas=omega, **opts, **kw)
@@ -490,3 +507,109 @@ def sightline_voigt(domain, view, lines, wavelengths=None, photon_energies=None,
         raise ValueError("lines must be a VoigtLineTable (utils.eos_opacity): it has no lorentz_width")
     return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_voigt,
                          continuum=continuum, wing=np.inf if wing is None else wing)
+
+
+class StokesSpectra(LineSpectra):
+    """A LineSpectra with polarisation: intensity (Stokes I), Q, U, V and optical_depth, each view.shape + (n_freq,), in the frame
+    of each chord -- with n^ the direction the light travels, e1 the part of `reference` ((3, N), the view's order) across n^,
+    normalised, and e2 = n^ x e1: Q > 0 is linear polarisation along e1, U > 0 along the bisector of e1 and e2, V > 0 the
+    helicity of a q = +1 Zeeman component emitted along +B.  moments(), fwhm() and signal() work unchanged on intensity."""
+
+    def __init__(self, view, intensity, optical_depth, column, chord, steps, omega, lines, Q, U, V, reference=None):
+        super().__init__(view, intensity, optical_depth, column, chord, steps, omega, lines)
+        self.Q, self.U, self.V = (np.asarray(a, np.float64) for a in (Q, U, V))
+        for name in ("Q", "U", "V"):
+            if getattr(self, name).shape != self.intensity.shape:
+                raise ValueError(f"{name} has shape {getattr(self, name).shape}, intensity {self.intensity.shape}")
+        self.reference = reference
+
+    def analysed(self, angle=None, circular=None):
+        """The spectral radiance behind an ideal analyser, the shape of intensity.  angle=psi [rad]: a linear polariser whose
+        axis is turned by psi from e1 towards e2, 0.5 (I + Q cos 2 psi + U sin 2 psi); circular=+1 or -1: a circular analyser
+        that passes positive or negative helicity, 0.5 (I +- V).  Exactly one of the two."""
+        if (angle is None) == (circular is None):
+            raise ValueError("exactly one of angle [rad] and circular (+1 or -1) must be given")
+        if circular is not None:
+            if circular not in (1, -1):
+                raise ValueError(f"circular must be +1 or -1, got {circular!r}")
+            return 0.5 * (self.intensity + circular * self.V)
+        psi = float(angle)
+        if not np.isfinite(psi):
+            raise ValueError(f"angle must be finite, got {angle!r}")
+        return 0.5 * (self.intensity + self.Q * np.cos(2 * psi) + self.U * np.sin(2 * psi))
+
+    def b_parallel(self, window, g_eff=None):
+        """The centre-of-gravity estimate of the field along the light [T], per chord and per line: view.shape + (n_line,), on the
+        host.  Inside |omega - omega0| <= window (moments()' window) the centroids of the two circular analysers' spectra,
+        0.5 (I + V) and 0.5 (I - V), are taken by the trapezoid over the frequencies in ascending order; their difference divided
+        by 2 g_eff kL, kL = e / (2 m_e), is the emission-weighted B . n^ a spectrometer with a circular analyser reports (positive:
+        B points along the light's travel).  g_eff: a number or one per line; None: lines.g_eff.  Exact for thin lines of any
+        splitting; self-absorption and a continuum inside the window bias it.  NaN where the window holds fewer than two
+        frequencies or either spectrum has no radiance."""
+        w0 = self.lines.omega0
+        win = np.broadcast_to(np.asarray(window, np.float64), w0.shape)
+        if not np.all(np.isfinite(win) & (win > 0)):
+            raise ValueError(f"window must be finite and positive (a number or one per line), got {window!r}")
+        g = np.broadcast_to(np.asarray(self.lines.g_eff if g_eff is None else g_eff, np.float64), w0.shape)
+        if not np.all(np.isfinite(g) & (g != 0)):
+            raise ValueError(f"g_eff must be finite and not zero (a number or one per line), got {g.tolist()}")
+        k = np.argsort(self.omega, kind="stable")
+        w = self.omega[k]
+        plus, minus = (0.5 * (self.intensity + self.V))[..., k], (0.5 * (self.intensity - self.V))[..., k]
+        out = np.full(tuple(self.view.shape) + w0.shape, np.nan)
+        with np.errstate(all="ignore"):
+            for l in range(len(w0)):
+                sel = np.abs(w - w0[l]) <= win[l]
+                if np.count_nonzero(sel) < 2:
+                    continue
+                x, dx = w[sel] - w0[l], np.diff(w[sel])
+                cen = []
+                for y in (plus[..., sel], minus[..., sel]):
+                    m0 = np.sum(0.5 * (y[..., 1:] + y[..., :-1]) * dx, axis=-1)
+                    yx = y * x
+                    m1 = np.sum(0.5 * (yx[..., 1:] + yx[..., :-1]) * dx, axis=-1)
+                    cen.append(np.where(m0 > 0, m1 / m0, np.nan))
+                out[..., l] = (cen[0] - cen[1]) / (2.0 * g[l] * engine.LARMOR)
+        return out
+
+
+def default_reference(view):
+    """The reference direction of every chord of `view`, (3, N) in the view's order: a pixel view's up (its frame's y), for Chords
+    the lab axis least aligned with each chord (the first of them where they tie)."""
+    o, d = view.lines()
+    if hasattr(view, "y") and np.shape(view.y) == (3,):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(view.y, np.float64)[:, None], d.shape))
+    ref = np.zeros(d.shape)
+    ref[np.argmin(np.abs(d), axis=0), np.arange(d.shape[1])] = 1.0
+    return ref
+
+
+def sightline_zeeman(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
+                     fields=None, reference=None):
+    """sightline_voigt in the domain's magnetic field (external_B): a StokesSpectra (engine.sightline_zeeman ->
+    sr_field_sightline_zeeman; include/synthray.h states the rule and the sign conventions).  lines: an
+    utils.eos_opacity.ZeemanLineTable -- a VoigtLineTable (or, without widths, a LineTable: Gaussian components) with a Zeeman
+    pattern per line (normal_triplet(), from_lande()); at every sample each line is split by B into its pi and sigma components,
+    shifted by g e |B| / (2 m_e), weighted and polarised by the angle between B and the chord, and I, Q, U, V are marched with the
+    line's self-absorption acting equally on all four.  reference: the direction Q is measured from -- (3,), or (3, N) in the
+    view's order; None: default_reference(view), a pixel view's up, for Chords the lab axis least aligned with each chord; it must
+    not be parallel to its chord.  StokesSpectra.analysed() gives what an analyser passes, b_parallel() the field a
+    circular-analyser spectrometer would infer.  rotated() domains work unchanged (B is carried as R^T B(R q)).  Everything else
+    is sightline_voigt's.  Not modelled: dichroism and magneto-optical (anomalous-dispersion) rotation in the absorption matrix,
+    Faraday rotation of the continuum, the Paschen-Back regime, hyperfine structure, and what sightline_voigt does not model; one
+    GPU."""
+    if getattr(lines, "patterns", None) is None:
+        raise ValueError("lines must be a ZeemanLineTable (utils.eos_opacity): it has no patterns")
+    _check_view(view)
+    n = int(np.prod(view.shape))
+    if reference is None:
+        ref = default_reference(view)
+    else:
+        ref = np.asarray(reference, np.float64)
+        if ref.shape == (3,):
+            ref = np.broadcast_to(ref[:, None], (3, n))
+        if ref.shape != (3, n):
+            raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
+        ref = np.ascontiguousarray(ref)
+    return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_zeeman,
+                         reference=ref, continuum=continuum, wing=np.inf if wing is None else wing)

@@ -8,7 +8,8 @@ engine.emission_table -> sr_field_emission_table; no reference counterpart).
 
 LineTable holds spectral lines on the same kind of lattice, from arrays: what sightlines.sightline_lines consumes
 (engine.sightline_lines -> sr_field_sightline_lines; no reference counterpart); VoigtLineTable adds each line's Lorentzian width for
-sightlines.sightline_voigt (engine.sightline_voigt -> sr_field_sightline_voigt).
+sightlines.sightline_voigt (engine.sightline_voigt -> sr_field_sightline_voigt), ZeemanLineTable each line's Zeeman pattern for
+sightlines.sightline_zeeman (engine.sightline_zeeman -> sr_field_sightline_zeeman).
 """
 from __future__ import annotations
 
@@ -394,3 +395,141 @@ class VoigtLineTable(LineTable):
         fL = 2.0 * np.exp(lo + ft * (hi - lo))
         fG = 2.0 * np.sqrt(np.log(2.0)) * self.thermal_width(Ti)
         return 0.5346 * fL + np.sqrt(0.2166 * fL ** 2 + fG ** 2)
+
+
+MAX_ZEEMAN = 24  # SR_MAX_ZEEMAN: components of one line (J = 7/2 <-> 7/2 has 22)
+_M_E = 9.1093837015e-31
+LARMOR = _E_CHARGE / (2.0 * _M_E)  # kL [rad/s/T]: the Larmor angular frequency per tesla, as sr_field_sightline_zeeman forms it
+
+
+def normal_triplet():
+    """The normal Zeeman triplet: (q, g, s) = (-1, -1, 1), (0, 0, 1), (+1, +1, 1)."""
+    return np.array([[-1.0, -1.0, 1.0], [0.0, 0.0, 1.0], [1.0, 1.0, 1.0]])
+
+
+def lande_pattern(J_upper, g_upper, J_lower, g_lower):
+    """The anomalous Zeeman pattern of J_upper -> J_lower in LS coupling and a weak field, (n, 3) rows (q, g, s): for every allowed
+    m_u -> m_l, q = m_u - m_l, the shift g = g_u m_u - g_l m_l in Larmor units, the strength the squared 3j symbol
+    (J_u 1 J_l; -m_u q m_l)^2 by its closed forms for J_u - J_l = 0, +1, -1, normalised to 1 over each q group.  Components of one
+    group whose shifts are the same float64 are merged (g_u = g_l: g = g_u q for all of them, the normal triplet scaled by g_u);
+    rows are ordered by q, then by g."""
+    Ju, Jl = float(J_upper), float(J_lower)
+    for name, J in (("J_upper", Ju), ("J_lower", Jl)):
+        if not (np.isfinite(J) and J >= 0 and 2 * J == np.rint(2 * J)):
+            raise ValueError(f"{name} must be a non-negative integer or half-integer, got {J!r}")
+    dJ = Ju - Jl
+    if dJ not in (-1.0, 0.0, 1.0) or (Ju == 0 and Jl == 0) or (2 * Ju) % 2 != (2 * Jl) % 2:
+        raise ValueError(f"J_upper -> J_lower = {Ju} -> {Jl} is not an electric-dipole transition (J changes by 0 or 1, not 0 -> 0)")
+    gu, gl = float(g_upper), float(g_lower)
+    if not (np.isfinite(gu) and np.isfinite(gl)):
+        raise ValueError(f"g_upper and g_lower must be finite, got {g_upper!r} and {g_lower!r}")
+    J = Jl
+    rows = {}
+    for q in (-1, 0, 1):
+        for m in np.arange(-Jl, Jl + 0.5):  # m: the lower level's
+            mu = m + q
+            if abs(mu) > Ju:
+                continue
+            if dJ == 0:
+                s = m * m if q == 0 else 0.5 * (J - q * m) * (J + q * m + 1)
+            elif dJ == 1:
+                s = (J + 1) ** 2 - m * m if q == 0 else 0.5 * (J + q * m + 1) * (J + q * m + 2)
+            else:
+                s = J * J - m * m if q == 0 else 0.5 * (J - q * m) * (J - q * m - 1)
+            if s > 0:
+                key = (float(q), gu * q if gu == gl else gu * mu - gl * m)  # equal factors: g (m_u - m_l), without rounding
+                rows[key] = rows.get(key, 0.0) + s
+    out = np.array([[q, g, s] for (q, g), s in sorted(rows.items())])
+    for q in (-1.0, 0.0, 1.0):
+        sel = out[:, 0] == q
+        if sel.any():
+            out[sel, 2] /= out[sel, 2].sum()
+    return out
+
+
+class ZeemanLineTable(VoigtLineTable):
+    """A line table whose lines also have a Zeeman pattern: what sr_field_sightline_zeeman takes (sightlines.sightline_zeeman,
+    engine.sightline_zeeman).
+
+    VoigtLineTable's arguments -- but lorentz_width may be None: Gaussian components -- and patterns: one (n, 3) array of rows
+    (q, g, s) per line (a single 2-D array serves every line), 1 to 24 rows: q in {-1, 0, +1} is m_upper - m_lower, g the
+    component's shift in units of the Larmor frequency e B / (2 m_e), s > 0 its strength; the strengths of every q group that is
+    present sum to 1 within 1e-9.  ValueError names the offending member.  from_lines() adds patterns to a LineTable or a
+    VoigtLineTable, from_lande() makes them from the levels' J and Lande factors."""
+
+    def __init__(self, temperatures, ion_densities, emissivity, wavelengths=None, photon_energy=None, mass_number=None,
+                 absorption=None, lorentz_width=None, patterns=None):
+        LineTable.__init__(self, temperatures, ion_densities, emissivity, wavelengths=wavelengths, photon_energy=photon_energy,
+                           mass_number=mass_number, absorption=absorption)
+        self.lorentz_width = None
+        if lorentz_width is not None:
+            self.lorentz_width = OpacityTable._opacity("lorentz_width", lorentz_width, (len(self.temperatures), len(self.ion_densities)))
+            if self.lorentz_width.shape != self.emissivity.shape:
+                raise ValueError(f"lorentz_width has shape {self.lorentz_width.shape}, emissivity {self.emissivity.shape}")
+        self.patterns = self._patterns(patterns, self.n_line)
+
+    @staticmethod
+    def _patterns(patterns, n_line):
+        if patterns is None:
+            raise ValueError("patterns must be given: the Zeeman components (q, g, s) of every line")
+        if isinstance(patterns, np.ndarray) and patterns.ndim == 2:
+            patterns = [patterns] * n_line
+        patterns = [np.array(p, np.float64, ndmin=2) for p in patterns]
+        if len(patterns) != n_line:
+            raise ValueError(f"patterns must hold one array per line ({n_line}), got {len(patterns)}")
+        for l, p in enumerate(patterns):
+            if p.ndim != 2 or p.shape[1] != 3 or not 1 <= len(p) <= MAX_ZEEMAN:
+                raise ValueError(f"patterns[{l}] must be (n, 3) with n in 1..{MAX_ZEEMAN}, got shape {p.shape}")
+            if not np.all(np.isin(p[:, 0], (-1.0, 0.0, 1.0))):
+                raise ValueError(f"patterns[{l}]: q must be -1, 0 or +1, got {p[:, 0].tolist()}")
+            if not np.all(np.isfinite(p[:, 1])):
+                raise ValueError(f"patterns[{l}]: g must be finite, got {p[:, 1].tolist()}")
+            if not np.all(np.isfinite(p[:, 2]) & (p[:, 2] > 0)):
+                raise ValueError(f"patterns[{l}]: s must be finite and positive, got {p[:, 2].tolist()}")
+            for q in (-1.0, 0.0, 1.0):
+                s = p[p[:, 0] == q, 2]
+                if len(s) and abs(float(np.sum(s)) - 1.0) > 1e-9:
+                    raise ValueError(f"patterns[{l}]: the strengths of the q = {q:+.0f} group sum to {float(np.sum(s))!r}, not 1")
+        return patterns
+
+    @classmethod
+    def from_lines(cls, table, patterns):
+        """`table` (a LineTable or a VoigtLineTable, whose widths are kept) with these patterns."""
+        out = cls(table.temperatures, table.ion_densities, table.emissivity, wavelengths=table.wavelengths, mass_number=table.mass_number,
+                  absorption=table.absorption, lorentz_width=getattr(table, "lorentz_width", None), patterns=patterns)
+        out.omega0 = np.array(table.omega0, np.float64)  # the bits of the table it came from
+        return out
+
+    @classmethod
+    def from_lande(cls, table, J_upper, g_upper, J_lower, g_lower):
+        """`table` with the anomalous pattern lande_pattern() gives each line; every argument is a number or one value per line."""
+        n = table.n_line
+        args = [np.broadcast_to(np.array(a, np.float64, ndmin=1), (n,)) if np.size(a) in (1, n) else None
+                for a in (J_upper, g_upper, J_lower, g_lower)]
+        if any(a is None for a in args):
+            raise ValueError(f"J_upper, g_upper, J_lower and g_lower must each be a number or {n} of them")
+        return cls.from_lines(table, [lande_pattern(*(a[l] for a in args)) for l in range(n)])
+
+    normal_triplet = staticmethod(normal_triplet)
+
+    @property
+    def g_eff(self):
+        """Per line, the strength-weighted mean shift of the q = +1 group in Larmor units: the effective Lande factor, which for an
+        LS pattern is (g_u + g_l)/2 + (g_u - g_l)(J_u(J_u + 1) - J_l(J_l + 1))/4.  NaN for a line without a q = +1 component."""
+        out = np.full(self.n_line, np.nan)
+        for l, p in enumerate(self.patterns):
+            sel = p[:, 0] == 1.0
+            if sel.any():
+                out[l] = float(np.sum(p[sel, 1] * p[sel, 2]) / np.sum(p[sel, 2]))
+        return out
+
+    def packed_patterns(self):
+        """(n_comp (n_line) int32, comp (sum n_comp, 3) float64) as sr_zeeman_table takes them."""
+        return (np.array([len(p) for p in self.patterns], np.int32), np.ascontiguousarray(np.concatenate(self.patterns, axis=0)))
+
+    def with_lte_absorption(self):
+        """LineTable.with_lte_absorption(), with the widths and the patterns kept."""
+        lte = LineTable.with_lte_absorption(self)
+        out = ZeemanLineTable.__new__(ZeemanLineTable)
+        out.__dict__.update(lte.__dict__)
+        return out
