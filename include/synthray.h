@@ -571,8 +571,8 @@ int sr_field_sightline_voigt(const sr_field *ne, const sr_field *Te, const sr_fi
  * section's; no atomics; a repeated call returns identical bits.  sr_zeeman_chunk() is the number of samples this kernel stages at
  * a time.
  * Not modelled: dichroism and magneto-optical (anomalous-dispersion) rotation in the absorption matrix -- absorption acts equally
- * on all four parameters; Faraday rotation of the continuum; the Paschen-Back regime and hyperfine structure; and what
- * sr_field_sightline_voigt does not model.
+ * on all four parameters; Faraday rotation of the continuum (sr_field_sightline_stokes has all three); the Paschen-Back regime and
+ * hyperfine structure; and what sr_field_sightline_voigt does not model.
  * Arguments are checked before the device is touched: everything sr_field_sightline_voigt checks (wing also where LG is NULL); with
  * B given a NULL table, n_comp, comp, ref, Q, U or Vs; an n_comp outside 1..SR_MAX_ZEEMAN; a q that is not -1, 0 or +1; a
  * non-finite g; an s that is not finite and positive; a q group whose strengths do not sum to 1; a ref as above; a B that is not a
@@ -589,6 +589,104 @@ int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te, const sr_f
                               const sr_zeeman_table *lines, const sr_voigt_params *p, int64_t n, const double *origin,
                               const double *dir, const double *ref /* (3, n) */, int32_t n_freq, const double *omega,
                               const double *e_ph, const double *c_omega, const double *backlight /* (n, n_freq) or NULL */,
+                              double *I, double *Q, double *U, double *Vs, double *tau /* (n, n_freq) */, double *column,
+                              double *chord, int32_t *steps /* (n), may be NULL */, double *kernel_ms);
+
+/* ---- Polarised transfer along sightlines: dichroism, magneto-optical and Faraday rotation ----------
+ * No reference counterpart.  sr_field_sightline_zeeman with the whole 4 x 4 absorption matrix of the polarised transfer equation in
+ * place of its one scalar attenuation, and a backlight that may be polarised -- what a polarisation-resolved spectrometer reads of
+ * a backlit or optically thick magnetised plasma.  Wherever nothing is said here the rule is sr_field_sightline_zeeman's, word for
+ * word: the chord, the frame, the samples, the gather, the dark conditions, zeeman_sample (Bn, Bu, Bv, wL, sP, cS, cQ, cU, cV), the
+ * component loop, x, cut = wing*wing, the wavefront skip, the continuum, column, chord and steps.  Everything is float64 and every
+ * operation rounds on its own (sightline_stokes.hip is compiled with -ffp-contract=off); exp, expm1, sqrt, sin, cos and rint are
+ * the device library's.
+ *   profiles  (H, L) = W(a, x): H = Re w(x + i a) is V(a, x) of the Voigt section, the same operations and bits; L = Im w(x + i a),
+ *             the dispersion (Faraday-Voigt) profile, comes from the same intermediates, region by region:
+ *               not z2 < 1e17:   L = (ISP*x)/z2
+ *               CF(K):           L = (ISP*(Dr*Nr + Di*Ni))/(Nr*Nr + Ni*Ni)
+ *               R(...):          reF = (Gr*Sr - Gi*Si)*ISP;   L = (2.0*ISP)*reF - exp(a2 - x*x)*sin((2.0*a)*x)
+ *             -- w = (i/sqrt(pi)) D/N, and w = e^(-z^2) + (2i/sqrt(pi)) F(z).  L is odd in x and cancels at the centre, so its
+ *             accuracy is stated relative to |w| = sqrt(H*H + L*L): measured against scipy.special.wofz on the Voigt section's grid
+ *             with both signs of x (tests/test_sightline_stokes.py), the worst error of L relative to |w| is 1.6e-13, at a just
+ *             under 2 as H's is.
+ *   term      per line, R0, Rp, Rm start at 0 beside P0, Pp, Pm, and a term that is not dropped adds to both:
+ *               (H, L) = W(a, x);   P_q = P_q + s_k*H;   R_q = R_q + s_k*L
+ *             A term is dropped, and a component skipped by a wavefront, for both profiles together.  After the components of a
+ *             line that has a term, with Ps, eI, eP, eV the Zeeman section's:
+ *               Rs = Rp + Rm;   fP = 0.5*(R0 - 0.5*Rs);   fV = 0.5*(Rp - Rm)
+ *               jI, jQ, jU, jV:  the Zeeman section's four sums, with aJ;     hI = hI + aK*eI  (that section's aL)
+ *               hQ = hQ + aK*(eP*cQ);   hU = hU + aK*(eP*cU);   hV = hV + aK*(eV*cV)
+ *               rQ = rQ + aK*(fP*cQ);   rU = rU + aK*(fP*cU);   rV = rV + aK*(fV*cV);   counted = true
+ *             All eleven start at 0 for every sample and frequency.
+ *   faraday   with faraday = 1, for every sample (dark or not, counted or not), after the lines:
+ *               rV = rV + ((kF2*(neh/h))*Bn)/(omega_f*omega_f)
+ *             neh = ne*h is the sample's staged column (the number `column` sums), h the chord's sample length, Bn zeeman_sample's
+ *             (B0*n0 + B1*n1) + B2*n2 -- B . n^ itself, 0 outside the box, not |B|*cV -- and kF2 = 2.0*kF,
+ *             kF = ((e*e)*e)/((((2.0*eps0)*m_e)*m_e)*c) = e^3/(2 eps0 m_e^2 c), formed on the host from the Zeeman section's e and
+ *             m_e, eps0 = 8.8541878128e-12 and c = 299792458.0: the plane of polarisation turns by kF*ne*(B . n^)*s/omega^2, the
+ *             cold-plasma Faraday rotation for omega far above the plasma and cyclotron frequencies.
+ *   matrix    eI = ac + hI;   eps = (ac*Sc + jI, jQ, jU, jV);
+ *               K = [[eI, hQ, hU, hV], [hQ, eI, rV, -rU], [hU, -rV, eI, rQ], [hV, rU, -rQ, eI]]
+ *             and dX/ds = -K X + eps for X = (I, Q, U, Vs).
+ *   signs     This layout means d(Q + iU)/ds = i*rV*(Q + iU): the plane of polarisation turns from e1 towards e2 = n^ x e1 by
+ *             rV*s/2.  (a) Free electrons with B along the light's travel turn the plane from e1 towards e2: the circular mode
+ *             whose field turns in the electrons' sense about B (e1 -> e2 in time, positive helicity, Vs > 0) has the smaller
+ *             refractive index, n^2 = 1 - wp^2/(omega*(omega + wc)) against 1 - wp^2/(omega*(omega - wc)), so it is the faster
+ *             one, and the sum of two counter-rotating fields points along half the difference of their phases, (k_- - k_+) s/2
+ *             > 0.  Hence the + of the faraday term.  (b) A normal triplet far to the blue of its centre is a classical bound
+ *             electron and turns the plane as (a) does for the same B: with B along the light (cV = +1) the q = +1, g = +1
+ *             component is the one of positive helicity, shifted to the blue, so at omega above both x_(+1) < x_(-1), and
+ *             L ~ ISP/x gives Rp > Rm: the refractive index of the positive-helicity mode deviates from 1 by -(const)*Rp, the
+ *             greater deviation, so it is the faster one, as in (a), and rV must be positive: rV = +aK*(0.5*(Rp - Rm)*cV).  The
+ *             overall sign of rQ, rU, rV is therefore +1.  (c) hQ, hU, hV carry the signs of jQ, jU, jV.
+ *   update    A sample and frequency whose six numbers hQ, hU, hV, rQ, rU, rV are all == 0.0 (a -0.0 is; a NaN is not) takes
+ *             sr_field_sightline_zeeman's update, the same operations, with aL = hI, including its two not-counted branches.
+ *             Otherwise, counted or not, the exact solution for coefficients constant over the sample, X <- O X + p with
+ *             O = exp(-K h) and p = (integral_0^h exp(-K s) ds) eps, by scaling and squaring with +, -, *, / alone:
+ *               r_i = ((|K_i0| + |K_i1|) + |K_i2|) + |K_i3|  (K's entries in the layout above);   nrm = the greatest r_i
+ *               t = nrm*h;  hs = h;  s = 0;   while t > 0.25:  t = 0.5*t;  hs = 0.5*hs;  s = s + 1
+ *                 (theta = 1/4; a t that is NaN or infinite takes s = 0, and all five come out NaN)
+ *               g0 = -(eI*hs);  gQ = -(hQ*hs);  gU = -(hU*hs);  gV = -(hV*hs);  fQ = -(rQ*hs);  fU = -(rU*hs);  fV = -(rV*hs)
+ *               b = ((ac*Sc + jI)*hs, jQ*hs, jU*hs, jV*hs);   O = the 4 x 4 identity;   p = (0, 0, 0, 0)
+ *               for k = 13, 12, ..., 1 in this order (Horner, order 13), with c = (double)k:
+ *                 A = [[g0/c, gQ/c, gU/c, gV/c], [gQ/c, g0/c, fV/c, -(fU/c)], [gU/c, -(fV/c), g0/c, fQ/c], [gV/c, fU/c, -(fQ/c), g0/c]]
+ *                 N_ij = ((A_i0*O_0j + A_i1*O_1j) + A_i2*O_2j) + A_i3*O_3j
+ *                 q_i = (((A_i0*p_0 + A_i1*p_1) + A_i2*p_2) + A_i3*p_3) + b_i/c
+ *                 O = N with 1.0 + N_ii on the diagonal;   p = q
+ *               s times:   q_i = p_i + (((O_i0*p_0 + O_i1*p_1) + O_i2*p_2) + O_i3*p_3)
+ *                          N_ij = ((O_i0*O_0j + O_i1*O_1j) + O_i2*O_2j) + O_i3*O_3j;   p = q;   O = N
+ *               X_i = (((O_i0*I + O_i1*Q) + O_i2*U) + O_i3*Vs) + p_i  (i = I, Q, U, Vs; from the old four);   tau = tau + eI*h
+ *             -- the Taylor sum of exp of the 5 x 5 matrix [[-K hs, eps hs], [0, 0]], whose blocks are O and p.  With
+ *             theta = 1/4 and order 13 the truncation is theta^14/14! = 4.3e-20, under u/4 = 2.8e-17.  The closed form in the
+ *             eigenvalues of K is not used: it is singular where |eta| = |rho| with eta . rho = 0, and K^-1 eps loses everything
+ *             where a sigma component is completely polarised (K singular to rounding).  Errors of this scheme against a
+ *             50-digit matrix exponential, relative to the larger of the norms of X and p, measured on the grid of
+ *             tests/test_sightline_stokes.py (eI*h from 1e-6 to 1e3, complete dichroism, |rho| up to 30 eI, the degenerate
+ *             case): at most 2.9 u where s = 0, and (4 + 2*s + 4.2*nrm*h) u everywhere -- the last term is set by modes that
+ *             do not decay and is the conditioning of exp itself, which the scalar rule has through the rounding of dtau; it
+ *             grows with nrm*h because every squaring doubles the error of the scaled step.  The symmetric part of K has the eigenvalues eI +- |(hQ, hU, hV)| >= 0, so the update is a
+ *             contraction in the 2-norm and the cone I*I >= Q*Q + U*U + Vs*Vs is kept up to rounding.
+ *   backlight pol: (3) or NULL, (q, u, v) with q*q + u*u + v*v <= 1 (up to 1 + 1e-12: a unit vector as rounded).  The march
+ *             starts at I = I0, Q = I0*q, U = I0*u, Vs = I0*v with I0 the backlight (or 0); NULL: Q = U = Vs = 0, unpolarised.  A
+ *             chord that misses the box returns this start and tau = 0.
+ *   zeeman    So with the table's LK NULL (aK = 0) and faraday = 0 every sample takes the scalar update, and with pol NULL the
+ *             entry returns sr_field_sightline_zeeman's bits in I, Q, U, Vs, tau (and column, chord, steps).
+ *   B NULL    the entry is sr_field_sightline_voigt, as sr_field_sightline_zeeman is: its bits in I, tau, column, chord and
+ *             steps, exact zeros in those of Q, U, Vs that are not NULL; faraday = 1 or a pol is then an argument error.
+ * NaN, poisoning and repeatability are the Zeeman section's: a NaN B is not dark and poisons every frequency of its sample (on
+ * either update); no atomics; a repeated call returns identical bits.  sr_stokes_chunk() is the number of samples this kernel
+ * stages at a time (a staged sample holds one word more than the Zeeman kernel's, B . n^, and one of padding).
+ * Not modelled: the Paschen-Back regime; hyperfine structure; cyclotron dichroism of the continuum (the continuum absorbs all four
+ * parameters alike and only rotates); scattering polarisation; the Hanle effect; and what sr_field_sightline_voigt does not model.
+ * Arguments are checked before the device is touched: a faraday that is not 0 or 1; a pol that is not finite or lies outside the
+ * unit ball; faraday = 1 or a pol with B NULL; then everything sr_field_sightline_zeeman checks. */
+int sr_stokes_chunk(void);
+int sr_field_sightline_stokes(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *Z,
+                              const sr_field *V /* or NULL */, const sr_field *B /* or NULL: sr_field_sightline_voigt */,
+                              const sr_zeeman_table *lines, const sr_voigt_params *p, int64_t n, const double *origin,
+                              const double *dir, const double *ref /* (3, n) */, int32_t n_freq, const double *omega,
+                              const double *e_ph, const double *c_omega, const double *backlight /* (n, n_freq) or NULL */,
+                              const double *pol /* (3): q, u, v of the backlight, or NULL */, int32_t faraday,
                               double *I, double *Q, double *U, double *Vs, double *tau /* (n, n_freq) */, double *column,
                               double *chord, int32_t *steps /* (n), may be NULL */, double *kernel_ms);
 

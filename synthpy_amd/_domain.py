@@ -184,6 +184,22 @@ class DomainExtras:
         return sightline_zeeman(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
                                 wing=wing, step=step, max_steps=max_steps, reference=reference)
 
+    def sightline_stokes(self, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
+                         reference=None, polarisation=None, faraday=False):
+        """sightline_zeeman with the full polarised transfer equation: the lines' absorption is dichroic (it takes the pi and
+        sigma components out of a backlight's Q, U, V and lets a thick line depolarise towards its source function), the plane of
+        polarisation turns inside the lines (magneto-optical rotation) and, with faraday=True, in the continuum (Faraday
+        rotation, kF ne B.n^ / omega^2 per metre) -- a sightlines.StokesSpectra.  polarisation: (q, u, v) of the view's backlight
+        as fractions of its intensity, q^2 + u^2 + v^2 <= 1; None: unpolarised.  Everything else is sightline_zeeman's; a table
+        without absorption, faraday=False and polarisation=None give its bits.  Not modelled: the Paschen-Back regime, hyperfine
+        structure, cyclotron dichroism of the continuum, scattering polarisation, the Hanle effect, and what sightline_voigt does
+        not model; one GPU."""
+        from .sightlines import sightline_stokes
+
+        return sightline_stokes(self, view, lines, wavelengths=wavelengths, photon_energies=photon_energies, continuum=continuum,
+                                wing=wing, step=step, max_steps=max_steps, reference=reference, polarisation=polarisation,
+                                faraday=faraday)
+
     def export_scalar_field(self, property: str = "ne", fname: str = None):
         """Save n_e as <fname>.vti + <fname>.pvti (full_solver.py:442-512, domain.py:505-579), written without pyvista."""
         from .utils.handle_filetypes import export_scalar_field

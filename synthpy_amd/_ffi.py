@@ -212,6 +212,10 @@ SYMBOLS = {
     "sr_zeeman_chunk": (_i, []),
     "sr_field_sightline_zeeman": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ZeemanTable), C.POINTER(VoigtParams), _i64, _vp, _vp, _vp,
                                        C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_stokes_chunk": (_i, []),
+    "sr_field_sightline_stokes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ZeemanTable), C.POINTER(VoigtParams), _i64, _vp, _vp, _vp,
+                                       C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
@@ -285,6 +289,7 @@ for _name, (_res, _args) in SYMBOLS.items():
 
 VOIGT_CHUNK = int(lib.sr_voigt_chunk())  # samples of a chord sr_field_sightline_voigt's kernel stages at a time
 ZEEMAN_CHUNK = int(lib.sr_zeeman_chunk())  # and sr_field_sightline_zeeman's
+STOKES_CHUNK = int(lib.sr_stokes_chunk())  # and sr_field_sightline_stokes'
 
 
 def last_error() -> str:

@@ -1,23 +1,17 @@
-// Zeeman-split lines along sightlines: sr_field_sightline_voigt's lines, each split by the magnetic field B of the sample into its
-// pi and sigma components, and four Stokes parameters marched per frequency instead of one intensity (sr_field_sightline_zeeman;
-// include/synthray.h states the rule).  No reference counterpart.  k_sightline_voigt's decomposition: a workgroup owns one chord
-// and one tile of FL frequencies, a lane one frequency with its (I, Q, U, Vs, tau) in registers; the chord's samples go through LDS
-// in chunks of kZeemanChunk, in march order, in two buffers, and the corner reads of chunk c+1 are issued before the march of chunk
-// c and blended after it.
-//
-// Staging: lanes 0 .. chunk-1 stage what k_sightline_voigt's do, word for word.  Lanes chunk .. 2*chunk-1 carry B: lane chunk+s
-// finds sample s's cell again (the same search, the same bits), reads the 24 corner values of B into the slots a staging lane keeps
-// for V, and after the march blends them, turns B into the chord's frame and writes the sample's six numbers (wL, sP, cS, cQ, cU,
-// cV: zeeman_node.inc) into the head of the same staged sample.  No lane's live state is larger than a staging lane's of
-// k_sightline_voigt with V (an instantiation without V keeps V's slots for B).  A sample is 16 + 6*n_line float64: at 32 lines
-// 1664 bytes, 16 samples a buffer (53 248 bytes; with the 8 KiB of the lattices 61 440, under the 64 KiB a workgroup may take
-// without asking).
-// March: per sample, line and component one shifted centre; a component is dropped when x*x > cut, exactly, and a wavefront skips
-// a component whose window holds none of its frequencies (zeeman_outside).  The component table (q, g, s per component, an offset
-// per line) is the same for every sample and lane: it is read where it lies with addresses that depend on the loop counters alone
-// -- wavefront-uniform, scalar loads through the constant cache -- and takes no LDS.
-// Instantiated per (dtype, Te field?, Z field?, Ti field?, V field?, FL); continuum, LK and LG are uniform branches.  Compiled with
-// -ffp-contract=off, as its siblings.  With B NULL the entry is sr_field_sightline_voigt.
+// Polarised transfer along sightlines: sr_field_sightline_zeeman's chords, samples, components and coefficients, with the full 4 x 4
+// absorption matrix in the update -- dichroism (hQ, hU, hV), magneto-optical rotation inside the lines (rQ, rU, rV, from the
+// imaginary part of w(x + i a)) and Faraday rotation of the continuum -- and a polarised backlight (sr_field_sightline_stokes;
+// include/synthray.h states the rule).  No reference counterpart.  k_sightline_zeeman's decomposition, word for word: a workgroup
+// owns one chord and one tile of FL frequencies, a lane one frequency with its (I, Q, U, Vs, tau) in registers; the chord's samples
+// go through LDS in chunks of kStokesChunk, in two buffers; lanes 0 .. chunk-1 stage the samples, lanes chunk .. 2*chunk-1 carry B
+// and write the sample's six angular numbers and, as a seventh word, B.n^ itself (for the continuum's rotation).  A sample is
+// 18 + 6*n_line float64: at 32 lines 1680 bytes, 16 samples a buffer (53 760 bytes; with the 8 KiB of the lattices 61 952, under
+// the 64 KiB a workgroup may take without asking).
+// March: per sample, line and component one voigt_w -- both profiles from one evaluation -- under k_sightline_zeeman's window tests;
+// the 4 x 4 propagator O and the particular solution p of stokes_update are live only after the line loop, when the Voigt
+// temporaries are dead, in registers.  A sample and frequency without dichroism and rotation takes zeeman_update's operations.
+// Instantiated per (dtype, Te field?, Z field?, Ti field?, V field?, FL); continuum, LK, LG, faraday and pol are uniform branches.
+// Compiled with -ffp-contract=off, as its siblings.  With B NULL the entry is sr_field_sightline_voigt.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -36,18 +30,22 @@ namespace {
 
 #include "zeeman_node.inc"
 
-constexpr int kZeemanChunk = 16;  // samples staged at a time (sr_zeeman_chunk)
-constexpr int kHead = 10 + kZeemanWords;  // float64 of a staged sample before its lines: k_sightline_voigt's ten and the six of B
-static_assert(sizeof(double) * 2 * kZeemanChunk * (kHead + kVoigtWords * SR_MAX_LINES) + sizeof(double) * 2 * kMaxLattice <= kLdsBudget,
-              "two buffers at 32 lines and the lattices must fit the LDS budget");
-static_assert(2 * kZeemanChunk <= 64, "the staging lanes and the lanes that carry B are one wavefront");
+#include "stokes_node.inc"
 
-struct ZeemanArgs {
+constexpr int kStokesChunk = 16;  // samples staged at a time (sr_stokes_chunk)
+constexpr int kHead = 10 + kStokesWords;  // float64 of a staged sample before its lines: an even number keeps a line's reads 16-byte
+static_assert(sizeof(double) * 2 * kStokesChunk * (kHead + kVoigtWords * SR_MAX_LINES) + sizeof(double) * 2 * kMaxLattice <= kLdsBudget,
+              "two buffers at 32 lines and the lattices must fit the LDS budget");
+static_assert(2 * kStokesChunk <= 64, "the staging lanes and the lanes that carry B are one wavefront");
+static_assert(kHead % 2 == 0, "a staged line starts on 16 bytes");
+
+struct StokesArgs {
   const double *omega, *e_ph, *c_omega;  // (n_freq)
   int n_freq, n_tiles;
   const double *LT, *LD, *w0, *ci, *LJ, *LK, *LG;  // the packed table where it lies
-  int nT, nD, n_line, has_lk, has_lg, continuum;
-  double cut, kL;
+  int nT, nD, n_line, has_lk, has_lg, continuum, faraday, has_pol;
+  double cut, kL, kF2;  // kF2 = 2.0*kF
+  double pq, pu, pv;    // the backlight's (q, u, v); not read where has_pol is 0
   const void *B;
   const double *frame;  // (n, 9): n^, e1, e2 of every chord
   const double *comp;   // (sum n_comp, 3): q, g, s
@@ -56,8 +54,8 @@ struct ZeemanArgs {
 };
 
 template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V, int FL>
-__global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, FlowArgs W, ZeemanArgs X) {
-  extern __shared__ double s_stage[];  // [2][kZeemanChunk][kHead + 6*n_line]
+__global__ void __launch_bounds__(FL) k_sightline_stokes(EmArgs A, LineArgs L, FlowArgs W, StokesArgs X) {
+  extern __shared__ double s_stage[];  // [2][kStokesChunk][kHead + 6*n_line]
   __shared__ double s_lat[2 * kMaxLattice];
   const int64_t i = blockIdx.x / (unsigned)X.n_tiles;
   const int tile = (int)(blockIdx.x % (unsigned)X.n_tiles);
@@ -66,12 +64,16 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
   const bool active = f < X.n_freq;
   const int64_t at = i * X.n_freq + f;
   const Line l = line_of(L, i);
+  const bool has_pol = X.has_pol != 0;
+  // the march starts at I0*(1, q, u, v); a chord that misses the box returns this start
+  double I = (active && A.back) ? A.back[at] : 0.0;
+  double Q = has_pol ? I * X.pq : 0.0, U = has_pol ? I * X.pu : 0.0, Vs = has_pol ? I * X.pv : 0.0;
   if (!l.hit) {  // the whole workgroup: one chord
     if (active) {
-      A.I[at] = A.back ? A.back[at] : 0.0;
-      X.Q[at] = 0.0;
-      X.U[at] = 0.0;
-      X.Vs[at] = 0.0;
+      A.I[at] = I;
+      X.Q[at] = Q;
+      X.U[at] = U;
+      X.Vs[at] = Vs;
       A.tau[at] = 0.0;
     }
     if (tile == 0 && lane == 0) {
@@ -91,25 +93,24 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
   const int64_t sy = L.f.n[2], sx = (int64_t)L.f.n[1] * sy;
   const int k0 = A.toward > 0 ? 0 : n - 1, dk = A.toward > 0 ? 1 : -1;
   const double su = (double)A.toward / sqrt((l.d0 * l.d0 + l.d1 * l.d1) + l.d2 * l.d2);  // len of line_of, the same bits
-  const bool cont = X.continuum != 0, has_lk = X.has_lk != 0, has_lg = X.has_lg != 0;
+  const bool cont = X.continuum != 0, has_lk = X.has_lk != 0, has_lg = X.has_lg != 0, faraday = X.faraday != 0;
   const double *frame = X.frame + 9 * i;
   // the frequency's constants; an idle lane of the last tile takes the last frequency's and stores nothing
   const int fc = active ? f : X.n_freq - 1;
   const double om = X.omega[fc], eph = X.e_ph[fc], com = X.c_omega[fc];
   // the wavefront's span of frequencies: idle lanes widen nothing
   const double wmin = wave_extreme<true>(active ? om : HUGE_VAL), wmax = wave_extreme<false>(active ? om : -HUGE_VAL);
-  double I = (active && A.back) ? A.back[at] : 0.0;
-  double Q = 0.0, U = 0.0, Vs = 0.0, tau = 0.0, column = 0.0;
+  double tau = 0.0, column = 0.0;
 
   // lanes 0 .. chunk-1 stage sample `mine` of a chunk, lanes chunk .. 2*chunk-1 carry its B
-  const bool stager = lane < kZeemanChunk, carrier = lane >= kZeemanChunk && lane < 2 * kZeemanChunk;
-  const int mine = stager ? lane : lane - kZeemanChunk;
+  const bool stager = lane < kStokesChunk, carrier = lane >= kStokesChunk && lane < 2 * kStokesChunk;
+  const int mine = stager ? lane : lane - kStokesChunk;
   FlowSample<T, HAS_TE, HAS_Z, HAS_TI, true> cur{};
   if (stager && mine < n) fetch_staged<T, HAS_TE, HAS_Z, HAS_TI, HAS_V>(A, W, L.f, sx, sy, l, k0 + mine * dk, cur);
   if (carrier && mine < n) fetch_vector<T, HAS_TE, HAS_Z, HAS_TI>(X.B, L.f, sx, sy, l, k0 + mine * dk, cur);
   int buf = 0;
-  for (int m0 = 0; m0 < n; m0 += kZeemanChunk, buf ^= 1) {
-    const int cnt = min(kZeemanChunk, n - m0);
+  for (int m0 = 0; m0 < n; m0 += kStokesChunk, buf ^= 1) {
+    const int cnt = min(kStokesChunk, n - m0);
     // this chunk's samples (their reads were issued a chunk ago): blend, the lattice search, the lines' constants, to LDS
     if (stager && mine < cnt) {
       double ne, Te, Z, Ti, V[3];
@@ -118,7 +119,7 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
       const bool dark = t.dark || Ti <= 0.0;  // outside the box ne = 0: dark
       double beta = 0.0;
       if (HAS_V) beta = ((((V[0] * l.d0 + V[1] * l.d1) + V[2] * l.d2)) * su) / sr::kC;
-      double *S = s_stage + (size_t)(buf * kZeemanChunk + mine) * stride;
+      double *S = s_stage + (size_t)(buf * kStokesChunk + mine) * stride;
       int flags = dark ? 2 : 0;
       S[0] = ne * h;
       if (cont) {
@@ -135,7 +136,7 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
           if (has_lg) {
             const VoigtConst k = voigt_const(X.w0[q], X.ci[q], X.LJ, X.LK, X.LG, has_lk, o + q, NL, st, t.ft, t.fd, beta, Ti);
             P[0] = k.wc, P[1] = k.iw, P[2] = k.aJ, P[3] = k.aK, P[4] = k.a;
-          } else {  // Gaussian components through the same V: a = 0
+          } else {  // Gaussian components through the same w: a = 0
             const LineConst k = line_const(X.w0[q], X.ci[q], X.LJ, X.LK, has_lk, o + q, NL, st, t.ft, t.fd, beta, Ti);
             P[0] = k.wc, P[1] = k.iw, P[2] = k.aJ, P[3] = k.aK, P[4] = 0.0;
           }
@@ -146,22 +147,23 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
       double B[3];
       blend_vector<T, HAS_TE, HAS_Z, HAS_TI>(cur, B);
       const ZeemanSample z = zeeman_sample(B, frame, X.kL);
-      double *S = s_stage + (size_t)(buf * kZeemanChunk + mine) * stride + 10;
+      double *S = s_stage + (size_t)(buf * kStokesChunk + mine) * stride + 10;
       S[0] = z.wL, S[1] = z.sP, S[2] = z.cS, S[3] = z.cQ, S[4] = z.cU, S[5] = z.cV;
+      S[6] = (B[0] * frame[0] + B[1] * frame[1]) + B[2] * frame[2];  // zeeman_sample's Bn, the same bits
     }
     __syncthreads();
     // the next chunk's cells and corner reads, in flight during this chunk's march
     cur.s.in = false;
-    if (stager && m0 + kZeemanChunk + mine < n)
-      fetch_staged<T, HAS_TE, HAS_Z, HAS_TI, HAS_V>(A, W, L.f, sx, sy, l, k0 + (m0 + kZeemanChunk + mine) * dk, cur);
-    if (carrier && m0 + kZeemanChunk + mine < n)
-      fetch_vector<T, HAS_TE, HAS_Z, HAS_TI>(X.B, L.f, sx, sy, l, k0 + (m0 + kZeemanChunk + mine) * dk, cur);
+    if (stager && m0 + kStokesChunk + mine < n)
+      fetch_staged<T, HAS_TE, HAS_Z, HAS_TI, HAS_V>(A, W, L.f, sx, sy, l, k0 + (m0 + kStokesChunk + mine) * dk, cur);
+    if (carrier && m0 + kStokesChunk + mine < n)
+      fetch_vector<T, HAS_TE, HAS_Z, HAS_TI>(X.B, L.f, sx, sy, l, k0 + (m0 + kStokesChunk + mine) * dk, cur);
     if (active) {
 #pragma unroll 1
       for (int s = 0; s < cnt; ++s) {
-        const double *S = s_stage + (size_t)(buf * kZeemanChunk + s) * stride;
+        const double *S = s_stage + (size_t)(buf * kStokesChunk + s) * stride;
         const int flags = (int)S[1];
-        double jI = 0.0, jQ = 0.0, jU = 0.0, jV = 0.0, aL = 0.0;
+        double jI = 0.0, jQ = 0.0, jU = 0.0, jV = 0.0, hI = 0.0, hQ = 0.0, hU = 0.0, hV = 0.0, rQ = 0.0, rU = 0.0, rV = 0.0;
         bool counted = false;
         if (!(flags & 2)) {
           ZeemanSample z;
@@ -170,7 +172,7 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
           for (int q = 0; q < NL; ++q) {
             const double *P = S + kHead + kVoigtWords * q;
             const double wc = P[0], iw = P[1], a = P[4];
-            double P0 = 0.0, Pp = 0.0, Pm = 0.0;
+            double P0 = 0.0, Pp = 0.0, Pm = 0.0, R0 = 0.0, Rp = 0.0, Rm = 0.0;
             bool any = false;
             const int k1 = X.off[q + 1];
 #pragma unroll 1
@@ -179,22 +181,25 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
               if (zeeman_outside(wc, sh, iw, wmin, wmax, cut)) continue;  // the same for every lane of the wavefront
               double x;
               if (zeeman_term(om, wc, sh, iw, cut, x)) {
-                const double v = sk * voigt(a, x);
+                double H, D;
+                voigt_w(a, x, &H, &D);
+                const double v = sk * H, d = sk * D;
                 if (cq == 0.0)
-                  P0 = P0 + v;
+                  P0 = P0 + v, R0 = R0 + d;
                 else if (cq > 0.0)
-                  Pp = Pp + v;
+                  Pp = Pp + v, Rp = Rp + d;
                 else
-                  Pm = Pm + v;
+                  Pm = Pm + v, Rm = Rm + d;
                 any = true;
               }
             }
             if (any) {
-              zeeman_line(z, P[2], P[3], P0, Pp, Pm, jI, jQ, jU, jV, aL);
+              stokes_line(z, P[2], P[3], P0, Pp, Pm, R0, Rp, Rm, jI, jQ, jU, jV, hI, hQ, hU, hV, rQ, rU, rV);
               counted = true;
             }
           }
         }
+        if (faraday) rV = rV + ((X.kF2 * (S[0] / h)) * S[16]) / (om * om);
         double ac = 0.0, Sc = 0.0;
         if (cont) {
           NodeTerms t;
@@ -202,8 +207,11 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
           t.Te = S[2], t.n = S[3], t.wp = S[4], t.L = S[5], t.num = S[6], t.zc = S[7], t.it = S[8];
           node_band(t, om, eph, com, ac, Sc);
         }
-        if (counted) {
-          zeeman_update(ac, Sc, jI, jQ, jU, jV, aL, h, I, Q, U, Vs, tau);
+        const bool scalar = hQ == 0.0 && hU == 0.0 && hV == 0.0 && rQ == 0.0 && rU == 0.0 && rV == 0.0;
+        if (!scalar) {
+          stokes_update(ac, Sc, jI, jQ, jU, jV, hI, hQ, hU, hV, rQ, rU, rV, h, I, Q, U, Vs, tau);
+        } else if (counted) {  // sr_field_sightline_zeeman's update, its operations
+          zeeman_update(ac, Sc, jI, jQ, jU, jV, hI, h, I, Q, U, Vs, tau);
         } else if (cont) {
           const double dtau = ac * h;
           const double E = exp(-dtau);
@@ -239,16 +247,24 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
 
 }  // namespace
 
-extern "C" int sr_zeeman_chunk(void) { return kZeemanChunk; }
+extern "C" int sr_stokes_chunk(void) { return kStokesChunk; }
 
-extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te, const sr_field *Ti, const sr_field *Z, const sr_field *V,
+extern "C" int sr_field_sightline_stokes(const sr_field *ne, const sr_field *Te, const sr_field *Ti, const sr_field *Z, const sr_field *V,
                                          const sr_field *B, const sr_zeeman_table *lines, const sr_voigt_params *p, int64_t n,
                                          const double *origin, const double *dir, const double *ref, int32_t n_freq, const double *omega,
-                                         const double *e_ph, const double *c_omega, const double *backlight, double *I, double *Q,
-                                         double *U, double *Vs, double *tau, double *column, double *chord, int32_t *steps,
-                                         double *kernel_ms) {
-  const char *who = "sr_field_sightline_zeeman";
-  if (B == nullptr) {  // no field: that entry's rule, kernel and bits; the component table and ref are not read
+                                         const double *e_ph, const double *c_omega, const double *backlight, const double *pol,
+                                         int32_t faraday, double *I, double *Q, double *U, double *Vs, double *tau, double *column,
+                                         double *chord, int32_t *steps, double *kernel_ms) {
+  const char *who = "sr_field_sightline_stokes";
+  SR_CHECK(faraday == 0 || faraday == 1, "%s: faraday must be 0 or 1, got %d", who, faraday);
+  if (pol) {
+    SR_CHECK(std::isfinite(pol[0]) && std::isfinite(pol[1]) && std::isfinite(pol[2]), "%s: non-finite pol", who);
+    SR_CHECK((pol[0] * pol[0] + pol[1] * pol[1]) + pol[2] * pol[2] <= 1.0 + kStokesPolTol,
+             "%s: pol = (%g, %g, %g) lies outside the unit ball", who, pol[0], pol[1], pol[2]);
+  }
+  if (B == nullptr) {  // no field: sr_field_sightline_voigt's rule, kernel and bits; the component table and ref are not read
+    SR_CHECK(!faraday, "%s: faraday needs B", who);
+    SR_CHECK(pol == nullptr, "%s: pol needs B", who);
     SR_CHECK(lines != nullptr, "%s: NULL line table", who);
     SR_CHECK(n >= 0 && n_freq >= 0, "%s: n and n_freq must not be negative, got %lld and %d", who, (long long)n, n_freq);
     if (int rc = sr_field_sightline_voigt(ne, Te, Ti, Z, V, &lines->voigt, p, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I,
@@ -259,6 +275,7 @@ extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te,
       if (out && bytes) memset(out, 0, bytes);
     return SR_OK;
   }
+  // sr_field_sightline_zeeman's checks, in its order
   SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
   SR_CHECK(ref != nullptr && Q != nullptr && U != nullptr && Vs != nullptr, "%s: NULL ref, Q, U or Vs (B is given)", who);
   SR_CHECK(omega != nullptr && e_ph != nullptr && c_omega != nullptr, "%s: NULL omega, e_ph or c_omega", who);
@@ -300,7 +317,7 @@ extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te,
   EmArgs A{};
   LineArgs L{};
   FlowArgs W{};
-  ZeemanArgs X{};
+  StokesArgs X{};
   double *tab = nullptr;
   sr::Carve carve;
   take_lines(carve, A, L, ne, n, m->step, m->max_steps, nf, backlight != nullptr);
@@ -334,8 +351,12 @@ extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te,
   X.has_lk = lt->LK != nullptr;
   X.has_lg = lines->voigt.LG != nullptr;
   X.continuum = m->continuum != 0;
+  X.faraday = faraday;
+  X.has_pol = pol != nullptr;
+  if (pol) X.pq = pol[0], X.pu = pol[1], X.pv = pol[2];
   X.cut = p->wing * p->wing;
   X.kL = kLineE / (2.0 * kZeemanMe);
+  X.kF2 = 2.0 * (((kLineE * kLineE) * kLineE) / ((((2.0 * kStokesEps0) * kZeemanMe) * kZeemanMe) * kStokesC));
 
   SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
   SR_HIP(hipMemcpyAsync(const_cast<double *>(X.frame), frames.data(), sizeof(double) * frames.size(), hipMemcpyHostToDevice, st));
@@ -347,12 +368,12 @@ extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te,
   SR_HIP(hipMemcpyAsync(const_cast<int *>(X.off), off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, st));
   SR_HIP(hipEventRecord(c.ev[0], st));
   const unsigned grid = (unsigned)(n * n_tiles);
-  const size_t lds = sizeof(double) * 2 * kZeemanChunk * (kHead + kVoigtWords * nl);  // at most 53 248 bytes
+  const size_t lds = sizeof(double) * 2 * kStokesChunk * (kHead + kVoigtWords * nl);  // at most 53 760 bytes
   sr::with_flags(
       [&](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
         using T = std::conditional_t<decltype(f64)::value, double, float>;
         constexpr int kFl = decltype(narrow)::value ? 64 : 256;
-        hipLaunchKernelGGL((k_sightline_zeeman<T, decltype(te)::value, decltype(z)::value, decltype(ti)::value, decltype(v)::value, kFl>),
+        hipLaunchKernelGGL((k_sightline_stokes<T, decltype(te)::value, decltype(z)::value, decltype(ti)::value, decltype(v)::value, kFl>),
                            dim3(grid), dim3(kFl), lds, st, A, L, W, X);
       },
       (bool)ne->is_f64, Te != nullptr, Z != nullptr, Ti != nullptr, V != nullptr, fl == 64);

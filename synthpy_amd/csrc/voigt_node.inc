@@ -87,6 +87,82 @@ __device__ __forceinline__ double voigt(double a, double x) {
   return voigt_sampled<18>(a, x, 0.1875, 2.6666666666666665, 0.375, C);
 }
 
+// ---- the whole of w(x + i a): H = Re w with voigt()'s operations and bits, L = Im w (the dispersion profile) from the same
+// intermediates (include/synthray.h's "Polarised transfer along sightlines" section).  voigt() and what it calls stay as they are.
+template <int K>
+__device__ __forceinline__ void voigt_cf_w(double a, double x, double &H, double &L) {
+  double Nr = x, Ni = a, Dr = 1.0, Di = 0.0;
+#pragma unroll
+  for (int k = K; k >= 1; --k) {
+    const double c = 0.5 * k;
+    const double tr = (Nr * x - Ni * a) - c * Dr;
+    const double ti = (Nr * a + Ni * x) - c * Di;
+    Dr = Nr, Di = Ni, Nr = tr, Ni = ti;
+  }
+  const double den = Nr * Nr + Ni * Ni;
+  H = (kLineISP * (Dr * Ni - Di * Nr)) / den;
+  L = (kLineISP * (Dr * Nr + Di * Ni)) / den;
+}
+
+template <int NP>
+__device__ __forceinline__ void voigt_sampled_w(double a, double x, double h, double ih2, double h2, const double (&C)[NP], double &H,
+                                                double &L) {
+  const double n0 = 2.0 * rint(ih2 * x);
+  const double xp = x - h * n0;
+  const double a2 = a * a;
+  const double g = exp(a2 - xp * xp);
+  const double th = (2.0 * a) * xp;
+  const double Gr = g * cos(th), Gi = -(g * sin(th));
+  const double pe = exp(h2 * xp);
+  const double me = 1.0 / pe;
+  const double ca = cos(h2 * a), sa = sin(h2 * a);
+  double pr = pe * ca, pi = pe * sa, mr = me * ca, mi = -(me * sa);
+  const double p2r = pr * pr - pi * pi, p2i = (2.0 * pr) * pi;
+  const double m2r = mr * mr - mi * mi, m2i = (2.0 * mr) * mi;
+  const double d0 = n0 * n0;
+  double Sr = 0.0, Si = 0.0;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const double n = 2 * k + 1;
+    const double q = C[k] / (d0 - n * n);
+    Sr = Sr + q * (pr * (n0 - n) + mr * (n0 + n));
+    Si = Si + q * (pi * (n0 - n) + mi * (n0 + n));
+    const double tp = pr * p2r - pi * p2i, tm = mr * m2r - mi * m2i;
+    pi = pr * p2i + pi * p2r, mi = mr * m2i + mi * m2r;
+    pr = tp, mr = tm;
+  }
+  const double imF = (Gr * Si + Gi * Sr) * kLineISP;
+  const double reF = (Gr * Sr - Gi * Si) * kLineISP;
+  const double e = exp(a2 - x * x), t2 = (2.0 * a) * x;
+  H = e * cos(t2) - (2.0 * kLineISP) * imF;
+  L = (2.0 * kLineISP) * reF - e * sin(t2);
+}
+
+__device__ __forceinline__ void voigt_w(double a, double x, double *H, double *L) {
+  const double z2 = x * x + a * a;
+  if (!(z2 < 1e17)) {
+    *H = (kLineISP * a) / z2;
+    *L = (kLineISP * x) / z2;
+  } else if (z2 >= 100.0) {
+    voigt_cf_w<10>(a, x, *H, *L);
+  } else if (a >= 2.0) {
+    voigt_cf_w<40>(a, x, *H, *L);
+  } else if (a <= 0.5) {
+    constexpr double C[13] = {0.9394130628134758,     0.569782824730923,      0.2096113871510978,     0.04677062238395898,
+                              0.006329715427485747,   0.0005195746821548384,  2.586810022265412e-05,  7.811489408304491e-07,
+                              1.4307241918567688e-08, 1.5893910094516368e-10, 1.0709232382508077e-12, 4.37661850287085e-15,
+                              1.0848552640429378e-17};
+    voigt_sampled_w<13>(a, x, 0.25, 2.0, 0.5, C, *H, *L);
+  } else {
+    constexpr double C[18] = {0.9654545521978378,     0.7287633299194912,     0.4152368286818413,     0.17859113461243561,
+                              0.0579800525002544,     0.014208622931196246,   0.002628330960567707,   0.0003669972327972938,
+                              3.8681223753184774e-05, 3.0774591584232196e-06, 1.8481578772048032e-07, 8.378003053124454e-09,
+                              2.866794996873118e-10,  7.404699497933558e-12,  1.4436865682659833e-13, 2.1246777523216493e-15,
+                              2.3603037795421644e-17, 1.9792352186549065e-19};
+    voigt_sampled_w<18>(a, x, 0.1875, 2.6666666666666665, 0.375, C, *H, *L);
+  }
+}
+
 // line_const's four and a = gam*iw, gam = exp(l(LG)): LG is packed line-innermost as LJ and LK are
 __device__ __forceinline__ VoigtConst voigt_const(double w0, double ci, const double *LJ, const double *LK, const double *LG, bool has_lk,
                                                   int o, int sd, int st, double ft, double fd, double beta, double Ti) {

@@ -83,6 +83,51 @@ __device__ __forceinline__ void zeeman_update(double ac, double Sc, double jI, d
   }
 }
 
+// ---- what the kernels that march Stokes parameters share (sightline_zeeman.hip, sightline_stokes.hip)
+
+// the least (LEAST) or the greatest value of a wavefront, in every lane
+template <bool LEAST>
+__device__ __forceinline__ double wave_extreme(double v) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const double o = __shfl_xor(v, s, 64);
+    v = LEAST ? (o < v ? o : v) : (o > v ? o : v);
+  }
+  return v;
+}
+
+// sightline_march.inc's fetch_sample and blend_sample of a FlowSample, on a sample that always has V's slots (a lane that carries
+// B fills them with B's corners): the same operations, so the same bits
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>
+__device__ __forceinline__ void fetch_staged(const EmArgs &A, const FlowArgs &W, const sr::FieldGrid &f, int64_t sx, int64_t sy,
+                                             const Line &l, int k, FlowSample<T, HAS_TE, HAS_Z, HAS_TI, true> &s) {
+  const double t = l.t0 + ((double)k + 0.5) * l.dt;
+  fetch<T, HAS_TE, HAS_Z>(A, f, sx, sy, l.o0 + l.d0 * t, l.o1 + l.d1 * t, l.o2 + l.d2 * t, s.s, [&](int ci, int cj, int ck) {
+    if (HAS_TI) s.Ti = sr::corners_load(static_cast<const T *>(W.Ti), 1, 0, sx, sy, ci, cj, ck);
+    if (HAS_V) {
+      s.V0 = sr::corners_load(static_cast<const T *>(W.V), 3, 0, sx, sy, ci, cj, ck);
+      s.V1 = sr::corners_load(static_cast<const T *>(W.V), 3, 1, sx, sy, ci, cj, ck);
+      s.V2 = sr::corners_load(static_cast<const T *>(W.V), 3, 2, sx, sy, ci, cj, ck);
+    }
+  });
+}
+template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>
+__device__ __forceinline__ void blend_staged(const EmArgs &A, const FlowSample<T, HAS_TE, HAS_Z, HAS_TI, true> &s, double &ne, double &Te,
+                                             double &Z, double &Ti, double (&V)[3]) {
+  blend_sample<T, HAS_TE, HAS_Z>(A, s.s, ne, Te, Z);
+  Ti = Te;
+  V[0] = V[1] = V[2] = 0.0;
+  if (s.s.in) {
+    const Sample<T, HAS_TE, HAS_Z> &c = s.s;
+    if (HAS_TI) Ti = sr::corners_blend(s.Ti, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    if (HAS_V) {
+      V[0] = sr::corners_blend(s.V0, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+      V[1] = sr::corners_blend(s.V1, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+      V[2] = sr::corners_blend(s.V2, c.ux, c.wx, c.w00, c.w01, c.w10, c.w11);
+    }
+  }
+}
+
 // ---- host: the chord frames, and the checks of a Zeeman table beyond check_voigt_table's
 
 // F[9*i ..]: n^ = d*su, e1 = ref minus its part along n^, normalised, e2 = n^ x e1 -- the header's operations in its order.  Runs

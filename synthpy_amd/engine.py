@@ -782,6 +782,14 @@ def sightline_zeeman(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lin
     back to engine.sightline_lines).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: dichroism and magneto-optical
     rotation in the absorption matrix (absorption acts equally on all four parameters), Faraday rotation of the continuum, the
     Paschen-Back regime, hyperfine structure, and what engine.sightline_voigt does not model; one GPU."""
+    return _stokes_family(lambda head, outs: lib.sr_field_sightline_zeeman(*head, *outs), ne, Te, Ti, Z, V, B, origins, directions,
+                          reference, lines, omegas, continuum, wing, toward, step, max_steps, backlight, want)
+
+
+def _stokes_family(call, ne, Te, Ti, Z, V, B, origins, directions, reference, lines, omegas, continuum, wing, toward, step, max_steps,
+                   backlight, want):
+    """What sightline_zeeman and sightline_stokes share: the handles, the table, the reference, the three maps beside I and tau.
+    call(head, outs): the library's entry, head its arguments up to the backlight, outs those from I on."""
     h_Ti, h_V, h_B = _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("B", B, none=True)
     t, keep = zeeman_table_params(lines)
     stokes_names = ("Q", "U", "V")
@@ -811,8 +819,8 @@ def sightline_zeeman(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lin
             stokes[k] = np.empty((n, len(om)))
 
         def entry(h_ne, h_Te, h_Z, _, p_, n_, o, d, nf, w, e, c, back, I, tau, *rest):  # the family's order -> this entry's
-            return lib.sr_field_sightline_zeeman(h_ne, h_Te, h_Ti, h_Z, h_V, h_B, C.byref(t), p_, n_, o, d, ptr(ref), nf, w, e, c, back, I,
-                                                 ptr(stokes["Q"]), ptr(stokes["U"]), ptr(stokes["V"]), tau, *rest)
+            return call((h_ne, h_Te, h_Ti, h_Z, h_V, h_B, C.byref(t), p_, n_, o, d, ptr(ref), nf, w, e, c, back),
+                        (I, ptr(stokes["Q"]), ptr(stokes["U"]), ptr(stokes["V"]), tau, *rest))
 
         return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
 
@@ -820,6 +828,35 @@ def sightline_zeeman(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lin
                       tuple(k for k in want if k in _SIGHT_WANT))
     out.update({k: stokes[k] for k in stokes_names if k in want})
     return out
+
+
+STOKES_CHUNK = _ffi.STOKES_CHUNK  # samples of a chord sr_field_sightline_stokes' kernel stages at a time
+EPS0 = 8.8541878128e-12  # F/m
+# kF [rad m^-1 per (m^-3 T (rad/s)^-2)]: the plane of polarisation turns by kF ne B.n^ s / omega^2; formed as the library forms it
+FARADAY = ((E_CHARGE * E_CHARGE) * E_CHARGE) / ((((2.0 * EPS0) * M_ELECTRON) * M_ELECTRON) * c)
+
+
+def sightline_stokes(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lines, omegas, continuum=False, wing=np.inf, toward,
+                     step, max_steps, backlight=None, polarisation=None, faraday=False, want=_SIGHT_WANT + ("Q", "U", "V")):
+    """engine.sightline_zeeman with the whole absorption matrix of the polarised transfer equation in the update
+    (sr_field_sightline_stokes; include/synthray.h states the rule, the algorithm and the sign conventions): the lines' absorption
+    is dichroic (hQ, hU, hV: the sums of jQ, jU, jV with the table's absorption), the plane of polarisation turns inside the lines
+    (rQ, rU, rV, from the imaginary part of the Faddeeva function) and, with faraday=True, in the continuum, by
+    FARADAY * ne * B.n^ / omega^2 per metre from e1 towards e2 for B along the light's travel.  polarisation: (q, u, v), the
+    backlight's Stokes parameters as fractions of its intensity, q^2 + u^2 + v^2 <= 1; None: unpolarised.  Everything else -- the
+    chords, the fields, reference, continuum, wing, toward, step, max_steps, backlight, want and the dict returned -- is
+    engine.sightline_zeeman's; with a table without absorption, faraday=False and polarisation=None it returns that entry's bits,
+    with B = None engine.sightline_voigt's (faraday or polarisation are then errors).  ne.last_kernel_ms keeps the kernel's time.
+    Not modelled: the Paschen-Back regime, hyperfine structure, cyclotron dichroism of the continuum, scattering polarisation, the
+    Hanle effect, and what engine.sightline_voigt does not model; one GPU."""
+    pol = None
+    if polarisation is not None:
+        pol = f64(polarisation)
+        if pol.shape != (3,):
+            raise ValueError(f"polarisation must be (q, u, v), got shape {pol.shape}")
+        pol = np.ascontiguousarray(pol)
+    return _stokes_family(lambda head, outs: lib.sr_field_sightline_stokes(*head, ptr(pol), 1 if faraday else 0, *outs), ne, Te, Ti, Z, V,
+                          B, origins, directions, reference, lines, omegas, continuum, wing, toward, step, max_steps, backlight, want)
 
 
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED

@@ -451,9 +451,10 @@ def sightline_lines(domain, view, lines, wavelengths=None, photon_energies=None,
 
 
 def _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, call, reference=None, **opts):
-    """What sightline_lines, sightline_voigt and sightline_zeeman share: the checks, the frequencies, the domain's Ti and V, and
+    """What sightline_lines, sightline_voigt, sightline_zeeman and sightline_stokes share: the checks, the frequencies, the domain's Ti and V, and
     `call` (the engine's entry, with `opts`) along the view.  reference (sightline_zeeman alone: (3, N) in the view's order, already
-    resolved): the domain's B goes up as well, the call is engine.sightline_zeeman's, and a StokesSpectra comes back."""
+    resolved): the domain's B goes up as well, the call is engine.sightline_zeeman's or engine.sightline_stokes', and a
+    StokesSpectra comes back."""
     if (wavelengths is None) == (photon_energies is None):
         raise ValueError("exactly one of wavelengths [m] and photon_energies [eV] must be given")
     _check_view(view)
@@ -572,6 +573,17 @@ class StokesSpectra(LineSpectra):
                 out[..., l] = (cen[0] - cen[1]) / (2.0 * g[l] * engine.LARMOR)
         return out
 
+    def polarisation_angle(self):
+        """The angle of the plane of linear polarisation from e1 towards e2 [rad], in (-pi/2, pi/2]: 0.5 arctan2(U, Q), the shape
+        of intensity (0 where Q = U = 0)."""
+        return 0.5 * np.arctan2(self.U, self.Q)
+
+    def degree(self):
+        """The degree of polarisation sqrt(Q^2 + U^2 + V^2) / I, the shape of intensity; NaN where there is no radiance."""
+        with np.errstate(all="ignore"):
+            p = np.sqrt(self.Q * self.Q + self.U * self.U + self.V * self.V)
+            return np.where(self.intensity > 0, p / self.intensity, np.nan)
+
 
 def default_reference(view):
     """The reference direction of every chord of `view`, (3, N) in the view's order: a pixel view's up (its frame's y), for Chords
@@ -582,6 +594,19 @@ def default_reference(view):
     ref = np.zeros(d.shape)
     ref[np.argmin(np.abs(d), axis=0), np.arange(d.shape[1])] = 1.0
     return ref
+
+
+def _resolved_reference(view, reference):
+    """reference as (3, N) in the view's order: (3,) for all chords, (3, N), or None: default_reference(view)."""
+    n = int(np.prod(view.shape))
+    if reference is None:
+        return default_reference(view)
+    ref = np.asarray(reference, np.float64)
+    if ref.shape == (3,):
+        ref = np.broadcast_to(ref[:, None], (3, n))
+    if ref.shape != (3, n):
+        raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
+    return np.ascontiguousarray(ref)
 
 
 def sightline_zeeman(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
@@ -601,15 +626,28 @@ def sightline_zeeman(domain, view, lines, wavelengths=None, photon_energies=None
     if getattr(lines, "patterns", None) is None:
         raise ValueError("lines must be a ZeemanLineTable (utils.eos_opacity): it has no patterns")
     _check_view(view)
-    n = int(np.prod(view.shape))
-    if reference is None:
-        ref = default_reference(view)
-    else:
-        ref = np.asarray(reference, np.float64)
-        if ref.shape == (3,):
-            ref = np.broadcast_to(ref[:, None], (3, n))
-        if ref.shape != (3, n):
-            raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
-        ref = np.ascontiguousarray(ref)
+    ref = _resolved_reference(view, reference)
     return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_zeeman,
                          reference=ref, continuum=continuum, wing=np.inf if wing is None else wing)
+
+
+def sightline_stokes(domain, view, lines, wavelengths=None, photon_energies=None, continuum=False, wing=None, step=None, max_steps=None,
+                     fields=None, reference=None, polarisation=None, faraday=False):
+    """sightline_zeeman with the full polarised transfer equation: a StokesSpectra (engine.sightline_stokes ->
+    sr_field_sightline_stokes; include/synthray.h states the rule, the algorithm and the sign conventions).  The table's absorption
+    acts through the 4 x 4 absorption matrix: it is dichroic -- an unpolarised backlight comes out of a Zeeman-split absorption
+    line with the opposite polarisation of the line's emission, and a thick emission line depolarises towards its source function
+    -- and the plane of polarisation turns inside the lines (magneto-optical rotation, from the dispersion profile) and, with
+    faraday=True, in the continuum: by engine.FARADAY * ne * B.n^ / omega^2 per metre, from e1 towards e2 for B along the light's
+    travel.  polarisation: (q, u, v), the Stokes parameters of view.backlight as fractions of its intensity, q^2 + u^2 + v^2 <= 1;
+    None: unpolarised.  StokesSpectra.polarisation_angle() and degree() read the result; b_parallel() works on absorption spectra
+    too.  Everything else is sightline_zeeman's; a table without absorption, faraday=False and polarisation=None give its bits.
+    Not modelled: the Paschen-Back regime, hyperfine structure, cyclotron dichroism of the continuum, scattering polarisation, the
+    Hanle effect, and what sightline_voigt does not model; one GPU."""
+    if getattr(lines, "patterns", None) is None:
+        raise ValueError("lines must be a ZeemanLineTable (utils.eos_opacity): it has no patterns")
+    _check_view(view)
+    ref = _resolved_reference(view, reference)
+    return _line_spectra(domain, view, lines, wavelengths, photon_energies, step, max_steps, fields, engine.sightline_stokes,
+                         reference=ref, continuum=continuum, wing=np.inf if wing is None else wing, polarisation=polarisation,
+                         faraday=faraday)
