@@ -2,7 +2,8 @@
 // the emission and absorption coefficient of one sample at one frequency, in three parts as nrl_node.inc's and table_node.inc's
 // nodes are: what a sample gives every line (the lattice search: table_node.inc's table_terms; beta), the constants of one line at
 // that sample (line_const: centre, inverse width, peak emission and absorption), and one frequency's term (line_term).  With them
-// the sample's update (line_update) and, on the host, the checks and the packing of a line table.  Included inside the including
+// the sample's update (line_update), the wavefront's least and greatest frequency for the skip of a whole line (wave_extreme: the
+// family's one definition) and, on the host, the checks and the packing of a line table.  Included inside the including
 // unit's anonymous namespace, after table_node.inc (bilinear, check_lattice, kMaxLattice).
 
 constexpr double kLineE = 1.602176634e-19, kLineMp = 1.67262192369e-27, kLineISP = 0.5641895835477563;
@@ -53,6 +54,17 @@ __device__ __forceinline__ void line_update(double ac, double Sc, double j, doub
     I = I * exp(-dtau) + ((ac * Sc + j) / a) * (-expm1(-dtau));
     tau = tau + dtau;
   }
+}
+
+// the least (LEAST) or the greatest value of a wavefront, in every lane
+template <bool LEAST>
+__device__ __forceinline__ double wave_extreme(double v) {
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const double o = __shfl_xor(v, s, 64);
+    v = LEAST ? (o < v ? o : v) : (o > v ? o : v);
+  }
+  return v;
 }
 
 // ---- host: the checks of a line table (`who` names the entry in the error text) and its packing

@@ -1,32 +1,30 @@
 // Line spectra along sightlines: Doppler-shifted, thermally broadened spectral lines, optionally on the NRL continuum
-// (sr_field_sightline_lines; include/synthray.h states the rule).  No reference counterpart.  k_sightline_spectra's decomposition:
-// a workgroup owns one chord and one tile of FL frequencies, a lane owns one frequency and keeps its (I, tau) in registers; the
-// chord's samples go through LDS in chunks of kLinesChunk, in march order, in two buffers, and the corner reads of chunk c+1 are
-// issued before the march of chunk c and blended after it.
+// (sr_field_sightline_lines; include/synthray.h states the rule).  No reference counterpart.  The decomposition is the family's
+// (line_family.inc: a workgroup per chord and tile of FL frequencies, a lane per frequency, the samples through LDS in chunks of
+// kLinesChunk in two buffers); what is this kernel's own:
 //
 // Staging: lane s < kLinesChunk takes sample s of the chunk -- the cell search and the 8 corner reads of ne, Te, Z, Ti and the three
-// components of V (sightline_march.inc's FlowSample), the blend, the ONE search of the (ln Te, ln ni) lattice (table_node.inc's
-// table_terms), beta, and then per line its centre, inverse width, peak emission and peak absorption (line_node.inc's line_const:
-// two bilinear reads and two exp a line) -- and writes them to LDS, a sample's lines one after the other, the four constants of a
-// line adjacent (two 16-byte reads; every marching lane reads the same address, a broadcast).  With the continuum on, nrl_node.inc's
-// node_terms go beside them.  A sample is 10 + 4*n_line float64: at 32 lines 1104 bytes, and the two buffers of 24 samples 52 KiB --
-// with the 8 KiB of the lattices under the 64 KiB a workgroup may take without asking, two workgroups to a CU's 160 KiB; the LDS is
-// sized by n_line at launch, so a single line takes 5 KiB.
+// components of V (sightline_march.inc's FlowSample), the blend, line_family.inc's stage_head, and then per line its centre, inverse
+// width, peak emission and peak absorption (line_node.inc's line_const: two bilinear reads and two exp a line) -- and writes them
+// to LDS, a sample's lines one after the other, the four constants of a line adjacent (two 16-byte reads; every marching lane
+// reads the same address, a broadcast).  A sample is 10 + 4*n_line float64: at 32 lines 1104 bytes, and the two buffers of 24
+// samples 52 KiB -- with the 8 KiB of the lattices under the 64 KiB a workgroup may take without asking, two workgroups to a CU's
+// 160 KiB; the LDS is sized by n_line at launch, so a single line takes 5 KiB.
 // March: after one barrier every active lane walks the staged samples in order and the lines of a sample in ascending order.  A
 // term with x*x > 40 is dropped, which is exact, so a WAVEFRONT skips a line whose window holds none of its frequencies
 // (line_outside on the least and the greatest frequency of the wavefront, found once with six shuffles each): lanes hold consecutive
 // list entries, so a sorted list makes most of a narrow line's tests one comparison per wavefront.  The skip changes no bit: it
 // only leaves out terms every lane would have dropped.  What a lane does per counted term is one exp and five multiply-adds worth
 // of float64; per sample with a counted term an exp, an expm1 and a division, and with the continuum node_band's log and expm1.
-// Trip counts are uniform in a workgroup, a missed chord leaves before the first barrier, the last tile's idle lanes stage but
-// neither march nor store, tile 0's lane 0 sums column and writes the chord's column, chord and steps.  No scratch (the line loop
-// runs over LDS, never over a register array), no atomics.
+// No scratch (the line loop runs over LDS, never over a register array), no atomics.
 // The line table is packed line-innermost, LT | LD | w0 | ci | LJ[nT][nD][n_line] | LK[nT][nD][n_line]: what a staging lane reads
 // for the lines of its sample are four contiguous runs per table.  The lattices are staged in LDS for the searches.
 // Instantiated per (dtype, Te field?, Z field?, Ti field?, V field?, FL); continuum and LK are uniform branches.
 // Compiled with -ffp-contract=off, as its siblings: column, chord and steps are the bits k_sightlines gives, and where every term
 // is dropped I and tau are the bits of k_sightline_spectra.
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "emission_march.inc"
@@ -38,8 +36,14 @@ namespace {
 
 #include "line_node.inc"
 
+#include "voigt_node.inc"
+
+#include "zeeman_node.inc"
+
+#include "line_family.inc"
+
 constexpr int kLinesChunk = 24;  // samples staged at a time (sr_lines_chunk)
-constexpr int kHead = 10;        // float64 of a staged sample before its lines: ne*h, flags, node_terms' seven, one of padding
+constexpr int kHead = 10;        // float64 of a staged sample before its lines: the family's head
 
 struct LinesArgs {
   const double *omega, *e_ph, *c_omega;  // (n_freq)
@@ -47,17 +51,6 @@ struct LinesArgs {
   const double *LT, *LD, *w0, *ci, *LJ, *LK;  // the packed table where it lies
   int nT, nD, n_line, has_lk, continuum;
 };
-
-// the least (LEAST) or the greatest value of a wavefront, in every lane
-template <bool LEAST>
-__device__ __forceinline__ double wave_extreme(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const double o = __shfl_xor(v, s, 64);
-    v = LEAST ? (o < v ? o : v) : (o > v ? o : v);
-  }
-  return v;
-}
 
 template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V, int FL>
 __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, FlowArgs W, LinesArgs X) {
@@ -71,15 +64,7 @@ __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, Fl
   const int64_t at = i * X.n_freq + f;
   const Line l = line_of(L, i);
   if (!l.hit) {  // the whole workgroup: one chord
-    if (active) {
-      A.I[at] = A.back ? A.back[at] : 0.0;
-      A.tau[at] = 0.0;
-    }
-    if (tile == 0 && lane == 0) {
-      L.column[i] = 0.0;
-      L.chord[i] = 0.0;
-      L.steps[i] = 0;
-    }
+    store_missed(A, L, i, at, active, tile, lane);
     return;
   }
   for (int k = lane; k < X.nT; k += FL) s_lat[k] = X.LT[k];
@@ -93,11 +78,7 @@ __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, Fl
   const int k0 = A.toward > 0 ? 0 : n - 1, dk = A.toward > 0 ? 1 : -1;
   const double su = (double)A.toward / sqrt((l.d0 * l.d0 + l.d1 * l.d1) + l.d2 * l.d2);  // len of line_of, the same bits
   const bool cont = X.continuum != 0, has_lk = X.has_lk != 0;
-  // the frequency's constants; an idle lane of the last tile takes the last frequency's and stores nothing
-  const int fc = active ? f : X.n_freq - 1;
-  const double om = X.omega[fc], eph = X.e_ph[fc], com = X.c_omega[fc];
-  // the wavefront's span of frequencies: idle lanes widen nothing
-  const double wmin = wave_extreme<true>(active ? om : HUGE_VAL), wmax = wave_extreme<false>(active ? om : -HUGE_VAL);
+  const LaneFreq w = lane_freq(X, f, active);
   double I = (active && A.back) ? A.back[at] : 0.0;
   double tau = 0.0, column = 0.0;
 
@@ -115,14 +96,7 @@ __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, Fl
       double beta = 0.0;
       if (HAS_V) beta = ((((V[0] * l.d0 + V[1] * l.d1) + V[2] * l.d2)) * su) / sr::kC;
       double *S = s_stage + (size_t)(buf * kLinesChunk + lane) * stride;
-      int flags = dark ? 2 : 0;
-      S[0] = ne * h;
-      if (cont) {
-        const NodeTerms c = node_terms(ne, Te, Z);
-        flags |= c.dark ? 1 : 0;
-        S[2] = c.Te, S[3] = c.n, S[4] = c.wp, S[5] = c.L, S[6] = c.num, S[7] = c.zc, S[8] = c.it;
-      }
-      S[1] = (double)flags;
+      stage_head(S, cont, dark, ne, Te, Z, h);
       if (!dark) {
         const int o = t.o * NL, st = X.nD * NL;
 #pragma unroll 1
@@ -150,9 +124,9 @@ __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, Fl
           for (int q = 0; q < NL; ++q) {
             const double *P = S + kHead + kLineWords * q;
             const double wc = P[0], iw = P[1];
-            if (line_outside(wc, iw, wmin, wmax)) continue;  // the same for every lane of the wavefront
+            if (line_outside(wc, iw, w.wmin, w.wmax)) continue;  // the same for every lane of the wavefront
             double x2;
-            if (line_term(om, wc, iw, x2)) {
+            if (line_term(w.om, wc, iw, x2)) {
               const double phi = exp(-x2);
               j = j + P[2] * phi;
               aL = aL + P[3] * phi;
@@ -165,17 +139,12 @@ __global__ void __launch_bounds__(FL) k_sightline_lines(EmArgs A, LineArgs L, Fl
           NodeTerms t;
           t.dark = (flags & 1) != 0;
           t.Te = S[2], t.n = S[3], t.wp = S[4], t.L = S[5], t.num = S[6], t.zc = S[7], t.it = S[8];
-          node_band(t, om, eph, com, ac, Sc);
+          node_band(t, w.om, w.eph, w.com, ac, Sc);
         }
         if (counted) {
           line_update(ac, Sc, j, aL, h, I, tau);
-        } else if (cont) {
-          const double dtau = ac * h;
-          I = I * exp(-dtau) + Sc * (-expm1(-dtau));
-          tau = tau + dtau;
-        } else {  // that update with ac = Sc = 0: exp(-0) = 1 and expm1(-0) = -0 exactly, I*1 + 0*0 and tau + 0
-          I = I + 0.0;
-          tau = tau + 0.0;
+        } else {
+          continuum_update(cont, ac, Sc, h, I, tau);
         }
         column = column + S[0];
       }
@@ -202,73 +171,12 @@ extern "C" int sr_field_sightline_lines(const sr_field *ne, const sr_field *Te, 
                                         const double *c_omega, const double *backlight, double *I, double *tau, double *column,
                                         double *chord, int32_t *steps, double *kernel_ms) {
   const char *who = "sr_field_sightline_lines";
-  SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
-  SR_CHECK(omega != nullptr && e_ph != nullptr && c_omega != nullptr, "%s: NULL omega, e_ph or c_omega", who);
-  SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  SR_CHECK(n_freq >= 0, "%s: n_freq must not be negative, got %d", who, n_freq);
-  if (n_freq != 0) SR_RC(check_bands(who, "frequency", n_freq, SR_MAX_FREQS, omega, e_ph, c_omega));
-  SR_RC(check_march(who, p->toward, p->step, p->max_steps));
-  SR_RC(check_line_table(who, lines));
-  const int fl = lane_width(n_freq);
-  const int64_t n_tiles = (n_freq + fl - 1) / fl;
-  SR_CHECK(n_tiles == 0 || n <= (int64_t)2147483647 / n_tiles, "%s: n x frequency tiles exceeds 2^31 - 1 workgroups", who);
-  SR_RC(check_lines(who, n, origin, dir, ne, Te, Z));
-  SR_RC(sr::check_fields(who, ne, "ne", {{"Ti", Ti, 1}, {"V", V, 3}}));
-  if (kernel_ms) *kernel_ms = 0.0;
-  if (n == 0 || n_freq == 0) return SR_OK;
-  SR_RC(sr::ensure_init());
-  sr::Context &c = sr::ctx();
-  hipStream_t st = c.stream;
-
-  const std::vector<double> pack = pack_line_table(lines);
-  const size_t nf = (size_t)n_freq, map_bytes = sizeof(double) * nf * (size_t)n, freq_bytes = sizeof(double) * nf;
-
-  // one scratch block: the chords' pieces (take_lines) | omega | e_ph | c_omega | table
-  EmArgs A{};
-  LineArgs L{};
-  FlowArgs W{};
+  Family F{who, ne, Te, Ti, Z, V, p, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I, tau, column, chord, steps, kernel_ms};
+  SR_RC(check_family(F, [&] { return check_line_table(who, lines); }));
+  const sr_voigt_table t{*lines, nullptr};
   LinesArgs X{};
-  double *tab = nullptr;
-  sr::Carve carve;
-  take_lines(carve, A, L, ne, n, p->step, p->max_steps, nf, backlight != nullptr);
-  carve.take(&X.omega, nf);
-  carve.take(&X.e_ph, nf);
-  carve.take(&X.c_omega, nf);
-  carve.take(&tab, pack.size());
-  if (!carve.alloc()) return SR_ERR_HIP;
-  fill_fields(A, ne, Te, Z, p->toward, p->Te, p->Z, 0, nullptr, nullptr, nullptr);  // the frequencies' constants are X's
-  W.Ti = Ti ? Ti->data : nullptr;
-  W.V = V ? V->data : nullptr;
-  const size_t nl = (size_t)lines->n_line, entries = (size_t)lines->nT * lines->nD * nl;
-  X.n_freq = n_freq;
-  X.n_tiles = (int)n_tiles;
-  X.LT = tab;
-  X.LD = X.LT + lines->nT;
-  X.w0 = X.LD + lines->nD;
-  X.ci = X.w0 + nl;
-  X.LJ = X.ci + nl;
-  X.LK = X.LJ + entries;
-  X.nT = lines->nT;
-  X.nD = lines->nD;
-  X.n_line = lines->n_line;
-  X.has_lk = lines->LK != nullptr;
-  X.continuum = p->continuum != 0;
-
-  SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.omega), omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.e_ph), e_ph, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.c_omega), c_omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(tab, pack.data(), sizeof(double) * pack.size(), hipMemcpyHostToDevice, st));
-  SR_HIP(hipEventRecord(c.ev[0], st));
-  const unsigned grid = (unsigned)(n * n_tiles);
-  const size_t lds = sizeof(double) * 2 * kLinesChunk * (kHead + kLineWords * nl);  // at most 52 992 bytes
-  sr::with_flags(
-      [&](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
-        using T = std::conditional_t<decltype(f64)::value, double, float>;
-        constexpr int kFl = decltype(narrow)::value ? 64 : 256;
-        hipLaunchKernelGGL((k_sightline_lines<T, decltype(te)::value, decltype(z)::value, decltype(ti)::value, decltype(v)::value, kFl>),
-                           dim3(grid), dim3(kFl), lds, st, A, L, W, X);
-      },
-      (bool)ne->is_f64, Te != nullptr, Z != nullptr, Ti != nullptr, V != nullptr, fl == 64);
-  return finish_lines(A, L, map_bytes, I, tau, column, chord, steps, kernel_ms);
+  const size_t lds = sizeof(double) * 2 * kLinesChunk * (kHead + kLineWords * (size_t)lines->n_line);  // at most 52 992 bytes
+  return run_family<kLinesArgs>(F, &t, nullptr, X, lds, [](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
+    return &k_sightline_lines<std::conditional_t<f64(), double, float>, te(), z(), ti(), v(), narrow() ? 64 : 256>;
+  });
 }

@@ -268,14 +268,16 @@ inline int upload_lines(const EmArgs &A, const LineArgs &L, const double *origin
   return SR_OK;
 }
 
-// After the launch: I, tau and the per-line outputs that were asked for come back, the kernel's time is read.
+// After the launch: I, tau and the per-line outputs that were asked for come back, the kernel's time is read.  `more`: further
+// maps of map_bytes (device, host), which come back before I (the polarised entries' Q, U and Vs).
 inline int finish_lines(const EmArgs &A, const LineArgs &L, size_t map_bytes, double *I, double *tau, double *column, double *chord,
-                        int32_t *steps, double *kernel_ms) {
+                        int32_t *steps, double *kernel_ms, std::initializer_list<std::pair<const double *, double *>> more = {}) {
   sr::Context &c = sr::ctx();
   hipStream_t st = c.stream;
   const size_t N = (size_t)L.n;
   SR_HIP(hipGetLastError());
   SR_HIP(hipEventRecord(c.ev[1], st));
+  for (const auto &m : more) SR_HIP(hipMemcpyAsync(m.second, m.first, map_bytes, hipMemcpyDeviceToHost, st));
   SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
   SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
   if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));

@@ -1,10 +1,8 @@
 // Voigt lines along sightlines: sr_field_sightline_lines' Doppler-shifted lines with a Lorentzian (Stark, natural) half-width from
 // the table, so that every line is a Voigt profile (sr_field_sightline_voigt; include/synthray.h states the rule).  No reference
-// counterpart.  k_sightline_lines' decomposition, word for word: a workgroup owns one chord and one tile of FL frequencies, a lane
-// one frequency with its (I, tau) in registers; the chord's samples go through LDS in chunks of kVoigtChunk, in march order, in two
-// buffers, and the corner reads of chunk c+1 are issued before the march of chunk c and blended after it.
+// counterpart.  The decomposition is the family's (line_family.inc), in chunks of kVoigtChunk; what is this kernel's own:
 //
-// Staging: as there, and per line one more bilinear read and exp for the damping parameter a = gam*iw (voigt_node.inc's
+// Staging: per line one more bilinear read and exp than k_sightline_lines, for the damping parameter a = gam*iw (voigt_node.inc's
 // voigt_const).  A staged line is five float64 padded to six -- three 16-byte reads, every marching lane at the same address, a
 // broadcast -- and a sample 10 + 6*n_line float64: at 32 lines 1616 bytes, so the two buffers hold 16 samples each (51 712 bytes;
 // with the 8 KiB of the lattices 59 904, under the 64 KiB a workgroup may take without asking).
@@ -18,7 +16,9 @@
 // V field?, FL); continuum and LK are uniform branches.  Compiled with -ffp-contract=off, as its siblings: column, chord and steps
 // are the bits k_sightlines gives, and where every term is dropped I and tau are the bits of k_sightline_spectra.  With LG NULL
 // the entry is sr_field_sightline_lines.
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "emission_march.inc"
@@ -32,8 +32,12 @@ namespace {
 
 #include "voigt_node.inc"
 
+#include "zeeman_node.inc"
+
+#include "line_family.inc"
+
 constexpr int kVoigtChunk = 16;  // samples staged at a time (sr_voigt_chunk)
-constexpr int kHead = 10;        // float64 of a staged sample before its lines, as k_sightline_lines'
+constexpr int kHead = 10;        // float64 of a staged sample before its lines: the family's head
 static_assert(sizeof(double) * 2 * kVoigtChunk * (kHead + kVoigtWords * SR_MAX_LINES) + sizeof(double) * 2 * kMaxLattice <= kLdsBudget,
               "two buffers at 32 lines and the lattices must fit the LDS budget");
 
@@ -44,17 +48,6 @@ struct VoigtArgs {
   int nT, nD, n_line, has_lk, continuum;
   double cut;
 };
-
-// the least (LEAST) or the greatest value of a wavefront, in every lane
-template <bool LEAST>
-__device__ __forceinline__ double wave_extreme(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const double o = __shfl_xor(v, s, 64);
-    v = LEAST ? (o < v ? o : v) : (o > v ? o : v);
-  }
-  return v;
-}
 
 template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V, int FL>
 __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, FlowArgs W, VoigtArgs X) {
@@ -68,15 +61,7 @@ __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, Fl
   const int64_t at = i * X.n_freq + f;
   const Line l = line_of(L, i);
   if (!l.hit) {  // the whole workgroup: one chord
-    if (active) {
-      A.I[at] = A.back ? A.back[at] : 0.0;
-      A.tau[at] = 0.0;
-    }
-    if (tile == 0 && lane == 0) {
-      L.column[i] = 0.0;
-      L.chord[i] = 0.0;
-      L.steps[i] = 0;
-    }
+    store_missed(A, L, i, at, active, tile, lane);
     return;
   }
   for (int k = lane; k < X.nT; k += FL) s_lat[k] = X.LT[k];
@@ -90,11 +75,7 @@ __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, Fl
   const int k0 = A.toward > 0 ? 0 : n - 1, dk = A.toward > 0 ? 1 : -1;
   const double su = (double)A.toward / sqrt((l.d0 * l.d0 + l.d1 * l.d1) + l.d2 * l.d2);  // len of line_of, the same bits
   const bool cont = X.continuum != 0, has_lk = X.has_lk != 0;
-  // the frequency's constants; an idle lane of the last tile takes the last frequency's and stores nothing
-  const int fc = active ? f : X.n_freq - 1;
-  const double om = X.omega[fc], eph = X.e_ph[fc], com = X.c_omega[fc];
-  // the wavefront's span of frequencies: idle lanes widen nothing
-  const double wmin = wave_extreme<true>(active ? om : HUGE_VAL), wmax = wave_extreme<false>(active ? om : -HUGE_VAL);
+  const LaneFreq w = lane_freq(X, f, active);
   double I = (active && A.back) ? A.back[at] : 0.0;
   double tau = 0.0, column = 0.0;
 
@@ -112,14 +93,7 @@ __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, Fl
       double beta = 0.0;
       if (HAS_V) beta = ((((V[0] * l.d0 + V[1] * l.d1) + V[2] * l.d2)) * su) / sr::kC;
       double *S = s_stage + (size_t)(buf * kVoigtChunk + lane) * stride;
-      int flags = dark ? 2 : 0;
-      S[0] = ne * h;
-      if (cont) {
-        const NodeTerms c = node_terms(ne, Te, Z);
-        flags |= c.dark ? 1 : 0;
-        S[2] = c.Te, S[3] = c.n, S[4] = c.wp, S[5] = c.L, S[6] = c.num, S[7] = c.zc, S[8] = c.it;
-      }
-      S[1] = (double)flags;
+      stage_head(S, cont, dark, ne, Te, Z, h);
       if (!dark) {
         const int o = t.o * NL, st = X.nD * NL;
 #pragma unroll 1
@@ -147,9 +121,9 @@ __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, Fl
           for (int q = 0; q < NL; ++q) {
             const double *P = S + kHead + kVoigtWords * q;
             const double wc = P[0], iw = P[1];
-            if (voigt_outside(wc, iw, wmin, wmax, cut)) continue;  // the same for every lane of the wavefront
+            if (voigt_outside(wc, iw, w.wmin, w.wmax, cut)) continue;  // the same for every lane of the wavefront
             double x;
-            if (voigt_term(om, wc, iw, cut, x)) {
+            if (voigt_term(w.om, wc, iw, cut, x)) {
               const double phi = voigt(P[4], x);
               j = j + P[2] * phi;
               aL = aL + P[3] * phi;
@@ -162,17 +136,12 @@ __global__ void __launch_bounds__(FL) k_sightline_voigt(EmArgs A, LineArgs L, Fl
           NodeTerms t;
           t.dark = (flags & 1) != 0;
           t.Te = S[2], t.n = S[3], t.wp = S[4], t.L = S[5], t.num = S[6], t.zc = S[7], t.it = S[8];
-          node_band(t, om, eph, com, ac, Sc);
+          node_band(t, w.om, w.eph, w.com, ac, Sc);
         }
         if (counted) {
           line_update(ac, Sc, j, aL, h, I, tau);
-        } else if (cont) {
-          const double dtau = ac * h;
-          I = I * exp(-dtau) + Sc * (-expm1(-dtau));
-          tau = tau + dtau;
-        } else {  // that update with ac = Sc = 0: exp(-0) = 1 and expm1(-0) = -0 exactly, I*1 + 0*0 and tau + 0
-          I = I + 0.0;
-          tau = tau + 0.0;
+        } else {
+          continuum_update(cont, ac, Sc, h, I, tau);
         }
         column = column + S[0];
       }
@@ -199,81 +168,19 @@ extern "C" int sr_field_sightline_voigt(const sr_field *ne, const sr_field *Te, 
                                         const double *c_omega, const double *backlight, double *I, double *tau, double *column,
                                         double *chord, int32_t *steps, double *kernel_ms) {
   const char *who = "sr_field_sightline_voigt";
-  SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
-  SR_CHECK(omega != nullptr && e_ph != nullptr && c_omega != nullptr, "%s: NULL omega, e_ph or c_omega", who);
-  SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  SR_CHECK(n_freq >= 0, "%s: n_freq must not be negative, got %d", who, n_freq);
-  if (n_freq != 0) SR_RC(check_bands(who, "frequency", n_freq, SR_MAX_FREQS, omega, e_ph, c_omega));
-  const sr_lines_params *m = &p->march;
-  SR_RC(check_march(who, m->toward, m->step, m->max_steps));
-  SR_RC(check_voigt_table(who, lines));
-  SR_CHECK(lines->LG == nullptr || p->wing > 0.0, "%s: wing must be positive (+inf is allowed), got %g", who, p->wing);
-  const int fl = lane_width(n_freq);
-  const int64_t n_tiles = (n_freq + fl - 1) / fl;
-  SR_CHECK(n_tiles == 0 || n <= (int64_t)2147483647 / n_tiles, "%s: n x frequency tiles exceeds 2^31 - 1 workgroups", who);
-  SR_RC(check_lines(who, n, origin, dir, ne, Te, Z));
-  SR_RC(sr::check_fields(who, ne, "ne", {{"Ti", Ti, 1}, {"V", V, 3}}));
-  if (lines->LG == nullptr)  // Gaussian lines: that entry's rule and its kernel; wing is not read
-    return sr_field_sightline_lines(ne, Te, Ti, Z, V, &lines->lines, m, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I, tau,
+  Family F{who, ne, Te, Ti, Z, V, p ? &p->march : nullptr, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I, tau, column, chord,
+           steps, kernel_ms};
+  SR_RC(check_family(F, [&] {  // wing is read only with LG
+    SR_RC(check_voigt_table(who, lines));
+    return lines->LG ? check_wing(who, p->wing) : SR_OK;
+  }));
+  if (lines->LG == nullptr)  // Gaussian lines: that entry's rule and its kernel
+    return sr_field_sightline_lines(ne, Te, Ti, Z, V, &lines->lines, F.m, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I, tau,
                                     column, chord, steps, kernel_ms);
-  if (kernel_ms) *kernel_ms = 0.0;
-  if (n == 0 || n_freq == 0) return SR_OK;
-  SR_RC(sr::ensure_init());
-  sr::Context &c = sr::ctx();
-  hipStream_t st = c.stream;
-
-  const sr_line_table *lt = &lines->lines;
-  const std::vector<double> pack = pack_voigt_table(lines);
-  const size_t nf = (size_t)n_freq, map_bytes = sizeof(double) * nf * (size_t)n, freq_bytes = sizeof(double) * nf;
-
-  // one scratch block: the chords' pieces (take_lines) | omega | e_ph | c_omega | table
-  EmArgs A{};
-  LineArgs L{};
-  FlowArgs W{};
   VoigtArgs X{};
-  double *tab = nullptr;
-  sr::Carve carve;
-  take_lines(carve, A, L, ne, n, m->step, m->max_steps, nf, backlight != nullptr);
-  carve.take(&X.omega, nf);
-  carve.take(&X.e_ph, nf);
-  carve.take(&X.c_omega, nf);
-  carve.take(&tab, pack.size());
-  if (!carve.alloc()) return SR_ERR_HIP;
-  fill_fields(A, ne, Te, Z, m->toward, m->Te, m->Z, 0, nullptr, nullptr, nullptr);  // the frequencies' constants are X's
-  W.Ti = Ti ? Ti->data : nullptr;
-  W.V = V ? V->data : nullptr;
-  const size_t nl = (size_t)lt->n_line, entries = (size_t)lt->nT * lt->nD * nl;
-  X.n_freq = n_freq;
-  X.n_tiles = (int)n_tiles;
-  X.LT = tab;
-  X.LD = X.LT + lt->nT;
-  X.w0 = X.LD + lt->nD;
-  X.ci = X.w0 + nl;
-  X.LJ = X.ci + nl;
-  X.LK = X.LJ + entries;  // not read where has_lk is false
-  X.LG = lt->LK ? X.LK + entries : X.LK;
-  X.nT = lt->nT;
-  X.nD = lt->nD;
-  X.n_line = lt->n_line;
-  X.has_lk = lt->LK != nullptr;
-  X.continuum = m->continuum != 0;
   X.cut = p->wing * p->wing;
-
-  SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.omega), omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.e_ph), e_ph, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.c_omega), c_omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(tab, pack.data(), sizeof(double) * pack.size(), hipMemcpyHostToDevice, st));
-  SR_HIP(hipEventRecord(c.ev[0], st));
-  const unsigned grid = (unsigned)(n * n_tiles);
-  const size_t lds = sizeof(double) * 2 * kVoigtChunk * (kHead + kVoigtWords * nl);  // at most 51 712 bytes
-  sr::with_flags(
-      [&](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
-        using T = std::conditional_t<decltype(f64)::value, double, float>;
-        constexpr int kFl = decltype(narrow)::value ? 64 : 256;
-        hipLaunchKernelGGL((k_sightline_voigt<T, decltype(te)::value, decltype(z)::value, decltype(ti)::value, decltype(v)::value, kFl>),
-                           dim3(grid), dim3(kFl), lds, st, A, L, W, X);
-      },
-      (bool)ne->is_f64, Te != nullptr, Z != nullptr, Ti != nullptr, V != nullptr, fl == 64);
-  return finish_lines(A, L, map_bytes, I, tau, column, chord, steps, kernel_ms);
+  const size_t lds = sizeof(double) * 2 * kVoigtChunk * (kHead + kVoigtWords * (size_t)lines->lines.n_line);  // at most 51 712 bytes
+  return run_family<kVoigtArgs>(F, lines, nullptr, X, lds, [](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
+    return &k_sightline_voigt<std::conditional_t<f64(), double, float>, te(), z(), ti(), v(), narrow() ? 64 : 256>;
+  });
 }

@@ -1,12 +1,10 @@
 // Zeeman-split lines along sightlines: sr_field_sightline_voigt's lines, each split by the magnetic field B of the sample into its
 // pi and sigma components, and four Stokes parameters marched per frequency instead of one intensity (sr_field_sightline_zeeman;
-// include/synthray.h states the rule).  No reference counterpart.  k_sightline_voigt's decomposition: a workgroup owns one chord
-// and one tile of FL frequencies, a lane one frequency with its (I, Q, U, Vs, tau) in registers; the chord's samples go through LDS
-// in chunks of kZeemanChunk, in march order, in two buffers, and the corner reads of chunk c+1 are issued before the march of chunk
-// c and blended after it.
+// include/synthray.h states the rule).  No reference counterpart.  The decomposition is the family's (line_family.inc), in chunks
+// of kZeemanChunk, a lane keeping (I, Q, U, Vs, tau) in registers; what is this kernel's own:
 //
-// Staging: lanes 0 .. chunk-1 stage what k_sightline_voigt's do, word for word.  Lanes chunk .. 2*chunk-1 carry B: lane chunk+s
-// finds sample s's cell again (the same search, the same bits), reads the 24 corner values of B into the slots a staging lane keeps
+// Staging: lanes 0 .. chunk-1 stage what k_sightline_voigt's do (a = 0 where the table has no LG).  Lanes chunk .. 2*chunk-1
+// carry B: lane chunk+s finds sample s's cell again (the same search, the same bits), reads the 24 corner values of B into the slots a staging lane keeps
 // for V, and after the march blends them, turns B into the chord's frame and writes the sample's six numbers (wL, sP, cS, cQ, cU,
 // cV: zeeman_node.inc) into the head of the same staged sample.  No lane's live state is larger than a staging lane's of
 // k_sightline_voigt with V (an instantiation without V keeps V's slots for B).  A sample is 16 + 6*n_line float64: at 32 lines
@@ -35,6 +33,8 @@ namespace {
 #include "voigt_node.inc"
 
 #include "zeeman_node.inc"
+
+#include "line_family.inc"
 
 constexpr int kZeemanChunk = 16;  // samples staged at a time (sr_zeeman_chunk)
 constexpr int kHead = 10 + kZeemanWords;  // float64 of a staged sample before its lines: k_sightline_voigt's ten and the six of B
@@ -93,11 +93,7 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
   const double su = (double)A.toward / sqrt((l.d0 * l.d0 + l.d1 * l.d1) + l.d2 * l.d2);  // len of line_of, the same bits
   const bool cont = X.continuum != 0, has_lk = X.has_lk != 0, has_lg = X.has_lg != 0;
   const double *frame = X.frame + 9 * i;
-  // the frequency's constants; an idle lane of the last tile takes the last frequency's and stores nothing
-  const int fc = active ? f : X.n_freq - 1;
-  const double om = X.omega[fc], eph = X.e_ph[fc], com = X.c_omega[fc];
-  // the wavefront's span of frequencies: idle lanes widen nothing
-  const double wmin = wave_extreme<true>(active ? om : HUGE_VAL), wmax = wave_extreme<false>(active ? om : -HUGE_VAL);
+  const LaneFreq w = lane_freq(X, f, active);
   double I = (active && A.back) ? A.back[at] : 0.0;
   double Q = 0.0, U = 0.0, Vs = 0.0, tau = 0.0, column = 0.0;
 
@@ -119,14 +115,7 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
       double beta = 0.0;
       if (HAS_V) beta = ((((V[0] * l.d0 + V[1] * l.d1) + V[2] * l.d2)) * su) / sr::kC;
       double *S = s_stage + (size_t)(buf * kZeemanChunk + mine) * stride;
-      int flags = dark ? 2 : 0;
-      S[0] = ne * h;
-      if (cont) {
-        const NodeTerms c = node_terms(ne, Te, Z);
-        flags |= c.dark ? 1 : 0;
-        S[2] = c.Te, S[3] = c.n, S[4] = c.wp, S[5] = c.L, S[6] = c.num, S[7] = c.zc, S[8] = c.it;
-      }
-      S[1] = (double)flags;
+      stage_head(S, cont, dark, ne, Te, Z, h);
       if (!dark) {
         const int o = t.o * NL, st = X.nD * NL;
 #pragma unroll 1
@@ -176,9 +165,9 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
 #pragma unroll 1
             for (int k = X.off[q]; k < k1; ++k) {
               const double cq = X.comp[3 * k], sh = X.comp[3 * k + 1] * z.wL, sk = X.comp[3 * k + 2];
-              if (zeeman_outside(wc, sh, iw, wmin, wmax, cut)) continue;  // the same for every lane of the wavefront
+              if (zeeman_outside(wc, sh, iw, w.wmin, w.wmax, cut)) continue;  // the same for every lane of the wavefront
               double x;
-              if (zeeman_term(om, wc, sh, iw, cut, x)) {
+              if (zeeman_term(w.om, wc, sh, iw, cut, x)) {
                 const double v = sk * voigt(a, x);
                 if (cq == 0.0)
                   P0 = P0 + v;
@@ -200,24 +189,12 @@ __global__ void __launch_bounds__(FL) k_sightline_zeeman(EmArgs A, LineArgs L, F
           NodeTerms t;
           t.dark = (flags & 1) != 0;
           t.Te = S[2], t.n = S[3], t.wp = S[4], t.L = S[5], t.num = S[6], t.zc = S[7], t.it = S[8];
-          node_band(t, om, eph, com, ac, Sc);
+          node_band(t, w.om, w.eph, w.com, ac, Sc);
         }
         if (counted) {
           zeeman_update(ac, Sc, jI, jQ, jU, jV, aL, h, I, Q, U, Vs, tau);
-        } else if (cont) {
-          const double dtau = ac * h;
-          const double E = exp(-dtau);
-          I = I * E + Sc * (-expm1(-dtau));
-          Q = Q * E;
-          U = U * E;
-          Vs = Vs * E;
-          tau = tau + dtau;
-        } else {  // that update with ac = Sc = 0, as the siblings write it
-          I = I + 0.0;
-          Q = Q + 0.0;
-          U = U + 0.0;
-          Vs = Vs + 0.0;
-          tau = tau + 0.0;
+        } else {
+          continuum_update(cont, ac, Sc, h, I, Q, U, Vs, tau);
         }
         column = column + S[0];
       }
@@ -248,125 +225,19 @@ extern "C" int sr_field_sightline_zeeman(const sr_field *ne, const sr_field *Te,
                                          double *U, double *Vs, double *tau, double *column, double *chord, int32_t *steps,
                                          double *kernel_ms) {
   const char *who = "sr_field_sightline_zeeman";
-  if (B == nullptr) {  // no field: that entry's rule, kernel and bits; the component table and ref are not read
-    SR_CHECK(lines != nullptr, "%s: NULL line table", who);
-    SR_CHECK(n >= 0 && n_freq >= 0, "%s: n and n_freq must not be negative, got %lld and %d", who, (long long)n, n_freq);
-    if (int rc = sr_field_sightline_voigt(ne, Te, Ti, Z, V, &lines->voigt, p, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I,
-                                          tau, column, chord, steps, kernel_ms))
-      return rc;
-    const size_t bytes = sizeof(double) * (size_t)n * (size_t)n_freq;
-    for (double *out : {Q, U, Vs})
-      if (out && bytes) memset(out, 0, bytes);
-    return SR_OK;
-  }
-  SR_CHECK(p != nullptr && origin != nullptr && dir != nullptr && I != nullptr && tau != nullptr, "%s: NULL argument", who);
-  SR_CHECK(ref != nullptr && Q != nullptr && U != nullptr && Vs != nullptr, "%s: NULL ref, Q, U or Vs (B is given)", who);
-  SR_CHECK(omega != nullptr && e_ph != nullptr && c_omega != nullptr, "%s: NULL omega, e_ph or c_omega", who);
-  SR_CHECK(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  SR_CHECK(n_freq >= 0, "%s: n_freq must not be negative, got %d", who, n_freq);
-  if (n_freq != 0) SR_RC(check_bands(who, "frequency", n_freq, SR_MAX_FREQS, omega, e_ph, c_omega));
-  const sr_lines_params *m = &p->march;
-  SR_RC(check_march(who, m->toward, m->step, m->max_steps));
-  SR_RC(check_zeeman_table(who, lines));
-  SR_CHECK(p->wing > 0.0, "%s: wing must be positive (+inf is allowed), got %g", who, p->wing);
-  const int fl = lane_width(n_freq);
-  const int64_t n_tiles = (n_freq + fl - 1) / fl;
-  SR_CHECK(n_tiles == 0 || n <= (int64_t)2147483647 / n_tiles, "%s: n x frequency tiles exceeds 2^31 - 1 workgroups", who);
-  std::vector<double> frames;
-  SR_RC(chord_frames(who, n, m->toward, dir, ref, frames));
-  SR_RC(check_lines(who, n, origin, dir, ne, Te, Z));
-  SR_RC(sr::check_fields(who, ne, "ne", {{"Ti", Ti, 1}, {"V", V, 3}, {"B", B, 3}}));
-  if (kernel_ms) *kernel_ms = 0.0;
-  if (n == 0 || n_freq == 0) return SR_OK;
-  SR_RC(sr::ensure_init());
-  sr::Context &c = sr::ctx();
-  hipStream_t st = c.stream;
-
-  const sr_line_table *lt = &lines->voigt.lines;
-  const size_t nl = (size_t)lt->n_line, entries = (size_t)lt->nT * lt->nD * nl;
-  std::vector<double> pack = pack_line_table(lt);
-  if (lines->voigt.LG) {  // pack_voigt_table's block
-    const size_t cells = (size_t)lt->nT * lt->nD, start = pack.size();
-    pack.resize(start + entries);
-    for (size_t q = 0; q < nl; ++q)
-      for (size_t k = 0; k < cells; ++k) pack[start + k * nl + q] = lines->voigt.LG[q * cells + k];
-  }
-  std::vector<int> off(nl + 1, 0);
-  for (size_t q = 0; q < nl; ++q) off[q + 1] = off[q] + lines->n_comp[q];
-  const size_t n_comp = (size_t)off[nl];
-  const size_t nf = (size_t)n_freq, map_bytes = sizeof(double) * nf * (size_t)n, freq_bytes = sizeof(double) * nf;
-
-  // one scratch block: the chords' pieces (take_lines) | Q | U | Vs | frames | omega | e_ph | c_omega | table | components | offsets
-  EmArgs A{};
-  LineArgs L{};
-  FlowArgs W{};
+  Family F{who, ne, Te, Ti, Z, V, p ? &p->march : nullptr, n, origin, dir, n_freq, omega, e_ph, c_omega, backlight, I, tau, column, chord,
+           steps, kernel_ms};
+  Polarised P{B, ref, Q, U, Vs, lines};
+  if (B == nullptr) return without_field(F, P, p);
+  SR_RC(check_family(F, [&] {  // LG NULL does not delegate: wing is always read
+    SR_RC(check_zeeman_table(who, lines));
+    return check_wing(who, p->wing);
+  }, &P));
   ZeemanArgs X{};
-  double *tab = nullptr;
-  sr::Carve carve;
-  take_lines(carve, A, L, ne, n, m->step, m->max_steps, nf, backlight != nullptr);
-  carve.take(&X.Q, nf * (size_t)n);
-  carve.take(&X.U, nf * (size_t)n);
-  carve.take(&X.Vs, nf * (size_t)n);
-  carve.take(&X.frame, frames.size());
-  carve.take(&X.omega, nf);
-  carve.take(&X.e_ph, nf);
-  carve.take(&X.c_omega, nf);
-  carve.take(&tab, pack.size());
-  carve.take(&X.comp, 3 * n_comp);
-  carve.take(&X.off, off.size());
-  if (!carve.alloc()) return SR_ERR_HIP;
-  fill_fields(A, ne, Te, Z, m->toward, m->Te, m->Z, 0, nullptr, nullptr, nullptr);  // the frequencies' constants are X's
-  W.Ti = Ti ? Ti->data : nullptr;
-  W.V = V ? V->data : nullptr;
-  X.B = B->data;
-  X.n_freq = n_freq;
-  X.n_tiles = (int)n_tiles;
-  X.LT = tab;
-  X.LD = X.LT + lt->nT;
-  X.w0 = X.LD + lt->nD;
-  X.ci = X.w0 + nl;
-  X.LJ = X.ci + nl;
-  X.LK = X.LJ + entries;  // not read where has_lk is false
-  X.LG = lt->LK ? X.LK + entries : X.LK;  // not read where has_lg is false
-  X.nT = lt->nT;
-  X.nD = lt->nD;
-  X.n_line = lt->n_line;
-  X.has_lk = lt->LK != nullptr;
-  X.has_lg = lines->voigt.LG != nullptr;
-  X.continuum = m->continuum != 0;
   X.cut = p->wing * p->wing;
   X.kL = kLineE / (2.0 * kZeemanMe);
-
-  SR_RC(upload_lines(A, L, origin, dir, backlight, map_bytes, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.frame), frames.data(), sizeof(double) * frames.size(), hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.omega), omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.e_ph), e_ph, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.c_omega), c_omega, freq_bytes, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(tab, pack.data(), sizeof(double) * pack.size(), hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<double *>(X.comp), lines->comp, sizeof(double) * 3 * n_comp, hipMemcpyHostToDevice, st));
-  SR_HIP(hipMemcpyAsync(const_cast<int *>(X.off), off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, st));
-  SR_HIP(hipEventRecord(c.ev[0], st));
-  const unsigned grid = (unsigned)(n * n_tiles);
-  const size_t lds = sizeof(double) * 2 * kZeemanChunk * (kHead + kVoigtWords * nl);  // at most 53 248 bytes
-  sr::with_flags(
-      [&](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
-        using T = std::conditional_t<decltype(f64)::value, double, float>;
-        constexpr int kFl = decltype(narrow)::value ? 64 : 256;
-        hipLaunchKernelGGL((k_sightline_zeeman<T, decltype(te)::value, decltype(z)::value, decltype(ti)::value, decltype(v)::value, kFl>),
-                           dim3(grid), dim3(kFl), lds, st, A, L, W, X);
-      },
-      (bool)ne->is_f64, Te != nullptr, Z != nullptr, Ti != nullptr, V != nullptr, fl == 64);
-  // finish_lines, with Q, U and Vs beside I and tau
-  SR_HIP(hipGetLastError());
-  SR_HIP(hipEventRecord(c.ev[1], st));
-  SR_HIP(hipMemcpyAsync(Q, X.Q, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(U, X.U, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(Vs, X.Vs, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(I, A.I, map_bytes, hipMemcpyDeviceToHost, st));
-  SR_HIP(hipMemcpyAsync(tau, A.tau, map_bytes, hipMemcpyDeviceToHost, st));
-  const size_t N = (size_t)n;
-  if (column) SR_HIP(hipMemcpyAsync(column, L.column, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (chord) SR_HIP(hipMemcpyAsync(chord, L.chord, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  if (steps) SR_HIP(hipMemcpyAsync(steps, L.steps, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  return sr::finish_timed(c, kernel_ms);
+  const size_t lds = sizeof(double) * 2 * kZeemanChunk * (kHead + kVoigtWords * (size_t)lines->voigt.lines.n_line);  // at most 53 248 bytes
+  return run_family<kPolarisedArgs>(F, &lines->voigt, &P, X, lds, [](auto f64, auto te, auto z, auto ti, auto v, auto narrow) {
+    return &k_sightline_zeeman<std::conditional_t<f64(), double, float>, te(), z(), ti(), v(), narrow() ? 64 : 256>;
+  });
 }

@@ -197,9 +197,10 @@ inline int check_voigt_table(const char *who, const sr_voigt_table *t) {
   return SR_OK;
 }
 
-// pack_line_table's block, then LG[nT][nD][n_line]
+// pack_line_table's block, then LG[nT][nD][n_line] where LG is given
 inline std::vector<double> pack_voigt_table(const sr_voigt_table *t) {
   std::vector<double> pack = pack_line_table(&t->lines);
+  if (!t->LG) return pack;
   const size_t cells = (size_t)t->lines.nT * t->lines.nD, nl = (size_t)t->lines.n_line, at = pack.size();
   pack.resize(at + cells * nl);
   double *q = pack.data() + at;

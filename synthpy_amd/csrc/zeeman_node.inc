@@ -85,17 +85,6 @@ __device__ __forceinline__ void zeeman_update(double ac, double Sc, double jI, d
 
 // ---- what the kernels that march Stokes parameters share (sightline_zeeman.hip, sightline_stokes.hip)
 
-// the least (LEAST) or the greatest value of a wavefront, in every lane
-template <bool LEAST>
-__device__ __forceinline__ double wave_extreme(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const double o = __shfl_xor(v, s, 64);
-    v = LEAST ? (o < v ? o : v) : (o > v ? o : v);
-  }
-  return v;
-}
-
 // sightline_march.inc's fetch_sample and blend_sample of a FlowSample, on a sample that always has V's slots (a lane that carries
 // B fills them with B's corners): the same operations, so the same bits
 template <typename T, bool HAS_TE, bool HAS_Z, bool HAS_TI, bool HAS_V>

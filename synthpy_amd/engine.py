@@ -681,21 +681,67 @@ def sightline_lines(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, con
     returned; where no line reaches a frequency its values have engine.sightline_spectra's bits (continuum) or are the backlight
     and 0.  ne.last_kernel_ms keeps the kernel's time.  Not modelled: Lorentzian, Stark and Voigt wings, Zeeman splitting, line
     blending through the cutoff at exp(-40), partial redistribution, refraction, the instrument function; one GPU."""
+    return _line_family(lib.sr_field_sightline_lines, line_table_params, "a LineTable", ne, Te, Ti, Z, V, origins, directions, lines,
+                        omegas, continuum, _NO_WING, toward, step, max_steps, backlight, want)
+
+
+_NO_WING = object()  # sr_field_sightline_lines' params have no wing
+
+
+def _line_family(entry, table_params, table_kind, ne, Te, Ti, Z, V, origins, directions, lines, omegas, continuum, wing, toward, step,
+                 max_steps, backlight, want, polarised=None):
+    """What sightline_lines, sightline_voigt, sightline_zeeman and sightline_stokes share under _sightlines: the handles of Ti and
+    V, the table (table_params(lines)), the march struct (wing _NO_WING: LinesParams; else VoigtParams, its march and wing), the
+    frequencies' constants and the call of the library's `entry`, whose argument order this function knows.  polarised: None, or
+    (B, reference, what the entry takes between the backlight and I) for the two entries that march four Stokes parameters: B's
+    handle, the reference, and the three maps beside I and tau, which `want` may then name."""
     h_Ti, h_V = _handle("Ti", Ti, none=True), _handle("V", V, none=True)
-    t, keep = line_table_params(lines)
+    fields, stokes_names, stokes = (), (), {}
+    if polarised is not None:
+        B, reference, after_backlight = polarised
+        h_B = _handle("B", B, none=True)
+        fields, stokes_names = (h_B,), ("Q", "U", "V")
+    t, keep = table_params(lines)
+    if polarised is not None:
+        unknown = set(want) - set(_SIGHT_WANT) - set(stokes_names)
+        if unknown:
+            raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT + stokes_names}")
+        want_all, want = want, tuple(k for k in want if k in _SIGHT_WANT)
 
     def params(omegas, n, uniform, _):
         om, e_ph, c_om = spectrum_constants(omegas)
-        p = _ffi.LinesParams()
-        p.toward, p.max_steps, p.continuum, p.reserved, p.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
-        p.Te, p.Z = uniform
+        p = _ffi.LinesParams() if wing is _NO_WING else _ffi.VoigtParams()
+        m = p if wing is _NO_WING else p.march
+        m.toward, m.max_steps, m.continuum, m.reserved, m.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
+        m.Te, m.Z = uniform
+        if wing is not _NO_WING:
+            p.wing = float(wing)
+        after_chords = after_back = after_I = ()
+        if polarised is not None:
+            ref = None
+            if h_B is not None:
+                if reference is None:
+                    raise ValueError("reference must be given with B: the direction Q is measured from, (3,) or (3, n)")
+                ref = f64(reference)
+                if ref.shape == (3,):
+                    ref = np.repeat(ref[:, None], n, axis=1)
+                if ref.shape != (3, n):
+                    raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
+                ref = np.ascontiguousarray(ref)
+            for k in stokes_names:
+                stokes[k] = np.empty((n, len(om)))
+            after_chords, after_back, after_I = (ptr(ref),), after_backlight, tuple(ptr(stokes[k]) for k in stokes_names)
 
-        def entry(h_ne, h_Te, h_Z, _, *rest):  # the family's argument order -> sr_field_sightline_lines'
-            return lib.sr_field_sightline_lines(h_ne, h_Te, h_Ti, h_Z, h_V, C.byref(t), *rest)
+        def call(h_ne, h_Te, h_Z, _, p_, n_, o, d, nf, w, e, c, back, I, tau, *rest):  # _sightlines' argument order -> the entry's
+            return entry(h_ne, h_Te, h_Ti, h_Z, h_V, *fields, C.byref(t), p_, n_, o, d, *after_chords, nf, w, e, c, back, *after_back,
+                         I, *after_I, tau, *rest)
 
-        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
+        return call, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
 
-    return _sightlines(params, "a LineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
+    out = _sightlines(params, table_kind, ne, Te, Z, origins, directions, omegas, None, backlight, want)
+    if polarised is not None:
+        out.update({k: stokes[k] for k in stokes_names if k in want_all})
+    return out
 
 
 VOIGT_CHUNK = _ffi.VOIGT_CHUNK  # samples of a chord sr_field_sightline_voigt's kernel stages at a time
@@ -725,23 +771,8 @@ def sightline_voigt(ne, Te, Ti, Z, V, origins, directions, *, lines, omegas, con
     returned -- is engine.sightline_lines'; a table without lorentz_width gives that entry's bits.  ne.last_kernel_ms keeps the
     kernel's time.  Not modelled: Zeeman splitting, asymmetric and shifted Stark profiles, ion dynamics, blending through wing,
     partial redistribution, refraction, the instrument function; one GPU."""
-    h_Ti, h_V = _handle("Ti", Ti, none=True), _handle("V", V, none=True)
-    t, keep = voigt_table_params(lines)
-
-    def params(omegas, n, uniform, _):
-        om, e_ph, c_om = spectrum_constants(omegas)
-        p = _ffi.VoigtParams()
-        m = p.march
-        m.toward, m.max_steps, m.continuum, m.reserved, m.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
-        m.Te, m.Z = uniform
-        p.wing = float(wing)
-
-        def entry(h_ne, h_Te, h_Z, _, *rest):  # the family's argument order -> sr_field_sightline_voigt's
-            return lib.sr_field_sightline_voigt(h_ne, h_Te, h_Ti, h_Z, h_V, C.byref(t), *rest)
-
-        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
-
-    return _sightlines(params, "a VoigtLineTable", ne, Te, Z, origins, directions, omegas, None, backlight, want)
+    return _line_family(lib.sr_field_sightline_voigt, voigt_table_params, "a VoigtLineTable", ne, Te, Ti, Z, V, origins, directions,
+                        lines, omegas, continuum, wing, toward, step, max_steps, backlight, want)
 
 
 ZEEMAN_CHUNK = _ffi.ZEEMAN_CHUNK  # samples of a chord sr_field_sightline_zeeman's kernel stages at a time
@@ -782,52 +813,8 @@ def sightline_zeeman(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lin
     back to engine.sightline_lines).  ne.last_kernel_ms keeps the kernel's time.  Not modelled: dichroism and magneto-optical
     rotation in the absorption matrix (absorption acts equally on all four parameters), Faraday rotation of the continuum, the
     Paschen-Back regime, hyperfine structure, and what engine.sightline_voigt does not model; one GPU."""
-    return _stokes_family(lambda head, outs: lib.sr_field_sightline_zeeman(*head, *outs), ne, Te, Ti, Z, V, B, origins, directions,
-                          reference, lines, omegas, continuum, wing, toward, step, max_steps, backlight, want)
-
-
-def _stokes_family(call, ne, Te, Ti, Z, V, B, origins, directions, reference, lines, omegas, continuum, wing, toward, step, max_steps,
-                   backlight, want):
-    """What sightline_zeeman and sightline_stokes share: the handles, the table, the reference, the three maps beside I and tau.
-    call(head, outs): the library's entry, head its arguments up to the backlight, outs those from I on."""
-    h_Ti, h_V, h_B = _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("B", B, none=True)
-    t, keep = zeeman_table_params(lines)
-    stokes_names = ("Q", "U", "V")
-    unknown = set(want) - set(_SIGHT_WANT) - set(stokes_names)
-    if unknown:
-        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_SIGHT_WANT + stokes_names}")
-    stokes = {}
-
-    def params(omegas, n, uniform, _):
-        om, e_ph, c_om = spectrum_constants(omegas)
-        p = _ffi.VoigtParams()
-        m = p.march
-        m.toward, m.max_steps, m.continuum, m.reserved, m.step = int(toward), int(max_steps), 1 if continuum else 0, 0, float(step)
-        m.Te, m.Z = uniform
-        p.wing = float(wing)
-        ref = None
-        if h_B is not None:
-            if reference is None:
-                raise ValueError("reference must be given with B: the direction Q is measured from, (3,) or (3, n)")
-            ref = f64(reference)
-            if ref.shape == (3,):
-                ref = np.repeat(ref[:, None], n, axis=1)
-            if ref.shape != (3, n):
-                raise ValueError(f"reference must have shape (3,) or (3, {n}), got {ref.shape}")
-            ref = np.ascontiguousarray(ref)
-        for k in stokes_names:
-            stokes[k] = np.empty((n, len(om)))
-
-        def entry(h_ne, h_Te, h_Z, _, p_, n_, o, d, nf, w, e, c, back, I, tau, *rest):  # the family's order -> this entry's
-            return call((h_ne, h_Te, h_Ti, h_Z, h_V, h_B, C.byref(t), p_, n_, o, d, ptr(ref), nf, w, e, c, back),
-                        (I, ptr(stokes["Q"]), ptr(stokes["U"]), ptr(stokes["V"]), tau, *rest))
-
-        return entry, p, (n, len(om)), "the chords and the frequencies", (len(om), ptr(om), ptr(e_ph), ptr(c_om))
-
-    out = _sightlines(params, "a ZeemanLineTable", ne, Te, Z, origins, directions, omegas, None, backlight,
-                      tuple(k for k in want if k in _SIGHT_WANT))
-    out.update({k: stokes[k] for k in stokes_names if k in want})
-    return out
+    return _line_family(lib.sr_field_sightline_zeeman, zeeman_table_params, "a ZeemanLineTable", ne, Te, Ti, Z, V, origins, directions,
+                        lines, omegas, continuum, wing, toward, step, max_steps, backlight, want, (B, reference, ()))
 
 
 STOKES_CHUNK = _ffi.STOKES_CHUNK  # samples of a chord sr_field_sightline_stokes' kernel stages at a time
@@ -855,8 +842,9 @@ def sightline_stokes(ne, Te, Ti, Z, V, B, origins, directions, reference, *, lin
         if pol.shape != (3,):
             raise ValueError(f"polarisation must be (q, u, v), got shape {pol.shape}")
         pol = np.ascontiguousarray(pol)
-    return _stokes_family(lambda head, outs: lib.sr_field_sightline_stokes(*head, ptr(pol), 1 if faraday else 0, *outs), ne, Te, Ti, Z, V,
-                          B, origins, directions, reference, lines, omegas, continuum, wing, toward, step, max_steps, backlight, want)
+    return _line_family(lib.sr_field_sightline_stokes, zeeman_table_params, "a ZeemanLineTable", ne, Te, Ti, Z, V, origins, directions,
+                        lines, omegas, continuum, wing, toward, step, max_steps, backlight, want,
+                        (B, reference, (ptr(pol), 1 if faraday else 0)))
 
 
 PUSH_UNFINISHED, PUSH_MISSED = _ffi.PUSH_UNFINISHED, _ffi.PUSH_MISSED
