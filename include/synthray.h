@@ -856,6 +856,84 @@ int sr_field_thomson_multi(const sr_field *ne, const sr_field *Te, const sr_fiel
                            int32_t n_quad, const double *pts, const double *wts, const double *ki, const double *ks,
                            int32_t n_lambda, const double *lambda, double *P, double *weight, double *kernel_ms);
 
+/* ---- optical Thomson scattering from super-Gaussian (Langdon) electrons ----------------------------------------
+ * No reference counterpart.  sr_field_thomson_multi's model -- species, flow V, drift Vd, one Ti -- with the electron distribution
+ *   f(v) = m/(4 pi Gamma(3/m) v_m^3) exp(-(v/v_m)^m),   v_m^2 = 3 (k Te/m_e) Gamma(3/m)/Gamma(5/m)
+ * in place of the Maxwellian (m = 2), the shape inverse-bremsstrahlung heating drives (Langdon 1980; Matte et al. 1988).  Te keeps
+ * its meaning as 2/3 of the mean energy.  The order m is LOCAL: either the scalar sr_field `order`, on the grid and of the dtype of
+ * the other fields and gathered with the same cell and weights, or, where `order` is NULL, the uniform p->order.  Everything
+ * sr_field_thomson_multi states holds unchanged -- the constants, the `volume`, `wavelength` and `output` lines, the gather rule,
+ * the `point` lines, D(x), float64 throughout, thomson_sg.hip compiled with -ffp-contract=off -- with, in sr_field_thomson_multi's
+ * names al, ae, ivte, xe:
+ *   point q       mo = the gathered order (or p->order).  The point is DROPPED under sr_field_thomson_multi's conditions or when mo
+ *                 is NaN.  Otherwise m = min(max(mo, 2.0), 5.0) (an infinite mo is clamped like any other), and
+ *                 when m - 2.0 <= 2^-30 the sample (l, q) follows sr_field_thomson_multi's `sample` lines exactly (a trilinear
+ *                 blend of nodes that all hold 2 need not round to 2, hence the threshold).  Else, with GAM below,
+ *                   im = 1.0/m;  z2 = 2.0*im;  G1 = GAM(im);  G2 = GAM(z2);  G3 = GAM(3.0*im);  G5 = GAM(5.0*im)
+ *                   r = sqrt((2.0*G5)/(3.0*G3));  b = m/(2.0*G1);  c = (G1*G5)/((3.0*G3)*G3);  T = pow(40.0, im)
+ *                   fe = (SP*r)/(2.0*G3);  pib = pi*b;   for i = 0 .. 47:  g_i = exp(-pow(T*S2[i], m))
+ *                 -- r = v_te/v_m (v_te^2 = 2 k Te/m_e), b = m/(2 Gamma(1/m)) normalises b int exp(-|t|^m) dt = 1, and
+ *                 al*c = omega_pe^2 Gamma(1/m)/(k^2 v_m^2 Gamma(3/m)).  At m = 2: r = c = 1, b = 1/sqrt(pi).
+ *   sample (l, q) wp, a, ae, xe, al as in sr_field_thomson_multi;  xs = xe*r;  x = |xs|;  y = pow(x, m);  gx = exp(-y);  x2 = x*x
+ *                 (R, below);  ac = al*c;  cer = ac*R;  cei = ac*((pib*xs)*gx);  (Q, below);  Ee = fe*Q
+ *                 and from `er = 1.0 + cer` on the lines of sr_field_thomson_multi with these cer, cei and Ee.
+ *               -- chi_e = al c [R_m(xs) + i pi b xs exp(-|xs|^m)], R_m(xs) = b P int t exp(-|t|^m)/(t - xs) dt = 1 - xs W_m(xs)
+ *               (W_2 = 2 Dawson), from chi = -(omega_pe^2/k^2) int f1'(u)/(u - w/k) du with the 1-D projection
+ *               f1(u) = Gamma(2/m, (|u|/v_m)^m)/(2 Gamma(3/m) v_m); the electron term of S is (2 pi/k) f1(w/k), so exp(-xe^2)*ivte
+ *               of the Maxwellian becomes sqrt(pi) Gamma(2/m, y)/(2 Gamma(3/m)) * r * ivte = Ee*ivte.
+ *   R             Both signs of t folded onto t > 0, the integral cut at T (exp(-T^m) = e^-40), t = T s^2 on the 48-point
+ *                 Gauss-Legendre rule (s_i, w_i) of [0, 1] -- the square removes the t^(m-1) behaviour of exp(-t^m) at 0 -- and,
+ *                 inside, exp(-x^m) subtracted so that the principal value is a logarithm.  S2[i] = s_i^2 and V[i] = 2 w_i s_i,
+ *                 ascending, are the float64 constants kS2 and kV of thomson_sg.hip.  x < T:
+ *                   tx = 2.0*x;  L = log((T - x)/(T + x));  s = 0;  for i ascending:  t = T*S2[i];  e = t - x;  dg = g_i - gx
+ *                       |e| < 1e-6 ?  pm1 = m*pow(x, m - 1.0);  g1 = -(pm1*gx);  g2 = gx*(pm1*pm1 - (m*(m - 1.0))*pow(x, m - 2.0))
+ *                                     h = (g1 + (0.5*g2)*e) - dg/(t + x)
+ *                                  :  h = (dg*tx)/(t*t - x2)
+ *                       s = s + V[i]*h
+ *                   R = 1.0 + (x*b)*(T*s + gx*L)
+ *                 x >= T (no cancellation against 1):
+ *                   s = 0;  for i ascending:  t = T*S2[i];  tt = t*t;  s = s + V[i]*((g_i*(2.0*tt))/(tt - x2))
+ *                   R = (b*T)*s
+ *                 -- one division per node serves t and -t; g1, g2 are the first two derivatives of exp(-x^m), which replace the
+ *                 1/(t - x) half of a node's term where the node collides with x.  R is even in xs and cei odd, bit for bit;
+ *                 R(0) = 1 exactly.  Against 34-digit quadrature max |R - R_ref| (1 + xs^2) = 1.5e-11 (m = 2.05, xs = 1.61).
+ *   Q             Gamma(z2, y), the upper incomplete gamma function, with y^z2 exp(-y) = x2*gx:  xg = x2*gx
+ *                 y < z2 + 1.0, the series:  ap = z2;  de = 1.0/z2;  sm = de;  at most 100 times:
+ *                       ap = ap + 1.0;  de = de*(y/ap);  sm = sm + de;  stop when |de| < |sm|*1e-16
+ *                   Q = G2 - sm*xg
+ *                 else the continued fraction by the modified Lentz scheme:  bb = (y + 1.0) - z2;  cc = 1.0/1e-300;  d = 1.0/bb
+ *                   h = d;  for i = 1 .. 100 (none when y is infinite):  an = -i*(i - z2);  bb = bb + 2.0
+ *                       d = an*d + bb;  |d| < 1e-300 ? d = 1e-300;  cc = bb + an/cc;  |cc| < 1e-300 ? cc = 1e-300;  d = 1.0/d
+ *                       de = d*cc;  h = h*de;  stop when |de - 1.0| < 1e-16
+ *                   Q = xg*h
+ *                 -- 1.1e-13 relative against scipy.special.gammaincc*gamma, at most 85 terms.
+ *   GAM(z)        The gamma function for 0.2 <= z <= 2.5 by its Chebyshev series on [1, 2] (24 coefficients GC[k], the float64
+ *                 constants kGC of thomson_sg.hip; the next is below 1e-18) and one step of the recurrence, so that host and
+ *                 device agree bit for bit (+, * and / only):
+ *                   w = z < 1.0 ? z + 1.0 : (z > 2.0 ? z - 1.0 : z);  tau = 2.0*w - 3.0;  t2 = 2.0*tau;  b1 = b2 = 0
+ *                   for k = 23 down to 1:  b0 = (GC[k] + t2*b1) - b2;  b2 = b1;  b1 = b0
+ *                   P = (GC[0] + tau*b1) - b2;   GAM = z < 1.0 ? P/z : (z > 2.0 ? (z - 1.0)*P : P)
+ * pow, exp and log are the device library's.  order NULL with p->order == 2, and an order field of 2.0 everywhere, return
+ * sr_field_thomson_multi's bits.  Arguments are checked before the device is touched: everything sr_field_thomson_multi checks; a
+ * uniform order (order NULL) outside [2, 5] or NaN; an order field with n_comp != 1, of another dtype or on another grid.
+ * Not modelled: per-species Ti, magnetised and relativistic corrections, anisotropic or otherwise non-isotropic distortions of
+ * the electron distribution, m outside [2, 5] (clamped), more than one GPU. */
+typedef struct {
+  double lambda_i;      /* probe wavelength [m] */
+  int32_t n_species;    /* 1 .. SR_MAX_SPECIES */
+  int32_t reserved;
+  double A[SR_MAX_SPECIES];     /* mass numbers (m_j = A_j*m_p) */
+  double Z[SR_MAX_SPECIES];     /* the uniform charge of species j where Zs[j] is NULL */
+  double frac[SR_MAX_SPECIES];  /* the uniform relative abundance of species j where fracs[j] is NULL */
+  double order;                 /* the uniform order m in [2, 5] where the order field is NULL */
+} sr_thomson_sg_params;         /* 120 bytes */
+int sr_field_thomson_sg(const sr_field *ne, const sr_field *Te, const sr_field *Ti /* or NULL */, const sr_field *V /* or NULL */,
+                        const sr_field *Vd /* or NULL */, const sr_field *const *Zs /* NULL, or n_species entries each field or NULL */,
+                        const sr_field *const *fracs /* likewise */, const sr_field *order /* or NULL: p->order */,
+                        const sr_thomson_sg_params *p, int64_t n_vol, int32_t n_quad, const double *pts, const double *wts,
+                        const double *ki, const double *ks, int32_t n_lambda, const double *lambda, double *P, double *weight,
+                        double *kernel_ms);
+
 /* ---- wave optics: a paraxial split-step march of a complex field through a domain ----------
  * No counterpart in the reference's sources (its authors compare the tracer with a CPU beam-propagation library,
  * evaluation/c.f._diffraction).  A complex scalar field U on a uniform lateral FRAME of mu x mv pixels is carried through the

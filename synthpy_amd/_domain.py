@@ -68,6 +68,11 @@ class DomainExtras:
         asymmetry of the ion-acoustic peaks in thomson_scattering_multi.  The tracer does not read it."""
         self.Vd = Vd
 
+    def external_order(self, m):
+        """(nx, ny, nz) grid (or one number) of the order m of the super-Gaussian electron distribution exp(-(v/v_m)^m), 2
+        (Maxwellian) to 5 (thomson.langdon_order): what thomson_scattering_sg reads.  The tracer does not read it."""
+        self.order = m
+
     def proton_radiograph(self, source, det_pos, **kw):
         """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
         particles have crossed this domain's B (external_B / test_B) and E (external_E): a radiography.Radiograph.
@@ -91,6 +96,14 @@ class DomainExtras:
         from .thomson import spectra_multi
 
         return spectra_multi(self, probe, collection, wavelengths, species, **kw)
+
+    def thomson_scattering_sg(self, probe, collection, wavelengths, species, order=None, **kw):
+        """thomson_scattering_multi with super-Gaussian (Langdon) electrons of the local order m -- `order`: None reads
+        external_order's grid, or an array or a number in [2, 5] -- as inverse-bremsstrahlung heating leaves them: a
+        thomson.ThomsonSpectra.  Keywords: thomson.spectra_sg's."""
+        from .thomson import spectra_sg
+
+        return spectra_sg(self, probe, collection, wavelengths, species, order=order, **kw)
 
     def wave_propagate(self, source, **kw):
         """The wave-optics march of a wave.Source through this domain's ne along its probing_direction: a wave.WaveField on

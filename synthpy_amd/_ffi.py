@@ -136,6 +136,10 @@ class ThomsonMultiParams(C.Structure):
                 ("Z", C.c_double * MAX_SPECIES), ("frac", C.c_double * MAX_SPECIES)]
 
 
+class ThomsonSgParams(C.Structure):
+    _fields_ = ThomsonMultiParams._fields_ + [("order", C.c_double)]
+
+
 class WaveParams(C.Structure):
     _fields_ = [("axis", C.c_int32), ("toward", C.c_int32), ("mu", C.c_int32), ("mv", C.c_int32), ("u0", C.c_double),
                 ("du", C.c_double), ("v0", C.c_double), ("dv", C.c_double), ("lambda_", C.c_double), ("omega", C.c_double),
@@ -221,6 +225,8 @@ SYMBOLS = {
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_thomson_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _pp, _pp, C.POINTER(ThomsonMultiParams), _i64, C.c_int32, _vp, _vp, _vp,
                                     _vp, C.c_int32, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "sr_field_thomson_sg": (_i, [_vp, _vp, _vp, _vp, _vp, _pp, _pp, _vp, C.POINTER(ThomsonSgParams), _i64, C.c_int32, _vp, _vp, _vp,
+                                 _vp, C.c_int32, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_wave": (_i, [_vp, _vp, _vp, C.POINTER(WaveParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_wave_image": (_i, [C.POINTER(WaveImageParams), _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_bytes": (_i64, [_vp]),

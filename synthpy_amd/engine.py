@@ -944,6 +944,22 @@ def _thomson(entry, ne, head, p, points, weights, ki, ks, wavelengths):
     return P, weight
 
 
+def _species_head(p, ne, Te, Ti, V, Vd, species, lambda_i):
+    """What thomson_multi and thomson_sg share: the handles of the fields and of the species' charges and fractions (the call's
+    arguments before the params), and the params p with lambda_i and the species filled in."""
+    head = [_handle("ne", ne), _handle("Te", Te), _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("Vd", Vd, none=True)]
+    species = [tuple(s) for s in species]
+    n = len(species)
+    if not 1 <= n <= _ffi.MAX_SPECIES or any(len(s) != 3 for s in species):
+        raise ValueError(f"species must be 1 to {_ffi.MAX_SPECIES} entries (A, Z, fraction), got {n}")
+    p.lambda_i, p.n_species, p.reserved = float(lambda_i), n, 0
+    Zs, fracs = (C.c_void_p * n)(), (C.c_void_p * n)()
+    for j, (A, Z, frac) in enumerate(species):
+        Zs[j], fracs[j] = _handle(f"Z{j}", Z, number=True), _handle(f"f{j}", frac, number=True)
+        p.A[j], p.Z[j], p.frac[j] = float(A), 0.0 if isinstance(Z, Field) else float(Z), 0.0 if isinstance(frac, Field) else float(frac)
+    return head + [Zs, fracs], p
+
+
 def thomson_multi(ne, Te, Ti, V, Vd, species, lambda_i, points, weights, ki, ks, wavelengths):
     """thomson for a plasma of 1 to _ffi.MAX_SPECIES ion species whose electrons may drift against the ions
     (sr_field_thomson_multi; include/synthray.h states the rule): (P (M, n_lambda), weight (M)) float64.  ne, Te, Ti, V and the
@@ -951,18 +967,19 @@ def thomson_multi(ne, Te, Ti, V, Vd, species, lambda_i, points, weights, ki, ks,
     drift).  species: a sequence of (A, Z, fraction) -- the mass number, and the charge and the relative number fraction (they need
     not sum to 1), each a scalar Field or a float (uniform, not negative).  All fields on one grid and of one dtype.
     ne.last_kernel_ms keeps the kernel's time."""
-    head = [_handle("ne", ne), _handle("Te", Te), _handle("Ti", Ti, none=True), _handle("V", V, none=True), _handle("Vd", Vd, none=True)]
-    species = [tuple(s) for s in species]
-    n = len(species)
-    if not 1 <= n <= _ffi.MAX_SPECIES or any(len(s) != 3 for s in species):
-        raise ValueError(f"species must be 1 to {_ffi.MAX_SPECIES} entries (A, Z, fraction), got {n}")
-    p = _ffi.ThomsonMultiParams()
-    p.lambda_i, p.n_species, p.reserved = float(lambda_i), n, 0
-    Zs, fracs = (C.c_void_p * n)(), (C.c_void_p * n)()
-    for j, (A, Z, frac) in enumerate(species):
-        Zs[j], fracs[j] = _handle(f"Z{j}", Z, number=True), _handle(f"f{j}", frac, number=True)
-        p.A[j], p.Z[j], p.frac[j] = float(A), 0.0 if isinstance(Z, Field) else float(Z), 0.0 if isinstance(frac, Field) else float(frac)
-    return _thomson(lib.sr_field_thomson_multi, ne, head + [Zs, fracs], p, points, weights, ki, ks, wavelengths)
+    head, p = _species_head(_ffi.ThomsonMultiParams(), ne, Te, Ti, V, Vd, species, lambda_i)
+    return _thomson(lib.sr_field_thomson_multi, ne, head, p, points, weights, ki, ks, wavelengths)
+
+
+def thomson_sg(ne, Te, Ti, V, Vd, species, order, lambda_i, points, weights, ki, ks, wavelengths):
+    """thomson_multi with super-Gaussian (Langdon) electrons f(v) ~ exp(-(v/v_m)^m) (sr_field_thomson_sg; include/synthray.h
+    states the rule): (P (M, n_lambda), weight (M)) float64.  order: the local m -- a scalar Field on the grid and of the dtype
+    of the others (gathered per point; NaN drops the point, other values are clamped to [2, 5]) or a float in [2, 5] (uniform).
+    m = 2 returns thomson_multi's bits.  Everything else is thomson_multi's."""
+    head, p = _species_head(_ffi.ThomsonSgParams(), ne, Te, Ti, V, Vd, species, lambda_i)
+    h_order = _handle("order", order, number=True)
+    p.order = 2.0 if isinstance(order, Field) else float(order)
+    return _thomson(lib.sr_field_thomson_sg, ne, head + [h_order], p, points, weights, ki, ks, wavelengths)
 
 
 def wave_params(frame, shape, lambda_, axis, toward=+1, Z=0.0, time_parts=False):

@@ -4,8 +4,8 @@
         f = src.get_all({"ne": ne, "Te": Te, "Z": None})      # one dtype for all the uploads
         engine.thomson(f["ne"], f["Te"], ...)
 
-orientation.rotated / views, emission.self_emission / table_emission, radiography.radiograph, thomson.spectra and
-wave.propagate stage through here, so a SourceFields of one domain serves them all: each field is uploaded once, at its first
+orientation.rotated / views, emission.self_emission / table_emission, radiography.radiograph, thomson.spectra / spectra_multi /
+spectra_sg and wave.propagate stage through here, so a SourceFields of one domain serves them all: each field is uploaded once, at its first
 use, and kept until close().  grid_f64 and locate are the host's restatement of what the kernels see: node coordinates rounded
 to float32 (sr_field_create takes float32) and sr_field_resample's cell rule (sr::locate_in, include/synthray.h).
 """

@@ -9,7 +9,8 @@ frame's axes are the lab's turned by R (its axis k is column k of R, so node q o
     ne'(q) = ne(R q)      Te'(q) = Te(R q)      Z'(q) = Z(R q)      B'(q) = R^T B(R q)      E'(q) = R^T E(R q)
 
 -- the fields on the view's own grid, the vector fields in the view's components; Ti (external_Ti) goes as Te and the flow V
-(external_V) as B when the domain holds them (Thomson scattering).  The result is an ordinary ScalarDomain of
+(external_V) as B when the domain holds them, the electrons' order (external_order) as Te (Thomson scattering).  The result
+is an ordinary ScalarDomain of
 the source's generation and flags: solve, the region loop, line_integrals and export_scalar_field work on it unchanged, and
 probing it along z looks along the lab direction R e_z.  The resampling is trilinear and runs on the GPU
 (engine.Field.resample -> sr_field_resample, include/synthray.h states its rule); each source field is uploaded once, and
@@ -27,7 +28,8 @@ _QUARTER = {0: (1.0, 0.0), 90: (0.0, 1.0), 180: (-1.0, 0.0), 270: (0.0, -1.0)}  
 # vacuum for ne and B; Te at external_Te's floor Te_min = 1.0; Z = 1.0 (kappa() divides by neither's zero)
 DEFAULT_FILL = {"ne": 0.0, "Te": 1.0, "Z": 1.0, "B": 0.0}
 _E_FILL = 0.0  # a domain's E (external_E; proton radiography) is vacuum outside the source box, or fill["E"]
-_EXTRA_FILL = {"E": _E_FILL, "Ti": DEFAULT_FILL["Te"], "V": 0.0, "Vd": 0.0}  # the fields only some domains hold: Ti as Te, V and Vd at rest
+# the fields only some domains hold: Ti as Te, V and Vd at rest, the electrons' order Maxwellian
+_EXTRA_FILL = {"E": _E_FILL, "Ti": DEFAULT_FILL["Te"], "V": 0.0, "Vd": 0.0, "order": 2.0}
 
 
 def rotation_matrix(angle_deg, about="y"):
@@ -93,11 +95,13 @@ def _new_domain(domain, dims, lengths):
 def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=None, lengths=None, source=None):
     """A new ScalarDomain of the same generation and flags holding the source's fields seen from the frame turned by R =
     rotation_matrix(angle_deg, about), or `matrix` (orthonormal to 1e-12, else ValueError): ne'(q) = ne(R q), Te and Z the
-    same when they are arrays (scalars pass through), B'(q) = R^T B(R q), and E as B when the domain holds one; Ti goes as Te and
-    the flow V and the electron drift Vd (external_Vd) as B when the domain holds them.  The view grid
+    same when they are arrays (scalars pass through), B'(q) = R^T B(R q), and E as B when the domain holds one; Ti and the
+    electrons' order (external_order) go as Te and the flow V and the electron drift Vd (external_Vd) as B when the domain holds
+    them.  The view grid
     is the source's lengths and dims unless `dims` / `lengths` say otherwise.  Outside the source box the fields take `fill`:
     None for the defaults
-    (DEFAULT_FILL: vacuum, Te_min, Z = 1), a number for ne, or a dict over "ne", "Te", "Z", "B", "E", "Ti", "V", "Vd" (Ti: Te_min, V and Vd: at rest).  `source`: a SourceFields
+    (DEFAULT_FILL: vacuum, Te_min, Z = 1), a number for ne, or a dict over "ne", "Te", "Z", "B", "E", "Ti", "V", "Vd", "order" (Ti: Te_min, V and Vd: at rest,
+    order: 2.0).  `source`: a SourceFields
     of the same domain whose uploads are reused (views())."""
     if (angle_deg is None) == (matrix is None):
         raise ValueError("give either angle_deg (with about) or matrix")
@@ -118,7 +122,7 @@ def rotated(domain, angle_deg=None, about="y", *, matrix=None, fill=None, dims=N
     zero = (0.0, 0.0, 0.0)
     with staged(domain, source, "source") as src:
         new.external_ne(src.get("ne", ne).resample(R, zero, grid, fill=fills["ne"]))
-        for name in ("Te", "Z", "Ti"):
+        for name in ("Te", "Z", "Ti", "order"):
             a = getattr(domain, name, None)
             if a is not None:
                 f = fills.get(name, _EXTRA_FILL.get(name))

@@ -19,6 +19,14 @@ Several ion species and a current (spectra_multi; engine.thomson_multi -> sr_fie
 
 1 to 4 Maxwellian ion species that share Ti and the flow; their relative Landau damping shapes the ion-acoustic feature, and the
 drift shows as the asymmetry of its two peaks.  A species' charge and fraction may vary over the grid.
+
+Super-Gaussian (Langdon) electrons (spectra_sg; engine.thomson_sg -> sr_field_thomson_sg):
+
+    domain.external_order(thomson.langdon_order(Z, intensity, domain.Te, 351e-9))   # m = 2..5, cell by cell
+    sp = domain.thomson_scattering_sg(probe, coll, wavelengths, ch)             # or order=3.2 for a uniform m
+
+The electrons follow exp(-(v/v_m)^m) with the local order m: the electron-plasma-wave peaks move and sharpen and the ion-acoustic
+peaks lose Landau damping.
 """
 from __future__ import annotations
 
@@ -32,6 +40,7 @@ from .fields import grid_f64, locate, staged
 E_CHARGE = engine.E_CHARGE    # C
 EPS0 = 8.8541878128e-12       # F/m (CODATA 2018)
 R_E = 2.8179403262e-15        # m, the classical electron radius (CODATA 2018)
+M_E = 9.1093837015e-31        # kg (CODATA 2018)
 
 # the 7-point rule of degree 5 on the unit disc (Abramowitz & Stegun 25.4.61): the centre and a hexagon of radius sqrt(2/3);
 # the weights are fractions of the disc's area
@@ -288,12 +297,9 @@ def drift_velocity(J, ne):
         return np.where((ne > 0)[..., None], -J / (E_CHARGE * ne[..., None]), 0.0)
 
 
-def spectra_multi(domain, probe, collection, wavelengths, species, instrument_fwhm=None, fields=None):
-    """spectra for a plasma of several ion species whose electrons may drift against the ions: `species` is a sequence of 1 to 4
-    Species (mass number, charge, relative number fraction; domain.Z is not read), the drift is domain.Vd (external_Vd; see
-    drift_velocity; without it none); ne, Te, Ti and V are read as spectra reads them, and all species share Ti and V.  A
-    ThomsonSpectra, power = r_e^2 (1 - (ks . e)^2) P with P engine.thomson_multi's.  The species' arrays go up under the names
-    Z0.., f0.. and the drift as Vd, so a fields.SourceFields serves a fit loop over other arguments."""
+def _species_arrays(domain, probe, collection, wavelengths, species):
+    """What spectra_multi and spectra_sg check and read alike: (wavelengths, the list of Species, {name: array | None} of ne, Te,
+    Ti, V, Vd and the species' arrays Z0.., f0..)."""
     if not isinstance(probe, Probe) or not isinstance(collection, Collection):
         raise ValueError("probe must be a thomson.Probe and collection a thomson.Collection")
     if getattr(domain, "ne", None) is None or getattr(domain, "Te", None) is None:
@@ -311,11 +317,69 @@ def spectra_multi(domain, probe, collection, wavelengths, species, instrument_fw
                 if v.shape != shape:
                     raise ValueError(f"the array {name} of species {j} has shape {v.shape}, the domain needs {shape}")
                 named[name] = v
+    return lam, species, named
+
+
+def spectra_multi(domain, probe, collection, wavelengths, species, instrument_fwhm=None, fields=None):
+    """spectra for a plasma of several ion species whose electrons may drift against the ions: `species` is a sequence of 1 to 4
+    Species (mass number, charge, relative number fraction; domain.Z is not read), the drift is domain.Vd (external_Vd; see
+    drift_velocity; without it none); ne, Te, Ti and V are read as spectra reads them, and all species share Ti and V.  A
+    ThomsonSpectra, power = r_e^2 (1 - (ks . e)^2) P with P engine.thomson_multi's.  The species' arrays go up under the names
+    Z0.., f0.. and the drift as Vd, so a fields.SourceFields serves a fit loop over other arguments."""
+    lam, species, named = _species_arrays(domain, probe, collection, wavelengths, species)
     pts, wts = collection.quadrature(probe)
     with staged(domain, fields) as src:
         f = src.get_all(named)  # the kernel reads every field in one dtype
         triples = [(s.mass, f.get(f"Z{j}", s.charge), f.get(f"f{j}", s.fraction)) for j, s in enumerate(species)]
         P, weight = engine.thomson_multi(f["ne"], f["Te"], f["Ti"], f["V"], f["Vd"], triples, probe.wavelength, pts, wts,
                                          probe.direction, collection.direction, lam)
+        kernel_ms = f["ne"].last_kernel_ms
+    return _spectra_of(domain, probe, collection, lam, named, P, weight, kernel_ms, instrument_fwhm)
+
+
+def langdon_order(Z, intensity, Te, wavelength):
+    """The order m of the super-Gaussian electron distribution exp(-(v/v_m)^m) that inverse-bremsstrahlung heating by a laser of
+    `intensity` [W/m^2] and vacuum `wavelength` [m] drives in a plasma of charge Z and electron temperature Te [eV] (Matte et al.
+    1988): m = 2 + 3/(1 + 1.66/alpha^0.724), alpha = Z v_osc^2/v_t^2 with v_osc = e E/(m_e omega), I = eps0 c E^2/2 and
+    v_t^2 = k Te/m_e.  Numbers or arrays (broadcast); alpha = 0 gives 2 (Maxwellian), alpha -> infinity 5.  What external_order
+    takes."""
+    Z, intensity, Te, wavelength = (np.asarray(a, np.float64) for a in (Z, intensity, Te, wavelength))
+    omega = 2.0 * np.pi * engine.c / wavelength
+    v_osc2 = (2.0 * intensity / (EPS0 * engine.c)) * (E_CHARGE / (M_E * omega)) ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        alpha = Z * v_osc2 / (E_CHARGE * Te / M_E)
+        m = np.where(alpha > 0, 2.0 + 3.0 / (1.0 + 1.66 / np.power(alpha, 0.724)), 2.0)
+    m = np.where(np.isnan(alpha), np.nan, m)
+    return float(m) if m.ndim == 0 else m
+
+
+def spectra_sg(domain, probe, collection, wavelengths, species, order=None, instrument_fwhm=None, fields=None):
+    """spectra_multi for super-Gaussian (Langdon) electrons, f(v) ~ exp(-(v/v_m)^m) with Te kept as 2/3 of the mean energy: what
+    inverse-bremsstrahlung heating by the probe or the drive makes of the electrons.  order: the local m -- None reads
+    domain.order (external_order; see langdon_order), an (nx, ny, nz) array or a number; an array's values are clamped to [2, 5]
+    and a NaN node drops the points that read it, a number must lie in [2, 5].  m = 2 returns spectra_multi's bits.  The order's
+    array goes up under the name "order".  A ThomsonSpectra, power = r_e^2 (1 - (ks . e)^2) P with P engine.thomson_sg's.  Not
+    modelled: per-species Ti, magnetised and relativistic corrections, anisotropic distortions of the electron distribution, m
+    outside [2, 5], more than one GPU."""
+    lam, species, named = _species_arrays(domain, probe, collection, wavelengths, species)
+    if order is None:
+        order = getattr(domain, "order", None)
+        if order is None:
+            raise ValueError("the domain holds no order (external_order); give order=")
+    if np.ndim(order) == 0:
+        order = float(order)
+        if not 2.0 <= order <= 5.0:
+            raise ValueError(f"a uniform order must lie in [2, 5], got {order!r}")
+    else:
+        order = np.asarray(order)
+        if order.shape != named["ne"].shape:
+            raise ValueError(f"order has shape {order.shape}, the domain needs {named['ne'].shape}")
+        named["order"] = order
+    pts, wts = collection.quadrature(probe)
+    with staged(domain, fields) as src:
+        f = src.get_all(named)  # the kernel reads every field in one dtype
+        triples = [(s.mass, f.get(f"Z{j}", s.charge), f.get(f"f{j}", s.fraction)) for j, s in enumerate(species)]
+        P, weight = engine.thomson_sg(f["ne"], f["Te"], f["Ti"], f["V"], f["Vd"], triples, f.get("order", order), probe.wavelength,
+                                      pts, wts, probe.direction, collection.direction, lam)
         kernel_ms = f["ne"].last_kernel_ms
     return _spectra_of(domain, probe, collection, lam, named, P, weight, kernel_ms, instrument_fwhm)
