@@ -723,8 +723,8 @@ int sr_field_sightline_stokes(const sr_field *ne, const sr_field *Te, const sr_f
  * (2, n), steps (n) and flags (n) are HOST arrays in the order of s0; each may be NULL.  stats (may be NULL): kernel_ms is the
  * HIP-event time of the push kernel alone; finished + unfinished == n; missed counts SR_PUSH_MISSED; deposited the particles
  * binned inside img.
- * Validity: prescribed fields only (no self-fields), no scattering or stopping in the plasma, a fixed step, trilinear fields (div B
- * is only as good as the input's).
+ * Validity: prescribed fields only (no self-fields), no scattering or stopping in the plasma (sr_particles_push_matter has
+ * both), a fixed step, trilinear fields (div B is only as good as the input's).
  * Arguments are checked before the device is touched: a NULL p or s0, n < 0, a non-finite or non-positive dt, a non-finite qm,
  * det_pos or hit_scale, max_steps < 1, an axis outside 0..2, an img of another kind, E and B both NULL, a field with n_comp != 3,
  * E and B of different dtypes or on grids that differ.  n == 0 succeeds. */
@@ -744,6 +744,72 @@ int sr_particles_push(const sr_field *E, const sr_field *B, const sr_push_params
                       double *sf /* host (6, n) or NULL */, double *hits /* host (2, n) or NULL */,
                       int32_t *steps /* host (n) or NULL */, uint8_t *flags /* host (n) or NULL */,
                       sr_image *img /* SR_IMG_COUNTS or NULL */, sr_push_stats *stats /* or NULL */);
+
+/* ---- proton radiography through matter: sr_particles_push with collisional stopping and scattering moments ----------------
+ * No reference counterpart.  sr_particles_push's particles, fields, step, detector, image and host outputs; E and B may now both
+ * be NULL (matter only).  ne [m^-3] (required) and Z, the mean ionisation, are scalar sr_fields (n_comp == 1) on the grid and of
+ * the dtype of E / B (node coordinates compared bit for bit).  Z NULL: the uniform p->Z, and nothing is read.  The projectile has
+ * the mass `mass` and the charge number z (p->push.qm stays what E and B act on); the material the nuclear charge Zn, the mean
+ * excitation energy I [J] and the scattering logarithm lnLs.  push_matter.hip is compiled with -ffp-contract=off: every operation
+ * below rounds on its own, in float64; sqrt and / are the correctly rounded ones, log is the device library's.
+ * Constants, each formed in float64 on the host exactly as written: c, ic2, hq, hd as sr_particles_push's; e = 1.602176634e-19,
+ * m_e = 9.1093837015e-31, eps0 = 8.8541878128e-12, hbar = 1.054571817e-34, pi = 3.141592653589793; e2 = e*e, mc2 = mass*(c*c),
+ * A2 = (2.0*m_e)*(c*c), HW = hbar*sqrt(e2/(eps0*m_e)), ze = (z*e2)/((4.0*pi)*eps0), KS = ((z*z)*(e2*e2))/((((4.0*pi)*eps0)*eps0)*m_e),
+ * KT = (((8.0*pi)*(Zn*(Zn + 1.0)))*(ze*ze))*lnLs.  Per particle, with s = M0 = M1 = M2 = 0.0 at the start:
+ *   do {
+ *     sr_particles_push's step up to its second half kick: xm, (E, B) at xm, um, up, u_a = up_a + hq*E_a
+ *     (ne, Z) at xm: the same cell, weights and corner order as E and B, fill 0 (Z: p->Z when no field is given)
+ *     uu = |u|^2;  q = uu*ic2;  gn = sqrt(1.0 + q);  un = sqrt(uu);  v = un/gn;  ds = v*dt
+ *     matter = xm inside the box on every axis && ne > 0.0 && Z > 0.0                      (a NaN fails a comparison)
+ *     if (matter && !(uu > 0.0)) stopped                                                   (at rest in matter)
+ *     else if (matter) {                                                                   (scattering power, Fermi-Eyges moments)
+ *       pv = (mass*uu)/gn;  Ts = (KT*(ne/Z))/(pv*pv);  sm = s + 0.5*ds;  t = Ts*ds
+ *       M0 = M0 + t;  M1 = M1 + t*sm;  M2 = M2 + (t*sm)*sm }
+ *     s = s + ds                                                                           (every step, matter or not)
+ *     if (matter && !stopped) {                                                            (Bethe stopping as a drag on u)
+ *       aq = A2*q;  b2 = q/(gn*gn);  Lf = log(aq/(HW*sqrt(ne))) - b2;  Lb = log(aq/I) - b2
+ *       dz = Zn - Z;  nb = (ne*(dz > 0.0 ? dz : 0.0))/Z
+ *       N = ne*(Lf > 0.0 ? Lf : 0.0) + nb*(Lb > 0.0 ? Lb : 0.0);  S = (KS/(v*v))*N;  fac = 1.0 - ((S/mass)*dt)/un
+ *       u_a = fac > 0.0 ? u_a*fac : 0.0;  q = |u|^2*ic2;  gn = sqrt(1.0 + q)
+ *       stopped = !(fac > 0.0) || (mc2*q)/(gn + 1.0) < stop_energy }
+ *     steps += 1
+ *     if (stopped) { x_a = xm_a; leave the loop }
+ *     x_a = xm_a + u_a*(hd/gn)                                                             (half drift)
+ *   } while (x inside the grid box on every axis && steps < max_steps)
+ * S = z^2 e^4/(4 pi eps0^2 m_e v^2) [ne Lf + nb Lb] is Bethe's stopping power of the free electrons (hbar*omega_p in the
+ * logarithm's place of I) and of the nb = ne (Zn - Z)/Z bound ones, a logarithm that is not positive dropped (the projectile is
+ * then no faster than those electrons); q/gn^2 = beta^2.  Ts = 8 pi (ne/Z) Zn (Zn + 1) (z e^2/(4 pi eps0))^2/(p v)^2 lnLs is the
+ * scattering power d<theta^2>/ds (Jackson 13.6 in SI, the electrons' share through Zn + 1), from the values before the drag.
+ * M0, M1, M2 are the moments of Ts over the path length s (midpoint rule), from which the caller forms the Fermi-Eyges
+ * variances on a plane; the kernel draws no random numbers and the scattering does not act on the path.  A stopped particle
+ * gets SR_PUSH_STOPPED, stays at the midpoint with the u the drag left it (0 when fac <= 0), is not binned, and is not
+ * SR_PUSH_UNFINISHED; the detector line is applied to it as to any other.  Where ne = 0 everywhere, sf, hits, steps and flags
+ * are sr_particles_push's bits.
+ * energy (n): (mc2*(|u|^2*ic2))/(gn + 1.0) of the final u [J].  moments (4, n): rows M0 [rad^2], M1 [rad^2 m], M2 [rad^2 m^2]
+ * and s of the last step [m].  Both are HOST arrays and may be NULL, as sf, hits, steps and flags.  stats: sr_push_stats'
+ * members, and stopped, the particles with SR_PUSH_STOPPED (they count as finished).
+ * Validity: sr_particles_push's, and a cold target or v >> the electrons' thermal speed, no nuclear reactions, no straggling (every
+ * particle loses the mean), a single material, small-angle scattering that does not feed back on the path.
+ * Arguments are checked before the device is touched: sr_particles_push's checks (E and B both NULL is allowed), a NULL ne, mass,
+ * Zn or I not finite and positive, a non-finite z, lnLs or stop_energy negative or not finite, Z NULL with p->Z not finite and
+ * positive, a field with the wrong n_comp, of another dtype or on another grid than ne.  n == 0 succeeds. */
+typedef struct {
+  sr_push_params push;
+  double mass;          /* the projectile's mass [kg], > 0 */
+  double z;             /* its charge number */
+  double Zn;            /* the material's nuclear charge, > 0 */
+  double I;             /* its mean excitation energy [J], > 0 */
+  double lnLs;          /* the scattering logarithm, >= 0 */
+  double Z;             /* the uniform mean ionisation, read when the Z field is NULL; then > 0 */
+  double stop_energy;   /* [J], >= 0: a particle whose kinetic energy falls below it is stopped */
+} sr_push_matter_params;
+typedef struct { double kernel_ms; int64_t finished, unfinished, missed, deposited, stopped; } sr_push_matter_stats;
+#define SR_PUSH_STOPPED    4   /* stopped in the matter */
+int sr_particles_push_matter(const sr_field *E /* or NULL */, const sr_field *B /* or NULL */, const sr_field *ne,
+                             const sr_field *Z /* or NULL */, const sr_push_matter_params *p, int64_t n,
+                             const double *s0 /* host (6, n) */, double *sf, double *hits, int32_t *steps, uint8_t *flags,
+                             double *energy /* host (n) or NULL */, double *moments /* host (4, n) or NULL */,
+                             sr_image *img /* SR_IMG_COUNTS or NULL */, sr_push_matter_stats *stats /* or NULL */);
 
 /* ---- optical Thomson scattering: the spectral density function summed over scattering volumes ----------------
  * No reference counterpart.  n_vol scattering volumes, each a quadrature of n_quad points p_q [m] with weights w_q [m] along the

@@ -76,7 +76,8 @@ class DomainExtras:
     def proton_radiograph(self, source, det_pos, **kw):
         """The fluence image a radiography.ProtonSource forms on the plane coordinate[source axis] == det_pos [m] after its
         particles have crossed this domain's B (external_B / test_B) and E (external_E): a radiography.Radiograph.
-        Keywords: radiography.radiograph's."""
+        Keywords: radiography.radiograph's -- material= (a radiography.Material), stop_energy_MeV= and scatter_seed= add the
+        stopping and multiple scattering in this domain's ne and Z (external_Z)."""
         from .radiography import radiograph
 
         return radiograph(self, source, det_pos, **kw)

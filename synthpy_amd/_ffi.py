@@ -124,6 +124,18 @@ class PushStats(C.Structure):
 PUSH_UNFINISHED, PUSH_MISSED = 1, 2  # SR_PUSH_*
 
 
+class PushMatterParams(C.Structure):
+    _fields_ = [("push", PushParams), ("mass", C.c_double), ("z", C.c_double), ("Zn", C.c_double), ("I", C.c_double),
+                ("lnLs", C.c_double), ("Z", C.c_double), ("stop_energy", C.c_double)]
+
+
+class PushMatterStats(C.Structure):
+    _fields_ = PushStats._fields_ + [("stopped", C.c_int64)]
+
+
+PUSH_STOPPED = 4  # SR_PUSH_STOPPED
+
+
 class ThomsonParams(C.Structure):
     _fields_ = [("lambda_i", C.c_double), ("A", C.c_double), ("Z", C.c_double)]
 
@@ -221,6 +233,8 @@ SYMBOLS = {
                                        C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        C.POINTER(C.c_double)]),
     "sr_particles_push": (_i, [_vp, _vp, C.POINTER(PushParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PushStats)]),
+    "sr_particles_push_matter": (_i, [_vp, _vp, _vp, _vp, C.POINTER(PushMatterParams), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      C.POINTER(PushMatterStats)]),
     "sr_field_thomson": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ThomsonParams), _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32,
                               _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "sr_field_thomson_multi": (_i, [_vp, _vp, _vp, _vp, _vp, _pp, _pp, C.POINTER(ThomsonMultiParams), _i64, C.c_int32, _vp, _vp, _vp,

@@ -902,6 +902,58 @@ def push_particles(E, B, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, im
     return out
 
 
+PUSH_STOPPED = _ffi.PUSH_STOPPED
+_PUSH_MATTER_WANT = _PUSH_WANT + ("energy", "moments")
+
+
+@dataclass
+class PushMatterStats(PushStats):
+    stopped: int       # stopped in the matter (PUSH_STOPPED); they count as finished
+
+
+def push_matter_params(qm, dt, max_steps, axis, det_pos, hit_scale=1e3, *, mass, z, Zn, I, lnLs, Z=0.0, stop_energy=0.0):
+    """sr_push_matter_params."""
+    p = _ffi.PushMatterParams()
+    p.push = push_params(qm, dt, max_steps, axis, det_pos, hit_scale)
+    p.mass, p.z, p.Zn, p.I, p.lnLs, p.Z, p.stop_energy = float(mass), float(z), float(Zn), float(I), float(lnLs), float(Z), float(stop_energy)
+    return p
+
+
+def push_particles_matter(E, B, ne, Z, s0, qm, dt, max_steps, axis, det_pos, hit_scale=1e3, *, mass, z, Zn, I, lnLs, stop_energy=0.0,
+                          image=None, want=_PUSH_MATTER_WANT):
+    """push_particles through matter (sr_particles_push_matter; include/synthray.h states the rule): beside E and B (both may be
+    None) the particles cross the electron density ne [m^-3] (a scalar Field) of mean ionisation Z (a scalar Field, or a number:
+    a uniform value, which is not read), in which they lose energy by Bethe's stopping power of the free and the bound electrons
+    and gather the moments of the multiple-scattering power.  mass [kg] and z: the projectile's mass and charge number; Zn, I [J],
+    lnLs: the material's nuclear charge, mean excitation energy and scattering logarithm; stop_energy [J]: a particle whose
+    kinetic energy falls below it is stopped (PUSH_STOPPED) and not binned.  Returns push_particles' dict with, when named in
+    `want`, "energy" (n) [J] on leaving or stopping and "moments" (4, n): M0, M1, M2 of the scattering power over the path
+    length, and the path length; "stats" is a PushMatterStats."""
+    unknown = set(want) - set(_PUSH_MATTER_WANT)
+    if unknown:
+        raise ValueError(f"want names {sorted(unknown)}; the outputs are {_PUSH_MATTER_WANT}")
+    h_E, h_B = _handle("E", E, none=True), _handle("B", B, none=True)
+    h_ne, h_Z = _handle("ne", ne), _handle("Z", Z, number=True)
+    s0 = f64(s0)
+    if s0.ndim != 2 or s0.shape[0] != 6:
+        raise ValueError(f"s0 must have shape (6, n), got {s0.shape}")
+    if image is not None and not isinstance(image, DetectorImage):
+        raise ValueError("image must be an engine.DetectorImage of counts")
+    n = s0.shape[1]
+    shapes = {"sf": ((6, n), np.float64), "hits": ((2, n), np.float64), "steps": (n, np.int32), "flags": (n, np.uint8),
+              "energy": (n, np.float64), "moments": ((4, n), np.float64)}
+    out = {name: np.empty(*shapes[name]) for name in _PUSH_MATTER_WANT if name in want}
+    p = push_matter_params(qm, dt, max_steps, axis, det_pos, hit_scale, mass=mass, z=z, Zn=Zn, I=I, lnLs=lnLs,
+                           Z=0.0 if h_Z else float(Z), stop_energy=stop_energy)
+    st = _ffi.PushMatterStats()
+    check(lib.sr_particles_push_matter(h_E, h_B, h_ne, h_Z, C.byref(p), n, ptr(s0),
+                                       *(ptr(out.get(name)) for name in _PUSH_MATTER_WANT),
+                                       None if image is None else image._h, C.byref(st)))
+    out["stats"] = PushMatterStats(float(st.kernel_ms), int(st.finished), int(st.unfinished), int(st.missed), int(st.deposited),
+                                   int(st.stopped))
+    return out
+
+
 MAX_SPECIES = _ffi.MAX_SPECIES  # the ion species thomson_multi takes at most
 
 

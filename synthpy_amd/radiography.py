@@ -1,4 +1,4 @@
-"""Proton (charged-particle) radiography of a domain's E and B (no reference counterpart).
+"""Proton (charged-particle) radiography of a domain's E and B, and of its matter (no reference counterpart).
 
     src = radiography.ProtonSource(14.7, position=(0, 0, -10e-3), axis="z", half_angle=0.2, n=1_000_000)
     rad = domain.proton_radiograph(src, det_pos=0.15)       # or radiography.radiograph(domain, src, 0.15)
@@ -9,6 +9,15 @@ grid box where it enters (host, float64), is pushed through the trilinear fields
 box (engine.push_particles -> sr_particles_push; include/synthray.h states the rule), and is projected onto the detector plane
 coordinate[axis] == det_pos.  The image shows the transverse fields with no density weighting.  Validity: prescribed fields only
 (no self-fields), no scattering or stopping in the plasma, a fixed step, trilinear fields (div B is only as good as the input's).
+
+    rad = domain.proton_radiograph(src, det_pos=0.15, material=radiography.Material.CH(), stop_energy_MeV=0.1)
+    rad.energy_MeV, rad.stopped, rad.scatter_sigma(), rad.scattered(seed=1).counts, rad.counts_in(10.0, 12.0)
+
+With a Material the particles also cross the domain's ne (mean ionisation: external_Z): Bethe stopping by the free and the bound
+electrons as a drag, and the Fermi-Eyges moments of the multiple-scattering power along each path, from which scatter_sigma() and
+scattered() give the blur on the detector (engine.push_particles_matter -> sr_particles_push_matter).  Validity there: a cold
+target or v >> the electrons' thermal speed, no nuclear reactions, no straggling, a single material, small-angle scattering that
+does not feed back on the path.
 """
 from __future__ import annotations
 
@@ -159,17 +168,144 @@ def project(s, axis, det_pos, hit_scale=1e3):
     return hits, ~(np.isfinite(tau) & (tau > 0.0))
 
 
+MEV = 1e6 * E_CHARGE  # J
+AMU = 1.66053906660e-27  # kg (CODATA 2018)
+
+
+class Material:
+    """What radiograph(material=...) needs of the matter the particles cross: the nuclear charge Zn and mass number A of its
+    (mean) atom, the mean excitation energy I_eV [eV] of Bethe's logarithm for the bound electrons, and the logarithm of the
+    multiple-scattering power, coulomb_log; None: ln(204 Zn^(-1/3)), the screened-nucleus value of Jackson 13.6 (Classical
+    Electrodynamics, 3rd ed., section 13.6).  A compound is its mean atom (CH: Zn = 3.5, A = 6.5)."""
+
+    # name: (Zn, A, I [eV]).  I: ICRU Report 49 (1993), Stopping Powers and Ranges for Protons and Alpha Particles, as tabulated
+    # by NIST PSTAR's material list (CH: polystyrene); A: the standard atomic weights
+    TABLE = {"CH": (3.5, 6.5095, 68.7), "Al": (13.0, 26.9815, 166.0), "Cu": (29.0, 63.546, 322.0), "W": (74.0, 183.84, 727.0)}
+
+    def __init__(self, Zn, A, I_eV, coulomb_log=None):
+        self.Zn, self.A, self.I_eV = float(Zn), float(A), float(I_eV)
+        if not (np.isfinite(self.Zn) and self.Zn > 0 and np.isfinite(self.A) and self.A > 0 and np.isfinite(self.I_eV) and self.I_eV > 0):
+            raise ValueError("Zn, A and I_eV must be finite and positive")
+        self.coulomb_log = float(np.log(204.0 * self.Zn ** (-1.0 / 3.0))) if coulomb_log is None else float(coulomb_log)
+        if not (np.isfinite(self.coulomb_log) and self.coulomb_log >= 0):
+            raise ValueError(f"coulomb_log must be finite and not negative, got {coulomb_log!r}")
+
+    @property
+    def I(self):
+        """The mean excitation energy [J]."""
+        return self.I_eV * E_CHARGE
+
+    def electron_density(self, rho, Z=None):
+        """ne [m^-3] of the mass density rho [kg/m^3] at the mean ionisation Z (None: fully ionised, Zn)."""
+        return np.asarray(rho, np.float64) * (self.Zn if Z is None else Z) / (self.A * AMU)
+
+    @classmethod
+    def named(cls, name, coulomb_log=None):
+        return cls(*cls.TABLE[name], coulomb_log=coulomb_log)
+
+    @classmethod
+    def CH(cls):
+        return cls.named("CH")
+
+    @classmethod
+    def Al(cls):
+        return cls.named("Al")
+
+    @classmethod
+    def Cu(cls):
+        return cls.named("Cu")
+
+    @classmethod
+    def W(cls):
+        return cls.named("W")
+
+
+def kinetic_energy(u, mass):
+    """m c^2 (gamma - 1) [J] of u = gamma*v (3, n), as m c^2 q/(gamma + 1) with q = |u|^2/c^2: no cancellation."""
+    q = np.sum(np.square(u), axis=0) / (c * c)
+    return mass * c * c * q / (np.sqrt(1.0 + q) + 1.0)
+
+
 class Radiograph:
     """counts (ny, nx) float64: particles per detector bin, x = the first lateral axis (x < y < z order) and y the second;
     edges = (x edges, y edges) in the unit of hits (mm with hit_scale = 1e3); hits (2, n), flags (n) uint8
-    (engine.PUSH_UNFINISHED | engine.PUSH_MISSED), steps (n) int32 (0: the particle never met the box) in the source's order;
-    sf (6, n) the states on leaving the box; magnification = (d_src + d_det)/d_src for the box's centre plane; stats: an
-    engine.PushStats of the pushed particles."""
+    (engine.PUSH_UNFINISHED | engine.PUSH_MISSED | engine.PUSH_STOPPED), steps (n) int32 (0: the particle never met the box) in
+    the source's order; sf (6, n) the states on leaving the box; magnification = (d_src + d_det)/d_src for the box's centre plane;
+    stats: an engine.PushStats of the pushed particles.  With radiograph(material=...): energy_MeV (n) on leaving the box or
+    stopping, stopped (n) bool, moments (4, n): M0, M1, M2 of the scattering power over each path and the path's length
+    (sr_particles_push_matter); stats is an engine.PushMatterStats.  Without a material these three are None."""
 
-    def __init__(self, counts, edges, hits, flags, steps, sf, magnification, stats, reference_hits, dt, max_steps):
+    def __init__(self, counts, edges, hits, flags, steps, sf, magnification, stats, reference_hits, dt, max_steps, *, energy_MeV=None,
+                 moments=None, axis=None, det_pos=None, hit_scale=1e3):
         self.counts, self.edges, self.hits, self.flags, self.steps, self.sf = counts, edges, hits, flags, steps, sf
         self.magnification, self.stats, self.dt, self.max_steps = magnification, stats, dt, max_steps
         self._reference_hits = reference_hits
+        self.energy_MeV, self.moments = energy_MeV, moments
+        self.stopped = None if moments is None else (np.asarray(flags) & engine.PUSH_STOPPED) > 0
+        self.axis, self.det_pos, self.hit_scale = axis, det_pos, hit_scale
+
+    def _need_matter(self):
+        if self.moments is None:
+            raise ValueError("this radiograph was made without a material: it has no energies and no scattering moments")
+
+    def _bin(self, hits, keep):
+        (x0, x1), (y0, y1) = ((e[0], e[-1]) for e in self.edges)
+        h = np.ascontiguousarray(hits[:, keep])
+        return engine.hist2d(h[0], h[1], len(self.edges[0]) - 1, len(self.edges[1]) - 1, x0, x1, y0, y1).astype(np.float64)
+
+    def scatter_sigma(self):
+        """(sigma_theta (n) [rad], sigma_y (n) [m]): the Fermi-Eyges standard deviations, per plane of projection, of each
+        particle's direction and of its position on the detector plane, perpendicular to its flight: with L = the path
+        length inside the box + the flight from there to the plane, sigma_theta^2 = M0/2 and sigma_y^2 = (L^2 M0 - 2 L M1 +
+        M2)/2 (M_k the moments of the scattering power d<theta^2>/ds over the path).  NaN sigma_y for a particle that does
+        not reach the plane."""
+        self._need_matter()
+        M0, M1, M2, s_end = self.moments
+        a = self.axis
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tau = (self.det_pos - self.sf[a]) / self.sf[3 + a]
+            L = s_end + tau * np.sqrt(np.sum(np.square(self.sf[3:]), axis=0))
+            var_y = 0.5 * ((L * L * M0 - 2.0 * L * M1) + M2)
+            ok = np.isfinite(tau) & (tau > 0)
+        return np.sqrt(0.5 * M0), np.where(ok, np.sqrt(np.maximum(var_y, 0.0)), np.nan)
+
+    def scattered_hits(self, seed):
+        """hits (2, n) displaced by multiple scattering: to each particle's point on the plane two normal deviates of
+        scatter_sigma()'s sigma_y (numpy's default_rng(seed), drawn in the source's order) are added along e1 and e2, the
+        two unit vectors perpendicular to its flight n^ (e1: the first lateral axis made perpendicular to n^, e2 = n^ x e1),
+        and the displaced line is met with the plane: a displacement d moves the hit by d - n^ d_a/n_a.  Hits that are not
+        finite, and particles without scattering, stay as they are."""
+        self._need_matter()
+        _, sig = self.scatter_sigma()
+        n = self.hits.shape[1]
+        z = np.random.default_rng(seed).standard_normal((2, n))
+        a = self.axis
+        b, cc = lateral_axes(a)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            nh = self.sf[3:] / np.sqrt(np.sum(np.square(self.sf[3:]), axis=0))
+            e1 = -nh[b] * nh
+            e1[b] += 1.0
+            e1 /= np.sqrt(np.sum(e1 * e1, axis=0))
+            e2 = np.cross(nh, e1, axis=0)
+            d = sig * (z[0] * e1 + z[1] * e2)
+            shift = np.stack([d[b] - nh[b] * d[a] / nh[a], d[cc] - nh[cc] * d[a] / nh[a]]) * self.hit_scale
+        ok = np.all(np.isfinite(shift), axis=0) & np.all(np.isfinite(self.hits), axis=0)
+        return np.where(ok, self.hits + np.where(ok, shift, 0.0), self.hits)
+
+    def scattered(self, seed):
+        """This radiograph with multiple scattering sampled on the host: a new Radiograph whose hits are scattered_hits(seed)
+        and whose counts are those hits (flags == 0) binned again by engine.hist2d on the same detector; everything else is
+        shared.  Not modelled: sampling on the device, the correlated change of direction (only the plane's image is kept)."""
+        hits = self.scattered_hits(seed)
+        return Radiograph(self._bin(hits, self.flags == 0), self.edges, hits, self.flags, self.steps, self.sf, self.magnification,
+                          self.stats, self._reference_hits, self.dt, self.max_steps, energy_MeV=self.energy_MeV,
+                          moments=self.moments, axis=self.axis, det_pos=self.det_pos, hit_scale=self.hit_scale)
+
+    def counts_in(self, e_lo, e_hi):
+        """The image of one energy window: the counts of the particles with flags == 0 and e_lo <= energy_MeV < e_hi, what one
+        layer of a film stack or one etch depth of CR-39 records."""
+        self._need_matter()
+        return self._bin(self.hits, (self.flags == 0) & (self.energy_MeV >= e_lo) & (self.energy_MeV < e_hi))
 
     def reference_counts(self):
         """The counts the same source gives without fields: its straight lines binned on the same detector."""
@@ -195,17 +331,32 @@ def default_steps(domain, source, dt=None):
 
 
 def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sort=True, hit_scale=1e3, bins=(256, 256),
-               fields=None):
+               fields=None, material=None, stop_energy_MeV=0.0, scatter_seed=None):
     """The radiograph of `domain` (B from external_B / test_B, E from external_E; at least one) by `source` on the plane
     coordinate[source.axis] == det_pos [m].  dt, max_steps: default_steps.  image: an engine.DetectorImage of counts the pushed
     particles are added to on the device (zero it first if it is reused), or None for a detector of `bins` over the shadow of
     the box's centre plane.  sort: order the particles by entry cell before the upload (neighbouring lanes gather neighbouring
     nodes) and undo the order on the outputs; the per-particle results are the same bits either way.  fields: a
-    fields.SourceFields of the domain whose uploads are reused.  Returns a Radiograph."""
+    fields.SourceFields of the domain whose uploads are reused.  Returns a Radiograph.
+    material: a Material switches to the push through matter (engine.push_particles_matter -> sr_particles_push_matter): the
+    particles lose energy in the domain's ne by Bethe's stopping power of the free and the bound electrons -- the mean
+    ionisation is the domain's Z (external_Z: a grid or a number) -- and gather the moments of the multiple-scattering power;
+    E and B may then both be absent.  stop_energy_MeV: a particle below it is stopped and not binned.  scatter_seed: not None
+    returns Radiograph.scattered(scatter_seed).  Not modelled: straggling, nuclear reactions, more than one material, large-angle
+    scattering, scattering that feeds back on the path, sampling on the device."""
     a = source.axis
     B, E = getattr(domain, "B", None), getattr(domain, "E", None)
-    if B is None and E is None:
-        raise ValueError("the domain holds neither B (external_B / test_B) nor E (external_E)")
+    if material is None:
+        if B is None and E is None:
+            raise ValueError("the domain holds neither B (external_B / test_B) nor E (external_E)")
+        if scatter_seed is not None or stop_energy_MeV:
+            raise ValueError("stop_energy_MeV and scatter_seed need a material")
+    else:
+        if not isinstance(material, Material):
+            raise ValueError("material must be a radiography.Material")
+        ne, Z = getattr(domain, "ne", None), getattr(domain, "Z", None)
+        if ne is None or Z is None:
+            raise ValueError("with a material the domain needs ne and Z (external_Z: a grid or a number)")
     det_pos = float(det_pos)
     g = grid_f64(domain)
     lo, hi = np.array([v[0] for v in g]), np.array([v[-1] for v in g])
@@ -237,16 +388,28 @@ def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sor
     flags = np.where(missed, engine.PUSH_MISSED, 0).astype(np.uint8)
     steps = np.zeros(n, np.int32)
     idx = np.nonzero(meets)[0]
-    stats = engine.PushStats(0.0, 0, 0, 0, 0)
+    stats = engine.PushStats(0.0, 0, 0, 0, 0) if material is None else engine.PushMatterStats(0.0, 0, 0, 0, 0, 0)
+    energy = moments = None
+    if material is not None:  # a line that never meets the box keeps the source's energy and gathers nothing
+        energy, moments = kinetic_energy(s0[3:], source.mass), np.zeros((4, n))
     with staged(domain, fields) as src:  # fields of another domain are refused whether or not a particle meets the box
         if len(idx):
             sub = s_in[:, idx]
             if sort:
                 order = entry_cell_order(sub, g)
                 idx, sub = idx[order], sub[:, order]
-            f = src.get_all({"E": None if E is None else np.asarray(E), "B": None if B is None else np.asarray(B)})
-            out = engine.push_particles(f["E"], f["B"], np.ascontiguousarray(sub), source.qm, dt, max_steps, a, det_pos, hit_scale,
-                                        image=image)
+            named = {"E": None if E is None else np.asarray(E), "B": None if B is None else np.asarray(B)}
+            if material is None:
+                f = src.get_all(named)
+                out = engine.push_particles(f["E"], f["B"], np.ascontiguousarray(sub), source.qm, dt, max_steps, a, det_pos, hit_scale,
+                                            image=image)
+            else:
+                f = src.get_all({**named, "ne": np.asarray(ne), "Z": np.asarray(Z) if np.ndim(Z) == 3 else None})
+                out = engine.push_particles_matter(f["E"], f["B"], f["ne"], f["Z"] if f["Z"] is not None else float(Z),
+                                                   np.ascontiguousarray(sub), source.qm, dt, max_steps, a, det_pos, hit_scale,
+                                                   mass=source.mass, z=source.charge / E_CHARGE, Zn=material.Zn, I=material.I,
+                                                   lnLs=material.coulomb_log, stop_energy=stop_energy_MeV * MEV, image=image)
+                energy[idx], moments[:, idx] = out["energy"], out["moments"]
             sf[:, idx], hits[:, idx], flags[idx], steps[idx], stats = out["sf"], out["hits"], out["flags"], out["steps"], out["stats"]
     counts = np.array(image.counts_f64())
     x_lo, x_hi, y_lo, y_hi = image.range
@@ -256,4 +419,7 @@ def radiograph(domain, source, det_pos, dt=None, max_steps=None, image=None, sor
     edges = (np.linspace(x_lo, x_hi, image.nx + 1), np.linspace(y_lo, y_hi, image.ny + 1))
     if own_image:
         image.close()
-    return Radiograph(np.asarray(counts, np.float64), edges, hits, flags, steps, sf, magnification, stats, ref_hits, dt, max_steps)
+    rad = Radiograph(np.asarray(counts, np.float64), edges, hits, flags, steps, sf, magnification, stats, ref_hits, dt, max_steps,
+                     energy_MeV=None if energy is None else energy / MEV, moments=moments, axis=a, det_pos=det_pos,
+                     hit_scale=hit_scale)
+    return rad if scatter_seed is None else rad.scattered(scatter_seed)
