@@ -81,6 +81,11 @@ int sr_stream_wait(int waiting, int on);
  * arrays over such blocks and returns them when the arrays are collected). */
 int sr_host_alloc(void **out, size_t bytes);
 void sr_host_free(void *p);
+/* SYNTHRAY_ALLOC_FILL=<0..255>, a test knob read at every allocation: every device buffer of the library, the whole staging block
+ * of the selected stream at every hand-out, and every block of sr_host_alloc is filled with that byte before it is used (unset or
+ * empty: nothing is filled).  No result may depend on it.  sr_alloc_probe shows the knob at work: `bytes` of a fresh device buffer
+ * and `bytes` of the selected stream's staging block, as they are handed out, copied to the caller (either may be NULL). */
+int sr_alloc_probe(size_t bytes, unsigned char *from_alloc, unsigned char *from_scratch);
 /* sr_trace on a large host bundle keeps its device-side working set (three chunk-sized ray bundles and two staging blocks,
  * ~1.5 GB of HBM at the default chunk) between calls, so that a loop of solve() calls does not allocate and release it
  * every time (trace_pipeline.hip).  This releases it (SYNTHRAY_TRACE_CACHE=0: never kept). */

@@ -187,6 +187,7 @@ SYMBOLS = {
     "sr_stream_wait": (_i, [_i, _i]),
     "sr_host_alloc": (_i, [_pp, C.c_size_t]),
     "sr_host_free": (None, [_vp]),
+    "sr_alloc_probe": (_i, [C.c_size_t, _vp, _vp]),
     "sr_volume_create": (_i, [_pp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _i]),
     "sr_volume_create_from_fields": (_i, [_pp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _i]),
     "sr_volume_fields": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
 #include <map>
 #include <string>
@@ -70,11 +71,45 @@ struct Context {
 Context &ctx();
 int ensure_init();  // sr_init(0) on first use
 
+// SYNTHRAY_ALLOC_FILL=<0..255> (a test knob, read at every allocation and every hand-out of the scratch block): the byte every
+// buffer of the library is filled with before it is handed out, so that a kernel or host path that depends on what device memory
+// held before shows (docs/ALLOCATIONS.md, tests/test_alloc_poison.py).  -1: unset, empty or not a byte -- nothing is filled.
+inline int alloc_fill() {
+  const char *e = getenv("SYNTHRAY_ALLOC_FILL");
+  if (!e || !e[0]) return -1;
+  char *end = nullptr;
+  const long v = strtol(e, &end, 0);
+  return (end && *end == '\0' && v >= 0 && v <= 255) ? (int)v : -1;
+}
+// `bytes` at p hold `fill` when this returns: waited for, because the buffer may next be used on the side stream or the other
+// library stream.  Memsets, uploads and kernels of the caller come after it.
+inline hipError_t dev_fill(void *p, size_t bytes, int fill) {
+  if (fill < 0 || !p || bytes == 0) return hipSuccess;
+  hipStream_t st = ctx().stream;
+  const hipError_t e = hipMemsetAsync(p, fill, bytes, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+// THE device allocation of the library (every other site goes through it): raw bytes and the runtime's own status, for the
+// callers that have a failure path of their own (the scratch block's second try, the tile records that may be refused).
+inline hipError_t dev_alloc_bytes(void **p, size_t bytes) {
+  *p = nullptr;
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    return e;
+  }
+  e = dev_fill(*p, bytes, alloc_fill());
+  if (e != hipSuccess) {
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
+  return e;
+}
 template <typename T>
 int dev_alloc(T **p, size_t count) {
   *p = nullptr;
   if (count == 0) return SR_OK;
-  SR_HIP(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
+  SR_HIP(dev_alloc_bytes(reinterpret_cast<void **>(p), count * sizeof(T)));
   return SR_OK;
 }
 inline void dev_free(void *p) {

@@ -751,8 +751,8 @@ int image_alloc(sr_image **out, int kind, int n_ch, int nx, int ny, double x_lo,
   int rc = sr::ensure_init();
   if (rc) return rc;
   void *d = nullptr;
-  hipError_t e = hipMalloc(&d, (size_t)bytes);
-  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_image_create: hipMalloc(%lld) failed: %s", (long long)bytes, hipGetErrorString(e));
+  hipError_t e = sr::dev_alloc_bytes(&d, (size_t)bytes);
+  if (e != hipSuccess) return sr::fail(SR_ERR_HIP, "sr_image_create: allocating %lld bytes failed: %s", (long long)bytes, hipGetErrorString(e));
   e = hipMemsetAsync(d, 0, (size_t)bytes, sr::ctx().stream);
   if (e != hipSuccess) {
     sr::dev_free(d);
@@ -978,7 +978,7 @@ int sr_rays_refine(const sr_rays *r, int n_diag, const sr_optic *const *chains, 
   // the set travels through a buffer that belongs to the bundle (device side) and a copy the bundle keeps (host side): no wait
   // is needed for either, so a chunked driver can queue refine + deposits without a host round trip (retraced == NULL)
   sr_rays *rw = const_cast<sr_rays *>(r);
-  if (!rw->guard_set) SR_HIP(hipMalloc(&rw->guard_set, sizeof(GuardSet)));
+  if (!rw->guard_set) SR_HIP(sr::dev_alloc_bytes(&rw->guard_set, sizeof(GuardSet)));
   rw->guard_set_host.assign(reinterpret_cast<const char *>(&S), reinterpret_cast<const char *>(&S) + sizeof(GuardSet));
   SR_HIP(hipMemcpyAsync(rw->guard_set, rw->guard_set_host.data(), sizeof(GuardSet), hipMemcpyHostToDevice, st));
   int rc = guard_queue_reset(r, st);

@@ -152,11 +152,11 @@ int sr_field_create(sr_field **out, const void *data, int is_f64, int n_comp, in
   f->n_comp = n_comp;
   f->is_f64 = is_f64 != 0;
   const size_t bytes = (size_t)nx * ny * nz * n_comp * (is_f64 ? sizeof(double) : sizeof(float));
-  hipError_t e = hipMalloc(&f->data, bytes);
+  hipError_t e = sr::dev_alloc_bytes(&f->data, bytes);
   if (e != hipSuccess) {
     f->data = nullptr;
     delete f;
-    return sr::fail(SR_ERR_HIP, "sr_field_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    return sr::fail(SR_ERR_HIP, "sr_field_create: allocating %zu bytes failed: %s", bytes, hipGetErrorString(e));
   }
   rc = sr::upload_sync(f->data, data, bytes, st);
   for (int k = 0; k < 3 && !rc; ++k) {

@@ -56,24 +56,30 @@ struct ScratchBlock {
 
 void *scratch(size_t bytes) {
   ScratchBlock &b = g_scratch[ctx().current];
-  if (b.bytes >= bytes && b.p) return b.p;
+  if (b.bytes >= bytes && b.p) {
+    // a kept block holds the last call's data: under SYNTHRAY_ALLOC_FILL the WHOLE block is filled at every hand-out
+    const hipError_t e = dev_fill(b.p, b.bytes, alloc_fill());
+    if (e != hipSuccess) {
+      fail(SR_ERR_HIP, "filling the staging block (%zu bytes) failed: %s", b.bytes, hipGetErrorString(e));
+      return nullptr;
+    }
+    return b.p;
+  }
   if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.bytes = 0;
   const size_t want = bytes + bytes / 8;  // a little room: the next call's rays may differ by a few
-  hipError_t e = hipMalloc(&b.p, want ? want : 1);
+  b.bytes = want ? want : 1;
+  hipError_t e = dev_alloc_bytes(&b.p, b.bytes);
   if (e != hipSuccess) {
-    b.p = nullptr;
-    e = hipMalloc(&b.p, bytes ? bytes : 1);
+    b.bytes = bytes ? bytes : 1;
+    e = dev_alloc_bytes(&b.p, b.bytes);
     if (e != hipSuccess) {
-      b.p = nullptr;
-      fail(SR_ERR_HIP, "hipMalloc(%zu) for staging failed: %s", bytes, hipGetErrorString(e));
+      b.bytes = 0;
+      fail(SR_ERR_HIP, "allocating %zu bytes for staging failed: %s", bytes, hipGetErrorString(e));
       return nullptr;
     }
-    b.bytes = bytes;
-    return b.p;
   }
-  b.bytes = want;
   return b.p;
 }
 
@@ -405,7 +411,23 @@ int sr_host_alloc(void **out, size_t bytes) {
   if (rc) return rc;
   if (bytes == 0) return SR_OK;
   SR_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  if (const int fill = sr::alloc_fill(); fill >= 0) memset(*out, fill, bytes);
   return SR_OK;
+}
+
+// What SYNTHRAY_ALLOC_FILL does, seen from outside: `bytes` of a fresh buffer from the library's allocation and `bytes` of the
+// selected stream's staging block, as they are handed out, copied to the caller (either destination may be NULL).
+int sr_alloc_probe(size_t bytes, unsigned char *from_alloc, unsigned char *from_scratch) {
+  int rc = sr::ensure_init();
+  if (rc) return rc;
+  if (bytes == 0) return SR_OK;
+  hipStream_t st = sr::ctx().stream;
+  sr::CallBuffers buf;
+  unsigned char *d_fresh = nullptr;
+  SR_RC(buf.alloc(&d_fresh, bytes));
+  unsigned char *d_kept = static_cast<unsigned char *>(sr::scratch(bytes));
+  if (!d_kept) return SR_ERR_HIP;
+  return sr::stage_out(st, {{from_alloc, d_fresh, bytes}, {from_scratch, d_kept, bytes}});
 }
 
 void sr_host_free(void *p) {

@@ -913,7 +913,7 @@ int tile_records(const sr_volume *v, const TraceKnobs &knobs, hipStream_t st, bo
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || count * sizeof(double) > free_b / 3) return SR_OK;
     double *R = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&R), count * sizeof(double)) != hipSuccess) {
+    if (sr::dev_alloc_bytes(reinterpret_cast<void **>(&R), count * sizeof(double)) != hipSuccess) {
       (void)hipGetLastError();
       return SR_OK;
     }
@@ -1256,7 +1256,7 @@ int make_trace_args(const sr_rays *r, const sr_volume *v, const sr_trace_params 
         }
       }
       void *d = nullptr;
-      SR_HIP(hipMalloc(&d, sizeof(StepTab) * (size_t)(2 * nt)));
+      SR_HIP(sr::dev_alloc_bytes(&d, sizeof(StepTab) * (size_t)(2 * nt)));
       hipError_t e = hipMemcpy(d, tab.data(), sizeof(StepTab) * (size_t)(2 * nt), hipMemcpyHostToDevice);  // synchronous
       if (e != hipSuccess) {
         (void)hipFree(d);
@@ -1376,7 +1376,7 @@ int sr::download_rows(const sr_rays *r, double *sf, double *rf, double *Jf, int6
   double *tmp = staging;
   const size_t rows = (sf ? 9 : 0) + (rf ? 4 : 0) + (Jf ? 4 : 0);
   if (rows == 0) return SR_OK;
-  if (!tmp) {  // the library's per-call staging block (kept between calls: no hipMalloc / hipFree in a loop of solve() calls)
+  if (!tmp) {  // the library's per-call staging block (kept between calls: no allocation / release in a loop of solve() calls)
     tmp = static_cast<double *>(sr::scratch(sizeof(double) * rows * (size_t)N));
     if (!tmp) return SR_ERR_HIP;
   }

@@ -38,6 +38,9 @@ def test_library_exports_every_declared_symbol(built):
     assert built.SYMBOLS["sr_grid_stats"] == (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int])
     header = open(os.path.join(ROOT, "include", "synthray.h")).read()
     assert "int sr_grid_cus(int n_cu, int *in_force);" in header and "int sr_grid_stats(int64_t out[2], int reset);" in header
+    # the allocation-fill knob's probe (tests/test_alloc_poison.py)
+    assert built.SYMBOLS["sr_alloc_probe"] == (ctypes.c_int, [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p])
+    assert "int sr_alloc_probe(size_t bytes, unsigned char *from_alloc, unsigned char *from_scratch);" in header
     lib = ctypes.CDLL(built.LIB_PATH)
     missing =[s for s in declared if not hasattr(lib, s)]
     assert not missing, f"declared in synthray.h but not exported: {missing}"
